@@ -10,11 +10,14 @@ Workloads (BASELINE.json ``configs``; ``--config``):
 
 A *step* follows the reference's published protocol (benchmark/CPU+AMDGPU/run_benchmarks.jl:80-90):
 ``set_points!`` + ``exec_type1!`` on inputs already resident in HBM.  ``value`` = whole-job NU-points/s of K such
-steps (max over ranks).  BASELINE.json does not fix the window evaluation, and the reference has two defaults:
-``FastApproximation()`` on its CPU backend and ``Direct()`` on ROC (ext/NonuniformFFTsAMDGPUExt.jl:56).  Both are measured
-and reported as equally complete records (value, stage times, type 2, roofline fraction): the top-level ``value`` is the
-polynomial window (continuity with round 1's line), the sibling record ``direct`` the ROC default.  Type-2 is timed the
-same way in a second region.  Stage times come from HIP events recorded on the launch stream *inside* the timed region (torch events
+steps (max over ranks), ``ms_per_step`` = milliseconds of one of them.  A plain run (``--steps K --warmup W``) sets up, warms
+up, times the K steps and prints the line; ``--dump-outputs DIR`` then writes what the last step computed (a fixed, seeded
+sample of the type-1 spectra, ``output_sample``).  ``--full`` measures everything else as well: BASELINE.json does not fix the
+window evaluation, and the reference has two defaults: ``FastApproximation()`` on its CPU backend and ``Direct()`` on ROC
+(ext/NonuniformFFTsAMDGPUExt.jl:56).  Both are measured and reported as equally complete records (value, stage times, type 2,
+roofline fraction): the top-level ``value`` is ``--evalmode`` (default Direct()), the sibling record the other mode.  Type-2 is
+timed the same way in a second region; the C3 / C4 records, the reference protocol, the HBM probe and the CPU baseline follow.
+Stage times come from HIP events recorded on the launch stream *inside* the timed region (torch events
 on the current stream, which is the stream handed to the C ABI).
 
 N > 1 (``--gpus N``; without a launcher this script starts the N ranks itself): one process per GPU, every rank
@@ -67,8 +70,15 @@ def parse():
                     help="window evaluation of the top-level value (default: Direct(), the reference's default on ROCBackend, "
                          "ext/NonuniformFFTsAMDGPUExt.jl:56 — since round 5; rounds 1-4 led with FastApproximation; the other mode is "
                          "measured too and reported as an equally complete sibling record, and as config.fast_value / config.direct_value)")
-    ap.add_argument("--only-headline", action="store_true", help="skip the sibling evaluation mode, the reference "
-                    "protocol, the density sweep, the HBM probe and the CPU baseline (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline as well: the type-2 region (and on the halo variant the plain FFT stage), "
+                         "the sibling evaluation mode, the C3 / C4 records, the reference protocol and its density sweep, the HBM probe and "
+                         "the CPU baseline.  Without it a run times the headline type-1 steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the type-1 spectra, a fixed seeded sample of "
+                         "at most DUMP_SAMPLE coefficients in all) as DIR/<name>.npy")
+    ap.add_argument("--only-headline", action="store_true", help="with --full: skip the sibling evaluation mode, the reference "
+                    "protocol, the density sweep, the HBM probe and the CPU baseline, but keep the type-2 region (profiling runs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-gather", action="store_true")
     ap.add_argument("--no-reference-protocol", action="store_true")
@@ -249,6 +259,20 @@ def timed_steps(step_fn, K, W, dev, distributed, after=None):
     return dt, events
 
 
+DUMP_SAMPLE = 1 << 20      # --dump-outputs: complex coefficients written at most, over all components (16 MB in complex128)
+
+
+def output_sample(outs, seed=0):
+    """{name: array} of the type-1 spectra `outs` (one complex tensor per component) for --dump-outputs: the coefficients at a fixed,
+    seeded set of flat indices (all of them when they fit), as (re, im) pairs in the spectrum's real precision.  The indices depend on
+    the shape alone, so two builds of the project write the same coefficients."""
+    n = outs[0].numel()
+    k = DUMP_SAMPLE // len(outs)
+    idx = np.arange(n) if n <= k else np.unique(np.random.default_rng(seed).integers(0, n, k))
+    idx_t = torch.from_numpy(idx).to(outs[0].device)
+    return {f"type1_uhat_c{c}": torch.view_as_real(o.reshape(-1)[idx_t]).cpu().numpy() for c, o in enumerate(outs)}
+
+
 def gather_components(outs, recv, rank, dst=0):
     """The single collective of the path: every component's output spectrum of every rank to rank `dst`.
     outs: C tensors of this rank; recv: on rank dst, C lists of world-size receive buffers (None elsewhere).  Complex
@@ -318,7 +342,7 @@ def main():
         if getattr(a, k):
             cfg[k] = getattr(a, k)
     steps = a.steps if a.steps > 0 else cfg["steps"]
-    full = world == 1 and not a.only_headline
+    full = world == 1 and a.full and not a.only_headline
 
     gather_stream = torch.cuda.Stream(device=dev) if distributed and not a.no_gather else None
 
@@ -347,8 +371,9 @@ def main():
             P["rounds"] = (P["C_total"] + world - 1) // world       # gathers per step: ranks with fewer components send a placeholder
         return P
 
-    def measure(P, evalmode_name, steps, gather):
-        """K steps of set_points! + exec_type1!, then of set_points! + exec_type2!, with stage events."""
+    def measure(P, evalmode_name, steps, gather, type2=True, dump=None):
+        """K steps of set_points! + exec_type1!, then (type2) of set_points! + exec_type2!, with stage events.  `dump` (a dict)
+        receives the output sample of the last type-1 step."""
         cfg, Z, CT, Np, Cn, dims, xs, vps = P["cfg"], P["Z"], P["CT"], P["Np"], P["Cn"], P["dims"], P["xs"], P["vps"]
         mode = nufft.Direct() if evalmode_name == "direct" else nufft.FastApproximation()
         plan = nufft.PlanNUFFT(Z, dims, m=cfg["m"], sigma=cfg["sigma"], ntransforms=Cn, kernel_evalmode=mode,
@@ -425,17 +450,23 @@ def main():
 
         dt1, ev1 = timed(step_type1, steps, a.warmup)
         st1 = stage_ms(ev1, ["set_points", "spread", "fft", "deconv"])
-        use_gather[0] = False                              # the type-2 region has no gather
-        dt2, ev2 = timed(step_type2, steps, a.warmup)
-        st2 = stage_ms(ev2, ["set_points", "deconv_pad", "fft", "interp"])
+        if dump is not None:
+            dump.update(output_sample(uhat[(steps - 1) % 2]))
         exec1_ms = st1["spread"] + st1["fft"] + st1["deconv"]
-        exec2_ms = st2["deconv_pad"] + st2["fft"] + st2["interp"]
         jobs = 1 if P.get("sharded") else world
+        rec_type2 = None
+        if type2:
+            use_gather[0] = False                              # the type-2 region has no gather
+            dt2, ev2 = timed(step_type2, steps, a.warmup)
+            st2 = stage_ms(ev2, ["set_points", "deconv_pad", "fft", "interp"])
+            exec2_ms = st2["deconv_pad"] + st2["fft"] + st2["interp"]
+            rec_type2 = {"stages_ms": st2, "exec_only_pts_per_s": Np / (exec2_ms * 1e-3), "with_set_points_pts_per_s": jobs * Np * steps / dt2,
+                         "ms_per_step": dt2 / steps * 1e3}
         engine_used = plan.spread_engine_used()          # the per-point-set decision read back from the device (after the timed regions)
         # Halo variant of the spreading ring: the FFT stage's first pass adds the side buffer of the stencil reach, i.e. part of the
         # "spread" work is timed under "fft".  How much: the same FFT stage behind the self-contained nufft_spread (plain first pass).
         fft_plain_ms = None
-        if int(info.ring_halo) and engine_used == "marching_ring":
+        if type2 and int(info.ring_halo) and engine_used == "marching_ring":
             s = stream_ptr()
             ts = []
             for _ in range(6):
@@ -452,8 +483,7 @@ def main():
             # independent problems: every rank transforms its own Np points; sharded components: the job is ONE transform of Np points
             "value": jobs * Np * steps / dt1, "ms_per_step": dt1 / steps * 1e3,
             "type1": {"stages_ms": st1, "exec_only_pts_per_s": Np / (exec1_ms * 1e-3), "with_set_points_pts_per_s": jobs * Np * steps / dt1},
-            "type2": {"stages_ms": st2, "exec_only_pts_per_s": Np / (exec2_ms * 1e-3), "with_set_points_pts_per_s": jobs * Np * steps / dt2,
-                      "ms_per_step": dt2 / steps * 1e3},
+            "type2": rec_type2,
             "workspace_bytes": int(plan.info().workspace_bytes),       # plan-owned device memory with this point set in place
             "ring_column": [int(info.ring_column[0]), int(info.ring_column[1])], "ring_segments": int(info.ring_segments),
             "ring_halo": int(info.ring_halo), "fft_plain_ms": fft_plain_ms,
@@ -469,13 +499,19 @@ def main():
     P = prepare(cfg)
     Np, Cn, is_complex, real_bytes = P["Np"], P["Cn"], P["is_complex"], P["real_bytes"]
     P_sharded, C_total = bool(P.get("sharded")), P["C_total"]
-    head = measure(P, a.evalmode, steps, True)
+    dumped = {} if a.dump_outputs and rank == 0 else None
+    head = measure(P, a.evalmode, steps, True, type2=a.full, dump=dumped)
+    if dumped:
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in dumped.items():
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), arr)
     other = measure(P, "fast" if a.evalmode == "direct" else "direct", steps, True) if full else None
 
     ab = algorithmic_bytes(Np, head["oversampled"], head["size"], is_complex, real_bytes, Cn)
-    st1, st2 = head["type1"]["stages_ms"], head["type2"]["stages_ms"]
+    # (a plain run times type 1 only: what derives from the type-2 region is None there)
+    st1, st2 = head["type1"]["stages_ms"], (head["type2"]["stages_ms"] if head["type2"] else None)
     exec1_ms = st1["spread"] + st1["fft"] + st1["deconv"]
-    exec2_ms = st2["deconv_pad"] + st2["fft"] + st2["interp"]
+    exec2_ms = st2["deconv_pad"] + st2["fft"] + st2["interp"] if st2 else None
     # the dominant kernel of the step: spreading (one launch per component)
     tname = {"float64": "double", "float32": "float", "complex64": "float", "complex128": "double"}[cfg["Z"]]
     if head["spread_engine"] == "mfma_patches" and head["patch_f32acc"]:
@@ -513,10 +549,21 @@ def main():
         ab["spread_kernel_min"] += Cn * ab["G"] * ((n1c + xr) * (n2c + yr) / float(n1c * n2c) - 1.0)
     traffic_b, traffic_src, profile_us = pmc_traffic(kname, a.config, head["evalmode"])
     sq = sq_counters(kname, a.config, head["evalmode"])
-    # (the interpolation ring's name carries the window mode as its last template argument; the lookup is restricted to this mode's profiles as well)
-    interp_kname = (("interp_march_staged_kernel" if head.get("sort_columns") else "interp_march_kernel")
-                    + f"<{tname}, {'true' if is_complex and cfg['Z'] != 'complex128' else 'false'}, {cfg['m']}, {'false' if head['evalmode'] == 'Direct' else 'true'}>")
-    interp_traffic_b, interp_traffic_src, interp_profile_us = pmc_traffic(interp_kname, a.config, head["evalmode"])
+    interp = None
+    if st2:
+        # (the interpolation ring's name carries the window mode as its last template argument; the lookup is restricted to this mode's profiles as well)
+        interp_kname = (("interp_march_staged_kernel" if head.get("sort_columns") else "interp_march_kernel")
+                        + f"<{tname}, {'true' if is_complex and cfg['Z'] != 'complex128' else 'false'}, {cfg['m']}, {'false' if head['evalmode'] == 'Direct' else 'true'}>")
+        interp_traffic_b, interp_traffic_src, interp_profile_us = pmc_traffic(interp_kname, a.config, head["evalmode"])
+        interp = {"kernel_ms": st2["interp"], "algorithmic_bytes_per_stage": ab["interp_kernel"],
+                  "achieved": ab["interp_kernel"] / (st2["interp"] * 1e-3) / 1e9, "frac": ab["interp_kernel"] / (st2["interp"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                  "kernel": interp_kname,
+                  "traffic": (interp_traffic_b / 1e9) if interp_traffic_b is not None else None, "traffic_source": interp_traffic_src,
+                  "profile_kernel_us": interp_profile_us,
+                  # the interpolation stage is one launch of this kernel (+ a stand-by launch of the tile kernel that exits on the device flag)
+                  "profile_matches_run": (abs(interp_profile_us / 1e3 - st2["interp"]) < 0.1 * st2["interp"]) if interp_profile_us else None,
+                  "binding_resource_counters": sq_counters(interp_kname, a.config, head["evalmode"]),
+                  "note": "type-2 gather stage (R(G) + R(points) + W(values)); z-marching LDS ring where the point set is not sliced"}
     probe = hbm_probe(dev) if full else None
     peak_m = probe["peak_measured_GBs"] if probe else None
     achieved = ab["spread_kernel"] / spread_s / 1e9
@@ -542,22 +589,14 @@ def main():
         "frac_own_traffic": ab["spread_kernel_min"] / spread_s / 1e9 / HBM_PEAK_GBS,
         "frac_own": ab["spread_kernel_min"] / spread_s / 1e9 / HBM_PEAK_GBS,      # the kernel's own compulsory traffic (G + P [+ side buffer]) against the peak
         "kernel_ms": st1["spread"],
-        # halo variant only: the stage charged with the extra time of the FFT pass that adds the side buffer (else = frac)
-        "consumer_extra_ms": halo_extra_s * 1e3,
-        "frac_incl_consumer": ab["spread_kernel"] / (spread_s + halo_extra_s) / 1e9 / HBM_PEAK_GBS,
-        "interp": {"kernel_ms": st2["interp"], "algorithmic_bytes_per_stage": ab["interp_kernel"],
-                   "achieved": ab["interp_kernel"] / (st2["interp"] * 1e-3) / 1e9, "frac": ab["interp_kernel"] / (st2["interp"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                   "kernel": interp_kname,
-                   "traffic": (interp_traffic_b / 1e9) if interp_traffic_b is not None else None, "traffic_source": interp_traffic_src,
-                   "profile_kernel_us": interp_profile_us,
-                   # the interpolation stage is one launch of this kernel (+ a stand-by launch of the tile kernel that exits on the device flag)
-                   "profile_matches_run": (abs(interp_profile_us / 1e3 - st2["interp"]) < 0.1 * st2["interp"]) if interp_profile_us else None,
-                   "binding_resource_counters": sq_counters(interp_kname, a.config, head["evalmode"]),
-                   "note": "type-2 gather stage (R(G) + R(points) + W(values)); z-marching LDS ring where the point set is not sliced"},
+        # halo variant only: the stage charged with the extra time of the FFT pass that adds the side buffer (else = frac; measured with --full)
+        "consumer_extra_ms": halo_extra_s * 1e3 if a.full else None,
+        "frac_incl_consumer": ab["spread_kernel"] / (spread_s + halo_extra_s) / 1e9 / HBM_PEAK_GBS if a.full else None,
+        "interp": interp,
         "type1_exec_frac": ab["type1_exec"] / (exec1_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-        "type2_exec_frac": ab["type2_exec"] / (exec2_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+        "type2_exec_frac": ab["type2_exec"] / (exec2_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if exec2_ms else None,
         "type1_exec_frac_of_measured_peak": (ab["type1_exec"] / (exec1_ms * 1e-3) / 1e9 / peak_m) if peak_m else None,
-        "type2_exec_frac_of_measured_peak": (ab["type2_exec"] / (exec2_ms * 1e-3) / 1e9 / peak_m) if peak_m else None,
+        "type2_exec_frac_of_measured_peak": (ab["type2_exec"] / (exec2_ms * 1e-3) / 1e9 / peak_m) if peak_m and exec2_ms else None,
         "hbm_probe": probe,
     }
     tname_z = {"float64": "Float64", "float32": "Float32", "complex64": "ComplexF32", "complex128": "ComplexF64"}[cfg["Z"]]
@@ -583,8 +622,8 @@ def main():
             "spread_engine": head["spread_engine"], "spread_tile": head["spread_tile"], "interp_tile": head["interp_tile"],
             "ring_column": head["ring_column"], "ring_segments": head["ring_segments"], "ring_halo": head["ring_halo"], "workspace_bytes": head["workspace_bytes"],
             "sort_columns": head["sort_columns"], "sort_method": head["sort_method"], "sort_column_bins": head["sort_column_bins"],
-            "set_points_ms": st1["set_points"], "spread_ms": st1["spread"], "fft_ms": st1["fft"], "deconv_ms": st1["deconv"], "interp_ms": st2["interp"],
-            "type2_value": head["type2"]["with_set_points_pts_per_s"],
+            "set_points_ms": st1["set_points"], "spread_ms": st1["spread"], "fft_ms": st1["fft"], "deconv_ms": st1["deconv"], "interp_ms": st2["interp"] if st2 else None,
+            "type2_value": head["type2"]["with_set_points_pts_per_s"] if st2 else None,
             "parallelism": (f"ntransforms = {C_total} components of one transform sharded over {world} GPU(s) (component c on rank c mod N, same points)"
                             if P_sharded else f"{world} independent plan(s), one per GPU")
                            + ("" if not distributed or a.no_gather else "; RCCL gather of spectra to rank 0 overlapped on a side stream"),
@@ -609,7 +648,7 @@ def main():
     if fast_rec is not None:
         result["config"]["fast_value"] = fast_rec["value"]
         result["config"]["fast_ms_per_step"] = fast_rec["ms_per_step"]
-        result["config"]["fast_type2_value"] = fast_rec["type2"]["with_set_points_pts_per_s"]
+        result["config"]["fast_type2_value"] = fast_rec["type2"]["with_set_points_pts_per_s"] if fast_rec["type2"] else None
     if full and a.config == "c2" and not a.no_other_configs:
         del P
         torch.cuda.empty_cache()

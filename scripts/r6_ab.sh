@@ -2,7 +2,7 @@
 # final tree (spreading window restructured into prep + accum, experiments off): whole GPU suite, smoke, C-ABI driver, bench line
 R=$(pwd); O=$R/gpurun_out; TAG=${1:-r6ab}
 bash scripts/r6_gputests.sh $TAG
-python3 bench.py > $O/${TAG}_bench_line.json 2> $O/${TAG}_bench_stderr.txt; echo "bench rc=$?"
+python3 bench.py --full > $O/${TAG}_bench_line.json 2> $O/${TAG}_bench_stderr.txt; echo "bench rc=$?"
 python3 - <<PY
 import json
 d = json.loads(open('gpurun_out/${TAG}_bench_line.json').read().strip().splitlines()[-1])

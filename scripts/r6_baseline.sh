@@ -2,7 +2,7 @@
 # round 6, first GPU call: the driver-style bench line of the tree as committed (are C3 / C4 among the first 20 scalars of config?),
 # and the round-5 state of the plans that review item 3 names (set_points / interpolation of Float32 m = 4, Float64 m = 6, ComplexF64 m = 6)
 R=$(pwd); O=$R/gpurun_out; mkdir -p $O
-python3 bench.py > $O/r6_a_bench_line.json 2> $O/r6_a_bench_stderr.txt
+python3 bench.py --full > $O/r6_a_bench_line.json 2> $O/r6_a_bench_stderr.txt
 python3 - <<'P' > $O/r6_a_first20.txt
 import json, sys
 sys.path.insert(0, '.')

@@ -7,7 +7,7 @@ for cfg in "--sigma 1.5 --np 1e7 --dist randn" "--sigma 1.5 --np 16777216 --dist
   NUFFT_SORT_ADAPTIVE=$ad python3 scripts/perf_probe.py --z f64 --m 4 --reps 6 $cfg 2>&1 | grep -E "set_points |t1_spread|t2_interp|with set_points|engines" >> $P
 done; done
 cat $P
-python3 bench.py > $O/${TAG}_bench_line.json 2> $O/${TAG}_bench_stderr.txt
+python3 bench.py --full > $O/${TAG}_bench_line.json 2> $O/${TAG}_bench_stderr.txt
 python3 - <<PY
 import json
 d = json.loads(open('gpurun_out/${TAG}_bench_line.json').read().strip().splitlines()[-1])

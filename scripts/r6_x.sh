@@ -1,7 +1,7 @@
 #!/bin/bash
 # final driver-style bench line of the round, and which test skipped
 R=$(pwd); O=$R/gpurun_out; TAG=${1:-r6x}
-python3 bench.py > $O/${TAG}_bench_line.json 2> $O/${TAG}_bench_stderr.txt; echo "bench rc=$?"
+python3 bench.py --full > $O/${TAG}_bench_line.json 2> $O/${TAG}_bench_stderr.txt; echo "bench rc=$?"
 python3 - <<PY
 import json
 d = json.loads(open('gpurun_out/${TAG}_bench_line.json').read().strip().splitlines()[-1])

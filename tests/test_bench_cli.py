@@ -88,3 +88,38 @@ def test_profile_lookup_is_window_mode_aware():
     assert b.pmc_traffic("interp_march_staged_kernel<double, false, 4, true>", "c2", "Direct")[0] is None
     sq = b.sq_counters("interp_march_staged_kernel<double, false, 4, false>", "c2", "Direct")
     assert sq is None or "_c2_direct_" in sq["source"]
+
+
+def test_full_and_dump_outputs_are_options():
+    """A plain run times the headline only; what else the benchmark measures sits behind --full, and --dump-outputs DIR writes
+    the last timed step's outputs."""
+    r = _run(["--help"])
+    assert r.returncode == 0, r.stderr
+    assert "--full" in r.stdout and "--dump-outputs" in r.stdout
+    src = open(os.path.join(ROOT, "bench.py")).read()
+    assert "full = world == 1 and a.full and not a.only_headline" in src
+    assert "type2=a.full" in src
+
+
+def test_output_sample_is_fixed_and_bounded():
+    """--dump-outputs: the same coefficients on every run (indices seeded, depending on the shape only), all of them when they
+    fit, at most DUMP_SAMPLE over all components (64 MB in complex128 at the most), (re, im) in the spectrum's precision."""
+    import numpy as np
+    import torch
+    b = _load_bench()
+    assert b.DUMP_SAMPLE * 16 <= 64 * 2 ** 20
+    g = torch.Generator().manual_seed(1)
+    outs = tuple(torch.randn(40, 32, 9, dtype=torch.complex128, generator=g) for _ in range(3))
+    b.DUMP_SAMPLE = 3 * 1000
+    s1, s2 = b.output_sample(outs), b.output_sample(tuple(o.clone() for o in outs))
+    assert sorted(s1) == ["type1_uhat_c0", "type1_uhat_c1", "type1_uhat_c2"]
+    for name, arr in s1.items():
+        assert arr.dtype == np.float64 and arr.ndim == 2 and arr.shape[1] == 2 and 900 < arr.shape[0] <= 1000
+        assert np.array_equal(arr, s2[name])
+    # the sampled coefficients are the ones at the seeded flat indices
+    idx = np.unique(np.random.default_rng(0).integers(0, outs[0].numel(), 1000))
+    assert np.array_equal(s1["type1_uhat_c1"], torch.view_as_real(outs[1].reshape(-1)).numpy()[idx])
+    # small spectra are written whole; complex64 spectra as float32
+    small = (torch.randn(4, 5, 3, dtype=torch.complex64, generator=g),)
+    whole = b.output_sample(small)["type1_uhat_c0"]
+    assert whole.dtype == np.float32 and np.array_equal(whole, torch.view_as_real(small[0].reshape(-1)).numpy())
