@@ -325,6 +325,74 @@ int nufft_spread_engine_used(nufft_plan* plan, int* engine_out, void* stream);
 enum { NUFFT_INTERP_LDS_TILES = 1, NUFFT_INTERP_MARCHING_RING = 2 };
 int nufft_interp_engine_used(nufft_plan* plan, int* engine_out, void* stream);
 
+/* ---- type 3 (nonuniform to nonuniform) ------------------------------------------------ */
+/* f_k = Σ_j c_j exp(sign i s_k · x_j) for sources x_j ∈ R^D and targets s_k ∈ R^D (no reference counterpart: NonuniformFFTs.jl has
+ * type 1 and 2 only).  The scheme of Barnett, Magland & af Klinteberg (SISC 2019, section 3.3): the sources, rescaled and prephased,
+ * are spread onto a grid of nf cells per axis by an internal plan of this library, a type-2 transform of an internal complex plan
+ * (N = nf, same σ, M, kernel) reads that grid as its spectrum at the rescaled targets, and a per-target factor corrects the window and
+ * the phase of the centres.  Added after ABI 104 without changing NUFFT_MI355X_VERSION: a caller detects these
+ * entry points by symbol (dlsym nufft_plan3_create) and compares nufft_sizeof_type3_params() / nufft_sizeof_info3() with its own.
+ *
+ * The declared boxes: sources in source_center ± source_halfwidth, targets in target_center ± target_halfwidth (per dimension; only the
+ * first ndim entries are read).  They set the fine grid; results for points outside them are UNDEFINED (the spread of such a source can
+ * wrap around the grid; such a target can fall beyond the window's band) and nufft_type3_points_outside counts them. */
+typedef struct nufft_type3_params {
+    int32_t struct_size;     /* sizeof(nufft_type3_params) of the caller's header (as nufft_params.struct_size); 0 = this layout   */
+    int32_t sign;            /* -1 (0 -> -1, the sign of the reference's type 1) or +1                                             */
+    double  source_center[3], source_halfwidth[3];
+    double  target_center[3], target_halfwidth[3];
+} nufft_type3_params;
+
+typedef struct nufft_plan3 nufft_plan3; /* opaque */
+
+typedef struct nufft_info3 {
+    int32_t ndim, ntransforms, dtype, half_support, sign, kernel, evalmode, device;
+    int64_t nf[3];           /* fine grid: smallest multiple of 4 that is 2,3,5-smooth and >= 2σ X S / π + 2M + 2 (X, S the half-widths) */
+    double  gamma[3];        /* γ = nf / (2σ S): sources are spread at (x - C) / γ                                                     */
+    double  h[3];            /* 2π / nf                                                                                                */
+    double  source_halfwidth[3], target_halfwidth[3];  /* X, S the rule used (a zero half-width replaced: X = 1/S, S = 1/X, or 1 and 1) */
+    int64_t inner_N_over[3]; /* oversampled grid of the internal type-2 plan (nextprod235(σ nf))                                        */
+    double  sigma;           /* requested σ                                                                                           */
+    double  beta[3];         /* window shape parameter of both internal plans (optimal for the requested σ and M)                     */
+    int32_t spread_method;   /* nufft_info.spread_method of the internal spreading plan                                               */
+    int32_t reserved;
+    int64_t num_sources, num_targets;   /* of the last nufft_set_points3 (-1: none yet)                                                */
+    int64_t workspace_bytes; /* device bytes owned right now: both internal plans plus the type-3 buffers                              */
+} nufft_info3;
+
+/* From `params`: dtype, is_complex (must be 1), ndim 1..3, half_support, sigma, kernel, kernel_param, evalmode, ntransforms, device,
+ * options; N, N_over, fftshift and point_transform must be zero (NUFFT_ERR_INVALID_ARG).  A negative or non-finite half-width is
+ * NUFFT_ERR_INVALID_ARG; an nf beyond 2^30 or a pair of grids beyond the device's memory NUFFT_ERR_UNSUPPORTED.  device = -1: a host-only
+ * plan (parameter rule and info only). */
+int nufft_plan3_create(nufft_plan3** out, const nufft_params* params, const nufft_type3_params* t3);
+int nufft_plan3_destroy(nufft_plan3* plan);
+int nufft_plan3_info(const nufft_plan3* plan, nufft_info3* out);
+/* x[d]: device vectors of num_sources reals, s[d]: of num_targets reals (plan precision).  Rescales and prephases the sources, computes
+ * the targets' coordinates and correction factors (in Float64 from the caller's values, stored in the plan's precision), counts points
+ * outside the boxes, and sets the points of both internal plans.  Buffers grow when a size exceeds what the plan holds (never on a
+ * capturing stream: pre-size the plan with the largest point sets before capturing into a hipGraph); the caller's arrays are only read. */
+int nufft_set_points3(nufft_plan3* plan, int64_t num_sources, const void* const* x, int64_t num_targets, const void* const* s,
+                      void* stream);
+/* f_out[c]: device vector complex(T)[num_targets]; c_in[c]: device vector complex(T)[num_sources], c < ntransforms. */
+int nufft_exec_type3(nufft_plan3* plan, void* const* f_out, const void* const* c_in, void* stream);
+/* Sources / targets of the last nufft_set_points3 outside the declared boxes (|x_d - C_d| > X_d in some dimension, with the caller's
+ * half-widths).  Synchronises `stream`. */
+int nufft_type3_points_outside(nufft_plan3* plan, int64_t* sources_out, int64_t* targets_out, void* stream);
+/* The internal plans, for inspection (nufft_plan_info, nufft_spread_engine_used, nufft_interp_engine_used, nufft_set_timing /
+ * nufft_get_stage_times): which = 0 the spreading plan (N_over = nf), 1 the type-2 plan (N = nf).  Owned by the type-3 plan: do not
+ * destroy them or set their points. */
+int nufft_plan3_internal(const nufft_plan3* plan, int which, nufft_plan** out);
+/* enable != 0: bracket the four type-3 kernels and the two internal stages with hipEvents; nufft_get_stage_times3 returns
+ * NUFFT3_NUM_STAGES milliseconds of their latest runs (-1 = never run) and synchronises on the events. */
+enum {
+    NUFFT3_STAGE_PREP_SOURCES = 0, NUFFT3_STAGE_PREP_TARGETS = 1, NUFFT3_STAGE_PREMULTIPLY = 2, NUFFT3_STAGE_SPREAD = 3,
+    NUFFT3_STAGE_TYPE2 = 4, NUFFT3_STAGE_POSTMULTIPLY = 5, NUFFT3_NUM_STAGES = 6
+};
+int nufft_set_timing3(nufft_plan3* plan, int enable);
+int nufft_get_stage_times3(nufft_plan3* plan, float* ms_out);
+int64_t nufft_sizeof_type3_params(void);
+int64_t nufft_sizeof_info3(void);
+
 /* ---- misc ----------------------------------------------------------------------------- */
 /* sizeof(nufft_params) / sizeof(nufft_info) of the library build: a binding that mirrors the structs by hand
  * (ctypes, Julia) compares them with its own layout before the first call. */

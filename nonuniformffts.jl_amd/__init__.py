@@ -15,10 +15,12 @@ from .plan import (  # noqa: F401
     set_points, set_points_, sort_result, spread_from_points, transform_point_convention,
 )
 from .nfft_interface import NFFTPlan, plan_nfft  # noqa: F401
+from .type3 import PlanNUFFT3, exec_type3, set_points3  # noqa: F401
 
 __all__ = [
     "PlanNUFFT", "NUFFTCallbacks", "PointWeights", "ModeFactors", "HalfSupport", "Direct", "FastApproximation",
     "BackwardsKaiserBesselKernel", "KaiserBesselKernel", "GaussianKernel", "BSplineKernel", "ROCBackend", "DimensionMismatch",
     "set_points", "exec_type1", "exec_type2", "set_points_", "exec_type1_", "exec_type2_",
     "NFFTPlan", "plan_nfft",
+    "PlanNUFFT3", "set_points3", "exec_type3",
 ]

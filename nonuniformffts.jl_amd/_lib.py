@@ -75,6 +75,30 @@ class NufftInfo(C.Structure):
     ]
 
 
+class NufftType3Params(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("sign", C.c_int32),
+        ("source_center", C.c_double * 3), ("source_halfwidth", C.c_double * 3),
+        ("target_center", C.c_double * 3), ("target_halfwidth", C.c_double * 3),
+    ]
+
+
+class NufftInfo3(C.Structure):
+    _fields_ = [
+        ("ndim", C.c_int32), ("ntransforms", C.c_int32), ("dtype", C.c_int32), ("half_support", C.c_int32),
+        ("sign", C.c_int32), ("kernel", C.c_int32), ("evalmode", C.c_int32), ("device", C.c_int32),
+        ("nf", C.c_int64 * 3), ("gamma", C.c_double * 3), ("h", C.c_double * 3),
+        ("source_halfwidth", C.c_double * 3), ("target_halfwidth", C.c_double * 3),
+        ("inner_N_over", C.c_int64 * 3), ("sigma", C.c_double), ("beta", C.c_double * 3),
+        ("spread_method", C.c_int32), ("reserved", C.c_int32),
+        ("num_sources", C.c_int64), ("num_targets", C.c_int64), ("workspace_bytes", C.c_int64),
+    ]
+
+
+NUM_STAGES3 = 6
+STAGE_NAMES3 = ("prep_sources", "prep_targets", "premultiply", "spread", "type2", "postmultiply")
+
+
 #: every symbol include/nufft_mi355x.h declares, with (restype, argtypes)
 _P = C.c_void_p
 _PP = C.POINTER(C.c_void_p)
@@ -112,6 +136,17 @@ SYMBOLS = {
     "nufft_interp_engine_used": (C.c_int, [_P, C.POINTER(C.c_int), _P]),
     "nufft_plan_options": (C.c_char_p, [_P]),
     "nufft_workspace_breakdown": (C.c_int, [_P, C.c_char_p, C.c_int64]),
+    "nufft_plan3_create": (C.c_int, [C.POINTER(_P), C.POINTER(NufftParams), C.POINTER(NufftType3Params)]),
+    "nufft_plan3_destroy": (C.c_int, [_P]),
+    "nufft_plan3_info": (C.c_int, [_P, C.POINTER(NufftInfo3)]),
+    "nufft_set_points3": (C.c_int, [_P, C.c_int64, _PP, C.c_int64, _PP, _P]),
+    "nufft_exec_type3": (C.c_int, [_P, _PP, _PP, _P]),
+    "nufft_type3_points_outside": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
+    "nufft_plan3_internal": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),
+    "nufft_set_timing3": (C.c_int, [_P, C.c_int]),
+    "nufft_get_stage_times3": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "nufft_sizeof_type3_params": (C.c_int64, []),
+    "nufft_sizeof_info3": (C.c_int64, []),
     "nufft_sizeof_params": (C.c_int64, []),
     "nufft_sizeof_info": (C.c_int64, []),
     "nufft_strerror": (C.c_char_p, [C.c_int]),
@@ -138,7 +173,8 @@ def _load():
         fn.restype = res
         fn.argtypes = args
     # the two structs are mirrored by hand above: refuse a library whose layout differs
-    for name, mirror in (("nufft_sizeof_params", NufftParams), ("nufft_sizeof_info", NufftInfo)):
+    for name, mirror in (("nufft_sizeof_params", NufftParams), ("nufft_sizeof_info", NufftInfo),
+                         ("nufft_sizeof_type3_params", NufftType3Params), ("nufft_sizeof_info3", NufftInfo3)):
         if getattr(lib, name)() != C.sizeof(mirror):
             raise ImportError(f"{LIB_PATH}: {name}() = {getattr(lib, name)()} but the ctypes mirror has {C.sizeof(mirror)} bytes "
                               "(include/nufft_mi355x.h and _lib.py disagree)")

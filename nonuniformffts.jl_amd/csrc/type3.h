@@ -1,0 +1,54 @@
+// Launchers of the type-3 streaming kernels (type3_kernels.hip), used by the type-3 plan (type3.cpp).
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+#include "device_common.h"
+
+namespace nufft {
+
+// Sources: y = x - C; rescaled coordinate y / γ folded into [0, 2π) (plan precision), prephase exp(sign i D·y), count of |y_d| > X_d.
+struct T3SourceArgs {
+    int dtype, D;
+    int64_t n;
+    const void* x[3];          // caller's coordinates, T[n]
+    void* xr[3];               // rescaled coordinates, T[n] (plan-owned, 16-byte aligned)
+    void* phase;               // complex<T>[n]
+    unsigned long long* outside;
+    double center[3], halfwidth[3], inv_gamma[3], target_center[3];
+    double sign;
+};
+
+// Targets: t = s - D; θ = sign π t / (σ S) folded into [0, 2π); post factor exp(sign i s·C) Π_d h_d / (ϕ̂_d(γ_d t_d) 2^k_d).
+struct T3TargetArgs {
+    int dtype, D;
+    int64_t n;
+    const void* s[3];
+    void* theta[3];
+    void* post;                // complex<T>[n]
+    unsigned long long* outside;
+    double center[3], halfwidth[3], theta_scale[3], gamma[3], source_center[3];
+    double sign;
+    // ϕ̂ of the spreading plan's window on its grid of nf cells (plan_math.cpp: fourier_coefficients_kernel) at real wavenumbers
+    int kernel, M;
+    double dx[3];              // 2π / nf_d
+    double param[3];           // β (Kaiser-Bessel windows), τ (Gaussian), unused (B-spline)
+    double h_scaled[3];        // h_d 2^-k_d: the deconvolution's normalisation and the window's power-of-two scale
+};
+
+// c'_j = c_j phase_j (premultiply) or f_k *= post_k in place (postmultiply), every component in one launch.
+struct T3MultArgs {
+    int dtype;
+    int64_t n;
+    int ncomp;                 // <= kMaxCompPerLaunch
+    const void* in[kMaxCompPerLaunch];
+    void* out[kMaxCompPerLaunch];
+    const void* factor;        // complex<T>[n]
+};
+
+hipError_t launch_t3_source_prep(const T3SourceArgs& a, int num_cus, hipStream_t stream);
+hipError_t launch_t3_target_prep(const T3TargetArgs& a, int num_cus, hipStream_t stream);
+hipError_t launch_t3_multiply(const T3MultArgs& a, int num_cus, hipStream_t stream);
+
+}  // namespace nufft
