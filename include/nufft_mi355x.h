@@ -277,6 +277,22 @@ int nufft_fft_backward(nufft_plan* plan, void* stream);
 /* interpolate!(::GPU, ...), src/interpolation/gpu.jl:40-118. */
 int nufft_interpolate(nufft_plan* plan, void* const* values_out, void* stream);
 
+/* ---- gradients of type 2 (no reference counterpart) ----------------
+ * The type-2 interpolant v_c(x) = prod(Δx_d) Σ_l g_l φ(x − x_l) and its derivatives ∂_d v_c(x_j) at the plan's points, from the grids
+ * the last backward FFT left: the exact derivative of what nufft_interpolate returns (window derivatives, same grid).
+ *   values_out: C device vectors Z[Np], or NULL (gradients only);  grad_out[c * D + d]: C * D device vectors Z[Np] (caller order).
+ * The outputs have type Z: the gradient of a real plan is real.  Derivatives are taken with respect to the coordinates the caller
+ * passed to nufft_set_points: plans with NUFFT_POINT_TRANSFORM_NFFT (internal point = −2π x, folded) include the factor −2π;
+ * fftshift changes nothing.  A mode-factor callback in force applies as in type 2 (it lives in nufft_deconvolve_pad); a point-weight
+ * callback in force is refused with NUFFT_ERR_UNSUPPORTED.  A host-only plan gives NUFFT_ERR_NO_DEVICE (checked first), a plan
+ * without points NUFFT_ERR_NO_POINTS, a null table or vector NUFFT_ERR_INVALID_ARG; Np = 0 is a no-op.  Like nufft_interpolate the
+ * stage completes a deferred spread first, allocates nothing and does not synchronise (hipGraph-capture safe); it is timed into
+ * NUFFT_STAGE_T2_INTERP and adds no plan memory.  Added after ABI 104 without changing NUFFT_MI355X_VERSION: a caller detects
+ * these two symbols by lookup. */
+int nufft_interpolate_grad(nufft_plan* plan, void* const* values_out, void* const* grad_out, void* stream);
+/* nufft_deconvolve_pad -> nufft_fft_backward -> nufft_interpolate_grad. */
+int nufft_exec_type2_grad(nufft_plan* plan, void* const* values_out, void* const* grad_out, const void* const* uhat_in, void* stream);
+
 /* Adds the side buffer of a deferred spread to `us` if that has not happened yet (no-op otherwise): after it, `us` holds the full
  * spread field as after the reference's spread_from_points! (src/NonuniformFFTs.jl:169-172), also behind nufft_exec_type1. */
 int nufft_complete_grid(nufft_plan* plan, void* stream);

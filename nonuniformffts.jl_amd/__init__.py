@@ -11,11 +11,13 @@ from ._lib import LIB_PATH, lib  # noqa: F401  (fails loudly if the extension is
 from .plan import (  # noqa: F401
     BackwardsKaiserBesselKernel, BSplineKernel, DimensionMismatch, Direct, FastApproximation, GaussianKernel,
     HalfSupport, KaiserBesselKernel, ModeFactors, NUFFTCallbacks, PlanNUFFT, PointWeights, ROCBackend, default_kernel,
-    default_kernel_evalmode, exec_type1, exec_type1_, exec_type2, exec_type2_, interpolate, oversampled_grid,
+    default_kernel_evalmode, exec_type1, exec_type1_, exec_type2, exec_type2_, exec_type2_grad, interpolate, interpolate_grad,
+    oversampled_grid,
     set_points, set_points_, sort_result, spread_from_points, transform_point_convention,
 )
 from .nfft_interface import NFFTPlan, plan_nfft  # noqa: F401
 from .type3 import PlanNUFFT3, exec_type3, set_points3  # noqa: F401
+from . import autograd  # noqa: F401
 
 __all__ = [
     "PlanNUFFT", "NUFFTCallbacks", "PointWeights", "ModeFactors", "HalfSupport", "Direct", "FastApproximation",
@@ -23,4 +25,5 @@ __all__ = [
     "set_points", "exec_type1", "exec_type2", "set_points_", "exec_type1_", "exec_type2_",
     "NFFTPlan", "plan_nfft",
     "PlanNUFFT3", "set_points3", "exec_type3",
+    "exec_type2_grad", "interpolate_grad", "autograd",
 ]

@@ -125,6 +125,8 @@ SYMBOLS = {
     "nufft_deconvolve_pad": (C.c_int, [_P, _PP, _P]),
     "nufft_fft_backward": (C.c_int, [_P, _P]),
     "nufft_interpolate": (C.c_int, [_P, _PP, _P]),
+    "nufft_interpolate_grad": (C.c_int, [_P, _PP, _PP, _P]),
+    "nufft_exec_type2_grad": (C.c_int, [_P, _PP, _PP, _PP, _P]),
     "nufft_complete_grid": (C.c_int, [_P, _P]),
     "nufft_grid_ptr": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(_P), C.POINTER(C.c_int64)]),
     "nufft_copy_grid": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64, _P]),

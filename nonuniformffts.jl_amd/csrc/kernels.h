@@ -177,6 +177,38 @@ hipError_t launch_smarch_halo_add(const TileKernelArgs& a, const SMarchPlan& sp,
 hipError_t launch_smarch_tasks(const Geom& g, const SMarchPlan& sp, const uint32_t* offsets, int64_t np, int cus, double advantage,
                                uint32_t* choice, uint32_t* slots_in_use, uint32_t* colsum, uint32_t* first, uint2* tasktab, hipStream_t stream);
 
+// ---- type-2 gradient gather (interp_grad_kernels.h, interp_grad_*.hip) ---------------------------------------------
+// Walks the sorted records directly (every sort); values (optional) and D derivatives per component in caller order.
+struct GradLaunchArgs {
+    int dtype, is_complex, D, M, C;
+    int kernel, evalmode;      // NUFFT_KERNEL_*, NUFFT_EVAL_*
+    int Nover[3];
+    const void* sorted;        // PointRec<T, D>[np]
+    int64_t np;
+    const void* coefs;         // T[D][npoly][2M]
+    double p0[3], p1[3];       // window parameters per dimension, as TileKernelArgs::beta / beta_over_pi
+    const void* grid;          // C grids, contiguous, Z[Nover...]
+    int64_t grid_stride;       // elements of Z between components
+    void* const* values_out;   // C device vectors Z[np], or null
+    void* const* grad_out;     // C * D device vectors Z[np], grad_out[c * D + d]
+    double prefactor;          // prod(Δx_d)
+    double dscale[3];          // prefactor * dX_d / dx_d
+};
+// which window form a plan's gradient kernels are instantiated for (interp_grad_kernels.h: GradWindow)
+inline int grad_window_select(int kernel, int evalmode) {
+    if (kernel == NUFFT_KERNEL_BACKWARDS_KAISER_BESSEL && evalmode == NUFFT_EVAL_DIRECT) return 0;
+    if (evalmode != NUFFT_EVAL_DIRECT && (kernel == NUFFT_KERNEL_BACKWARDS_KAISER_BESSEL || kernel == NUFFT_KERNEL_KAISER_BESSEL)) return 1;
+    return 2;
+}
+hipError_t launch_interp_grad_f32r(const GradLaunchArgs& a, hipStream_t stream);
+hipError_t launch_interp_grad_f32c(const GradLaunchArgs& a, hipStream_t stream);
+hipError_t launch_interp_grad_f64r(const GradLaunchArgs& a, hipStream_t stream);
+hipError_t launch_interp_grad_f64c(const GradLaunchArgs& a, hipStream_t stream);
+inline hipError_t launch_interp_grad(const GradLaunchArgs& a, hipStream_t stream) {
+    if (a.dtype == NUFFT_F32) return a.is_complex ? launch_interp_grad_f32c(a, stream) : launch_interp_grad_f32r(a, stream);
+    return a.is_complex ? launch_interp_grad_f64c(a, stream) : launch_interp_grad_f64r(a, stream);
+}
+
 // ---- deconvolution (deconv.hip) ------------------------------------------------------------------
 struct DeconvArgs {
     int dtype, D, C;

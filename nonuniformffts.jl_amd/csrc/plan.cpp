@@ -1815,6 +1815,70 @@ int nufft_interpolate(nufft_plan* p, void* const* values_out, void* stream_) {
     return NUFFT_OK;
 }
 
+// Gradient gather (interp_grad_kernels.h): the derivative of what nufft_interpolate computes, from the same grids.
+// the refusals of both gradient entry points, before anything is enqueued
+static int check_grad_args(const nufft_plan* p, void* const* values_out, void* const* grad_out) {
+    int rc = require_points(p);
+    if (rc) return rc;
+    if (p->cb_point_weights) return fail(NUFFT_ERR_UNSUPPORTED, "point-weight callbacks are not supported by the gradient gather");
+    if (!grad_out) return fail(NUFFT_ERR_INVALID_ARG, "null gradient table");
+    for (int c = 0; c < p->C && p->Np > 0; ++c) {
+        if (values_out && !values_out[c]) return fail(NUFFT_ERR_INVALID_ARG, "null output vector");
+        for (int d = 0; d < p->D; ++d)
+            if (!grad_out[c * p->D + d]) return fail(NUFFT_ERR_INVALID_ARG, "null gradient vector");
+    }
+    return NUFFT_OK;
+}
+
+int nufft_interpolate_grad(nufft_plan* p, void* const* values_out, void* const* grad_out, void* stream_) {
+    int rc = check_grad_args(p, values_out, grad_out);
+    if (rc) return rc;
+    DeviceGuard guard(p->device);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    StageTimer tm(p, NUFFT_STAGE_T2_INTERP, stream);
+    note_capture(p, stream);
+    if ((rc = complete_halo(p, stream))) return rc;
+    if (p->Np == 0) return NUFFT_OK;
+    GradLaunchArgs a{};
+    a.dtype = p->dtype;
+    a.is_complex = p->is_complex;
+    a.D = p->D;
+    a.M = p->M;
+    a.C = p->C;
+    a.kernel = p->kernel;
+    a.evalmode = p->evalmode;
+    a.sorted = p->d_sorted;
+    a.np = p->Np;
+    a.coefs = p->d_coefs;
+    a.grid = p->d_us;
+    a.grid_stride = p->grid_elems;
+    a.values_out = values_out;
+    a.grad_out = grad_out;
+    a.prefactor = 1.0;
+    for (int d = 0; d < p->D; ++d) a.prefactor *= 2.0 * M_PI / (double)p->Nover[d];
+    for (int d = 0; d < 3; ++d) {
+        a.Nover[d] = d < p->D ? (int)p->Nover[d] : 1;
+        a.p0[d] = p->eval_p0[d];
+        a.p1[d] = p->beta_over_pi_scaled[d];
+        // r_d = (x / 2π) Ñ_d of the folded internal point; the NFFT convention's internal point is −2π x (folded)
+        const double dxint = p->point_transform == NUFFT_POINT_TRANSFORM_NFFT ? -2.0 * M_PI : 1.0;
+        a.dscale[d] = d < p->D ? a.prefactor * (double)p->Nover[d] / (2.0 * M_PI) * dxint : 0.0;
+    }
+    NUFFT_HIP(launch_interp_grad(a, stream));
+    return NUFFT_OK;
+}
+
+int nufft_exec_type2_grad(nufft_plan* p, void* const* values_out, void* const* grad_out, const void* const* uhat_in, void* stream) {
+    int rc = check_grad_args(p, values_out, grad_out);
+    if (rc) return rc;
+    if (!uhat_in) return fail(NUFFT_ERR_INVALID_ARG, "null input table");
+    for (int c = 0; c < p->C; ++c)
+        if (!uhat_in[c]) return fail(NUFFT_ERR_INVALID_ARG, "null input array");
+    if ((rc = nufft_deconvolve_pad(p, uhat_in, stream))) return rc;
+    if ((rc = nufft_fft_backward(p, stream))) return rc;
+    return nufft_interpolate_grad(p, values_out, grad_out, stream);
+}
+
 int nufft_exec_type1(nufft_plan* p, void* const* uhat_out, const void* const* values_in, void* stream) {
     int rc = require_points(p);
     if (rc) return rc;

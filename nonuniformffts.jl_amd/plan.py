@@ -600,6 +600,50 @@ def exec_type2(vp, p: PlanNUFFT, us, *, callbacks: Optional[NUFFTCallbacks] = No
     return vp
 
 
+def _grad_tables(p: PlanNUFFT, gp, vp):
+    """(values table or None, gradient table, the tensors) for the gradient entry points: ``gp`` is a tuple of D vectors
+    (ntransforms = 1) or a tuple of ntransforms such tuples; ``vp`` as for exec_type2, or None."""
+    if p.ntransforms == 1 and len(gp) == p.ndim and all(isinstance(g, torch.Tensor) for g in gp):
+        gp = (tuple(gp),)
+    gp = tuple(tuple(g) for g in gp)
+    if len(gp) != p.ntransforms:
+        raise DimensionMismatch(f"wrong amount of gradient tuples (expected {p.ntransforms} tuples of {p.ndim} vectors)")
+    for g in gp:
+        if len(g) != p.ndim:
+            raise DimensionMismatch(f"wrong amount of gradient vectors (expected {p.ndim} per component)")
+    for d in range(p.ndim):
+        p._check_nonuniform(tuple(g[d] for g in gp), "gradient outputs")
+    flat = tuple(v for g in gp for v in g)
+    vtbl = None
+    if vp is not None:
+        vp_t = (vp,) if isinstance(vp, torch.Tensor) else tuple(vp)
+        p._check_nonuniform(vp_t, "output values")
+        vtbl = _ptr_table(vp_t)
+    return vtbl, _ptr_table(flat)
+
+
+def exec_type2_grad(gp, p: PlanNUFFT, us, *, vp=None, callbacks: Optional[NUFFTCallbacks] = None):
+    """Type 2 with the gradient of the interpolant at the points: ``gp[c][d] = ∂v_c/∂x_d`` (with respect to the coordinates
+    passed to ``set_points``), and optionally the values ``vp`` themselves: deconvolve + pad, one backward FFT and one gather
+    with window derivatives (measured at C2: about 3x a value-only type 2).  ``gp``: a tuple of D vectors of type Z
+    (a tuple of ntransforms such tuples for several transforms).  A ``ModeFactors`` callback applies as in exec_type2;
+    ``PointWeights`` is refused.  Returns ``gp``."""
+    p._require_gpu()
+    us_t = (us,) if isinstance(us, torch.Tensor) else tuple(us)
+    p._check_uniform(us_t)
+    vtbl, gtbl = _grad_tables(p, gp, vp)
+    if callbacks is not None and (callbacks.nonuniform is not None or callbacks.uniform is not None):
+        cb = callbacks._struct(p, p.num_points)
+        _check(lib.nufft_set_callbacks(p._handle, C.byref(cb)))
+        try:
+            _check(lib.nufft_exec_type2_grad(p._handle, vtbl, gtbl, _ptr_table(us_t), p._stream()))
+        finally:
+            lib.nufft_set_callbacks(p._handle, None)
+    else:
+        _check(lib.nufft_exec_type2_grad(p._handle, vtbl, gtbl, _ptr_table(us_t), p._stream()))
+    return gp
+
+
 set_points_ = set_points
 exec_type1_ = exec_type1
 exec_type2_ = exec_type2
@@ -622,6 +666,14 @@ def interpolate(p: PlanNUFFT, vp):
     p._check_nonuniform(vp_t, "output values")
     _check(lib.nufft_interpolate(p._handle, _ptr_table(vp_t), p._stream()))
     return vp
+
+
+def interpolate_grad(p: PlanNUFFT, gp, vp=None):
+    """The gradient gather alone, from the plan's oversampled grids (what the last backward FFT left): see exec_type2_grad."""
+    p._require_gpu()
+    vtbl, gtbl = _grad_tables(p, gp, vp)
+    _check(lib.nufft_interpolate_grad(p._handle, vtbl, gtbl, p._stream()))
+    return gp
 
 
 def oversampled_grid(p: PlanNUFFT, component: int = 0, spectrum: bool = False) -> torch.Tensor:
