@@ -391,6 +391,22 @@ int nufft_set_points3(nufft_plan3* plan, int64_t num_sources, const void* const*
                       void* stream);
 /* f_out[c]: device vector complex(T)[num_targets]; c_in[c]: device vector complex(T)[num_sources], c < ntransforms. */
 int nufft_exec_type3(nufft_plan3* plan, void* const* f_out, const void* const* c_in, void* stream);
+/* ---- gradient of type 3 with respect to the targets ----
+ * f_out[c]: complex(T)[num_targets], required (the derivative needs the values);
+ * grad_out[c * D + d]: complex(T)[num_targets] = ∂f_c/∂s_d with respect to the caller's target coordinates.
+ * Premultiply and spread as nufft_exec_type3, the inner plan's nufft_exec_type2_grad straight into f_out / grad_out, then one kernel in
+ * place: ∂f/∂s_d = P(s) [sign γ_d h_d ∂v/∂θ_d + (sign i C_d − ρ_d(t_d)) v(θ)], P the per-target factor, ρ_d = γ_d (d ln ϕ̂_d/dk)(γ_d t_d).
+ * t = s − D is recovered from the stored θ (no new per-target table): exact for targets inside the box, except that at σ = 1 a target at
+ * exactly |t_d| = S_d is ambiguous (t = +S reads back as −S).  Refusals as nufft_exec_type3, all before anything is enqueued: a host-only
+ * plan NUFFT_ERR_NO_DEVICE, no points NUFFT_ERR_NO_POINTS, a null table or vector NUFFT_ERR_INVALID_ARG.  num_targets = 0 is a no-op;
+ * num_sources = 0 writes zeros to the values and the gradients.  Allocates nothing, does not synchronise (hipGraph-capture safe); timed
+ * into NUFFT3_STAGE_TYPE2 (the inner gradient) and NUFFT3_STAGE_POSTMULTIPLY (the finish).  Added after ABI 104 without changing
+ * NUFFT_MI355X_VERSION: detect it by symbol.
+ * Gradients with respect to the sources need no entry point of their own.  For L = Re Σ_k conj(G_k) f_k, let u(x) = Σ_k G_k
+ * exp(−sign i s_k·x): then ∂L/∂c_j (conjugate-Wirtinger) = u(x_j) and ∂L/∂x_{j,d} = Re(c_j conj(∂_d u(x_j))).  u is the type 3 of the
+ * adjoint plan — sign −sign, the two boxes swapped, sources s_k with values G_k, targets x_j — and one nufft_exec_type3_grad on that plan
+ * returns u and ∂_d u together. */
+int nufft_exec_type3_grad(nufft_plan3* plan, void* const* f_out, void* const* grad_out, const void* const* c_in, void* stream);
 /* Sources / targets of the last nufft_set_points3 outside the declared boxes (|x_d - C_d| > X_d in some dimension, with the caller's
  * half-widths).  Synchronises `stream`. */
 int nufft_type3_points_outside(nufft_plan3* plan, int64_t* sources_out, int64_t* targets_out, void* stream);

@@ -16,7 +16,7 @@ from .plan import (  # noqa: F401
     set_points, set_points_, sort_result, spread_from_points, transform_point_convention,
 )
 from .nfft_interface import NFFTPlan, plan_nfft  # noqa: F401
-from .type3 import PlanNUFFT3, exec_type3, set_points3  # noqa: F401
+from .type3 import PlanNUFFT3, exec_type3, exec_type3_grad, set_points3  # noqa: F401
 from . import autograd  # noqa: F401
 
 __all__ = [
@@ -24,6 +24,6 @@ __all__ = [
     "BackwardsKaiserBesselKernel", "KaiserBesselKernel", "GaussianKernel", "BSplineKernel", "ROCBackend", "DimensionMismatch",
     "set_points", "exec_type1", "exec_type2", "set_points_", "exec_type1_", "exec_type2_",
     "NFFTPlan", "plan_nfft",
-    "PlanNUFFT3", "set_points3", "exec_type3",
+    "PlanNUFFT3", "set_points3", "exec_type3", "exec_type3_grad",
     "exec_type2_grad", "interpolate_grad", "autograd",
 ]

@@ -143,6 +143,7 @@ SYMBOLS = {
     "nufft_plan3_info": (C.c_int, [_P, C.POINTER(NufftInfo3)]),
     "nufft_set_points3": (C.c_int, [_P, C.c_int64, _PP, C.c_int64, _PP, _P]),
     "nufft_exec_type3": (C.c_int, [_P, _PP, _PP, _P]),
+    "nufft_exec_type3_grad": (C.c_int, [_P, _PP, _PP, _PP, _P]),
     "nufft_type3_points_outside": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
     "nufft_plan3_internal": (C.c_int, [_P, C.c_int, C.POINTER(_P)]),
     "nufft_set_timing3": (C.c_int, [_P, C.c_int]),

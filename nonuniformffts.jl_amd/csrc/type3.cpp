@@ -163,6 +163,39 @@ int64_t fine_grid(double sigma, int M, double X, double S) {
     return n <= ((int64_t)1 << 30) ? n : 0;
 }
 
+// The stages exec_type3 and exec_type3_grad share: premultiply c' = c · phase, then the completing spread of c'; `us` receives the
+// spread grid of every component (the type-2 plan's input spectrum).
+int prephase_and_spread(nufft_plan3* p, const void* const* c_in, std::vector<const void*>& us, hipStream_t stream) {
+    const size_t cb = 2 * real_bytes(p);
+    std::vector<const void*> cv(p->C);
+    for (int c = 0; c < p->C; ++c) cv[c] = static_cast<char*>(p->d_cvals) + (size_t)c * p->Np * cb;
+    {
+        Timer tm(p, NUFFT3_STAGE_PREMULTIPLY, stream);
+        for (int c0 = 0; c0 < p->C; c0 += nufft::kMaxCompPerLaunch) {
+            nufft::T3MultArgs m{};
+            m.dtype = p->dtype;
+            m.n = p->Np;
+            m.ncomp = std::min(nufft::kMaxCompPerLaunch, p->C - c0);
+            m.factor = p->d_phase;
+            for (int i = 0; i < m.ncomp; ++i) { m.in[i] = c_in[c0 + i]; m.out[i] = const_cast<void*>(cv[c0 + i]); }
+            T3_HIP(nufft::launch_t3_multiply(m, p->num_cus, stream));
+        }
+    }
+    int rc;
+    {
+        Timer tm(p, NUFFT3_STAGE_SPREAD, stream);
+        // the completing spread: `us` holds the whole field (the halo variant's side buffer added) before the type-2 plan reads it
+        if ((rc = nufft_spread(p->sp, cv.data(), stream))) return rc;
+    }
+    us.assign(p->C, nullptr);
+    for (int c = 0; c < p->C; ++c) {
+        void* ptr = nullptr;
+        if ((rc = nufft_grid_ptr(p->sp, 0, c, &ptr, nullptr))) return rc;
+        us[c] = ptr;
+    }
+    return NUFFT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -461,32 +494,9 @@ int nufft_exec_type3(nufft_plan3* p, void* const* f_out, const void* const* c_in
         for (int c = 0; c < p->C; ++c) T3_HIP(hipMemsetAsync(f_out[c], 0, (size_t)p->Nk * cb, stream));
         return NUFFT_OK;
     }
-    std::vector<const void*> cv(p->C);
-    for (int c = 0; c < p->C; ++c) cv[c] = static_cast<char*>(p->d_cvals) + (size_t)c * p->Np * cb;
-    {
-        Timer tm(p, NUFFT3_STAGE_PREMULTIPLY, stream);
-        for (int c0 = 0; c0 < p->C; c0 += nufft::kMaxCompPerLaunch) {
-            nufft::T3MultArgs m{};
-            m.dtype = p->dtype;
-            m.n = p->Np;
-            m.ncomp = std::min(nufft::kMaxCompPerLaunch, p->C - c0);
-            m.factor = p->d_phase;
-            for (int i = 0; i < m.ncomp; ++i) { m.in[i] = c_in[c0 + i]; m.out[i] = const_cast<void*>(cv[c0 + i]); }
-            T3_HIP(nufft::launch_t3_multiply(m, p->num_cus, stream));
-        }
-    }
-    int rc;
-    {
-        Timer tm(p, NUFFT3_STAGE_SPREAD, stream);
-        // the completing spread: `us` holds the whole field (the halo variant's side buffer added) before the type-2 plan reads it
-        if ((rc = nufft_spread(p->sp, cv.data(), stream))) return rc;
-    }
-    std::vector<const void*> us(p->C);
-    for (int c = 0; c < p->C; ++c) {
-        void* ptr = nullptr;
-        if ((rc = nufft_grid_ptr(p->sp, 0, c, &ptr, nullptr))) return rc;
-        us[c] = ptr;
-    }
+    std::vector<const void*> us;
+    int rc = prephase_and_spread(p, c_in, us, stream);
+    if (rc) return rc;
     {
         Timer tm(p, NUFFT3_STAGE_TYPE2, stream);
         if ((rc = nufft_exec_type2(p->t2, f_out, us.data(), stream))) return rc;
@@ -501,6 +511,67 @@ int nufft_exec_type3(nufft_plan3* p, void* const* f_out, const void* const* c_in
             m.factor = p->d_post;
             for (int i = 0; i < m.ncomp; ++i) { m.in[i] = f_out[c0 + i]; m.out[i] = f_out[c0 + i]; }
             T3_HIP(nufft::launch_t3_multiply(m, p->num_cus, stream));
+        }
+    }
+    return NUFFT_OK;
+}
+
+// Gradient with respect to the targets: the same premultiply and spread, the inner type-2 gradient straight into
+// the caller's vectors, then the finish kernel in place (f = P v, ∂f/∂s_d from ∂v/∂θ_d, v and the window's ln-derivative).
+int nufft_exec_type3_grad(nufft_plan3* p, void* const* f_out, void* const* grad_out, const void* const* c_in, void* stream_) {
+    if (!p) return fail(NUFFT_ERR_INVALID_ARG, "null plan");
+    if (p->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only plan (device = -1)");
+    if (p->Np < 0 || p->Nk < 0) return fail(NUFFT_ERR_NO_POINTS, "nufft_set_points3 must be called before nufft_exec_type3_grad");
+    if (p->Nk == 0) return NUFFT_OK;
+    if (!f_out || !grad_out || (p->Np > 0 && !c_in)) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    for (int c = 0; c < p->C; ++c) {
+        if (!f_out[c] || (p->Np > 0 && !c_in[c])) return fail(NUFFT_ERR_INVALID_ARG, "null data vector");
+        for (int d = 0; d < p->D; ++d)
+            if (!grad_out[c * p->D + d]) return fail(NUFFT_ERR_INVALID_ARG, "null gradient vector");
+    }
+    DeviceGuard guard(p->device);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const size_t cb = 2 * real_bytes(p);
+    if (p->Np == 0) {
+        for (int c = 0; c < p->C; ++c) {
+            T3_HIP(hipMemsetAsync(f_out[c], 0, (size_t)p->Nk * cb, stream));
+            for (int d = 0; d < p->D; ++d) T3_HIP(hipMemsetAsync(grad_out[c * p->D + d], 0, (size_t)p->Nk * cb, stream));
+        }
+        return NUFFT_OK;
+    }
+    std::vector<const void*> us;
+    int rc = prephase_and_spread(p, c_in, us, stream);
+    if (rc) return rc;
+    {
+        Timer tm(p, NUFFT3_STAGE_TYPE2, stream);
+        if ((rc = nufft_exec_type2_grad(p->t2, f_out, grad_out, us.data(), stream))) return rc;
+    }
+    {
+        Timer tm(p, NUFFT3_STAGE_POSTMULTIPLY, stream);
+        const size_t rb = real_bytes(p);
+        for (int c0 = 0; c0 < p->C; c0 += nufft::kMaxCompPerLaunch) {
+            nufft::T3GradArgs g{};
+            g.dtype = p->dtype;
+            g.D = p->D;
+            g.n = p->Nk;
+            g.ncomp = std::min(nufft::kMaxCompPerLaunch, p->C - c0);
+            g.post = p->d_post;
+            g.sign = (double)p->sign;
+            g.kernel = p->kernel;
+            g.M = p->M;
+            for (int d = 0; d < p->D; ++d) {
+                g.theta[d] = static_cast<const char*>(p->d_theta) + (size_t)d * p->Nk * rb;
+                g.theta_scale[d] = (double)p->sign * p->gamma[d] * p->h[d];      // as nufft_set_points3 forms θ
+                g.gamma[d] = p->gamma[d];
+                g.source_center[d] = p->src_c[d];
+                g.dx[d] = p->h[d];
+                g.param[d] = p->kernel == NUFFT_KERNEL_GAUSSIAN ? p->sp->tau[d] : p->sp->beta[d];
+            }
+            for (int i = 0; i < g.ncomp; ++i) {
+                g.f[i] = f_out[c0 + i];
+                for (int d = 0; d < p->D; ++d) g.grad[i][d] = grad_out[(c0 + i) * p->D + d];
+            }
+            T3_HIP(nufft::launch_t3_grad_finish(g, p->num_cus, stream));
         }
     }
     return NUFFT_OK;

@@ -47,8 +47,28 @@ struct T3MultArgs {
     const void* factor;        // complex<T>[n]
 };
 
+// Finish of the type-3 gradient, in place: f[c] holds v_c and grad[c][d] holds ∂v_c/∂θ_d (the inner type-2
+// gradient at θ) on entry; on exit f[c] = P v_c and grad[c][d] = ∂f_c/∂s_d = P [sign γ_d h_d ∂v_c/∂θ_d + (sign i C_d − ρ_d) v_c],
+// ρ_d = γ_d (d ln ϕ̂_d / dk)(γ_d t_d).  t_d = r / (sign γ_d h_d), r = θ_d if θ_d <= π else θ_d − 2π: the fold is invertible for targets
+// inside the box (|sign γ h t| = π |t| / (σ S) <= π / σ <= π); at σ = 1 exactly, |t| = S is ambiguous (t = S reads back as −S).
+struct T3GradArgs {
+    int dtype, D;
+    int64_t n;
+    int ncomp;                 // <= kMaxCompPerLaunch
+    const void* theta[3];      // T[n]: the type-2 plan's points (set_points3)
+    const void* post;          // complex<T>[n]: post factor P (set_points3)
+    void* f[kMaxCompPerLaunch];            // complex<T>[n]
+    void* grad[kMaxCompPerLaunch][3];      // complex<T>[n]
+    double theta_scale[3];     // sign γ_d h_d
+    double gamma[3], source_center[3];
+    double sign;
+    int kernel, M;             // ϕ̂ of the spreading plan's window, as T3TargetArgs
+    double dx[3], param[3];
+};
+
 hipError_t launch_t3_source_prep(const T3SourceArgs& a, int num_cus, hipStream_t stream);
 hipError_t launch_t3_target_prep(const T3TargetArgs& a, int num_cus, hipStream_t stream);
 hipError_t launch_t3_multiply(const T3MultArgs& a, int num_cus, hipStream_t stream);
+hipError_t launch_t3_grad_finish(const T3GradArgs& a, int num_cus, hipStream_t stream);
 
 }  // namespace nufft

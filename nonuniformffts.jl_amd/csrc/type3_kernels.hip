@@ -1,7 +1,8 @@
-// Streaming kernels of the type-3 transform (type3.cpp): source preparation, target preparation, and the
-// complex multiply that prephases the values before the spread and corrects the targets after the type-2 stage.
+// Streaming kernels of the type-3 transform (type3.cpp): source preparation, target preparation, the
+// complex multiply that prephases the values before the spread and corrects the targets after the type-2 stage, and the finish of
+// the type-3 gradient.
 //
-// All four are HBM-bound: every thread moves whole 16-byte packs (2 Float64 / 4 Float32 coordinates, 1 ComplexF64 / 2 ComplexF32
+// All of them are HBM-bound (the target prep and the gradient finish are bound by their FP64 window terms): every thread moves whole 16-byte packs (2 Float64 / 4 Float32 coordinates, 1 ComplexF64 / 2 ComplexF32
 // values) with global_load_dwordx4 / global_store_dwordx4; a pack that runs past the end (or an unaligned caller array) takes the
 // scalar path.  Grid-stride loops over a grid sized to the device.  Phase arguments and rescaled coordinates are formed in Float64
 // from the caller's values (s·C reaches 1e5 rad with ordinary centres, where a Float32 sincos alone is off by 1e-2); the results
@@ -78,6 +79,66 @@ __device__ double phihat_dev(int kernel, int M, double dx, double param, double 
     double r = 1.0;
     for (int i = 0; i < 2 * M; ++i) r *= sn;
     return r * dx;
+}
+
+// Σ_n 2n/(2n+1)! z^(n−1) over Σ_n z^n/(2n+1)!: (s coth s − 1)/s² at z = s², (1 − u cot u)/u² at z = −u² (both → 1/3 at z → 0).
+__device__ __forceinline__ double kb_dlog_series(double z) {
+    double num = 0.0, den = 1.0, fac = 1.0, zn = 1.0;     // fac = (2n+1)!, zn = z^(n−1), then z^n
+    for (int n = 1; n < 12; ++n) {
+        fac *= (2.0 * n) * (2.0 * n + 1.0);
+        num += 2.0 * n / fac * zn;
+        zn *= z;
+        den += zn / fac;
+    }
+    return num / den;
+}
+
+// d ln ϕ̂ / dk of phihat_dev at the same arguments.  Past the Kaiser-Bessel band and past the sinc zeros of
+// the B-spline (targets outside the declared box) the value is finite and undefined, as ϕ̂ is there.
+__device__ __forceinline__ double dlogphihat_dev(int kernel, int M, double dx, double param, double k) {
+    if (kernel == NUFFT_KERNEL_BACKWARDS_KAISER_BESSEL || kernel == NUFFT_KERNEL_KAISER_BESSEL) {
+        const double w = M * dx, q = w * k;
+        const double z = param * param - q * q;
+        double r;                                          // d ln ϕ̂ / dk = −w² k r
+        if (kernel == NUFFT_KERNEL_BACKWARDS_KAISER_BESSEL) {
+            if (z < -625.0) {                              // u > 25: J0, J1 asymptotics (as bessel_j0_dev)
+                const double u = sqrt(-z);
+                r = cos(u - 0.75 * kPi) / (u * cos(u - 0.25 * kPi));
+            } else {                                       // I1(√z) / (√z I0(√z)) = ½ Σ q^n/(n!(n+1)!) / Σ q^n/(n!)², q = z/4
+                const double qq = 0.25 * z;
+                double t0 = 1.0, t1 = 0.5, s0 = 1.0, s1 = 0.5;
+                for (int n = 1; n < 500; ++n) {
+                    t0 *= qq / ((double)n * (double)n);
+                    t1 *= qq / ((double)n * (double)(n + 1));
+                    s0 += t0;
+                    s1 += t1;
+                    if (fabs(t0) < 1e-17 * fabs(s0) && fabs(t1) < 1e-17 * fabs(s1)) break;
+                }
+                r = s1 / s0;
+            }
+        } else if (fabs(z) < 1.0) {
+            r = kb_dlog_series(z);
+        } else if (z > 0.0) {
+            const double s = sqrt(z);
+            r = (s / tanh(s) - 1.0) / z;
+        } else {
+            const double u = sqrt(-z);
+            r = (1.0 - u * cos(u) / sin(u)) / (-z);
+        }
+        const double out = -w * w * k * r;
+        return isfinite(out) ? out : 0.0;
+    }
+    if (kernel == NUFFT_KERNEL_GAUSSIAN) return -0.5 * param * k;
+    const double a = k * dx * 0.5;                         // 2M (dx/2) (cot a − 1/a)
+    double g;
+    if (fabs(a) < 1e-3) {
+        const double a2 = a * a;
+        g = -a * (1.0 / 3.0 + a2 * (1.0 / 45.0 + a2 * (2.0 / 945.0)));
+    } else {
+        g = cos(a) / sin(a) - 1.0 / a;
+    }
+    const double out = M * dx * g;
+    return isfinite(out) ? out : 0.0;
 }
 
 template <typename T, int D>
@@ -226,6 +287,90 @@ __global__ __launch_bounds__(kThreads) void t3_multiply_kernel(T3MultArgs a, int
     }
 }
 
+// Finish of the type-3 gradient, in place on the outputs of the inner type-2 gradient (component c = blockIdx.y): v_c -> f_c = P v_c,
+// ∂_θd v_c -> ∂f_c/∂s_d = P [sign γ_d h_d ∂_θd v_c + (sign i C_d − ρ_d(t_d)) v_c] with ρ_d = γ_d (d ln ϕ̂_d / dk)(γ_d t_d).  t_d comes
+// back from the stored θ (r = θ or θ − 2π, t = r / (sign γ_d h_d)): no per-target table beyond the ones set_points3 wrote.
+template <typename T, int D, int K>     // K: the window (a.kernel), a template parameter so that one branch of dlogphihat_dev is inlined
+__global__ __launch_bounds__(kThreads) void t3_grad_finish_kernel(T3GradArgs a, int vec_theta, int vec_io) {
+    constexpr int W = Pack<T>::W;          // targets per thread: one pack of θ per dimension, two packs of each complex vector
+    const int c = blockIdx.y;
+    T* fv = static_cast<T*>(a.f[c]);
+    T* gv[D];
+#pragma unroll
+    for (int d = 0; d < D; ++d) gv[d] = static_cast<T*>(a.grad[c][d]);
+    const T* post = static_cast<const T*>(a.post);
+    const int64_t nchunks = (a.n + W - 1) / W;
+    for (int64_t q = (int64_t)blockIdx.x * kThreads + threadIdx.x; q < nchunks; q += (int64_t)gridDim.x * kThreads) {
+        const int64_t i0 = q * W;
+        const bool full = i0 + W <= a.n;
+        T th[D][W];
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            const T* x = static_cast<const T*>(a.theta[d]);
+            if (full && vec_theta) {
+                const Pack<T> pk = *reinterpret_cast<const Pack<T>*>(x + i0);
+#pragma unroll
+                for (int w = 0; w < W; ++w) th[d][w] = pk.v[w];
+            } else {
+#pragma unroll
+                for (int w = 0; w < W; ++w) th[d][w] = i0 + w < a.n ? x[i0 + w] : (T)0;
+            }
+        }
+        Pack<T> pf[2], vv[2], gg[D][2];
+        if (full && vec_io) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                pf[h] = reinterpret_cast<const Pack<T>*>(post + 2 * i0)[h];
+                vv[h] = reinterpret_cast<const Pack<T>*>(fv + 2 * i0)[h];
+#pragma unroll
+                for (int d = 0; d < D; ++d) gg[d][h] = reinterpret_cast<const Pack<T>*>(gv[d] + 2 * i0)[h];
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 2 * W; ++e) {
+                const bool in = i0 + e / 2 < a.n;
+                pf[e / W].v[e % W] = in ? post[2 * i0 + e] : (T)0;
+                vv[e / W].v[e % W] = in ? fv[2 * i0 + e] : (T)0;
+#pragma unroll
+                for (int d = 0; d < D; ++d) gg[d][e / W].v[e % W] = in ? gv[d][2 * i0 + e] : (T)0;
+            }
+        }
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+            const int h = (2 * w) / W, e = (2 * w) % W;
+            const double pr = (double)pf[h].v[e], pi = (double)pf[h].v[e + 1];
+            const double vr = (double)vv[h].v[e], vi = (double)vv[h].v[e + 1];
+            vv[h].v[e] = (T)(pr * vr - pi * vi);
+            vv[h].v[e + 1] = (T)(pr * vi + pi * vr);
+#pragma unroll
+            for (int d = 0; d < D; ++d) {
+                const double theta = (double)th[d][w];
+                const double t = (theta <= kPi ? theta : theta - kTwoPi) / a.theta_scale[d];
+                const double rho = a.gamma[d] * dlogphihat_dev(K, a.M, a.dx[d], a.param[d], a.gamma[d] * t);
+                const double sc = a.sign * a.source_center[d];
+                const double xr = a.theta_scale[d] * (double)gg[d][h].v[e] - rho * vr - sc * vi;
+                const double xi = a.theta_scale[d] * (double)gg[d][h].v[e + 1] - rho * vi + sc * vr;
+                gg[d][h].v[e] = (T)(pr * xr - pi * xi);
+                gg[d][h].v[e + 1] = (T)(pr * xi + pi * xr);
+            }
+        }
+        if (full && vec_io) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                reinterpret_cast<Pack<T>*>(fv + 2 * i0)[h] = vv[h];
+#pragma unroll
+                for (int d = 0; d < D; ++d) reinterpret_cast<Pack<T>*>(gv[d] + 2 * i0)[h] = gg[d][h];
+            }
+        } else {
+            for (int e = 0; e < 2 * W && i0 + e / 2 < a.n; ++e) {
+                fv[2 * i0 + e] = vv[e / W].v[e % W];
+#pragma unroll
+                for (int d = 0; d < D; ++d) gv[d][2 * i0 + e] = gg[d][e / W].v[e % W];
+            }
+        }
+    }
+}
+
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 unsigned grid_for(int64_t chunks, int num_cus) {
@@ -288,6 +433,55 @@ hipError_t launch_t3_multiply(const T3MultArgs& a, int num_cus, hipStream_t stre
     const dim3 grid(grid_for((a.n + W - 1) / W, std::max(1, num_cus / a.ncomp)), a.ncomp), block(kThreads);
     if (a.dtype == NUFFT_F32) hipLaunchKernelGGL((t3_multiply_kernel<float>), grid, block, 0, stream, a, vec);
     else hipLaunchKernelGGL((t3_multiply_kernel<double>), grid, block, 0, stream, a, vec);
+    return hipGetLastError();
+}
+
+namespace {
+
+template <typename T, int D>
+void launch_grad_finish_t(const T3GradArgs& a, dim3 grid, hipStream_t stream, int vec_theta, int vec_io) {
+    const dim3 block(kThreads);
+    switch (a.kernel) {
+        case NUFFT_KERNEL_BACKWARDS_KAISER_BESSEL:
+            hipLaunchKernelGGL((t3_grad_finish_kernel<T, D, NUFFT_KERNEL_BACKWARDS_KAISER_BESSEL>), grid, block, 0, stream, a, vec_theta, vec_io);
+            break;
+        case NUFFT_KERNEL_KAISER_BESSEL:
+            hipLaunchKernelGGL((t3_grad_finish_kernel<T, D, NUFFT_KERNEL_KAISER_BESSEL>), grid, block, 0, stream, a, vec_theta, vec_io);
+            break;
+        case NUFFT_KERNEL_GAUSSIAN:
+            hipLaunchKernelGGL((t3_grad_finish_kernel<T, D, NUFFT_KERNEL_GAUSSIAN>), grid, block, 0, stream, a, vec_theta, vec_io);
+            break;
+        default:
+            hipLaunchKernelGGL((t3_grad_finish_kernel<T, D, NUFFT_KERNEL_BSPLINE>), grid, block, 0, stream, a, vec_theta, vec_io);
+            break;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_t3_grad_finish(const T3GradArgs& a, int num_cus, hipStream_t stream) {
+    if (a.n <= 0 || a.ncomp <= 0) return hipSuccess;
+    int vec_theta = 1, vec_io = aligned16(a.post);
+    for (int d = 0; d < a.D; ++d) vec_theta &= aligned16(a.theta[d]);
+    for (int c = 0; c < a.ncomp; ++c) {
+        vec_io &= aligned16(a.f[c]) ? 1 : 0;
+        for (int d = 0; d < a.D; ++d) vec_io &= aligned16(a.grad[c][d]) ? 1 : 0;
+    }
+    const int W = a.dtype == NUFFT_F32 ? 4 : 2;
+    const dim3 grid(grid_for((a.n + W - 1) / W, std::max(1, num_cus / a.ncomp)), a.ncomp);
+    if (a.dtype == NUFFT_F32) {
+        switch (a.D) {
+            case 1: launch_grad_finish_t<float, 1>(a, grid, stream, vec_theta, vec_io); break;
+            case 2: launch_grad_finish_t<float, 2>(a, grid, stream, vec_theta, vec_io); break;
+            default: launch_grad_finish_t<float, 3>(a, grid, stream, vec_theta, vec_io); break;
+        }
+    } else {
+        switch (a.D) {
+            case 1: launch_grad_finish_t<double, 1>(a, grid, stream, vec_theta, vec_io); break;
+            case 2: launch_grad_finish_t<double, 2>(a, grid, stream, vec_theta, vec_io); break;
+            default: launch_grad_finish_t<double, 3>(a, grid, stream, vec_theta, vec_io); break;
+        }
+    }
     return hipGetLastError();
 }
 

@@ -74,6 +74,8 @@ class PlanNUFFT3:
         self.kernel_evalmode = kernel_evalmode
         self.backend = backend
         self.sign = int(sign)
+        self._M, self._sigma = M, float(sigma)
+        self._adjoint_plan = None
         self._ndim = int(ndim)
         self._ntransforms = int(ntransforms)
         self._sources = self._targets = None
@@ -103,15 +105,18 @@ class PlanNUFFT3:
             self.device = torch.device("cuda", int(dev))
         opts = {k: v for k, v in os.environ.items() if k.startswith("NUFFT_") and k not in _HARNESS_ENV and v != ""}
         opts.update({str(k): str(v) for k, v in (options or {}).items()})
+        self._options = opts
         self._options_text = ";".join(f"{k}={v}" for k, v in sorted(opts.items())).encode()
         prm.options = self._options_text if opts else None
 
         t3 = _lib.NufftType3Params()
         t3.struct_size = C.sizeof(_lib.NufftType3Params)
         t3.sign = self.sign
+        self._source_bounds = source_bounds if source_bounds is not None else [(-math.pi, math.pi)] * self._ndim
+        self._target_bounds = target_bounds if target_bounds is not None else [(-1.0, 1.0)] * self._ndim
         if 1 <= self._ndim <= 3:
-            sc, sw = _bounds(source_bounds if source_bounds is not None else [(-math.pi, math.pi)] * self._ndim, self._ndim, "source_bounds")
-            tc, tw = _bounds(target_bounds if target_bounds is not None else [(-1.0, 1.0)] * self._ndim, self._ndim, "target_bounds")
+            sc, sw = _bounds(self._source_bounds, self._ndim, "source_bounds")
+            tc, tw = _bounds(self._target_bounds, self._ndim, "target_bounds")
             for d in range(self._ndim):
                 t3.source_center[d], t3.source_halfwidth[d] = sc[d], sw[d]
                 t3.target_center[d], t3.target_halfwidth[d] = tc[d], tw[d]
@@ -138,6 +143,16 @@ class PlanNUFFT3:
             return out
 
         return cls(Z, len(xs), source_bounds=box(xs), target_bounds=box(ss), **kwargs)
+
+    def adjoint(self) -> "PlanNUFFT3":
+        """A new plan of the adjoint transform ``u(x) = Σ_k G_k exp(−sign i s_k · x)``: the same element type, dimension, M, σ,
+        kernel, evaluation mode, ntransforms, backend and options, with ``sign = −sign`` and the source and target boxes swapped
+        (its sources are this plan's targets).  Its fine grid ``nf`` equals this plan's (the rule depends on the product of the
+        half-widths).  Its type 3 applied to ``G`` is the gradient of ``Re Σ_k conj(G_k) f_k`` with respect to the values, and its
+        ``exec_type3_grad`` the one with respect to the sources.  The new plan owns its own grids."""
+        return PlanNUFFT3(self.Z, self._ndim, m=self._M, sigma=self._sigma, kernel=self.kernel, kernel_evalmode=self.kernel_evalmode,
+                          ntransforms=self._ntransforms, sign=-self.sign, backend=self.backend,
+                          source_bounds=self._target_bounds, target_bounds=self._source_bounds, options=self._options)
 
     def close(self):
         h = getattr(self, "_handle", None)
@@ -306,3 +321,36 @@ def exec_type3(f, p: PlanNUFFT3, c):
     _check_vectors(p, c_t, p._sources[0].numel(), "input")
     _check(lib.nufft_exec_type3(p._handle, _ptr_table(f_t), _ptr_table(c_t), p._stream()))
     return f
+
+
+def _grad_table(p: PlanNUFFT3, gp, n: int):
+    """``gp``: a tuple of D vectors (ntransforms = 1) or a tuple of ntransforms such tuples -> (nested tuple, flat table)."""
+    if p.ntransforms == 1 and len(gp) == p.ndim and all(isinstance(g, torch.Tensor) for g in gp):
+        gp = (tuple(gp),)
+    gp = tuple(tuple(g) for g in gp)
+    if len(gp) != p.ntransforms:
+        raise DimensionMismatch(f"wrong amount of gradient tuples (expected {p.ntransforms} tuples of {p.ndim} vectors)")
+    for g in gp:
+        if len(g) != p.ndim:
+            raise DimensionMismatch(f"wrong amount of gradient vectors (expected {p.ndim} per component)")
+    for d in range(p.ndim):
+        _check_vectors(p, tuple(g[d] for g in gp), n, "gradient output")
+    return _ptr_table(tuple(v for g in gp for v in g))
+
+
+def exec_type3_grad(f, gp, p: PlanNUFFT3, c):
+    """exec_type3 with the derivatives with respect to the targets: ``gp[c][d] = ∂f_c/∂s_d`` at every target (same sizes and
+    element type as ``f``), from one premultiply and spread, the inner type-2 gradient and one finishing kernel.
+    ``gp``: a tuple of D vectors, or a tuple of ntransforms such tuples.  Derivatives with respect to the sources come from the
+    ``adjoint()`` plan.  Returns ``(f, gp)``."""
+    p._require_gpu()
+    if p._sources is None:
+        raise ValueError("set_points3 must be called before exec_type3_grad")
+    f_t = (f,) if isinstance(f, torch.Tensor) else tuple(f)
+    c_t = (c,) if isinstance(c, torch.Tensor) else tuple(c)
+    nk = p._targets[0].numel()
+    _check_vectors(p, f_t, nk, "output")
+    _check_vectors(p, c_t, p._sources[0].numel(), "input")
+    gtbl = _grad_table(p, gp, nk)
+    _check(lib.nufft_exec_type3_grad(p._handle, _ptr_table(f_t), gtbl, _ptr_table(c_t), p._stream()))
+    return f, gp
