@@ -425,6 +425,71 @@ int nufft_get_stage_times3(nufft_plan3* plan, float* ms_out);
 int64_t nufft_sizeof_type3_params(void);
 int64_t nufft_sizeof_info3(void);
 
+/* ---- Toeplitz normal operator ----------------------------------- */
+/* G û = exec_type1(w ⊙ exec_type2(û)) for real weights w_j at the points — the Gram operator A^H W A that CG / LSQR on the normal
+ * equations applies once per iteration — without touching the points: G[k, k'] = T[k − k'] with T_d = Σ_j w_j exp(−i d·x_j), so G is
+ * applied by FFTs of size 2 N_d at a cost that does not depend on the number of points (NFFT.jl: calculateToeplitzKernel /
+ * convolveToeplitzKernel!).  The object holds the real multiplier K = backwardDFT_{2N}(T) / Π 2N_d (T with its Nyquist planes zeroed:
+ * differences of the plan's modes never reach them) and applies  û -> crop(forwardDFT(K ⊙ backwardDFT(pad(û)))).
+ *
+ * Complex plans only (is_complex = 1): the type 2 of a real-data plan extends its half spectrum Hermitian-ly, which for even N_d adds
+ * the mode +N_d/2 next to −N_d/2; mode differences then reach ±N_d, the 2N embedding aliases and the identity fails (rel-L2 0.04 – 0.25
+ * measured on small grids; exact only when every N_d is odd).  A real plan is refused with NUFFT_ERR_UNSUPPORTED.  The weights are real
+ * (K would not be real otherwise).
+ *
+ * Two apply paths, chosen at creation (nufft_toeplitz_info.path, from nufft_toeplitz_get_info):
+ *   fused — D = 2, 3 and every 2 N_d among the line lengths of the pruned FFT passes (N_d ∈ {32, 40, 48, 64, 80, 96, 128, 160, 192, 256,
+ *           320, 384, 512}): pruned strided passes along dimensions 3 and 2 straight from / into the caller's arrays and one kernel along
+ *           dimension 1 that transforms, multiplies by K and transforms back inside LDS (2 D − 1 launches per component); the (2N)^D
+ *           complex grid never exists.  Workspace: K and two intermediates, complex[N_1, N_2, 2N_3] and complex[N_1, 2N_2, 2N_3].
+ *   dense — everything else: pad kernel, rocFFT backward of size 2N, multiply kernel, rocFFT forward, crop kernel, on a (2N)^D complex
+ *           work grid.  The option NUFFT_TOEPLITZ_FUSED=0 in the plan's options string forces this path.
+ * Added after ABI 104 without changing NUFFT_MI355X_VERSION: detect by symbol (dlsym nufft_toeplitz_create) and compare
+ * nufft_sizeof_toeplitz_info() with your own. */
+typedef struct nufft_toeplitz nufft_toeplitz; /* opaque */
+
+enum { NUFFT_TOEPLITZ_PATH_DENSE = 0, NUFFT_TOEPLITZ_PATH_FUSED = 1 };
+
+typedef struct nufft_toeplitz_info {
+    int32_t struct_size;     /* sizeof(nufft_toeplitz_info) of the CALLER's header, set before the call: the library writes only that many
+                                bytes (0 = this layout)                                                                            */
+    int32_t ndim, dtype, ntransforms, fftshift, device;
+    int32_t path;            /* NUFFT_TOEPLITZ_PATH_*                                                                              */
+    int32_t has_spectrum;    /* 1 once nufft_toeplitz_set_spectrum / _set_points has completed                                     */
+    int64_t N[3];            /* the plan's modes per dimension                                                                     */
+    int64_t N2[3];           /* the embedding grid, 2 N_d (1 beyond ndim)                                                          */
+    int64_t multiplier_bytes;/* bytes of K: real(T)[2N_1, 2N_2, 2N_3]                                                              */
+    int64_t workspace_bytes; /* device bytes owned right now (a host-only object: what a device object of these parameters holds at
+                                rest): K, the intermediates or the work grid, tables, rocFFT work; while nufft_toeplitz_set_points
+                                runs, plus the internal 2N plan                                                                   */
+} nufft_toeplitz_info;
+
+/* Geometry (dtype, ndim, N, ntransforms, fftshift, index maps, window parameters, device, options) is copied from `plan`; no pointer to it
+ * is kept, so the plan may be destroyed first.  Allocates K and the intermediates (fused) or the work grid (dense).  A host-only plan
+ * (device = -1) gives a host-only object that answers nufft_toeplitz_get_info only. */
+int nufft_toeplitz_create(nufft_toeplitz** out, const nufft_plan* plan);
+int nufft_toeplitz_destroy(nufft_toeplitz* tz);
+int nufft_toeplitz_get_info(const nufft_toeplitz* tz, nufft_toeplitz_info* out);
+/* T_modes: device array complex(T)[2N_1, 2N_2, 2N_3] in FFT order — what nufft_exec_type1 of a plan with 2 N_d modes, the same Z and
+ * fftshift = 0 returns for the weights.  Zeroes the Nyquist planes, transforms (rocFFT, once per point set), keeps the scaled real part
+ * as K.  The fused path needs a temporary (2N)^D complex grid for this, allocated and freed inside the call: the call synchronises the
+ * stream and is refused on a capturing stream (NUFFT_ERR_INVALID_ARG). */
+int nufft_toeplitz_set_spectrum(nufft_toeplitz* tz, const void* T_modes, void* stream);
+/* The convenience path: builds an internal plan with 2 N_d modes (window parameters of the parent plan unless `build_params` — may be
+ * NULL — gives half_support / sigma / kernel / kernel_param / evalmode; always ntransforms = 1, fftshift = 0), sets its points,
+ * runs nufft_exec_type1 of the weights (real(T)[num_points] on the device; NULL = ones), then nufft_toeplitz_set_spectrum, then
+ * DESTROYS the internal plan.  That plan is large while it lives: at N = 256³, σ = 2 its oversampled grid is 1024³ complex, 17 GB in
+ * ComplexF64 (reported in workspace_bytes during the call).  Never on a capturing stream. */
+int nufft_toeplitz_set_points(nufft_toeplitz* tz, const nufft_params* build_params, int64_t num_points, const void* const* coords,
+                              const void* weights, void* stream);
+/* out[c] = G in[c], c < ntransforms: device arrays complex(T)[N_out...] in the plan's mode order (fftshift plans work unchanged);
+ * out[c] may equal in[c].  Allocates nothing, does not synchronise, is hipGraph-capture safe.  Refusals, all before anything is
+ * enqueued: a host-only object NUFFT_ERR_NO_DEVICE, no spectrum yet NUFFT_ERR_NO_POINTS, a null table or vector NUFFT_ERR_INVALID_ARG. */
+int nufft_toeplitz_apply(nufft_toeplitz* tz, void* const* out, const void* const* in, void* stream);
+/* Device pointer and bytes of K (inspection and tests). */
+int nufft_toeplitz_multiplier_ptr(const nufft_toeplitz* tz, void** out_ptr, int64_t* out_bytes);
+int64_t nufft_sizeof_toeplitz_info(void);
+
 /* ---- misc ----------------------------------------------------------------------------- */
 /* sizeof(nufft_params) / sizeof(nufft_info) of the library build: a binding that mirrors the structs by hand
  * (ctypes, Julia) compares them with its own layout before the first call. */

@@ -95,6 +95,17 @@ class NufftInfo3(C.Structure):
     ]
 
 
+class NufftToeplitzInfo(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("ndim", C.c_int32), ("dtype", C.c_int32), ("ntransforms", C.c_int32),
+        ("fftshift", C.c_int32), ("device", C.c_int32), ("path", C.c_int32), ("has_spectrum", C.c_int32),
+        ("N", C.c_int64 * 3), ("N2", C.c_int64 * 3),
+        ("multiplier_bytes", C.c_int64), ("workspace_bytes", C.c_int64),
+    ]
+
+
+TOEPLITZ_PATH_DENSE, TOEPLITZ_PATH_FUSED = 0, 1
+
 NUM_STAGES3 = 6
 STAGE_NAMES3 = ("prep_sources", "prep_targets", "premultiply", "spread", "type2", "postmultiply")
 
@@ -150,6 +161,14 @@ SYMBOLS = {
     "nufft_get_stage_times3": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "nufft_sizeof_type3_params": (C.c_int64, []),
     "nufft_sizeof_info3": (C.c_int64, []),
+    "nufft_toeplitz_create": (C.c_int, [C.POINTER(_P), _P]),
+    "nufft_toeplitz_destroy": (C.c_int, [_P]),
+    "nufft_toeplitz_get_info": (C.c_int, [_P, C.POINTER(NufftToeplitzInfo)]),
+    "nufft_toeplitz_set_spectrum": (C.c_int, [_P, _P, _P]),
+    "nufft_toeplitz_set_points": (C.c_int, [_P, C.POINTER(NufftParams), C.c_int64, _PP, _P, _P]),
+    "nufft_toeplitz_apply": (C.c_int, [_P, _PP, _PP, _P]),
+    "nufft_toeplitz_multiplier_ptr": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int64)]),
+    "nufft_sizeof_toeplitz_info": (C.c_int64, []),
     "nufft_sizeof_params": (C.c_int64, []),
     "nufft_sizeof_info": (C.c_int64, []),
     "nufft_strerror": (C.c_char_p, [C.c_int]),
@@ -177,7 +196,8 @@ def _load():
         fn.argtypes = args
     # the two structs are mirrored by hand above: refuse a library whose layout differs
     for name, mirror in (("nufft_sizeof_params", NufftParams), ("nufft_sizeof_info", NufftInfo),
-                         ("nufft_sizeof_type3_params", NufftType3Params), ("nufft_sizeof_info3", NufftInfo3)):
+                         ("nufft_sizeof_type3_params", NufftType3Params), ("nufft_sizeof_info3", NufftInfo3),
+                         ("nufft_sizeof_toeplitz_info", NufftToeplitzInfo)):
         if getattr(lib, name)() != C.sizeof(mirror):
             raise ImportError(f"{LIB_PATH}: {name}() = {getattr(lib, name)()} but the ctypes mirror has {C.sizeof(mirror)} bytes "
                               "(include/nufft_mi355x.h and _lib.py disagree)")

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "toeplitz.h"
 
 namespace nufft {
 
@@ -882,6 +883,149 @@ hipError_t launch_fft_lines(int dtype, int64_t n, bool forward, const FftLinePas
     a.row_a = p.row_a; a.row_valid = p.row_valid; a.row_in = p.row_in; a.row_out = p.row_out;
     if (dtype == NUFFT_F32) return forward ? launch_t<float, true>((int)n, a, stream) : launch_t<float, false>((int)n, a, stream);
     return forward ? launch_t<double, true>((int)n, a, stream) : launch_t<double, false>((int)n, a, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Dimension 1 of the Toeplitz normal operator's fused apply (toeplitz.cpp), in place: per contiguous line
+// of k1 kept modes — zero-padded backward FFT of length N, times the line of the real multiplier K, forward FFT, kept modes
+// stored back.  One wave per line as in cplx_lines_kernel; the padded line never leaves LDS.
+//
+// One twiddle table serves both transforms: the kept modes are conjugated while they are loaded, so the forward FFT leaves
+// w = conj(B x) (B the backward transform), and the multiply writes K conj(w) = K (B x) — K is real.
+// ---------------------------------------------------------------------------------------------------
+struct ToeplitzLineArgs {
+    void* data;             // complex<T>[nlines][k1]
+    const void* mult;       // T[nlines][N]
+    int64_t nlines;
+    int k1;
+    const int32_t* map;     // [k1]: kept mode -> index of the line
+    const void* twiddle;    // complex<T>[N]: exp(-2πi m / N)
+};
+
+template <typename T, int N, int TL>
+__global__ __launch_bounds__(TL * kWave) void toeplitz_lines_kernel(ToeplitzLineArgs a) {
+    using C = typename Cplx2<T>::type;
+    constexpr int LINE = N + (N >> 4) + 1;
+    constexpr int PW = 16 / sizeof(T);                        // reals of K per 16-byte load
+    constexpr int KIT = (N / PW + kWave - 1) / kWave;         // loads of K per lane
+    // K is fetched before the first transform where it fits in 16 registers per lane (it is the only HBM read of the middle of
+    // the kernel: this way it is in flight under the backward FFT); longer lines would carry 32 registers across the FFT
+    constexpr bool PREFETCH = KIT * 16 <= 64;
+    struct alignas(16) KPack { T v[PW]; };
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    C* tw = reinterpret_cast<C*>(smem);                       // [N]
+    C* lines = tw + N;                                        // [TL][LINE]
+    const int tid = threadIdx.x;
+    const int lane = tid & (kWave - 1);
+    const int wave = tid / kWave;
+    const C* twg = static_cast<const C*>(a.twiddle);
+    for (int i = tid; i < N; i += TL * kWave) tw[i] = twg[i];
+    __syncthreads();
+    const int64_t line_id = (int64_t)blockIdx.x * TL + wave;
+    if (line_id >= a.nlines) return;
+    C* line = lines + wave * LINE;
+    C* x = static_cast<C*>(a.data) + line_id * a.k1;
+    const KPack* kg = reinterpret_cast<const KPack*>(static_cast<const T*>(a.mult) + line_id * N);
+
+    C z; z.x = T(0); z.y = T(0);
+    for (int n = lane; n < N; n += kWave) line[lpad(n)] = z;
+    wave_lds_fence();
+    if (sizeof(C) == 8 && (a.k1 & 1) == 0) {                  // Float32: two kept modes (16 bytes) per lane and step
+        const float4* x4 = reinterpret_cast<const float4*>(x);
+        for (int k = lane; k < a.k1 / 2; k += kWave) {
+            const float4 w = x4[k];
+            C u, v;
+            u.x = w.x; u.y = -w.y; v.x = w.z; v.y = -w.w;
+            line[lpad(a.map[2 * k])] = u;
+            line[lpad(a.map[2 * k + 1])] = v;
+        }
+    } else {
+        for (int k = lane; k < a.k1; k += kWave) {
+            C u = x[k];
+            u.y = -u.y;
+            line[lpad(a.map[k])] = u;
+        }
+    }
+    KPack kp[KIT];
+    if constexpr (PREFETCH) {
+#pragma unroll
+        for (int i = 0; i < KIT; ++i) {
+            const int q = lane + i * kWave;
+            if (q < N / PW) kp[i] = kg[q];
+        }
+    }
+    wave_lds_fence();
+    fft_line<T, N, -1>(line, tw, lane);
+#pragma unroll
+    for (int i = 0; i < KIT; ++i) {
+        const int q = lane + i * kWave;
+        if (q < N / PW) {
+            if constexpr (!PREFETCH) kp[i] = kg[q];
+#pragma unroll
+            for (int t = 0; t < PW; ++t) {
+                C v = line[lpad(q * PW + t)];
+                v.x *= kp[i].v[t];
+                v.y *= -kp[i].v[t];
+                line[lpad(q * PW + t)] = v;
+            }
+        }
+    }
+    wave_lds_fence();
+    fft_line<T, N, -1>(line, tw, lane);
+    if (sizeof(C) == 8 && (a.k1 & 1) == 0) {
+        float4* x4 = reinterpret_cast<float4*>(x);
+        for (int k = lane; k < a.k1 / 2; k += kWave) {
+            const C u = line[lpad(a.map[2 * k])], v = line[lpad(a.map[2 * k + 1])];
+            x4[k] = make_float4((float)u.x, (float)u.y, (float)v.x, (float)v.y);
+        }
+    } else {
+        for (int k = lane; k < a.k1; k += kWave) x[k] = line[lpad(a.map[k])];
+    }
+}
+
+template <typename T, int N>
+static hipError_t launch_toeplitz_n(const ToeplitzLineArgs& a, hipStream_t stream) {
+    using C = typename Cplx2<T>::type;
+    constexpr int LINE = N + (N >> 4) + 1;
+    constexpr int TL = (sizeof(C) * (16 * LINE + N) <= 80 * 1024) ? 16 : 8;      // as launch_cplx_n
+    static_assert(sizeof(C) * (size_t)(TL * LINE + N) <= kFftLdsLimit, "line buffers exceed the 160 KiB of LDS");
+    const size_t lds = sizeof(C) * (size_t)(TL * LINE + N);
+    auto fn = toeplitz_lines_kernel<T, N, TL>;
+    static std::atomic<unsigned long long> prepared{0};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (!(prepared.load(std::memory_order_relaxed) & bit)) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        prepared.fetch_or(bit, std::memory_order_relaxed);
+    }
+    hipLaunchKernelGGL(fn, dim3((unsigned)((a.nlines + TL - 1) / TL)), dim3(TL * kWave), lds, stream, a);
+    return hipGetLastError();
+}
+
+template <typename T>
+static hipError_t launch_toeplitz_t(int n, const ToeplitzLineArgs& a, hipStream_t stream) {
+    switch (n) {
+#define NUFFT_CASE(NN) case NN: return launch_toeplitz_n<T, NN>(a, stream);
+        NUFFT_FFT_SIZES(NUFFT_CASE)
+#undef NUFFT_CASE
+        default: return hipErrorInvalidValue;
+    }
+}
+
+bool toeplitz_lines_supported(int dtype, int64_t n) {
+    (void)dtype;
+    return size_instantiated(n);
+}
+
+hipError_t launch_toeplitz_lines(int dtype, int64_t n, void* data, const void* K, int64_t nlines, int k1, const int32_t* map,
+                                 const void* twiddle, hipStream_t stream) {
+    if (nlines <= 0) return hipSuccess;
+    if (k1 < 1 || k1 > n) return hipErrorInvalidValue;
+    ToeplitzLineArgs a{};
+    a.data = data; a.mult = K; a.nlines = nlines; a.k1 = k1; a.map = map; a.twiddle = twiddle;
+    return dtype == NUFFT_F32 ? launch_toeplitz_t<float>((int)n, a, stream) : launch_toeplitz_t<double>((int)n, a, stream);
 }
 
 }  // namespace nufft

@@ -1,0 +1,545 @@
+// Toeplitz normal operator G = A^H W A of a complex plan (include/nufft_mi355x.h, Toeplitz section).
+//
+// G[k, k'] = T[k − k'] with T_d = Σ_j w_j exp(−i d·x_j): a multi-level Toeplitz matrix, embedded in a circulant of size 2 N_d per
+// dimension.  With K = backwardDFT_{2N}(T) / Π 2N_d (real for real weights, once the never-used Nyquist planes of T are zeroed),
+//   G û = crop(forwardDFT_{2N}(K ⊙ backwardDFT_{2N}(pad(û)))).
+// The fused path runs pad + backward transform and forward transform + crop as the pruned line passes of fft_lines.hip (kept modes
+// in, full line out and back) with the multiply inside the dimension-1 kernel; the dense path runs rocFFT on a (2N)^D grid.
+#include <hip/hip_runtime.h>
+#include <rocfft/rocfft.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "kernels.h"
+#include "nufft_internal.h"
+#include "toeplitz.h"
+
+using nufft::set_error;
+
+struct nufft_toeplitz {
+    int dtype = NUFFT_F64, D = 1, C = 1, device = -1, num_cus = 256;
+    bool fftshift = false;
+    int64_t N[3] = {1, 1, 1}, N2[3] = {1, 1, 1};
+    int path = NUFFT_TOEPLITZ_PATH_DENSE;
+    // the parent plan's window parameters (the internal 2N plan of set_points takes them)
+    int M = 4, kernel = 0, evalmode = 0, point_transform = 0;
+    double sigma_req = 2.0;
+    std::string options;
+    std::vector<int32_t> map[3], inv[3];
+    // device
+    int32_t* d_map[3] = {nullptr, nullptr, nullptr};
+    int32_t* d_inv[3] = {nullptr, nullptr, nullptr};
+    void* d_tw_fw[3] = {nullptr, nullptr, nullptr};    // complex<T>[2N_d]: exp(-2πi m / 2N_d)
+    void* d_tw_bw[3] = {nullptr, nullptr, nullptr};    // (dimensions 2, 3 of the fused path)
+    void* d_ones = nullptr;                            // T[max N_d] = 1: the unit factor tables of the strided passes
+    void* d_K = nullptr;                               // T[2N_1, 2N_2, 2N_3]
+    void* d_tmpA = nullptr;                            // fused, 3-D: complex<T>[N_1, N_2, 2N_3]
+    void* d_tmpB = nullptr;                            // fused: complex<T>[N_1, 2N_2, 2N_3]
+    void* d_work = nullptr;                            // dense: complex<T>[2N_1, 2N_2, 2N_3]
+    rocfft_plan_t* fft_bw = nullptr;                   // in-place c2c of the embedding grid (multiplier; dense apply)
+    rocfft_plan_t* fft_fw = nullptr;                   // dense apply
+    rocfft_execution_info_t* fft_info = nullptr;
+    void* d_fft_work = nullptr;                        // dense: kept; fused: lives inside set_spectrum
+    size_t fft_work_bytes = 0;
+    int64_t own_bytes = 0, build_bytes = 0;
+    bool has_spectrum = false;
+};
+
+namespace {
+
+int fail(int code, const std::string& msg) {
+    set_error(msg);
+    return code;
+}
+
+#define TZ_HIP(expr)                                                                           \
+    do {                                                                                       \
+        hipError_t e__ = (expr);                                                               \
+        if (e__ != hipSuccess)                                                                 \
+            return fail(e__ == hipErrorOutOfMemory ? NUFFT_ERR_ALLOC : NUFFT_ERR_HIP,          \
+                        std::string(#expr) + ": " + hipGetErrorString(e__));                   \
+    } while (0)
+
+#define TZ_ROCFFT(expr)                                                                        \
+    do {                                                                                       \
+        rocfft_status s__ = (expr);                                                            \
+        if (s__ != rocfft_status_success)                                                      \
+            return fail(NUFFT_ERR_ROCFFT, std::string(#expr) + ": rocfft status " + std::to_string((int)s__)); \
+    } while (0)
+
+struct DeviceGuard {
+    int prev = -1;
+    bool active = false;
+    explicit DeviceGuard(int dev) {
+        if (dev >= 0 && hipGetDevice(&prev) == hipSuccess && prev != dev) active = hipSetDevice(dev) == hipSuccess;
+    }
+    ~DeviceGuard() {
+        if (active) (void)hipSetDevice(prev);
+    }
+};
+
+size_t real_bytes(const nufft_toeplitz* t) { return t->dtype == NUFFT_F32 ? 4 : 8; }
+size_t padded(size_t bytes) { return (std::max<size_t>(bytes, 16) + 255) / 256 * 256; }
+
+int64_t grid_cells(const nufft_toeplitz* t) { return t->N2[0] * t->N2[1] * t->N2[2]; }
+int64_t num_modes(const nufft_toeplitz* t) { return t->N[0] * t->N[1] * t->N[2]; }
+
+// Bytes of every buffer the object holds at rest, in allocation order (a host-only object reports their sum; rocFFT's own work
+// buffer, known only on a device, comes on top for the dense path).
+struct Sizes {
+    size_t K, tmpA, tmpB, work, maps, twiddles, ones;
+    size_t total() const { return K + tmpA + tmpB + work + maps + twiddles + ones; }
+};
+Sizes sizes_of(const nufft_toeplitz* t) {
+    const size_t rb = real_bytes(t), cb = 2 * rb;
+    const bool fused = t->path == NUFFT_TOEPLITZ_PATH_FUSED;
+    Sizes s{};
+    s.K = padded((size_t)grid_cells(t) * rb);
+    s.tmpA = fused && t->D == 3 ? padded((size_t)(t->N[0] * t->N[1] * t->N2[2]) * cb) : 0;
+    s.tmpB = fused ? padded((size_t)(t->N[0] * t->N2[1] * t->N2[2]) * cb) : 0;
+    s.work = fused ? 0 : padded((size_t)grid_cells(t) * cb);
+    int64_t nmax = 1;
+    for (int d = 0; d < 3; ++d) {
+        s.maps += padded((size_t)t->N[d] * 4) + padded((size_t)t->N2[d] * 4);
+        if (fused && d < t->D) s.twiddles += padded((size_t)t->N2[d] * cb) * (d == 0 ? 1 : 2);
+        nmax = std::max(nmax, t->N[d]);
+    }
+    s.ones = fused ? padded((size_t)nmax * rb) : 0;
+    return s;
+}
+
+int alloc(nufft_toeplitz* t, void** ptr, size_t bytes) {
+    bytes = padded(bytes);
+    hipError_t e = hipMalloc(ptr, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        *ptr = nullptr;
+        return fail(NUFFT_ERR_ALLOC, "hipMalloc(" + std::to_string(bytes) + ") of a Toeplitz buffer: " + hipGetErrorString(e));
+    }
+    t->own_bytes += (int64_t)bytes;
+    return NUFFT_OK;
+}
+
+template <typename P>
+void release_buf(nufft_toeplitz* t, P*& ptr, size_t bytes) {
+    if (!ptr) return;
+    (void)hipFree(ptr);
+    t->own_bytes -= (int64_t)padded(bytes);
+    ptr = nullptr;
+}
+
+template <typename T>
+int upload_real(nufft_toeplitz* t, void** dst, const std::vector<double>& src) {
+    std::vector<T> tmp(src.begin(), src.end());
+    int rc = alloc(t, dst, tmp.size() * sizeof(T));
+    if (rc) return rc;
+    TZ_HIP(hipMemcpy(*dst, tmp.data(), tmp.size() * sizeof(T), hipMemcpyHostToDevice));
+    return NUFFT_OK;
+}
+int upload(nufft_toeplitz* t, void** dst, const std::vector<double>& src) {
+    return t->dtype == NUFFT_F32 ? upload_real<float>(t, dst, src) : upload_real<double>(t, dst, src);
+}
+int upload_i32(nufft_toeplitz* t, int32_t** dst, const std::vector<int32_t>& src) {
+    int rc = alloc(t, reinterpret_cast<void**>(dst), src.size() * sizeof(int32_t));
+    if (rc) return rc;
+    TZ_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    return NUFFT_OK;
+}
+
+void release(nufft_toeplitz* t) {
+    if (!t) return;
+    if (t->device >= 0) {
+        DeviceGuard g(t->device);
+        for (int d = 0; d < 3; ++d) {
+            if (t->d_map[d]) (void)hipFree(t->d_map[d]);
+            if (t->d_inv[d]) (void)hipFree(t->d_inv[d]);
+            if (t->d_tw_fw[d]) (void)hipFree(t->d_tw_fw[d]);
+            if (t->d_tw_bw[d]) (void)hipFree(t->d_tw_bw[d]);
+        }
+        for (void* p : {t->d_ones, t->d_K, t->d_tmpA, t->d_tmpB, t->d_work, t->d_fft_work})
+            if (p) (void)hipFree(p);
+        if (t->fft_bw) (void)rocfft_plan_destroy(t->fft_bw);
+        if (t->fft_fw) (void)rocfft_plan_destroy(t->fft_fw);
+        if (t->fft_info) (void)rocfft_execution_info_destroy(t->fft_info);
+    }
+    delete t;
+}
+
+bool capturing(hipStream_t stream) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return st != hipStreamCaptureStatusNone;
+}
+
+nufft::TzGrid grid_of(const nufft_toeplitz* t) {
+    nufft::TzGrid g{};
+    g.dtype = t->dtype;
+    g.D = t->D;
+    for (int d = 0; d < 3; ++d) {
+        g.n2[d] = (int)t->N2[d];
+        g.nk[d] = (int)t->N[d];
+        g.map[d] = t->d_map[d];
+        g.inv[d] = t->d_inv[d];
+    }
+    return g;
+}
+
+int build_device(nufft_toeplitz* t) {
+    DeviceGuard guard(t->device);
+    const size_t rb = real_bytes(t), cb = 2 * rb;
+    const bool fused = t->path == NUFFT_TOEPLITZ_PATH_FUSED;
+    int rc;
+    if ((rc = alloc(t, &t->d_K, (size_t)grid_cells(t) * rb))) return rc;
+    if (fused) {
+        if (t->D == 3 && (rc = alloc(t, &t->d_tmpA, (size_t)(t->N[0] * t->N[1] * t->N2[2]) * cb))) return rc;
+        if ((rc = alloc(t, &t->d_tmpB, (size_t)(t->N[0] * t->N2[1] * t->N2[2]) * cb))) return rc;
+    } else {
+        if ((rc = alloc(t, &t->d_work, (size_t)grid_cells(t) * cb))) return rc;
+    }
+    int64_t nmax = 1;
+    for (int d = 0; d < 3; ++d) {
+        if ((rc = upload_i32(t, &t->d_map[d], t->map[d])) || (rc = upload_i32(t, &t->d_inv[d], t->inv[d]))) return rc;
+        nmax = std::max(nmax, t->N[d]);
+        if (!fused || d >= t->D) continue;
+        const int64_t n = t->N2[d];
+        std::vector<double> twf(2 * (size_t)n), twb(2 * (size_t)n);
+        for (int64_t m = 0; m < n; ++m) {
+            const double ang = 2.0 * M_PI * (double)m / (double)n;
+            twf[2 * m] = std::cos(ang); twf[2 * m + 1] = -std::sin(ang);
+            twb[2 * m] = std::cos(ang); twb[2 * m + 1] = std::sin(ang);
+        }
+        if ((rc = upload(t, &t->d_tw_fw[d], twf))) return rc;
+        if (d > 0 && (rc = upload(t, &t->d_tw_bw[d], twb))) return rc;
+    }
+    if (fused && (rc = upload(t, &t->d_ones, std::vector<double>((size_t)nmax, 1.0)))) return rc;
+
+    size_t lengths[3] = {1, 1, 1};
+    for (int d = 0; d < t->D; ++d) lengths[d] = (size_t)t->N2[d];
+    const rocfft_precision prec = t->dtype == NUFFT_F32 ? rocfft_precision_single : rocfft_precision_double;
+    TZ_ROCFFT(rocfft_execution_info_create(&t->fft_info));
+    TZ_ROCFFT(rocfft_plan_create(&t->fft_bw, rocfft_placement_inplace, rocfft_transform_type_complex_inverse, prec, (size_t)t->D, lengths, 1, nullptr));
+    TZ_ROCFFT(rocfft_plan_get_work_buffer_size(t->fft_bw, &t->fft_work_bytes));
+    if (!fused) {
+        size_t wf = 0;
+        TZ_ROCFFT(rocfft_plan_create(&t->fft_fw, rocfft_placement_inplace, rocfft_transform_type_complex_forward, prec, (size_t)t->D, lengths, 1, nullptr));
+        TZ_ROCFFT(rocfft_plan_get_work_buffer_size(t->fft_fw, &wf));
+        t->fft_work_bytes = std::max(t->fft_work_bytes, wf);
+        if (t->fft_work_bytes > 0) {
+            if ((rc = alloc(t, &t->d_fft_work, t->fft_work_bytes))) return rc;
+            TZ_ROCFFT(rocfft_execution_info_set_work_buffer(t->fft_info, t->d_fft_work, t->fft_work_bytes));
+        }
+    }
+    return NUFFT_OK;
+}
+
+// K from the spectrum held in `grid` (complex<T>[2N...], overwritten): Nyquist planes zeroed, backward transform, scaled real part.
+// `src` may be `grid` itself.
+int multiplier_from(nufft_toeplitz* t, void* grid, const void* src, hipStream_t stream) {
+    const nufft::TzGrid g = grid_of(t);
+    TZ_HIP(nufft::launch_tz_spectrum_load(g, grid, src, t->num_cus, stream));
+    TZ_ROCFFT(rocfft_execution_info_set_stream(t->fft_info, stream));
+    void* io[1] = {grid};
+    TZ_ROCFFT(rocfft_execute(t->fft_bw, io, nullptr, t->fft_info));
+    TZ_HIP(nufft::launch_tz_real_part(g, t->d_K, grid, 1.0 / (double)grid_cells(t), t->num_cus, stream));
+    return NUFFT_OK;
+}
+
+// The fused path's temporaries of set_spectrum / set_points: the (2N)^D complex grid and rocFFT's work buffer.
+struct Scratch {
+    nufft_toeplitz* t;
+    void* grid = nullptr;
+    void* fft_work = nullptr;
+    explicit Scratch(nufft_toeplitz* tz) : t(tz) {}
+    int acquire_grid() {
+        if (t->path != NUFFT_TOEPLITZ_PATH_FUSED) { grid = t->d_work; return NUFFT_OK; }
+        return alloc(t, &grid, (size_t)grid_cells(t) * 2 * real_bytes(t));
+    }
+    int acquire_fft_work() {
+        if (t->path != NUFFT_TOEPLITZ_PATH_FUSED || t->fft_work_bytes == 0) return NUFFT_OK;
+        int rc = alloc(t, &fft_work, t->fft_work_bytes);
+        if (rc) return rc;
+        if (rocfft_execution_info_set_work_buffer(t->fft_info, fft_work, t->fft_work_bytes) != rocfft_status_success)
+            return fail(NUFFT_ERR_ROCFFT, "rocfft_execution_info_set_work_buffer failed");
+        return NUFFT_OK;
+    }
+    ~Scratch() {
+        if (t->path != NUFFT_TOEPLITZ_PATH_FUSED) return;
+        release_buf(t, grid, (size_t)grid_cells(t) * 2 * real_bytes(t));
+        release_buf(t, fft_work, t->fft_work_bytes);
+    }
+};
+
+// One pruned strided pass of the fused apply along dimension `dim` (1 or 2, zero-based): backward = kept modes in, full line out.
+int strided_pass(const nufft_toeplitz* t, int dim, bool forward, const void* in, void* out, hipStream_t stream) {
+    // pruned side: N_dim kept modes; full side: 2 N_dim.  Columns: dimension 1 (and 2 for the pass along dimension 3) of the KEPT
+    // modes; the outer index of the pass along dimension 2 of a 3-D grid is the full dimension 3.
+    nufft::FftLinePass q{};
+    q.in = in;
+    q.out = out;
+    q.map = t->d_map[dim];
+    q.nk = (int)t->N[dim];
+    q.twiddle = forward ? t->d_tw_fw[dim] : t->d_tw_bw[dim];
+    q.fa = t->d_ones; q.ka = 1;
+    q.fk = t->d_ones;
+    q.scale = 1.0;
+    q.mult = nullptr;
+    const int64_t N1 = t->N[0];
+    if (dim == 2) {
+        q.a_total = q.a_out = N1 * t->N[1];
+        q.in_stride_j = q.out_stride_j = N1 * t->N[1];
+        q.in_stride_c = q.out_stride_c = 0;
+        q.nc = 1;
+    } else {
+        q.a_total = q.a_out = N1;
+        q.in_stride_j = q.out_stride_j = N1;
+        q.nc = (int)t->N2[2];
+        const int64_t pruned_c = N1 * t->N[1], full_c = N1 * t->N2[1];
+        q.in_stride_c = forward ? full_c : pruned_c;
+        q.out_stride_c = forward ? pruned_c : full_c;
+    }
+    TZ_HIP(nufft::launch_fft_lines(t->dtype, t->N2[dim], forward, q, stream));
+    return NUFFT_OK;
+}
+
+int apply_fused(nufft_toeplitz* t, void* out, const void* in, hipStream_t stream) {
+    int rc;
+    const void* src = in;
+    if (t->D == 3) {
+        if ((rc = strided_pass(t, 2, false, in, t->d_tmpA, stream))) return rc;
+        src = t->d_tmpA;
+    }
+    if ((rc = strided_pass(t, 1, false, src, t->d_tmpB, stream))) return rc;
+    TZ_HIP(nufft::launch_toeplitz_lines(t->dtype, t->N2[0], t->d_tmpB, t->d_K, t->N2[1] * t->N2[2], (int)t->N[0], t->d_map[0],
+                                        t->d_tw_fw[0], stream));
+    if ((rc = strided_pass(t, 1, true, t->d_tmpB, t->D == 3 ? t->d_tmpA : out, stream))) return rc;
+    if (t->D == 3 && (rc = strided_pass(t, 2, true, t->d_tmpA, out, stream))) return rc;
+    return NUFFT_OK;
+}
+
+int apply_dense(nufft_toeplitz* t, void* out, const void* in, hipStream_t stream) {
+    const nufft::TzGrid g = grid_of(t);
+    void* io[1] = {t->d_work};
+    TZ_HIP(nufft::launch_tz_pad(g, t->d_work, in, t->num_cus, stream));
+    TZ_ROCFFT(rocfft_execute(t->fft_bw, io, nullptr, t->fft_info));
+    TZ_HIP(nufft::launch_tz_multiply(g, t->d_work, t->d_K, t->num_cus, stream));
+    TZ_ROCFFT(rocfft_execute(t->fft_fw, io, nullptr, t->fft_info));
+    TZ_HIP(nufft::launch_tz_crop(g, out, t->d_work, t->num_cus, stream));
+    return NUFFT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t nufft_sizeof_toeplitz_info(void) { return (int64_t)sizeof(nufft_toeplitz_info); }
+
+int nufft_toeplitz_create(nufft_toeplitz** out, const nufft_plan* plan) {
+    if (!out || !plan) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    if (!plan->is_complex)
+        return fail(NUFFT_ERR_UNSUPPORTED,
+                    "the Toeplitz normal operator needs a complex plan: the type 2 of a real-data plan extends its half spectrum "
+                    "Hermitian-ly, which for even N adds the mode +N/2 next to -N/2; mode differences then reach +-N and the 2N "
+                    "embedding aliases");
+    for (int d = 0; d < plan->D; ++d)
+        if (plan->N[d] > ((int64_t)1 << 29)) return fail(NUFFT_ERR_UNSUPPORTED, "2 N exceeds 2^30 cells per axis");
+    nufft_toeplitz* t = new (std::nothrow) nufft_toeplitz();
+    if (!t) return fail(NUFFT_ERR_ALLOC, "out of host memory");
+    t->dtype = plan->dtype;
+    t->D = plan->D;
+    t->C = plan->C;
+    t->device = plan->device;
+    t->num_cus = plan->num_cus;
+    t->fftshift = plan->fftshift;
+    t->M = plan->M;
+    t->kernel = plan->kernel;
+    t->evalmode = plan->evalmode;
+    t->point_transform = plan->point_transform;
+    t->sigma_req = plan->sigma_req;
+    t->options = plan->opts.str();
+    nufft::set_current_options(&plan->opts);
+    bool fused = plan->D >= 2 && nufft::option_int("NUFFT_TOEPLITZ_FUSED", 1) != 0;
+    for (int d = 0; d < 3; ++d) {
+        const bool in = d < plan->D;
+        t->N[d] = in ? plan->N[d] : 1;
+        t->N2[d] = in ? 2 * plan->N[d] : 1;
+        if (in) {
+            // mode k of the plan's mode order -> cell k mod 2N of the embedding grid (the same rule that places the kept modes in
+            // the oversampled spectrum)
+            std::vector<double> ks;
+            std::vector<int64_t> m64;
+            nufft::wavenumbers(t->N[d], false, ks);
+            nufft::non_oversampled_indices(ks, t->N2[d], t->fftshift, m64);
+            t->map[d].assign(m64.begin(), m64.end());
+            fused = fused && nufft::fft_lines_supported(t->dtype, t->N2[d]) && nufft::toeplitz_lines_supported(t->dtype, t->N2[d]);
+        } else {
+            t->map[d].assign(1, 0);
+        }
+        t->inv[d].assign((size_t)t->N2[d], -1);
+        for (size_t k = 0; k < t->map[d].size(); ++k) t->inv[d][(size_t)t->map[d][k]] = (int32_t)k;
+    }
+    t->path = fused ? NUFFT_TOEPLITZ_PATH_FUSED : NUFFT_TOEPLITZ_PATH_DENSE;
+    if (t->device >= 0) {
+        const int rc = build_device(t);
+        if (rc) {
+            const std::string keep = nufft_last_error_message();
+            release(t);
+            return fail(rc, keep);
+        }
+    }
+    *out = t;
+    return NUFFT_OK;
+}
+
+int nufft_toeplitz_destroy(nufft_toeplitz* t) {
+    release(t);
+    return NUFFT_OK;
+}
+
+int nufft_toeplitz_get_info(const nufft_toeplitz* t, nufft_toeplitz_info* o) {
+    if (!t || !o) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    nufft_toeplitz_info i;
+    std::memset(&i, 0, sizeof(i));
+    const size_t known = o->struct_size > 0 ? std::min((size_t)o->struct_size, sizeof(i)) : sizeof(i);
+    i.struct_size = (int32_t)known;
+    i.ndim = t->D;
+    i.dtype = t->dtype;
+    i.ntransforms = t->C;
+    i.fftshift = t->fftshift;
+    i.device = t->device;
+    i.path = t->path;
+    i.has_spectrum = t->has_spectrum;
+    for (int d = 0; d < 3; ++d) { i.N[d] = t->N[d]; i.N2[d] = t->N2[d]; }
+    i.multiplier_bytes = grid_cells(t) * (int64_t)real_bytes(t);
+    i.workspace_bytes = t->device >= 0 ? t->own_bytes + t->build_bytes : (int64_t)sizes_of(t).total();
+    std::memcpy(o, &i, known);
+    return NUFFT_OK;
+}
+
+int nufft_toeplitz_multiplier_ptr(const nufft_toeplitz* t, void** out_ptr, int64_t* out_bytes) {
+    if (!t || !out_ptr) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
+    *out_ptr = t->d_K;
+    if (out_bytes) *out_bytes = grid_cells(t) * (int64_t)real_bytes(t);
+    return NUFFT_OK;
+}
+
+int nufft_toeplitz_set_spectrum(nufft_toeplitz* t, const void* T_modes, void* stream_) {
+    if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
+    if (!T_modes) return fail(NUFFT_ERR_INVALID_ARG, "null spectrum");
+    DeviceGuard guard(t->device);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (capturing(stream))
+        return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_set_spectrum allocates and synchronises: not on a capturing stream");
+    t->has_spectrum = false;
+    Scratch s(t);
+    int rc;
+    if ((rc = s.acquire_grid()) || (rc = s.acquire_fft_work())) return rc;
+    if ((rc = multiplier_from(t, s.grid, T_modes, stream))) return rc;
+    TZ_HIP(hipStreamSynchronize(stream));      // the temporaries are freed on return
+    t->has_spectrum = true;
+    return NUFFT_OK;
+}
+
+int nufft_toeplitz_set_points(nufft_toeplitz* t, const nufft_params* build, int64_t np, const void* const* coords, const void* weights,
+                              void* stream_) {
+    if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
+    if (np < 0) return fail(NUFFT_ERR_INVALID_ARG, "negative number of points");
+    if (!coords) return fail(NUFFT_ERR_INVALID_ARG, "null coordinate table");
+    for (int d = 0; d < t->D; ++d)
+        if (np > 0 && !coords[d]) return fail(NUFFT_ERR_INVALID_ARG, "null coordinate vector");
+    DeviceGuard guard(t->device);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (capturing(stream))
+        return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_set_points builds and destroys a plan: not on a capturing stream");
+    t->has_spectrum = false;
+
+    nufft_params prm;
+    std::memset(&prm, 0, sizeof(prm));
+    prm.struct_size = (int32_t)sizeof(prm);
+    prm.dtype = t->dtype;
+    prm.is_complex = 1;
+    prm.ndim = t->D;
+    for (int d = 0; d < t->D; ++d) prm.N[d] = t->N2[d];
+    prm.half_support = t->M;
+    prm.sigma = t->sigma_req;
+    prm.kernel = t->kernel;
+    prm.evalmode = t->evalmode;
+    prm.ntransforms = 1;
+    prm.fftshift = 0;
+    prm.point_transform = t->point_transform;
+    prm.device = t->device;
+    prm.options = t->options.empty() ? nullptr : t->options.c_str();
+    if (build) {        // the caller's window for the build: half_support and sigma where set, kernel / kernel_param / evalmode verbatim
+        nufft_params b;
+        std::memset(&b, 0, sizeof(b));
+        const size_t known = build->struct_size > 0 ? (size_t)build->struct_size : offsetof(nufft_params, kernel_param_dim);
+        if (known < offsetof(nufft_params, kernel_param_dim)) return fail(NUFFT_ERR_INVALID_ARG, "nufft_params.struct_size is smaller than any published layout");
+        std::memcpy(&b, build, std::min(known, sizeof(b)));
+        if (b.half_support > 0) prm.half_support = b.half_support;
+        if (b.sigma > 0) prm.sigma = b.sigma;
+        prm.kernel = b.kernel;
+        prm.kernel_param = b.kernel_param;
+        prm.evalmode = b.evalmode;
+    }
+
+    Scratch s(t);
+    int rc;
+    if ((rc = s.acquire_grid())) return rc;
+    void* values = nullptr;
+    const size_t vbytes = (size_t)std::max<int64_t>(np, 1) * 2 * real_bytes(t);
+    if ((rc = alloc(t, &values, vbytes))) return rc;
+    nufft_plan* bp = nullptr;
+    rc = nufft_plan_create_ex(&bp, &prm);
+    if (rc == NUFFT_OK) {
+        t->build_bytes = bp->workspace_bytes;
+        rc = nufft_set_points(bp, np, coords, stream);
+        t->build_bytes = bp->workspace_bytes;
+    }
+    if (rc == NUFFT_OK) {
+        hipError_t e = nufft::launch_tz_weights(t->dtype, values, weights, np, t->num_cus, stream);
+        if (e != hipSuccess) rc = fail(NUFFT_ERR_HIP, std::string("launch_tz_weights: ") + hipGetErrorString(e));
+    }
+    if (rc == NUFFT_OK) {
+        void* outs[1] = {s.grid};
+        const void* ins[1] = {values};
+        rc = nufft_exec_type1(bp, outs, ins, stream);
+    }
+    if (rc == NUFFT_OK && hipStreamSynchronize(stream) != hipSuccess) rc = fail(NUFFT_ERR_HIP, "hipStreamSynchronize failed");
+    const std::string keep = rc ? nufft_last_error_message() : "";
+    if (bp) nufft_plan_destroy(bp);            // before the transform's own work buffer is allocated
+    t->build_bytes = 0;
+    release_buf(t, values, vbytes);
+    if (rc) return fail(rc, "Toeplitz build (type 1 of the weights on the 2N grid): " + keep);
+    if ((rc = s.acquire_fft_work())) return rc;
+    if ((rc = multiplier_from(t, s.grid, s.grid, stream))) return rc;
+    TZ_HIP(hipStreamSynchronize(stream));
+    t->has_spectrum = true;
+    return NUFFT_OK;
+}
+
+int nufft_toeplitz_apply(nufft_toeplitz* t, void* const* out, const void* const* in, void* stream_) {
+    if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
+    if (!t->has_spectrum) return fail(NUFFT_ERR_NO_POINTS, "nufft_toeplitz_set_spectrum or nufft_toeplitz_set_points must be called before nufft_toeplitz_apply");
+    if (!out || !in) return fail(NUFFT_ERR_INVALID_ARG, "null table");
+    for (int c = 0; c < t->C; ++c)
+        if (!out[c] || !in[c]) return fail(NUFFT_ERR_INVALID_ARG, "null data vector");
+    DeviceGuard guard(t->device);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (t->path == NUFFT_TOEPLITZ_PATH_DENSE) TZ_ROCFFT(rocfft_execution_info_set_stream(t->fft_info, stream));
+    for (int c = 0; c < t->C; ++c) {
+        const int rc = t->path == NUFFT_TOEPLITZ_PATH_FUSED ? apply_fused(t, out[c], in[c], stream) : apply_dense(t, out[c], in[c], stream);
+        if (rc) return rc;
+    }
+    return NUFFT_OK;
+}
+
+}  // extern "C"

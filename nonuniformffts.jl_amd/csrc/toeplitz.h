@@ -1,0 +1,38 @@
+// Launchers of the Toeplitz normal operator's kernels (toeplitz.cpp): the streaming kernels of the dense
+// path and of the multiplier's construction (toeplitz_kernels.hip) and the fused dimension-1 pass (fft_lines.hip).
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+namespace nufft {
+
+// The embedding grid: n2[d] = 2 N_d cells (dimension 1 fastest), the plan's nk[d] = N_d modes sit at map[d][k'] (= k mod 2 N_d);
+// inv[d][j] is the kept index at cell j or -1.  Unused dimensions have n2 = nk = 1 and one-entry maps.
+struct TzGrid {
+    int dtype, D;
+    int n2[3], nk[3];
+    const int32_t* map[3];
+    const int32_t* inv[3];
+};
+
+// grid = zero-padded û: every cell written once (the kept modes gathered through inv, zeros elsewhere)
+hipError_t launch_tz_pad(const TzGrid& g, void* grid, const void* u, int num_cus, hipStream_t stream);
+// grid *= K (K real, same shape)
+hipError_t launch_tz_multiply(const TzGrid& g, void* grid, const void* K, int num_cus, hipStream_t stream);
+// out = grid at the kept modes
+hipError_t launch_tz_crop(const TzGrid& g, void* out, const void* grid, int num_cus, hipStream_t stream);
+// grid = T with the Nyquist planes (index N_d of dimension d) zeroed; T_modes may be grid itself
+hipError_t launch_tz_spectrum_load(const TzGrid& g, void* grid, const void* T_modes, int num_cus, hipStream_t stream);
+// K = scale * Re(grid)
+hipError_t launch_tz_real_part(const TzGrid& g, void* K, const void* grid, double scale, int num_cus, hipStream_t stream);
+// values = weights + 0 i (complex<T>[n] from T[n]; weights = null: ones)
+hipError_t launch_tz_weights(int dtype, void* values, const void* weights, int64_t n, int num_cus, hipStream_t stream);
+
+// Dimension 1 of the fused apply, in place: per contiguous line of k1 kept modes, backward FFT of length n (= 2 k1), times the
+// line of K, forward FFT, kept modes stored back.  data: complex<T>[nlines][k1]; K: T[nlines][n]; twiddle: exp(-2πi m / n).
+bool toeplitz_lines_supported(int dtype, int64_t n);
+hipError_t launch_toeplitz_lines(int dtype, int64_t n, void* data, const void* K, int64_t nlines, int k1, const int32_t* map,
+                                 const void* twiddle, hipStream_t stream);
+
+}  // namespace nufft

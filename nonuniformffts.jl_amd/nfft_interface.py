@@ -91,6 +91,12 @@ class NFFTPlan:
         exec_type1(out, self.p, vp)
         return out
 
+    def toeplitz(self, weights: Optional[torch.Tensor] = None, **build_overrides):
+        """The normal operator ``A^H W A`` of this plan's nodes as a ``ToeplitzOperator`` (NFFT.jl: calculateToeplitzKernel +
+        convolveToeplitzKernel!): built from the current nodes and the real ``weights`` (None = ones)."""
+        from .toeplitz import ToeplitzOperator
+        return ToeplitzOperator(self.p).set_points(self.p.points, weights, **build_overrides)
+
     def __repr__(self):
         return f"NonuniformFFTs.NFFTPlan{{{self.T}, {self.p.ndim}}} wrapping a PlanNUFFT:\n{self.p!r}"
 

@@ -1,0 +1,204 @@
+"""Toeplitz normal operator ``G = A^H W A`` of a complex plan, above the C ABI's ``nufft_toeplitz_*`` entry points.
+
+    G û = exec_type1( w ⊙ exec_type2(û) ),   w_j real weights at the points
+
+is what CG / LSQR on the normal equations applies once per iteration.  ``G[k, k'] = T[k − k']`` with ``T_d = Σ_j w_j exp(−i d·x_j)``,
+so after one build per point set it is applied with FFTs of size 2N alone, at a cost that does not depend on the number of points
+(NFFT.jl: ``calculateToeplitzKernel`` / ``convolveToeplitzKernel!``).  Plumbing only: every array operation runs in the library.
+
+    op = ToeplitzOperator(plan).set_points(points, weights)
+    g = op(u)                      # = exec_type1(w * exec_type2(u)) up to the accuracy of one NUFFT
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Sequence
+
+import torch
+
+from . import _lib
+from ._lib import lib
+from .plan import (_KERNEL_IDS, _check, _ptr_table, Direct, DimensionMismatch, FastApproximation, GaussianKernel, HalfSupport,
+                   PlanNUFFT)
+
+_PATHS = {_lib.TOEPLITZ_PATH_DENSE: "dense", _lib.TOEPLITZ_PATH_FUSED: "fused"}
+
+
+class ToeplitzOperator:
+    """``ToeplitzOperator(plan)``: tied to the geometry of a complex ``PlanNUFFT`` (element type, dims, ntransforms, fftshift, point
+    convention, window parameters, device); the plan itself is not kept and may be closed afterwards.  Real-data plans are refused:
+    their type 2 extends the half spectrum Hermitian-ly, which for even N adds the mode +N/2, and the 2N embedding aliases."""
+
+    def __init__(self, plan: PlanNUFFT):
+        if not isinstance(plan, PlanNUFFT):
+            raise ValueError("ToeplitzOperator takes a PlanNUFFT")
+        self._handle = C.c_void_p()
+        _check(lib.nufft_toeplitz_create(C.byref(self._handle), plan._handle))
+        self.Z, self.T = plan.eltype, plan.T
+        self.device = plan.device
+        self.shape = plan.shape
+        self.ndim = plan.ndim
+        self.ntransforms = plan.ntransforms
+        self._kernel, self._evalmode = plan.kernel, plan.kernel_evalmode
+
+    def close(self):
+        h = getattr(self, "_handle", None)
+        if h is not None and h.value:
+            lib.nufft_toeplitz_destroy(h)
+            self._handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self) -> _lib.NufftToeplitzInfo:
+        out = _lib.NufftToeplitzInfo()
+        out.struct_size = C.sizeof(_lib.NufftToeplitzInfo)
+        _check(lib.nufft_toeplitz_get_info(self._handle, C.byref(out)))
+        return out
+
+    @property
+    def path(self) -> str:
+        """``"fused"`` (pruned line passes, the 2N grid never exists) or ``"dense"`` (rocFFT on the 2N grid)."""
+        return _PATHS[self.info().path]
+
+    @property
+    def padded_shape(self):
+        """Tensor shape of the multiplier: 2N per dimension, reversed like ``plan.shape``."""
+        i = self.info()
+        return tuple(int(i.N2[d]) for d in reversed(range(self.ndim)))
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _require_gpu(self):
+        if self.device is None:
+            raise ValueError("host-only Toeplitz operator (plan with backend=None) has no device path")
+
+    def set_spectrum(self, T: torch.Tensor) -> "ToeplitzOperator":
+        """``T``: the type 1 of the weights on the mode set of a plan with 2N modes per dimension and ``fftshift=False`` (a complex
+        tensor of shape ``padded_shape``).  Only read."""
+        self._require_gpu()
+        if not isinstance(T, torch.Tensor) or T.device != self.device:
+            raise ValueError(f"the spectrum must be a torch tensor on {self.device}")
+        if T.dtype != self.Z:
+            raise ValueError(f"the spectrum must have element type {self.Z} (got {T.dtype})")
+        if tuple(T.shape) != self.padded_shape:
+            raise DimensionMismatch(f"wrong dimensions of the spectrum (expected tensor shape {self.padded_shape}, got {tuple(T.shape)})")
+        if not T.is_contiguous():
+            raise ValueError("the spectrum must be contiguous")
+        _check(lib.nufft_toeplitz_set_spectrum(self._handle, C.c_void_p(T.data_ptr()), self._stream()))
+        return self
+
+    def set_points(self, points, weights: Optional[torch.Tensor] = None, *, m=None, sigma: Optional[float] = None,
+                   σ: Optional[float] = None, kernel=None, kernel_evalmode=None) -> "ToeplitzOperator":
+        """Builds the multiplier from ``points`` (what ``set_points`` of the plan accepts) and real ``weights`` (None = ones) with an
+        internal plan of 2N modes that is destroyed before the call returns (it is large while it lives: 17 GB at 256³, σ = 2,
+        ComplexF64).  ``m`` / ``sigma`` / ``kernel`` / ``kernel_evalmode`` override the parent plan's window for this build."""
+        self._require_gpu()
+        if isinstance(points, torch.Tensor):
+            if points.dim() == 1:
+                points = (points,)
+            elif points.dim() == 2:
+                points = tuple(points[:, d].contiguous() for d in range(points.shape[1]))
+            else:
+                raise ValueError("unexpected point container")
+        points = tuple(points)
+        if len(points) != self.ndim:
+            raise DimensionMismatch(f"expected {self.ndim}-dimensional points")
+        for x in points:
+            if not isinstance(x, torch.Tensor) or x.device != self.device:
+                raise ValueError(f"unexpected point container: expected torch tensors on {self.device}")
+            if x.dtype != self.T:
+                raise ValueError(f"input points must have the same accuracy as the created plan (got {x.dtype})")
+            if x.dim() != 1 or not x.is_contiguous():
+                raise ValueError("unexpected point container: expected contiguous vectors")
+        n = points[0].numel()
+        if any(x.numel() != n for x in points):
+            raise DimensionMismatch("input points must have the same length along all dimensions")
+        wptr = None
+        if weights is not None:
+            if not isinstance(weights, torch.Tensor) or weights.device != self.device:
+                raise ValueError(f"weights must be a torch tensor on {self.device}")
+            if weights.dtype != self.T:
+                raise ValueError(f"weights must be real with the plan's accuracy ({self.T}); complex weights are not supported")
+            if weights.dim() != 1 or not weights.is_contiguous():
+                raise ValueError("weights must be a contiguous vector")
+            if weights.numel() != n:
+                raise DimensionMismatch(f"wrong length of the weights (expected {n}, got {weights.numel()})")
+            wptr = C.c_void_p(weights.data_ptr())
+        if σ is not None:
+            sigma = σ
+        build = None
+        if any(v is not None for v in (m, sigma, kernel, kernel_evalmode)):
+            kernel = self._kernel if kernel is None else (kernel() if isinstance(kernel, type) else kernel)
+            mode = self._evalmode if kernel_evalmode is None else (kernel_evalmode() if isinstance(kernel_evalmode, type) else kernel_evalmode)
+            if type(kernel) not in _KERNEL_IDS:
+                raise ValueError("kernel must be BackwardsKaiserBesselKernel, KaiserBesselKernel, GaussianKernel or BSplineKernel")
+            if not isinstance(mode, (Direct, FastApproximation)):
+                raise ValueError("kernel_evalmode must be Direct() or FastApproximation()")
+            prm = _lib.NufftParams()
+            prm.struct_size = C.sizeof(_lib.NufftParams)
+            prm.half_support = 0 if m is None else (m.M if isinstance(m, HalfSupport) else int(m))
+            prm.sigma = 0.0 if sigma is None else float(sigma)
+            prm.kernel = _KERNEL_IDS[type(kernel)]
+            kparam = getattr(kernel, "beta", None) if not isinstance(kernel, GaussianKernel) else kernel.ell
+            prm.kernel_param = 0.0 if kparam is None else float(kparam)
+            prm.evalmode = _lib.EVAL_DIRECT if isinstance(mode, Direct) else _lib.EVAL_FAST_APPROXIMATION
+            build = C.byref(prm)
+        _check(lib.nufft_toeplitz_set_points(self._handle, build, n, _ptr_table(points), wptr, self._stream()))
+        return self
+
+    def _check_uniform(self, us: Sequence[torch.Tensor], what: str):
+        if len(us) != self.ntransforms:
+            raise DimensionMismatch(f"wrong amount of {what} arrays (expected a tuple of {self.ntransforms} arrays)")
+        for u in us:
+            if not isinstance(u, torch.Tensor) or u.device != self.device:
+                raise ValueError(f"{what} must be torch tensors on {self.device}")
+            if u.dtype != self.Z:
+                raise ValueError(f"{what} must have element type {self.Z} (got {u.dtype})")
+            if tuple(u.shape) != self.shape:
+                raise DimensionMismatch(f"wrong dimensions of {what} array (expected tensor shape {self.shape}, got {tuple(u.shape)})")
+            if not u.is_contiguous():
+                raise ValueError(f"{what} must be contiguous")
+
+    def apply(self, u, out=None):
+        """``out = G u`` for every component; ``u``: a tensor of ``plan.shape`` or a tuple of ntransforms such tensors; ``out`` may be
+        ``u``.  Returns ``out``."""
+        self._require_gpu()
+        single = isinstance(u, torch.Tensor)
+        u_t = (u,) if single else tuple(u)
+        self._check_uniform(u_t, "input")
+        if out is None:
+            out_t = tuple(torch.empty_like(v) for v in u_t)
+            out = out_t[0] if single else out_t
+        else:
+            out_t = (out,) if isinstance(out, torch.Tensor) else tuple(out)
+            self._check_uniform(out_t, "output")
+        _check(lib.nufft_toeplitz_apply(self._handle, _ptr_table(out_t), _ptr_table(u_t), self._stream()))
+        return out
+
+    __call__ = apply
+
+    def multiplier(self) -> torch.Tensor:
+        """The real multiplier ``K`` (shape ``padded_shape``): a view of the device array the operator holds — valid while the
+        operator lives, rewritten by the next ``set_points`` / ``set_spectrum``; ``.clone()`` it to keep it."""
+        self._require_gpu()
+        ptr, nbytes = C.c_void_p(), C.c_int64()
+        _check(lib.nufft_toeplitz_multiplier_ptr(self._handle, C.byref(ptr), C.byref(nbytes)))
+        shape = self.padded_shape
+
+        class _View:       # the array-interface protocol: torch wraps the pointer without copying
+            __cuda_array_interface__ = {"shape": shape, "typestr": "<f4" if self.T == torch.float32 else "<f8",
+                                        "data": (int(ptr.value), False), "version": 2, "strides": None}
+
+        k = torch.as_tensor(_View(), device=self.device)
+        assert k.numel() * k.element_size() == nbytes.value
+        return k
+
+    def __repr__(self):
+        i = self.info()
+        return (f"ToeplitzOperator of a {self.ndim}-dimensional {self.Z} plan, N = {tuple(int(i.N[d]) for d in range(self.ndim))}, "
+                f"{self.path} path, {i.workspace_bytes / 1e6:.1f} MB")
