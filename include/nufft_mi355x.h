@@ -490,6 +490,81 @@ int nufft_toeplitz_apply(nufft_toeplitz* tz, void* const* out, const void* const
 int nufft_toeplitz_multiplier_ptr(const nufft_toeplitz* tz, void** out_ptr, int64_t* out_bytes);
 int64_t nufft_sizeof_toeplitz_info(void);
 
+/* ---- Conjugate gradients on the Toeplitz normal operator --------- */
+/* Solves (G + λ I) x_c = b_c for every component c < ntransforms independently (G is block-diagonal over components: each has its
+ * own scalars), G = what a nufft_toeplitz object applies, λ >= 0 real.  With b = nufft_exec_type1(w ⊙ y) this is the weighted,
+ * Tikhonov-regularised least-squares inverse of nufft_exec_type2.  Everything runs on the device; no scalar visits the host.
+ *
+ *     r = b − (G + λ) x0  (no x0: x = 0, r = b, no apply)     p = r     ρ = ‖r‖²     β0 = ‖b‖²
+ *     for it = 1 ... max_iter:
+ *         done ← done or (ρ <= rtol² β0)                                  per component, sticky
+ *         q = G p                                                         nufft_toeplitz_apply
+ *         γ = Re<p, q> + λ ‖p‖²                                           cg_dot_kernel
+ *         α = ρ / γ;  x += α p;  r −= α (q + λ p);  ρ' = ‖r‖²             cg_update_kernel
+ *         p = r + (ρ'/ρ) p;  ρ = ρ'                                       cg_direction_kernel
+ *         history[it][c] = sqrt(ρ / β0)
+ *
+ * A component that is done is FROZEN: the three kernels leave its x, r, p, scalars and iteration count bit-for-bit untouched.  b = 0
+ * gives x = 0 and done at once.  A γ that is not positive and finite (G is only positive semi-definite) sets done with the status
+ * NUFFT_CG_BREAKDOWN instead of dividing.  Sums and scalars are FP64 also for ComplexF32 operators; the arrays keep the operator's
+ * precision.  Sums are formed in one fixed order without atomics: two runs, and a replayed hipGraph, give the same bits.
+ *
+ * check_every = 0: all max_iter iterations are enqueued without synchronising or allocating (hipGraph-capture safe; frozen components
+ *                  cost their share of the apply only).
+ * check_every = k > 0: after every k iterations the host reads the done flags (one small copy and a stream synchronise) and stops
+ *                  enqueuing once every component is done.  Refused on a capturing stream.  Because frozen components do not change,
+ *                  both modes return bit-identical x, iteration counts and history.
+ *
+ * Added after ABI 104 without changing NUFFT_MI355X_VERSION: detect by symbol (dlsym nufft_cg_create) and compare
+ * nufft_sizeof_cg_params() / nufft_sizeof_cg_info() with your own. */
+typedef struct nufft_cg nufft_cg; /* opaque */
+
+enum { NUFFT_CG_MAX_ITER = 0,   /* max_iter iterations ran without reaching rtol */
+       NUFFT_CG_CONVERGED = 1,  /* ‖r‖ <= rtol ‖b‖ (recursive residual)         */
+       NUFFT_CG_BREAKDOWN = 2   /* γ <= 0 or not finite: stopped before dividing */ };
+
+typedef struct nufft_cg_params {
+    int32_t struct_size;     /* sizeof(nufft_cg_params) of the caller's header (0 = this layout)                                   */
+    int32_t max_iter;        /* 1 ... 2^24                                                                                         */
+    int32_t check_every;     /* 0, or the number of iterations between two looks at the done flags                                 */
+    int32_t reserved;        /* 0                                                                                                  */
+    double rtol;             /* >= 0, finite; 0 = run max_iter iterations unless ρ reaches 0 exactly                               */
+    double lambda;           /* >= 0, finite                                                                                       */
+} nufft_cg_params;
+
+typedef struct nufft_cg_info {
+    int32_t struct_size;     /* sizeof(nufft_cg_info) of the caller's header, set before the call (0 = this layout)                */
+    int32_t ntransforms, dtype, max_iter, check_every;
+    int32_t workgroups;      /* per component and kernel = length of a row of partial sums                                         */
+    int32_t iterations_enqueued; /* by the last nufft_cg_solve (check_every > 0 stops early); -1 before the first                  */
+    int32_t reserved;
+    double rtol, lambda;
+    int64_t array_bytes;     /* r, p, q: 3 arrays per component                                                                    */
+    int64_t workspace_bytes; /* device bytes owned: array_bytes + partial sums + scalars + history                                 */
+} nufft_cg_info;
+
+/* Allocates r, p, q (3 arrays per component), the partial sums, scalars and history on the operator's device, and a few pinned host
+ * words.  The solver keeps the POINTER `tz`: the operator must outlive it; nufft_toeplitz_set_points / _set_spectrum on it between two
+ * solves is allowed and simply changes G.  Refusals: a host-only operator NUFFT_ERR_NO_DEVICE; null arguments, max_iter < 1 or
+ * > 2^24, check_every < 0, rtol < 0, lambda < 0 or non-finite values NUFFT_ERR_INVALID_ARG. */
+int nufft_cg_create(nufft_cg** out, nufft_toeplitz* tz, const nufft_cg_params* params);
+int nufft_cg_destroy(nufft_cg* cg);
+/* x_inout[c], b[c]: device arrays complex(T)[N...] like those of nufft_toeplitz_apply, 16-byte aligned; b is only read.  use_x0 = 0:
+ * x is overwritten (start from zero); use_x0 != 0: x holds the starting guess (one extra apply).  Allocates nothing.  Refusals, all
+ * before anything is enqueued: operator without spectrum NUFFT_ERR_NO_POINTS; a null table or vector, a pointer that is not 16-byte
+ * aligned, x[c] overlapping any b[c'], two x overlapping, check_every > 0 on a capturing stream NUFFT_ERR_INVALID_ARG. */
+int nufft_cg_solve(nufft_cg* cg, void* const* x_inout, const void* const* b, int use_x0, void* stream);
+/* Static facts and sizes; does not synchronise. */
+int nufft_cg_get_info(const nufft_cg* cg, nufft_cg_info* out);
+/* Per-component outcome of the last solve: iterations that changed the component, NUFFT_CG_* status, sqrt(ρ / β0) (∞ if b = 0 but
+ * r != 0).  Each output may be NULL; `capacity` entries each, at least ntransforms.  Synchronises `stream` (never a capturing one). */
+int nufft_cg_get_result(nufft_cg* cg, int32_t* iterations, int32_t* status, double* residual, int64_t capacity, void* stream);
+/* host_out[(max_iter + 1) * ntransforms], row it = sqrt(ρ / β0) of every component after iteration it (row 0: the start); NaN where
+ * the component was not changed by that iteration (frozen, or beyond the last iteration run).  Synchronises `stream`. */
+int nufft_cg_history(nufft_cg* cg, double* host_out, int64_t capacity, void* stream);
+int64_t nufft_sizeof_cg_params(void);
+int64_t nufft_sizeof_cg_info(void);
+
 /* ---- misc ----------------------------------------------------------------------------- */
 /* sizeof(nufft_params) / sizeof(nufft_info) of the library build: a binding that mirrors the structs by hand
  * (ctypes, Julia) compares them with its own layout before the first call. */

@@ -106,6 +106,25 @@ class NufftToeplitzInfo(C.Structure):
 
 TOEPLITZ_PATH_DENSE, TOEPLITZ_PATH_FUSED = 0, 1
 
+
+class NufftCgParams(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("max_iter", C.c_int32), ("check_every", C.c_int32), ("reserved", C.c_int32),
+        ("rtol", C.c_double), ("lambda_", C.c_double),
+    ]
+
+
+class NufftCgInfo(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("ntransforms", C.c_int32), ("dtype", C.c_int32), ("max_iter", C.c_int32),
+        ("check_every", C.c_int32), ("workgroups", C.c_int32), ("iterations_enqueued", C.c_int32), ("reserved", C.c_int32),
+        ("rtol", C.c_double), ("lambda_", C.c_double), ("array_bytes", C.c_int64), ("workspace_bytes", C.c_int64),
+    ]
+
+
+CG_MAX_ITER, CG_CONVERGED, CG_BREAKDOWN = 0, 1, 2
+CG_STATUS_NAMES = {CG_MAX_ITER: "max_iter", CG_CONVERGED: "converged", CG_BREAKDOWN: "breakdown"}
+
 NUM_STAGES3 = 6
 STAGE_NAMES3 = ("prep_sources", "prep_targets", "premultiply", "spread", "type2", "postmultiply")
 
@@ -169,6 +188,14 @@ SYMBOLS = {
     "nufft_toeplitz_apply": (C.c_int, [_P, _PP, _PP, _P]),
     "nufft_toeplitz_multiplier_ptr": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int64)]),
     "nufft_sizeof_toeplitz_info": (C.c_int64, []),
+    "nufft_cg_create": (C.c_int, [C.POINTER(_P), _P, C.POINTER(NufftCgParams)]),
+    "nufft_cg_destroy": (C.c_int, [_P]),
+    "nufft_cg_solve": (C.c_int, [_P, _PP, _PP, C.c_int, _P]),
+    "nufft_cg_get_info": (C.c_int, [_P, C.POINTER(NufftCgInfo)]),
+    "nufft_cg_get_result": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int64, _P]),
+    "nufft_cg_history": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int64, _P]),
+    "nufft_sizeof_cg_params": (C.c_int64, []),
+    "nufft_sizeof_cg_info": (C.c_int64, []),
     "nufft_sizeof_params": (C.c_int64, []),
     "nufft_sizeof_info": (C.c_int64, []),
     "nufft_strerror": (C.c_char_p, [C.c_int]),
@@ -197,7 +224,8 @@ def _load():
     # the two structs are mirrored by hand above: refuse a library whose layout differs
     for name, mirror in (("nufft_sizeof_params", NufftParams), ("nufft_sizeof_info", NufftInfo),
                          ("nufft_sizeof_type3_params", NufftType3Params), ("nufft_sizeof_info3", NufftInfo3),
-                         ("nufft_sizeof_toeplitz_info", NufftToeplitzInfo)):
+                         ("nufft_sizeof_toeplitz_info", NufftToeplitzInfo), ("nufft_sizeof_cg_params", NufftCgParams),
+                         ("nufft_sizeof_cg_info", NufftCgInfo)):
         if getattr(lib, name)() != C.sizeof(mirror):
             raise ImportError(f"{LIB_PATH}: {name}() = {getattr(lib, name)()} but the ctypes mirror has {C.sizeof(mirror)} bytes "
                               "(include/nufft_mi355x.h and _lib.py disagree)")

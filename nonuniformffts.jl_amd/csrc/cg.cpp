@@ -1,0 +1,334 @@
+// Conjugate gradients on (G + λI) x = b, G a Toeplitz normal operator (include/nufft_mi355x.h, CG section).
+//
+// The host side only enqueues: per iteration one nufft_toeplitz_apply (unchanged) and the three kernels of cg_kernels.hip.  Every
+// scalar lives on the device; with check_every > 0 the host looks at the done flags now and then, and at nothing else.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "cg.h"
+#include "nufft_internal.h"
+
+using nufft::set_error;
+
+struct nufft_cg {
+    nufft_toeplitz* tz = nullptr;
+    int dtype = NUFFT_F64, C = 1, device = -1, num_cus = 256, G = 1;
+    int max_iter = 1, check_every = 0, enqueued = -1;
+    double rtol = 0.0, lambda = 0.0;
+    int64_t n = 0;                    // complex elements per component
+    int64_t stride = 0;               // reals between components of r, p, q
+    void* d_r = nullptr;
+    void* d_p = nullptr;
+    void* d_q = nullptr;
+    void* d_part = nullptr;           // double[C][G][2] + double[C][G]
+    void* d_scal = nullptr;           // double rho[2][C], beta0[C], res[C]; int32 flag[2][C], brk[C], iters[C], status[C]
+    void* d_hist = nullptr;           // double[max_iter + 1][C]
+    void* h_scal = nullptr;           // pinned mirror of d_scal
+    int64_t array_bytes = 0, own_bytes = 0;
+    std::vector<void*> ptab, qtab;    // the pointer tables nufft_toeplitz_apply takes
+};
+
+namespace {
+
+int fail(int code, const std::string& msg) {
+    set_error(msg);
+    return code;
+}
+
+#define CG_HIP(expr)                                                                           \
+    do {                                                                                       \
+        hipError_t e__ = (expr);                                                               \
+        if (e__ != hipSuccess)                                                                 \
+            return fail(e__ == hipErrorOutOfMemory ? NUFFT_ERR_ALLOC : NUFFT_ERR_HIP,          \
+                        std::string(#expr) + ": " + hipGetErrorString(e__));                   \
+    } while (0)
+
+struct DeviceGuard {
+    int prev = -1;
+    bool active = false;
+    explicit DeviceGuard(int dev) {
+        if (dev >= 0 && hipGetDevice(&prev) == hipSuccess && prev != dev) active = hipSetDevice(dev) == hipSuccess;
+    }
+    ~DeviceGuard() {
+        if (active) (void)hipSetDevice(prev);
+    }
+};
+
+size_t padded(size_t bytes) { return (std::max<size_t>(bytes, 16) + 255) / 256 * 256; }
+size_t real_bytes(const nufft_cg* s) { return s->dtype == NUFFT_F32 ? 4 : 8; }
+size_t scal_bytes(const nufft_cg* s) { return (size_t)s->C * (4 * sizeof(double) + 5 * sizeof(int32_t)); }
+size_t part_bytes(const nufft_cg* s) { return (size_t)s->C * s->G * 3 * sizeof(double); }
+size_t hist_bytes(const nufft_cg* s) { return (size_t)(s->max_iter + 1) * s->C * sizeof(double); }
+
+int alloc(nufft_cg* s, void** ptr, size_t bytes) {
+    bytes = padded(bytes);
+    hipError_t e = hipMalloc(ptr, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        *ptr = nullptr;
+        return fail(NUFFT_ERR_ALLOC, "hipMalloc(" + std::to_string(bytes) + ") of a CG buffer: " + hipGetErrorString(e));
+    }
+    s->own_bytes += (int64_t)bytes;
+    return NUFFT_OK;
+}
+
+void release(nufft_cg* s) {
+    if (!s) return;
+    if (s->device >= 0) {
+        DeviceGuard g(s->device);
+        for (void* p : {s->d_r, s->d_p, s->d_q, s->d_part, s->d_scal, s->d_hist})
+            if (p) (void)hipFree(p);
+        if (s->h_scal) (void)hipHostFree(s->h_scal);
+    }
+    delete s;
+}
+
+bool capturing(hipStream_t stream) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return st != hipStreamCaptureStatusNone;
+}
+
+nufft::CgScalars scalars_at(const nufft_cg* s, void* base) {
+    const int C = s->C;
+    nufft::CgScalars k{};
+    double* d = static_cast<double*>(base);
+    k.rho = d;
+    k.beta0 = d + 2 * C;
+    k.res = d + 3 * C;
+    int32_t* i = reinterpret_cast<int32_t*>(d + 4 * C);
+    k.flag = i;
+    k.brk = i + 2 * C;
+    k.iters = i + 3 * C;
+    k.status = i + 4 * C;
+    k.history = static_cast<double*>(s->d_hist);
+    k.part1 = static_cast<double*>(s->d_part);
+    k.part2 = k.part1 + (size_t)C * s->G * 2;
+    return k;
+}
+
+bool overlap(const void* a, const void* b, size_t bytes) {
+    const char* x = static_cast<const char*>(a);
+    const char* y = static_cast<const char*>(b);
+    return x < y + bytes && y < x + bytes;
+}
+
+// One kernel over all components, kCgBatch at a time.
+template <typename F>
+int for_batches(const nufft_cg* s, nufft::CgLaunch& a, void* const* x, const void* const* b, F&& launch) {
+    for (int c0 = 0; c0 < s->C; c0 += nufft::kCgBatch) {
+        a.c0 = c0;
+        a.nc = std::min(nufft::kCgBatch, s->C - c0);
+        for (int k = 0; k < a.nc; ++k) {
+            a.x[k] = x[c0 + k];
+            a.b[k] = b ? b[c0 + k] : nullptr;
+        }
+        hipError_t e = launch(a);
+        if (e != hipSuccess) return fail(NUFFT_ERR_HIP, std::string("launch of a CG kernel: ") + hipGetErrorString(e));
+    }
+    return NUFFT_OK;
+}
+
+int fetch_scalars(nufft_cg* s, hipStream_t stream) {
+    CG_HIP(hipMemcpyAsync(s->h_scal, s->d_scal, scal_bytes(s), hipMemcpyDeviceToHost, stream));
+    CG_HIP(hipStreamSynchronize(stream));
+    return NUFFT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t nufft_sizeof_cg_params(void) { return (int64_t)sizeof(nufft_cg_params); }
+int64_t nufft_sizeof_cg_info(void) { return (int64_t)sizeof(nufft_cg_info); }
+
+int nufft_cg_create(nufft_cg** out, nufft_toeplitz* tz, const nufft_cg_params* params) {
+    if (!out || !tz || !params) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    nufft_toeplitz_info ti;
+    std::memset(&ti, 0, sizeof(ti));
+    ti.struct_size = (int32_t)sizeof(ti);
+    int rc = nufft_toeplitz_get_info(tz, &ti);
+    if (rc) return rc;
+    if (ti.device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1): the solver runs on the device");
+    nufft_cg_params p;
+    std::memset(&p, 0, sizeof(p));
+    const size_t known = params->struct_size > 0 ? (size_t)params->struct_size : sizeof(p);
+    if (known < sizeof(p)) return fail(NUFFT_ERR_INVALID_ARG, "nufft_cg_params.struct_size is smaller than the published layout");
+    std::memcpy(&p, params, sizeof(p));
+    if (p.max_iter < 1) return fail(NUFFT_ERR_INVALID_ARG, "max_iter must be at least 1");
+    if (p.max_iter > (1 << 24)) return fail(NUFFT_ERR_INVALID_ARG, "max_iter beyond 2^24");
+    if (p.check_every < 0) return fail(NUFFT_ERR_INVALID_ARG, "check_every must not be negative");
+    if (!std::isfinite(p.rtol) || p.rtol < 0) return fail(NUFFT_ERR_INVALID_ARG, "rtol must be finite and not negative");
+    if (!std::isfinite(p.lambda) || p.lambda < 0) return fail(NUFFT_ERR_INVALID_ARG, "lambda must be finite and not negative");
+
+    nufft_cg* s = new (std::nothrow) nufft_cg();
+    if (!s) return fail(NUFFT_ERR_ALLOC, "out of host memory");
+    s->tz = tz;
+    s->dtype = ti.dtype;
+    s->C = ti.ntransforms;
+    s->device = ti.device;
+    s->max_iter = p.max_iter;
+    s->check_every = p.check_every;
+    s->rtol = p.rtol;
+    s->lambda = p.lambda;
+    s->n = ti.N[0] * ti.N[1] * ti.N[2];
+    const size_t rb = real_bytes(s), comp = padded((size_t)s->n * 2 * rb);
+    s->stride = (int64_t)(comp / rb);
+    s->array_bytes = 3 * (int64_t)s->C * (int64_t)comp;
+
+    DeviceGuard guard(s->device);
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device) == hipSuccess && cus > 0) s->num_cus = cus;
+    else (void)hipGetLastError();
+    s->G = nufft::cg_workgroups(s->dtype, s->n, s->num_cus);
+    if ((rc = alloc(s, &s->d_r, (size_t)s->C * comp)) || (rc = alloc(s, &s->d_p, (size_t)s->C * comp)) ||
+        (rc = alloc(s, &s->d_q, (size_t)s->C * comp)) || (rc = alloc(s, &s->d_part, part_bytes(s))) ||
+        (rc = alloc(s, &s->d_scal, scal_bytes(s))) || (rc = alloc(s, &s->d_hist, hist_bytes(s)))) {
+        const std::string keep = nufft_last_error_message();
+        release(s);
+        return fail(rc, keep);
+    }
+    if (hipHostMalloc(&s->h_scal, scal_bytes(s), hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        s->h_scal = nullptr;
+        release(s);
+        return fail(NUFFT_ERR_ALLOC, "hipHostMalloc of the solver's host mirror failed");
+    }
+    // a defined answer from nufft_cg_get_result / nufft_cg_history before the first solve
+    if (hipMemset(s->d_scal, 0, scal_bytes(s)) != hipSuccess || hipMemset(s->d_hist, 0xFF, hist_bytes(s)) != hipSuccess) {
+        (void)hipGetLastError();
+        release(s);
+        return fail(NUFFT_ERR_HIP, "hipMemset of the solver's scalars failed");
+    }
+    for (int c = 0; c < s->C; ++c) {
+        s->ptab.push_back(static_cast<char*>(s->d_p) + (size_t)c * comp);
+        s->qtab.push_back(static_cast<char*>(s->d_q) + (size_t)c * comp);
+    }
+    *out = s;
+    return NUFFT_OK;
+}
+
+int nufft_cg_destroy(nufft_cg* cg) {
+    release(cg);
+    return NUFFT_OK;
+}
+
+int nufft_cg_get_info(const nufft_cg* s, nufft_cg_info* o) {
+    if (!s || !o) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    nufft_cg_info i;
+    std::memset(&i, 0, sizeof(i));
+    const size_t known = o->struct_size > 0 ? std::min((size_t)o->struct_size, sizeof(i)) : sizeof(i);
+    i.struct_size = (int32_t)known;
+    i.ntransforms = s->C;
+    i.dtype = s->dtype;
+    i.max_iter = s->max_iter;
+    i.check_every = s->check_every;
+    i.workgroups = s->G;
+    i.iterations_enqueued = s->enqueued;
+    i.rtol = s->rtol;
+    i.lambda = s->lambda;
+    i.array_bytes = s->array_bytes;
+    i.workspace_bytes = s->own_bytes;
+    std::memcpy(o, &i, known);
+    return NUFFT_OK;
+}
+
+int nufft_cg_solve(nufft_cg* s, void* const* x, const void* const* b, int use_x0, void* stream_) {
+    if (!s) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    nufft_toeplitz_info ti;
+    std::memset(&ti, 0, sizeof(ti));
+    ti.struct_size = (int32_t)sizeof(ti);
+    int rc = nufft_toeplitz_get_info(s->tz, &ti);
+    if (rc) return rc;
+    if (!ti.has_spectrum)
+        return fail(NUFFT_ERR_NO_POINTS, "nufft_toeplitz_set_spectrum or nufft_toeplitz_set_points must be called before nufft_cg_solve");
+    if (!x || !b) return fail(NUFFT_ERR_INVALID_ARG, "null table");
+    const size_t bytes = (size_t)s->n * 2 * real_bytes(s);
+    for (int c = 0; c < s->C; ++c) {
+        if (!x[c] || !b[c]) return fail(NUFFT_ERR_INVALID_ARG, "null data vector");
+        if (((uintptr_t)x[c] | (uintptr_t)b[c]) & 15) return fail(NUFFT_ERR_INVALID_ARG, "x and b must be 16-byte aligned");
+    }
+    for (int c = 0; c < s->C; ++c)
+        for (int k = 0; k < s->C; ++k) {
+            if (overlap(x[c], b[k], bytes)) return fail(NUFFT_ERR_INVALID_ARG, "x overlaps b: the right-hand side is read while x is written");
+            if (k != c && overlap(x[c], x[k], bytes)) return fail(NUFFT_ERR_INVALID_ARG, "two components of x overlap");
+        }
+    DeviceGuard guard(s->device);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (s->check_every > 0 && capturing(stream))
+        return fail(NUFFT_ERR_INVALID_ARG, "check_every > 0 synchronises the stream: not on a capturing stream (use check_every = 0)");
+
+    nufft::CgLaunch a{};
+    a.dtype = s->dtype;
+    a.C = s->C;
+    a.G = s->G;
+    a.n = s->n;
+    a.stride = s->stride;
+    a.r = s->d_r;
+    a.p = s->d_p;
+    a.q = s->d_q;
+    a.lambda = s->lambda;
+    a.rtol = s->rtol;
+    a.max_iter = s->max_iter;
+    a.it = 0;
+    a.s = scalars_at(s, s->d_scal);
+
+    s->enqueued = 0;
+    const bool warm = use_x0 != 0;
+    if (warm && (rc = nufft_toeplitz_apply(s->tz, s->qtab.data(), x, stream))) return rc;      // q = G x0
+    if ((rc = for_batches(s, a, x, b, [&](const nufft::CgLaunch& l) { return nufft::launch_cg_residual(l, warm, stream); }))) return rc;
+    if ((rc = for_batches(s, a, x, b, [&](const nufft::CgLaunch& l) { return nufft::launch_cg_start(l, stream); }))) return rc;
+    const nufft::CgScalars host = scalars_at(s, s->h_scal);
+    for (int it = 1; it <= s->max_iter; ++it) {
+        a.it = it;
+        if ((rc = nufft_toeplitz_apply(s->tz, s->qtab.data(), s->ptab.data(), stream))) return rc;
+        if ((rc = for_batches(s, a, x, nullptr, [&](const nufft::CgLaunch& l) { return nufft::launch_cg_dot(l, stream); }))) return rc;
+        if ((rc = for_batches(s, a, x, nullptr, [&](const nufft::CgLaunch& l) { return nufft::launch_cg_update(l, stream); }))) return rc;
+        if ((rc = for_batches(s, a, x, nullptr, [&](const nufft::CgLaunch& l) { return nufft::launch_cg_direction(l, stream); }))) return rc;
+        s->enqueued = it;
+        if (s->check_every > 0 && it % s->check_every == 0 && it < s->max_iter) {
+            if ((rc = fetch_scalars(s, stream))) return rc;
+            bool all = true;
+            for (int c = 0; c < s->C; ++c) all = all && host.flag[((it + 1) & 1) * s->C + c] != 0;
+            if (all) break;
+        }
+    }
+    return NUFFT_OK;
+}
+
+int nufft_cg_get_result(nufft_cg* s, int32_t* iterations, int32_t* status, double* residual, int64_t capacity, void* stream_) {
+    if (!s) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    if (capacity < s->C) return fail(NUFFT_ERR_INVALID_ARG, "capacity is smaller than ntransforms");
+    DeviceGuard guard(s->device);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (capturing(stream)) return fail(NUFFT_ERR_INVALID_ARG, "nufft_cg_get_result synchronises: not on a capturing stream");
+    int rc = fetch_scalars(s, stream);
+    if (rc) return rc;
+    const nufft::CgScalars host = scalars_at(s, s->h_scal);
+    for (int c = 0; c < s->C; ++c) {
+        if (iterations) iterations[c] = host.iters[c];
+        if (status) status[c] = host.status[c];
+        if (residual) residual[c] = host.res[c];
+    }
+    return NUFFT_OK;
+}
+
+int nufft_cg_history(nufft_cg* s, double* host_out, int64_t capacity, void* stream_) {
+    if (!s || !host_out) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    if (capacity < (int64_t)(s->max_iter + 1) * s->C) return fail(NUFFT_ERR_INVALID_ARG, "capacity is smaller than (max_iter + 1) * ntransforms");
+    DeviceGuard guard(s->device);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (capturing(stream)) return fail(NUFFT_ERR_INVALID_ARG, "nufft_cg_history synchronises: not on a capturing stream");
+    CG_HIP(hipMemcpyAsync(host_out, s->d_hist, hist_bytes(s), hipMemcpyDeviceToHost, stream));
+    CG_HIP(hipStreamSynchronize(stream));
+    return NUFFT_OK;
+}
+
+}  // extern "C"

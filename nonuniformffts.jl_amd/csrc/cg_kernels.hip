@@ -1,0 +1,350 @@
+// Kernels of the conjugate-gradient solver on the Toeplitz normal operator (cg.cpp).
+//
+// Every scalar of CG here is real (α, ρ'/ρ, λ) and Re<p, q> = Σ over the 2n reals of p ⊙ q, so the kernels treat a component as a
+// vector of 2n reals: 16-byte packs (two Float64 or four Float32), grid-stride, two packs per thread and trip, gridDim.y = component.
+//
+// No workgroup hands anything to another inside a launch and there are no floating-point atomics: a kernel leaves one partial sum
+// per workgroup (plain stores), and every workgroup of the NEXT kernel adds that row up itself, in one fixed order (thread t takes
+// entries t, t + 256, ...; then the wave shuffles; then four LDS words).  The kernel boundary makes the partials visible, the fixed
+// order makes every workgroup, every run and every graph replay get the same bits.  Sums and scalars are FP64 for both element types.
+//
+// A component whose done flag is set is frozen: its workgroups leave after reading the flag.  The first workgroup of the last
+// kernel of an iteration writes the scalars of the next one into the other parity slot (every workgroup of that kernel still reads
+// the current slot); for a frozen component it only carries flag and ρ over.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+
+#include "cg.h"
+#include "nufft_mi355x.h"
+
+namespace nufft {
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+
+template <typename T>
+struct alignas(16) Pack {
+    static constexpr int W = 16 / sizeof(T);
+    T v[W];
+};
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+// Sum over the workgroup, returned to every thread.
+__device__ __forceinline__ double block_sum(double v, double* lds) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = lds[0];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) t += lds[w];
+    __syncthreads();
+    return t;
+}
+
+// Σ_g row[g * pitch], g < G, in the fixed order described at the top.
+__device__ __forceinline__ double row_sum(const double* row, int G, int pitch, double* lds) {
+    double v = 0.0;
+    for (int g = threadIdx.x; g < G; g += kThreads) v += row[(int64_t)g * pitch];
+    return block_sum(v, lds);
+}
+
+__device__ __forceinline__ double relative(double rho, double beta0) {
+    return beta0 > 0.0 ? sqrt(rho / beta0) : (rho == 0.0 ? 0.0 : INFINITY);
+}
+
+template <typename T>
+__device__ __forceinline__ Pack<T> load(const T* a, int64_t pack) {
+    return *reinterpret_cast<const Pack<T>*>(a + pack * Pack<T>::W);
+}
+template <typename T>
+__device__ __forceinline__ void store(T* a, int64_t pack, const Pack<T>& v) {
+    *reinterpret_cast<Pack<T>*>(a + pack * Pack<T>::W) = v;
+}
+
+// The loop shape shared by all kernels: BODY(first real, count) is called for whole packs (count = W, 16-byte aligned) and, by one
+// thread, for the reals behind the last whole pack (ComplexF32 with an odd number of elements).
+#define CG_FOR_EACH_PACK(T, nreal, i)                                                                        \
+    const int64_t npacks__ = (nreal) / Pack<T>::W;                                                           \
+    const int64_t step__ = (int64_t)gridDim.x * kThreads;                                                    \
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < npacks__; i += 2 * step__)
+
+// r = b − (q + λ x) (WARM; q = G x) or r = b, x = 0;  p = r;  partial sums of |r|² and |b|²
+template <typename T, bool WARM>
+__global__ __launch_bounds__(kThreads) void cg_residual_kernel(CgLaunch a) {
+    __shared__ double lds[kWaves];
+    constexpr int W = Pack<T>::W;
+    const int c = a.c0 + blockIdx.y;
+    T* x = static_cast<T*>(a.x[blockIdx.y]);
+    const T* b = static_cast<const T*>(a.b[blockIdx.y]);
+    T* r = static_cast<T*>(a.r) + c * a.stride;
+    T* p = static_cast<T*>(a.p) + c * a.stride;
+    const T* q = static_cast<const T*>(a.q) + c * a.stride;
+    const T lam = (T)a.lambda;
+    const int64_t nreal = 2 * a.n;
+    double srr = 0.0, sbb = 0.0;
+    auto one = [&](T bv, T qv, T xv) {
+        const T rv = WARM ? bv - (qv + lam * xv) : bv;
+        srr += (double)rv * (double)rv;
+        sbb += (double)bv * (double)bv;
+        return rv;
+    };
+    CG_FOR_EACH_PACK(T, nreal, i) {
+        const int64_t j = i + step__;
+        const bool two = j < npacks__;
+        Pack<T> b0 = load(b, i), b1{}, q0{}, q1{}, x0{}, x1{};
+        if (two) b1 = load(b, j);
+        if (WARM) {
+            q0 = load(q, i);
+            x0 = load(x, i);
+            if (two) { q1 = load(q, j); x1 = load(x, j); }
+        }
+        Pack<T> r0, r1;
+#pragma unroll
+        for (int w = 0; w < W; ++w) r0.v[w] = one(b0.v[w], q0.v[w], x0.v[w]);
+        store(r, i, r0);
+        store(p, i, r0);
+        if (!WARM) store(x, i, Pack<T>{});
+        if (two) {
+#pragma unroll
+            for (int w = 0; w < W; ++w) r1.v[w] = one(b1.v[w], q1.v[w], x1.v[w]);
+            store(r, j, r1);
+            store(p, j, r1);
+            if (!WARM) store(x, j, Pack<T>{});
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (int64_t e = npacks__ * W; e < nreal; ++e) {
+            const T rv = one(b[e], WARM ? q[e] : T(0), WARM ? x[e] : T(0));
+            r[e] = rv;
+            p[e] = rv;
+            if (!WARM) x[e] = T(0);
+        }
+    srr = block_sum(srr, lds);
+    sbb = block_sum(sbb, lds);
+    if (threadIdx.x == 0) {
+        double* out = a.s.part1 + ((int64_t)c * a.G + blockIdx.x) * 2;
+        out[0] = srr;
+        out[1] = sbb;
+    }
+}
+
+// One workgroup per component: the scalars before the first iteration, and NaN into the history rows no iteration has written.
+__global__ __launch_bounds__(kThreads) void cg_start_kernel(CgLaunch a) {
+    __shared__ double lds[kWaves];
+    const int c = a.c0 + blockIdx.y;
+    const double* row = a.s.part1 + (int64_t)c * a.G * 2;
+    const double rr = row_sum(row, a.G, 2, lds);
+    const double bb = row_sum(row + 1, a.G, 2, lds);
+    for (int it = 1 + threadIdx.x; it <= a.max_iter; it += kThreads) a.s.history[(int64_t)it * a.C + c] = NAN;
+    if (threadIdx.x == 0) {
+        const int done = rr <= a.rtol * a.rtol * bb ? 1 : 0;
+        a.s.rho[c] = rr;
+        a.s.rho[a.C + c] = rr;
+        a.s.beta0[c] = bb;
+        a.s.res[c] = relative(rr, bb);
+        a.s.history[c] = relative(rr, bb);
+        a.s.flag[c] = done;
+        a.s.flag[a.C + c] = done;
+        a.s.brk[c] = 0;
+        a.s.iters[c] = 0;
+        a.s.status[c] = done ? NUFFT_CG_CONVERGED : NUFFT_CG_MAX_ITER;
+    }
+}
+
+// Kernel 1: partial sums of Re<p, q> and |p|²
+template <typename T>
+__global__ __launch_bounds__(kThreads) void cg_dot_kernel(CgLaunch a) {
+    __shared__ double lds[kWaves];
+    constexpr int W = Pack<T>::W;
+    const int c = a.c0 + blockIdx.y;
+    if (a.s.flag[(a.it & 1) * a.C + c]) return;
+    const T* p = static_cast<const T*>(a.p) + c * a.stride;
+    const T* q = static_cast<const T*>(a.q) + c * a.stride;
+    const int64_t nreal = 2 * a.n;
+    double spq = 0.0, spp = 0.0;
+    CG_FOR_EACH_PACK(T, nreal, i) {
+        const int64_t j = i + step__;
+        const bool two = j < npacks__;
+        Pack<T> p0 = load(p, i), q0 = load(q, i), p1{}, q1{};
+        if (two) { p1 = load(p, j); q1 = load(q, j); }
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+            spq += (double)p0.v[w] * (double)q0.v[w];
+            spp += (double)p0.v[w] * (double)p0.v[w];
+        }
+#pragma unroll
+        for (int w = 0; w < W; ++w) {      // zeros when there is no second pack
+            spq += (double)p1.v[w] * (double)q1.v[w];
+            spp += (double)p1.v[w] * (double)p1.v[w];
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (int64_t e = npacks__ * W; e < nreal; ++e) {
+            spq += (double)p[e] * (double)q[e];
+            spp += (double)p[e] * (double)p[e];
+        }
+    spq = block_sum(spq, lds);
+    spp = block_sum(spp, lds);
+    if (threadIdx.x == 0) {
+        double* out = a.s.part1 + ((int64_t)c * a.G + blockIdx.x) * 2;
+        out[0] = spq;
+        out[1] = spp;
+    }
+}
+
+// Kernel 2: γ = Re<p, q> + λ|p|² from kernel 1's partials, α = ρ / γ;  x += α p;  r −= α (q + λ p);  partial sums of |r|²
+template <typename T>
+__global__ __launch_bounds__(kThreads) void cg_update_kernel(CgLaunch a) {
+    __shared__ double lds[kWaves];
+    constexpr int W = Pack<T>::W;
+    const int c = a.c0 + blockIdx.y;
+    const int slot = (a.it & 1) * a.C + c;
+    if (a.s.flag[slot]) return;
+    const double* row = a.s.part1 + (int64_t)c * a.G * 2;
+    const double pq = row_sum(row, a.G, 2, lds);
+    const double pp = row_sum(row + 1, a.G, 2, lds);
+    const double gamma = pq + a.lambda * pp;
+    const bool bad = !(gamma > 0.0) || !isfinite(gamma);      // the same bits in every workgroup: they all leave, or none does
+    if (blockIdx.x == 0 && threadIdx.x == 0) a.s.brk[c] = bad ? 1 : 0;
+    if (bad) return;
+    const T al = (T)(a.s.rho[slot] / gamma), lam = (T)a.lambda;
+    T* x = static_cast<T*>(a.x[blockIdx.y]);
+    T* r = static_cast<T*>(a.r) + c * a.stride;
+    const T* p = static_cast<const T*>(a.p) + c * a.stride;
+    const T* q = static_cast<const T*>(a.q) + c * a.stride;
+    const int64_t nreal = 2 * a.n;
+    double srr = 0.0;
+    auto one = [&](T& xv, T& rv, T pv, T qv) {
+        xv += al * pv;
+        rv -= al * (qv + lam * pv);
+        srr += (double)rv * (double)rv;
+    };
+    CG_FOR_EACH_PACK(T, nreal, i) {
+        const int64_t j = i + step__;
+        const bool two = j < npacks__;
+        Pack<T> x0 = load(x, i), r0 = load(r, i), p0 = load(p, i), q0 = load(q, i), x1{}, r1{}, p1{}, q1{};
+        if (two) { x1 = load(x, j); r1 = load(r, j); p1 = load(p, j); q1 = load(q, j); }
+#pragma unroll
+        for (int w = 0; w < W; ++w) one(x0.v[w], r0.v[w], p0.v[w], q0.v[w]);
+        store(x, i, x0);
+        store(r, i, r0);
+        if (two) {
+#pragma unroll
+            for (int w = 0; w < W; ++w) one(x1.v[w], r1.v[w], p1.v[w], q1.v[w]);
+            store(x, j, x1);
+            store(r, j, r1);
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (int64_t e = npacks__ * W; e < nreal; ++e) one(x[e], r[e], p[e], q[e]);
+    srr = block_sum(srr, lds);
+    if (threadIdx.x == 0) a.s.part2[(int64_t)c * a.G + blockIdx.x] = srr;
+}
+
+// Kernel 3: ρ' from kernel 2's partials;  p = r + (ρ'/ρ) p;  the first workgroup writes the scalars of the next iteration
+template <typename T>
+__global__ __launch_bounds__(kThreads) void cg_direction_kernel(CgLaunch a) {
+    __shared__ double lds[kWaves];
+    constexpr int W = Pack<T>::W;
+    const int c = a.c0 + blockIdx.y;
+    const int slot = (a.it & 1) * a.C + c, next = ((a.it + 1) & 1) * a.C + c;
+    const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+    const bool frozen = a.s.flag[slot] != 0, bad = !frozen && a.s.brk[c] != 0;
+    if (frozen || bad) {
+        if (first) {
+            a.s.flag[next] = 1;
+            a.s.rho[next] = a.s.rho[slot];
+            if (bad) a.s.status[c] = NUFFT_CG_BREAKDOWN;
+        }
+        return;
+    }
+    const double rr = row_sum(a.s.part2 + (int64_t)c * a.G, a.G, 1, lds);
+    const T bt = (T)(rr / a.s.rho[slot]);           // ρ > 0: the component is not done
+    const T* r = static_cast<const T*>(a.r) + c * a.stride;
+    T* p = static_cast<T*>(a.p) + c * a.stride;
+    const int64_t nreal = 2 * a.n;
+    CG_FOR_EACH_PACK(T, nreal, i) {
+        const int64_t j = i + step__;
+        const bool two = j < npacks__;
+        Pack<T> r0 = load(r, i), p0 = load(p, i), r1{}, p1{};
+        if (two) { r1 = load(r, j); p1 = load(p, j); }
+#pragma unroll
+        for (int w = 0; w < W; ++w) p0.v[w] = r0.v[w] + bt * p0.v[w];
+        store(p, i, p0);
+        if (two) {
+#pragma unroll
+            for (int w = 0; w < W; ++w) p1.v[w] = r1.v[w] + bt * p1.v[w];
+            store(p, j, p1);
+        }
+    }
+    if (first) {
+        for (int64_t e = npacks__ * W; e < nreal; ++e) p[e] = r[e] + bt * p[e];
+        const double bb = a.s.beta0[c];
+        const int done = rr <= a.rtol * a.rtol * bb ? 1 : 0;
+        a.s.rho[next] = rr;
+        a.s.flag[next] = done;
+        a.s.res[c] = relative(rr, bb);
+        a.s.history[(int64_t)a.it * a.C + c] = relative(rr, bb);
+        a.s.iters[c] = a.it;
+        a.s.status[c] = done ? NUFFT_CG_CONVERGED : NUFFT_CG_MAX_ITER;
+    }
+}
+
+#undef CG_FOR_EACH_PACK
+
+}  // namespace
+
+int cg_workgroups(int dtype, int64_t n, int num_cus) {
+    const int64_t packs = (2 * n) / (dtype == NUFFT_F32 ? 4 : 2);
+    const int64_t need = (packs + 2 * kThreads - 1) / (2 * kThreads);      // two packs per thread and trip
+    const int64_t cap = (int64_t)std::max(num_cus, 1) * 4;                 // 4 workgroups of 4 waves per CU, 32 – 128 B in flight per thread
+    return (int)std::max<int64_t>(1, std::min(need, cap));
+}
+
+hipError_t launch_cg_residual(const CgLaunch& a, bool warm, hipStream_t stream) {
+    const dim3 gr(a.G, a.nc), bl(kThreads);
+    if (a.dtype == NUFFT_F32) {
+        if (warm) hipLaunchKernelGGL((cg_residual_kernel<float, true>), gr, bl, 0, stream, a);
+        else hipLaunchKernelGGL((cg_residual_kernel<float, false>), gr, bl, 0, stream, a);
+    } else {
+        if (warm) hipLaunchKernelGGL((cg_residual_kernel<double, true>), gr, bl, 0, stream, a);
+        else hipLaunchKernelGGL((cg_residual_kernel<double, false>), gr, bl, 0, stream, a);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_cg_start(const CgLaunch& a, hipStream_t stream) {
+    hipLaunchKernelGGL(cg_start_kernel, dim3(1, a.nc), dim3(kThreads), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_cg_dot(const CgLaunch& a, hipStream_t stream) {
+    const dim3 gr(a.G, a.nc), bl(kThreads);
+    if (a.dtype == NUFFT_F32) hipLaunchKernelGGL((cg_dot_kernel<float>), gr, bl, 0, stream, a);
+    else hipLaunchKernelGGL((cg_dot_kernel<double>), gr, bl, 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_cg_update(const CgLaunch& a, hipStream_t stream) {
+    const dim3 gr(a.G, a.nc), bl(kThreads);
+    if (a.dtype == NUFFT_F32) hipLaunchKernelGGL((cg_update_kernel<float>), gr, bl, 0, stream, a);
+    else hipLaunchKernelGGL((cg_update_kernel<double>), gr, bl, 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_cg_direction(const CgLaunch& a, hipStream_t stream) {
+    const dim3 gr(a.G, a.nc), bl(kThreads);
+    if (a.dtype == NUFFT_F32) hipLaunchKernelGGL((cg_direction_kernel<float>), gr, bl, 0, stream, a);
+    else hipLaunchKernelGGL((cg_direction_kernel<double>), gr, bl, 0, stream, a);
+    return hipGetLastError();
+}
+
+}  // namespace nufft

@@ -182,6 +182,18 @@ class ToeplitzOperator:
 
     __call__ = apply
 
+    def solve(self, b, x0=None, out=None, **kw):
+        """One-shot ``ToeplitzCG(self, **kw).solve(b, x0, out)``: conjugate gradients on ``(G + lam I) x = b`` (cg.py); the solver's
+        arrays are freed before returning.  Returns ``out``."""
+        from .cg import ToeplitzCG
+        sol = ToeplitzCG(self, **kw)
+        try:
+            out = sol.solve(b, x0=x0, out=out)
+            torch.cuda.current_stream(self.device).synchronize()       # the solver's arrays go away below
+        finally:
+            sol.close()
+        return out
+
     def multiplier(self) -> torch.Tensor:
         """The real multiplier ``K`` (shape ``padded_shape``): a view of the device array the operator holds — valid while the
         operator lives, rewritten by the next ``set_points`` / ``set_spectrum``; ``.clone()`` it to keep it."""
