@@ -565,6 +565,101 @@ int nufft_cg_history(nufft_cg* cg, double* host_out, int64_t capacity, void* str
 int64_t nufft_sizeof_cg_params(void);
 int64_t nufft_sizeof_cg_info(void);
 
+/* ---- Sample-density compensation weights ------------------------ */
+/* The weights w_j of nufft_exec_type1_cb / nufft_toeplitz_set_points for a point set, by the fixed-point iteration of Pipe & Menon
+ * (MRM 41, 1999; NFFT.jl: sdc).  C is interpolation after spreading on the fine grid of a REAL-data plan with the parent plan's window:
+ * (C w)_j = nufft_interpolate of the grid that nufft_fill_zeros + nufft_spread of w leaves — no FFT, no deconvolution.  All four windows
+ * are non-negative, so C w > 0 for w > 0.
+ *
+ *     w = s 1 (or the caller's positive w0)
+ *     for k = 0 ... max_iter − 1:
+ *         v = C w                                                 nufft_fill_zeros, nufft_spread_deferred, nufft_interpolate
+ *         δ_k = max_j |v_j − 1|;  bad = some v_j not positive and finite      dcf_check_kernel
+ *         done ← done or bad or (k >= 1 and δ_k <= tol)           sticky      dcf_update_kernel
+ *         w ← w / v                                               not applied once done
+ *     finish: w ← w / Σ_j w_j  (NUFFT_DCF_NORMALIZE_SUM)  or unchanged (NUFFT_DCF_NORMALIZE_NONE)
+ *
+ * w / (C w) does not depend on the scale of w, so the first iterate is the same for every s, and δ_0 of the all-ones start only measures
+ * the normalisation of the window: it is neither reported nor tested.  With a caller's w0 δ_0 is reported (never tested: k >= 1).
+ * The window is not normalised (C 1 is about 1e30 in 2-D and 1e45 in 3-D at M = 4), which Float32 cannot hold.  The library's windows
+ * carry an exact factor 2^k_d (nufft_info.window_scale_log2), so its C is 2^κ times the mathematical one, κ = 2 Σ_d k_d
+ * (nufft_dcf_info.window_scale_log2), with values of order one.  The iteration runs on u = w / 2^κ, for which C w is what the device
+ * computes from u: s = 2^κ, no intermediate leaves the range of Float32 in any dimension, and the normalised result does not contain
+ * 2^κ at all.  NUFFT_DCF_NORMALIZE_NONE multiplies by 2^κ at the end, which in Float32 underflows where the true weights do (3-D);
+ * a caller's w0 is read in true units, and its C w0 overflows Float32 where the true value does (status NUFFT_DCF_BREAKDOWN).
+ * Σ w = 1 makes the diagonal of G = A^H W A one (G[k, k] = T_0 = Σ_j w_j): the scaling under which nufft_exec_type1 of w ⊙ y
+ * approximates the inverse of nufft_exec_type2.
+ *
+ * A v_j that is not positive and finite (possible only with NaN coordinates, or a w0 whose C w0 leaves the range), or a w0 entry that
+ * is not positive and finite, sets NUFFT_DCF_BREAKDOWN before anything is divided and leaves w as it was: the caller's w0, or the
+ * iterate of the last completed iteration in the units of u, without the finish.
+ * δ and Σ w are FP64 for both element types, formed without atomics in one fixed order; the weights are NOT bit-reproducible between
+ * runs all the same, because spreading accumulates with LDS and global atomics in an order that varies.
+ *
+ * check_every = 0: all max_iter iterations are enqueued without synchronising or allocating (hipGraph-capture safe); a finished
+ *                  state freezes w on the device, the remaining spreads and gathers run as scratch work.
+ * check_every = k > 0: after every k iterations the host reads the done flag and stops enqueuing.  Refused on a capturing stream.
+ *
+ * The object owns an internal real-data plan (dtype, ndim, N, σ, half support, kernel, the parent's shape parameter per dimension,
+ * evaluation mode, point convention, options, device of the parent; ntransforms = 1; fftshift does not matter) that is kept across
+ * point sets; no pointer to the parent is kept.  Its fine grid can differ from a complex parent's in dimension 1, where a real plan
+ * needs an even size: nufft_dcf_info.N_over is the grid actually used.
+ * Added after ABI 104 without changing NUFFT_MI355X_VERSION: detect by symbol (dlsym nufft_dcf_create) and compare
+ * nufft_sizeof_dcf_params() / nufft_sizeof_dcf_info() with your own. */
+typedef struct nufft_dcf nufft_dcf; /* opaque */
+
+enum { NUFFT_DCF_MAX_ITER = 0,   /* max_iter iterations ran                                     */
+       NUFFT_DCF_CONVERGED = 1,  /* δ_k <= tol at some k >= 1                                   */
+       NUFFT_DCF_BREAKDOWN = 2   /* a v_j or w0_j not positive and finite: nothing was divided  */ };
+enum { NUFFT_DCF_NORMALIZE_SUM = 0, NUFFT_DCF_NORMALIZE_NONE = 1 };
+
+typedef struct nufft_dcf_params {
+    int32_t struct_size;     /* sizeof(nufft_dcf_params) of the caller's header (0 = this layout)                                  */
+    int32_t max_iter;        /* 1 ... 2^24                                                                                         */
+    int32_t check_every;     /* 0, or the number of iterations between two looks at the done flag                                  */
+    int32_t normalize;       /* NUFFT_DCF_NORMALIZE_*                                                                              */
+    double tol;              /* >= 0, finite; 0 = run max_iter iterations                                                          */
+} nufft_dcf_params;
+
+typedef struct nufft_dcf_info {
+    int32_t struct_size;     /* sizeof(nufft_dcf_info) of the caller's header, set before the call (0 = this layout)               */
+    int32_t ndim, dtype, device, max_iter, check_every, normalize;
+    int32_t workgroups;      /* of the array kernels for the current point set (0: none yet)                                       */
+    int32_t iterations_enqueued; /* by the last nufft_dcf_compute (check_every > 0 stops early); -1 before the first              */
+    int32_t window_scale_log2;   /* κ: the device's C is 2^κ times the mathematical one                                            */
+    int64_t N_over[3];       /* fine grid of the internal real plan (1 beyond ndim)                                                */
+    double tol;
+    double beta[3];          /* window shape parameter per dimension (the parent's)                                                */
+    int64_t capacity;        /* points the vector v holds; grows with nufft_dcf_set_points, never shrinks                          */
+    int64_t num_points;      /* of the last nufft_dcf_set_points (-1: none yet)                                                    */
+    int64_t workspace_bytes; /* device bytes the object owns next to its plan (a host-only object: what a device object of these
+                                parameters and this capacity holds): v, partials, scalars, history                                 */
+    int64_t plan_bytes;      /* nufft_info.workspace_bytes of the internal plan right now (0 for a host-only object)               */
+} nufft_dcf_info;
+
+/* Builds the internal plan and allocates partials, scalars, history and a few pinned host words.  A host-only plan (device = -1) gives
+ * a host-only object that answers nufft_dcf_get_info only.  Refusals: null arguments, max_iter < 1 or > 2^24, check_every < 0, tol < 0
+ * or not finite, an unknown normalize NUFFT_ERR_INVALID_ARG; whatever nufft_plan_create_ex refuses for the internal plan. */
+int nufft_dcf_create(nufft_dcf** out, const nufft_plan* plan, const nufft_dcf_params* params);
+int nufft_dcf_destroy(nufft_dcf* dcf);
+/* As nufft_set_points on the internal plan.  Grows v when num_points exceeds the capacity (never on a capturing stream). */
+int nufft_dcf_set_points(nufft_dcf* dcf, int64_t num_points, const void* const* coords, void* stream);
+/* w_inout: device vector T[num_points] (real, the plan's precision, 16-byte aligned) in the caller's point order.  use_w0 = 0: it is
+ * overwritten; use_w0 != 0: it holds the start.  Allocates nothing.  num_points = 0 is a no-op.  Refusals, all before anything is
+ * enqueued: a host-only object NUFFT_ERR_NO_DEVICE, no points yet NUFFT_ERR_NO_POINTS, a null or misaligned pointer, check_every > 0
+ * on a capturing stream NUFFT_ERR_INVALID_ARG. */
+int nufft_dcf_compute(nufft_dcf* dcf, void* w_inout, int use_w0, void* stream);
+/* Static facts and sizes; does not synchronise. */
+int nufft_dcf_get_info(const nufft_dcf* dcf, nufft_dcf_info* out);
+/* Outcome of the last compute: divisions applied, NUFFT_DCF_* status, the last reported δ (NaN: none).  Each output may be NULL.
+ * Synchronises `stream` (never a capturing one). */
+int nufft_dcf_get_result(nufft_dcf* dcf, int32_t* iterations, int32_t* status, double* residual, void* stream);
+/* host_out[max_iter]: entry k = δ_k (entry 0 only with a caller's w0); NaN where iteration k reported nothing (δ_0 of the all-ones
+ * start, frozen, or beyond the last iteration run).  Synchronises `stream`. */
+int nufft_dcf_history(nufft_dcf* dcf, double* host_out, int64_t capacity, void* stream);
+int64_t nufft_sizeof_dcf_params(void);
+int64_t nufft_sizeof_dcf_info(void);
+
 /* ---- misc ----------------------------------------------------------------------------- */
 /* sizeof(nufft_params) / sizeof(nufft_info) of the library build: a binding that mirrors the structs by hand
  * (ctypes, Julia) compares them with its own layout before the first call. */

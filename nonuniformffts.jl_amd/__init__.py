@@ -19,6 +19,7 @@ from .nfft_interface import NFFTPlan, plan_nfft  # noqa: F401
 from .type3 import PlanNUFFT3, exec_type3, exec_type3_grad, set_points3  # noqa: F401
 from .toeplitz import ToeplitzOperator  # noqa: F401
 from .cg import ToeplitzCG  # noqa: F401
+from .dcf import DensityCompensation, density_weights  # noqa: F401
 from . import autograd  # noqa: F401
 
 __all__ = [
@@ -29,4 +30,5 @@ __all__ = [
     "PlanNUFFT3", "set_points3", "exec_type3", "exec_type3_grad",
     "exec_type2_grad", "interpolate_grad", "autograd",
     "ToeplitzOperator", "ToeplitzCG",
+    "DensityCompensation", "density_weights",
 ]

@@ -125,6 +125,28 @@ class NufftCgInfo(C.Structure):
 CG_MAX_ITER, CG_CONVERGED, CG_BREAKDOWN = 0, 1, 2
 CG_STATUS_NAMES = {CG_MAX_ITER: "max_iter", CG_CONVERGED: "converged", CG_BREAKDOWN: "breakdown"}
 
+
+class NufftDcfParams(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("max_iter", C.c_int32), ("check_every", C.c_int32), ("normalize", C.c_int32),
+        ("tol", C.c_double),
+    ]
+
+
+class NufftDcfInfo(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("ndim", C.c_int32), ("dtype", C.c_int32), ("device", C.c_int32), ("max_iter", C.c_int32),
+        ("check_every", C.c_int32), ("normalize", C.c_int32), ("workgroups", C.c_int32), ("iterations_enqueued", C.c_int32),
+        ("window_scale_log2", C.c_int32),
+        ("N_over", C.c_int64 * 3), ("tol", C.c_double), ("beta", C.c_double * 3),
+        ("capacity", C.c_int64), ("num_points", C.c_int64), ("workspace_bytes", C.c_int64), ("plan_bytes", C.c_int64),
+    ]
+
+
+DCF_MAX_ITER, DCF_CONVERGED, DCF_BREAKDOWN = 0, 1, 2
+DCF_STATUS_NAMES = {DCF_MAX_ITER: "max_iter", DCF_CONVERGED: "converged", DCF_BREAKDOWN: "breakdown"}
+DCF_NORMALIZE = {"sum": 0, "none": 1}
+
 NUM_STAGES3 = 6
 STAGE_NAMES3 = ("prep_sources", "prep_targets", "premultiply", "spread", "type2", "postmultiply")
 
@@ -196,6 +218,15 @@ SYMBOLS = {
     "nufft_cg_history": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int64, _P]),
     "nufft_sizeof_cg_params": (C.c_int64, []),
     "nufft_sizeof_cg_info": (C.c_int64, []),
+    "nufft_dcf_create": (C.c_int, [C.POINTER(_P), _P, C.POINTER(NufftDcfParams)]),
+    "nufft_dcf_destroy": (C.c_int, [_P]),
+    "nufft_dcf_set_points": (C.c_int, [_P, C.c_int64, _PP, _P]),
+    "nufft_dcf_compute": (C.c_int, [_P, _P, C.c_int, _P]),
+    "nufft_dcf_get_info": (C.c_int, [_P, C.POINTER(NufftDcfInfo)]),
+    "nufft_dcf_get_result": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), _P]),
+    "nufft_dcf_history": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int64, _P]),
+    "nufft_sizeof_dcf_params": (C.c_int64, []),
+    "nufft_sizeof_dcf_info": (C.c_int64, []),
     "nufft_sizeof_params": (C.c_int64, []),
     "nufft_sizeof_info": (C.c_int64, []),
     "nufft_strerror": (C.c_char_p, [C.c_int]),
@@ -225,7 +256,8 @@ def _load():
     for name, mirror in (("nufft_sizeof_params", NufftParams), ("nufft_sizeof_info", NufftInfo),
                          ("nufft_sizeof_type3_params", NufftType3Params), ("nufft_sizeof_info3", NufftInfo3),
                          ("nufft_sizeof_toeplitz_info", NufftToeplitzInfo), ("nufft_sizeof_cg_params", NufftCgParams),
-                         ("nufft_sizeof_cg_info", NufftCgInfo)):
+                         ("nufft_sizeof_cg_info", NufftCgInfo), ("nufft_sizeof_dcf_params", NufftDcfParams),
+                         ("nufft_sizeof_dcf_info", NufftDcfInfo)):
         if getattr(lib, name)() != C.sizeof(mirror):
             raise ImportError(f"{LIB_PATH}: {name}() = {getattr(lib, name)()} but the ctypes mirror has {C.sizeof(mirror)} bytes "
                               "(include/nufft_mi355x.h and _lib.py disagree)")

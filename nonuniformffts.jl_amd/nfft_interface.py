@@ -97,6 +97,12 @@ class NFFTPlan:
         from .toeplitz import ToeplitzOperator
         return ToeplitzOperator(self.p).set_points(self.p.points, weights, **build_overrides)
 
+    def sdc(self, iters: int = 20, **kw) -> torch.Tensor:
+        """Sample-density compensation weights of the current nodes (NFFT.jl: ``sdc(p; iters)``): ``iters`` iterations of Pipe & Menon
+        (dcf.py), normalised to ``Σ w = 1``."""
+        from .dcf import density_weights
+        return density_weights(self.p, self.p.points, maxiter=iters, **kw)
+
     def __repr__(self):
         return f"NonuniformFFTs.NFFTPlan{{{self.T}, {self.p.ndim}}} wrapping a PlanNUFFT:\n{self.p!r}"
 
