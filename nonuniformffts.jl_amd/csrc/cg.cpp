@@ -12,9 +12,9 @@
 #include <vector>
 
 #include "cg.h"
-#include "nufft_internal.h"
+#include "host_common.h"
 
-using nufft::set_error;
+using namespace nufft;
 
 struct nufft_cg {
     nufft_toeplitz* tz = nullptr;
@@ -27,77 +27,34 @@ struct nufft_cg {
     void* d_p = nullptr;
     void* d_q = nullptr;
     void* d_part = nullptr;           // double[C][G][2] + double[C][G]
-    void* d_scal = nullptr;           // double rho[2][C], beta0[C], res[C]; int32 flag[2][C], brk[C], iters[C], status[C]
+    ScalarMirror scal;                // double rho[2][C], beta0[C], res[C]; int32 flag[2][C], brk[C], iters[C], status[C]
     void* d_hist = nullptr;           // double[max_iter + 1][C]
-    void* h_scal = nullptr;           // pinned mirror of d_scal
     int64_t array_bytes = 0, own_bytes = 0;
     std::vector<void*> ptab, qtab;    // the pointer tables nufft_toeplitz_apply takes
 };
 
 namespace {
 
-int fail(int code, const std::string& msg) {
-    set_error(msg);
-    return code;
-}
-
-#define CG_HIP(expr)                                                                           \
-    do {                                                                                       \
-        hipError_t e__ = (expr);                                                               \
-        if (e__ != hipSuccess)                                                                 \
-            return fail(e__ == hipErrorOutOfMemory ? NUFFT_ERR_ALLOC : NUFFT_ERR_HIP,          \
-                        std::string(#expr) + ": " + hipGetErrorString(e__));                   \
-    } while (0)
-
-struct DeviceGuard {
-    int prev = -1;
-    bool active = false;
-    explicit DeviceGuard(int dev) {
-        if (dev >= 0 && hipGetDevice(&prev) == hipSuccess && prev != dev) active = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard() {
-        if (active) (void)hipSetDevice(prev);
-    }
-};
-
-size_t padded(size_t bytes) { return (std::max<size_t>(bytes, 16) + 255) / 256 * 256; }
-size_t real_bytes(const nufft_cg* s) { return s->dtype == NUFFT_F32 ? 4 : 8; }
 size_t scal_bytes(const nufft_cg* s) { return (size_t)s->C * (4 * sizeof(double) + 5 * sizeof(int32_t)); }
 size_t part_bytes(const nufft_cg* s) { return (size_t)s->C * s->G * 3 * sizeof(double); }
 size_t hist_bytes(const nufft_cg* s) { return (size_t)(s->max_iter + 1) * s->C * sizeof(double); }
 
-int alloc(nufft_cg* s, void** ptr, size_t bytes) {
-    bytes = padded(bytes);
-    hipError_t e = hipMalloc(ptr, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        *ptr = nullptr;
-        return fail(NUFFT_ERR_ALLOC, "hipMalloc(" + std::to_string(bytes) + ") of a CG buffer: " + hipGetErrorString(e));
-    }
-    s->own_bytes += (int64_t)bytes;
-    return NUFFT_OK;
-}
+int alloc(nufft_cg* s, void** ptr, size_t bytes) { return alloc_buffer(s->own_bytes, "CG", ptr, bytes); }
 
 void release(nufft_cg* s) {
     if (!s) return;
     if (s->device >= 0) {
         DeviceGuard g(s->device);
-        for (void* p : {s->d_r, s->d_p, s->d_q, s->d_part, s->d_scal, s->d_hist})
+        for (void* p : {s->d_r, s->d_p, s->d_q, s->d_part, s->d_hist})
             if (p) (void)hipFree(p);
-        if (s->h_scal) (void)hipHostFree(s->h_scal);
+        s->scal.release();
     }
     delete s;
 }
 
-bool capturing(hipStream_t stream) {
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return st != hipStreamCaptureStatusNone;
-}
-
-nufft::CgScalars scalars_at(const nufft_cg* s, void* base) {
+CgScalars scalars_at(const nufft_cg* s, void* base) {
     const int C = s->C;
-    nufft::CgScalars k{};
+    CgScalars k{};
     double* d = static_cast<double*>(base);
     k.rho = d;
     k.beta0 = d + 2 * C;
@@ -121,10 +78,10 @@ bool overlap(const void* a, const void* b, size_t bytes) {
 
 // One kernel over all components, kCgBatch at a time.
 template <typename F>
-int for_batches(const nufft_cg* s, nufft::CgLaunch& a, void* const* x, const void* const* b, F&& launch) {
-    for (int c0 = 0; c0 < s->C; c0 += nufft::kCgBatch) {
+int for_batches(const nufft_cg* s, CgLaunch& a, void* const* x, const void* const* b, F&& launch) {
+    for (int c0 = 0; c0 < s->C; c0 += kCgBatch) {
         a.c0 = c0;
-        a.nc = std::min(nufft::kCgBatch, s->C - c0);
+        a.nc = std::min(kCgBatch, s->C - c0);
         for (int k = 0; k < a.nc; ++k) {
             a.x[k] = x[c0 + k];
             a.b[k] = b ? b[c0 + k] : nullptr;
@@ -132,12 +89,6 @@ int for_batches(const nufft_cg* s, nufft::CgLaunch& a, void* const* x, const voi
         hipError_t e = launch(a);
         if (e != hipSuccess) return fail(NUFFT_ERR_HIP, std::string("launch of a CG kernel: ") + hipGetErrorString(e));
     }
-    return NUFFT_OK;
-}
-
-int fetch_scalars(nufft_cg* s, hipStream_t stream) {
-    CG_HIP(hipMemcpyAsync(s->h_scal, s->d_scal, scal_bytes(s), hipMemcpyDeviceToHost, stream));
-    CG_HIP(hipStreamSynchronize(stream));
     return NUFFT_OK;
 }
 
@@ -158,10 +109,7 @@ int nufft_cg_create(nufft_cg** out, nufft_toeplitz* tz, const nufft_cg_params* p
     if (rc) return rc;
     if (ti.device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1): the solver runs on the device");
     nufft_cg_params p;
-    std::memset(&p, 0, sizeof(p));
-    const size_t known = params->struct_size > 0 ? (size_t)params->struct_size : sizeof(p);
-    if (known < sizeof(p)) return fail(NUFFT_ERR_INVALID_ARG, "nufft_cg_params.struct_size is smaller than the published layout");
-    std::memcpy(&p, params, sizeof(p));
+    if ((rc = read_params(p, params, "nufft_cg_params"))) return rc;
     if (p.max_iter < 1) return fail(NUFFT_ERR_INVALID_ARG, "max_iter must be at least 1");
     if (p.max_iter > (1 << 24)) return fail(NUFFT_ERR_INVALID_ARG, "max_iter beyond 2^24");
     if (p.check_every < 0) return fail(NUFFT_ERR_INVALID_ARG, "check_every must not be negative");
@@ -179,7 +127,7 @@ int nufft_cg_create(nufft_cg** out, nufft_toeplitz* tz, const nufft_cg_params* p
     s->rtol = p.rtol;
     s->lambda = p.lambda;
     s->n = ti.N[0] * ti.N[1] * ti.N[2];
-    const size_t rb = real_bytes(s), comp = padded((size_t)s->n * 2 * rb);
+    const size_t rb = real_bytes(s->dtype), comp = padded((size_t)s->n * 2 * rb);
     s->stride = (int64_t)(comp / rb);
     s->array_bytes = 3 * (int64_t)s->C * (int64_t)comp;
 
@@ -187,22 +135,17 @@ int nufft_cg_create(nufft_cg** out, nufft_toeplitz* tz, const nufft_cg_params* p
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device) == hipSuccess && cus > 0) s->num_cus = cus;
     else (void)hipGetLastError();
-    s->G = nufft::cg_workgroups(s->dtype, s->n, s->num_cus);
+    s->G = cg_workgroups(s->dtype, s->n, s->num_cus);
     if ((rc = alloc(s, &s->d_r, (size_t)s->C * comp)) || (rc = alloc(s, &s->d_p, (size_t)s->C * comp)) ||
         (rc = alloc(s, &s->d_q, (size_t)s->C * comp)) || (rc = alloc(s, &s->d_part, part_bytes(s))) ||
-        (rc = alloc(s, &s->d_scal, scal_bytes(s))) || (rc = alloc(s, &s->d_hist, hist_bytes(s)))) {
+        (rc = alloc(s, &s->d_hist, hist_bytes(s))) ||
+        (rc = s->scal.create(s->own_bytes, "CG", scal_bytes(s), "hipHostMalloc of the solver's host mirror failed"))) {
         const std::string keep = nufft_last_error_message();
         release(s);
         return fail(rc, keep);
     }
-    if (hipHostMalloc(&s->h_scal, scal_bytes(s), hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        s->h_scal = nullptr;
-        release(s);
-        return fail(NUFFT_ERR_ALLOC, "hipHostMalloc of the solver's host mirror failed");
-    }
     // a defined answer from nufft_cg_get_result / nufft_cg_history before the first solve
-    if (hipMemset(s->d_scal, 0, scal_bytes(s)) != hipSuccess || hipMemset(s->d_hist, 0xFF, hist_bytes(s)) != hipSuccess) {
+    if (s->scal.zero() != hipSuccess || hipMemset(s->d_hist, 0xFF, hist_bytes(s)) != hipSuccess) {
         (void)hipGetLastError();
         release(s);
         return fail(NUFFT_ERR_HIP, "hipMemset of the solver's scalars failed");
@@ -224,8 +167,6 @@ int nufft_cg_get_info(const nufft_cg* s, nufft_cg_info* o) {
     if (!s || !o) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
     nufft_cg_info i;
     std::memset(&i, 0, sizeof(i));
-    const size_t known = o->struct_size > 0 ? std::min((size_t)o->struct_size, sizeof(i)) : sizeof(i);
-    i.struct_size = (int32_t)known;
     i.ntransforms = s->C;
     i.dtype = s->dtype;
     i.max_iter = s->max_iter;
@@ -236,7 +177,7 @@ int nufft_cg_get_info(const nufft_cg* s, nufft_cg_info* o) {
     i.lambda = s->lambda;
     i.array_bytes = s->array_bytes;
     i.workspace_bytes = s->own_bytes;
-    std::memcpy(o, &i, known);
+    write_info(o, i);
     return NUFFT_OK;
 }
 
@@ -250,7 +191,7 @@ int nufft_cg_solve(nufft_cg* s, void* const* x, const void* const* b, int use_x0
     if (!ti.has_spectrum)
         return fail(NUFFT_ERR_NO_POINTS, "nufft_toeplitz_set_spectrum or nufft_toeplitz_set_points must be called before nufft_cg_solve");
     if (!x || !b) return fail(NUFFT_ERR_INVALID_ARG, "null table");
-    const size_t bytes = (size_t)s->n * 2 * real_bytes(s);
+    const size_t bytes = (size_t)s->n * 2 * real_bytes(s->dtype);
     for (int c = 0; c < s->C; ++c) {
         if (!x[c] || !b[c]) return fail(NUFFT_ERR_INVALID_ARG, "null data vector");
         if (((uintptr_t)x[c] | (uintptr_t)b[c]) & 15) return fail(NUFFT_ERR_INVALID_ARG, "x and b must be 16-byte aligned");
@@ -265,7 +206,7 @@ int nufft_cg_solve(nufft_cg* s, void* const* x, const void* const* b, int use_x0
     if (s->check_every > 0 && capturing(stream))
         return fail(NUFFT_ERR_INVALID_ARG, "check_every > 0 synchronises the stream: not on a capturing stream (use check_every = 0)");
 
-    nufft::CgLaunch a{};
+    CgLaunch a{};
     a.dtype = s->dtype;
     a.C = s->C;
     a.G = s->G;
@@ -278,23 +219,23 @@ int nufft_cg_solve(nufft_cg* s, void* const* x, const void* const* b, int use_x0
     a.rtol = s->rtol;
     a.max_iter = s->max_iter;
     a.it = 0;
-    a.s = scalars_at(s, s->d_scal);
+    a.s = scalars_at(s, s->scal.dev);
 
     s->enqueued = 0;
     const bool warm = use_x0 != 0;
     if (warm && (rc = nufft_toeplitz_apply(s->tz, s->qtab.data(), x, stream))) return rc;      // q = G x0
-    if ((rc = for_batches(s, a, x, b, [&](const nufft::CgLaunch& l) { return nufft::launch_cg_residual(l, warm, stream); }))) return rc;
-    if ((rc = for_batches(s, a, x, b, [&](const nufft::CgLaunch& l) { return nufft::launch_cg_start(l, stream); }))) return rc;
-    const nufft::CgScalars host = scalars_at(s, s->h_scal);
+    if ((rc = for_batches(s, a, x, b, [&](const CgLaunch& l) { return launch_cg_residual(l, warm, stream); }))) return rc;
+    if ((rc = for_batches(s, a, x, b, [&](const CgLaunch& l) { return launch_cg_start(l, stream); }))) return rc;
+    const CgScalars host = scalars_at(s, s->scal.host);
     for (int it = 1; it <= s->max_iter; ++it) {
         a.it = it;
         if ((rc = nufft_toeplitz_apply(s->tz, s->qtab.data(), s->ptab.data(), stream))) return rc;
-        if ((rc = for_batches(s, a, x, nullptr, [&](const nufft::CgLaunch& l) { return nufft::launch_cg_dot(l, stream); }))) return rc;
-        if ((rc = for_batches(s, a, x, nullptr, [&](const nufft::CgLaunch& l) { return nufft::launch_cg_update(l, stream); }))) return rc;
-        if ((rc = for_batches(s, a, x, nullptr, [&](const nufft::CgLaunch& l) { return nufft::launch_cg_direction(l, stream); }))) return rc;
+        if ((rc = for_batches(s, a, x, nullptr, [&](const CgLaunch& l) { return launch_cg_dot(l, stream); }))) return rc;
+        if ((rc = for_batches(s, a, x, nullptr, [&](const CgLaunch& l) { return launch_cg_update(l, stream); }))) return rc;
+        if ((rc = for_batches(s, a, x, nullptr, [&](const CgLaunch& l) { return launch_cg_direction(l, stream); }))) return rc;
         s->enqueued = it;
         if (s->check_every > 0 && it % s->check_every == 0 && it < s->max_iter) {
-            if ((rc = fetch_scalars(s, stream))) return rc;
+            if ((rc = s->scal.fetch(stream))) return rc;
             bool all = true;
             for (int c = 0; c < s->C; ++c) all = all && host.flag[((it + 1) & 1) * s->C + c] != 0;
             if (all) break;
@@ -309,9 +250,9 @@ int nufft_cg_get_result(nufft_cg* s, int32_t* iterations, int32_t* status, doubl
     DeviceGuard guard(s->device);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (capturing(stream)) return fail(NUFFT_ERR_INVALID_ARG, "nufft_cg_get_result synchronises: not on a capturing stream");
-    int rc = fetch_scalars(s, stream);
+    int rc = s->scal.fetch(stream);
     if (rc) return rc;
-    const nufft::CgScalars host = scalars_at(s, s->h_scal);
+    const CgScalars host = scalars_at(s, s->scal.host);
     for (int c = 0; c < s->C; ++c) {
         if (iterations) iterations[c] = host.iters[c];
         if (status) status[c] = host.status[c];
@@ -326,8 +267,8 @@ int nufft_cg_history(nufft_cg* s, double* host_out, int64_t capacity, void* stre
     DeviceGuard guard(s->device);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (capturing(stream)) return fail(NUFFT_ERR_INVALID_ARG, "nufft_cg_history synchronises: not on a capturing stream");
-    CG_HIP(hipMemcpyAsync(host_out, s->d_hist, hist_bytes(s), hipMemcpyDeviceToHost, stream));
-    CG_HIP(hipStreamSynchronize(stream));
+    NUFFT_HIP(hipMemcpyAsync(host_out, s->d_hist, hist_bytes(s), hipMemcpyDeviceToHost, stream));
+    NUFFT_HIP(hipStreamSynchronize(stream));
     return NUFFT_OK;
 }
 

@@ -1,12 +1,8 @@
 // Kernels of the conjugate-gradient solver on the Toeplitz normal operator (cg.cpp).
 //
 // Every scalar of CG here is real (α, ρ'/ρ, λ) and Re<p, q> = Σ over the 2n reals of p ⊙ q, so the kernels treat a component as a
-// vector of 2n reals: 16-byte packs (two Float64 or four Float32), grid-stride, two packs per thread and trip, gridDim.y = component.
-//
-// No workgroup hands anything to another inside a launch and there are no floating-point atomics: a kernel leaves one partial sum
-// per workgroup (plain stores), and every workgroup of the NEXT kernel adds that row up itself, in one fixed order (thread t takes
-// entries t, t + 256, ...; then the wave shuffles; then four LDS words).  The kernel boundary makes the partials visible, the fixed
-// order makes every workgroup, every run and every graph replay get the same bits.  Sums and scalars are FP64 for both element types.
+// vector of 2n reals, gridDim.y = component.  Packs, the loop shape and the fixed-order reduction of the per-workgroup partials, which
+// makes every run and every graph replay get the same bits, are those of stream_kernels.h.
 //
 // A component whose done flag is set is frozen: its workgroups leave after reading the flag.  The first workgroup of the last
 // kernel of an iteration writes the scalars of the next one into the other parity slot (every workgroup of that kernel still reads
@@ -18,63 +14,15 @@
 
 #include "cg.h"
 #include "nufft_mi355x.h"
+#include "stream_kernels.h"
 
 namespace nufft {
+using namespace stream;
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-
-template <typename T>
-struct alignas(16) Pack {
-    static constexpr int W = 16 / sizeof(T);
-    T v[W];
-};
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
-// Sum over the workgroup, returned to every thread.
-__device__ __forceinline__ double block_sum(double v, double* lds) {
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = lds[0];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) t += lds[w];
-    __syncthreads();
-    return t;
-}
-
-// Σ_g row[g * pitch], g < G, in the fixed order described at the top.
-__device__ __forceinline__ double row_sum(const double* row, int G, int pitch, double* lds) {
-    double v = 0.0;
-    for (int g = threadIdx.x; g < G; g += kThreads) v += row[(int64_t)g * pitch];
-    return block_sum(v, lds);
-}
 
 __device__ __forceinline__ double relative(double rho, double beta0) {
     return beta0 > 0.0 ? sqrt(rho / beta0) : (rho == 0.0 ? 0.0 : INFINITY);
 }
-
-template <typename T>
-__device__ __forceinline__ Pack<T> load(const T* a, int64_t pack) {
-    return *reinterpret_cast<const Pack<T>*>(a + pack * Pack<T>::W);
-}
-template <typename T>
-__device__ __forceinline__ void store(T* a, int64_t pack, const Pack<T>& v) {
-    *reinterpret_cast<Pack<T>*>(a + pack * Pack<T>::W) = v;
-}
-
-// The loop shape shared by all kernels: BODY(first real, count) is called for whole packs (count = W, 16-byte aligned) and, by one
-// thread, for the reals behind the last whole pack (ComplexF32 with an odd number of elements).
-#define CG_FOR_EACH_PACK(T, nreal, i)                                                                        \
-    const int64_t npacks__ = (nreal) / Pack<T>::W;                                                           \
-    const int64_t step__ = (int64_t)gridDim.x * kThreads;                                                    \
-    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < npacks__; i += 2 * step__)
 
 // r = b − (q + λ x) (WARM; q = G x) or r = b, x = 0;  p = r;  partial sums of |r|² and |b|²
 template <typename T, bool WARM>
@@ -96,7 +44,7 @@ __global__ __launch_bounds__(kThreads) void cg_residual_kernel(CgLaunch a) {
         sbb += (double)bv * (double)bv;
         return rv;
     };
-    CG_FOR_EACH_PACK(T, nreal, i) {
+    NUFFT_FOR_EACH_PACK(T, nreal, i) {
         const int64_t j = i + step__;
         const bool two = j < npacks__;
         Pack<T> b0 = load(b, i), b1{}, q0{}, q1{}, x0{}, x1{};
@@ -127,8 +75,8 @@ __global__ __launch_bounds__(kThreads) void cg_residual_kernel(CgLaunch a) {
             p[e] = rv;
             if (!WARM) x[e] = T(0);
         }
-    srr = block_sum(srr, lds);
-    sbb = block_sum(sbb, lds);
+    srr = block_reduce<Sum>(srr, lds);
+    sbb = block_reduce<Sum>(sbb, lds);
     if (threadIdx.x == 0) {
         double* out = a.s.part1 + ((int64_t)c * a.G + blockIdx.x) * 2;
         out[0] = srr;
@@ -141,8 +89,8 @@ __global__ __launch_bounds__(kThreads) void cg_start_kernel(CgLaunch a) {
     __shared__ double lds[kWaves];
     const int c = a.c0 + blockIdx.y;
     const double* row = a.s.part1 + (int64_t)c * a.G * 2;
-    const double rr = row_sum(row, a.G, 2, lds);
-    const double bb = row_sum(row + 1, a.G, 2, lds);
+    const double rr = row_reduce<Sum>(row, a.G, 2, lds);
+    const double bb = row_reduce<Sum>(row + 1, a.G, 2, lds);
     for (int it = 1 + threadIdx.x; it <= a.max_iter; it += kThreads) a.s.history[(int64_t)it * a.C + c] = NAN;
     if (threadIdx.x == 0) {
         const int done = rr <= a.rtol * a.rtol * bb ? 1 : 0;
@@ -170,7 +118,7 @@ __global__ __launch_bounds__(kThreads) void cg_dot_kernel(CgLaunch a) {
     const T* q = static_cast<const T*>(a.q) + c * a.stride;
     const int64_t nreal = 2 * a.n;
     double spq = 0.0, spp = 0.0;
-    CG_FOR_EACH_PACK(T, nreal, i) {
+    NUFFT_FOR_EACH_PACK(T, nreal, i) {
         const int64_t j = i + step__;
         const bool two = j < npacks__;
         Pack<T> p0 = load(p, i), q0 = load(q, i), p1{}, q1{};
@@ -191,8 +139,8 @@ __global__ __launch_bounds__(kThreads) void cg_dot_kernel(CgLaunch a) {
             spq += (double)p[e] * (double)q[e];
             spp += (double)p[e] * (double)p[e];
         }
-    spq = block_sum(spq, lds);
-    spp = block_sum(spp, lds);
+    spq = block_reduce<Sum>(spq, lds);
+    spp = block_reduce<Sum>(spp, lds);
     if (threadIdx.x == 0) {
         double* out = a.s.part1 + ((int64_t)c * a.G + blockIdx.x) * 2;
         out[0] = spq;
@@ -209,8 +157,8 @@ __global__ __launch_bounds__(kThreads) void cg_update_kernel(CgLaunch a) {
     const int slot = (a.it & 1) * a.C + c;
     if (a.s.flag[slot]) return;
     const double* row = a.s.part1 + (int64_t)c * a.G * 2;
-    const double pq = row_sum(row, a.G, 2, lds);
-    const double pp = row_sum(row + 1, a.G, 2, lds);
+    const double pq = row_reduce<Sum>(row, a.G, 2, lds);
+    const double pp = row_reduce<Sum>(row + 1, a.G, 2, lds);
     const double gamma = pq + a.lambda * pp;
     const bool bad = !(gamma > 0.0) || !isfinite(gamma);      // the same bits in every workgroup: they all leave, or none does
     if (blockIdx.x == 0 && threadIdx.x == 0) a.s.brk[c] = bad ? 1 : 0;
@@ -227,7 +175,7 @@ __global__ __launch_bounds__(kThreads) void cg_update_kernel(CgLaunch a) {
         rv -= al * (qv + lam * pv);
         srr += (double)rv * (double)rv;
     };
-    CG_FOR_EACH_PACK(T, nreal, i) {
+    NUFFT_FOR_EACH_PACK(T, nreal, i) {
         const int64_t j = i + step__;
         const bool two = j < npacks__;
         Pack<T> x0 = load(x, i), r0 = load(r, i), p0 = load(p, i), q0 = load(q, i), x1{}, r1{}, p1{}, q1{};
@@ -245,7 +193,7 @@ __global__ __launch_bounds__(kThreads) void cg_update_kernel(CgLaunch a) {
     }
     if (blockIdx.x == 0 && threadIdx.x == 0)
         for (int64_t e = npacks__ * W; e < nreal; ++e) one(x[e], r[e], p[e], q[e]);
-    srr = block_sum(srr, lds);
+    srr = block_reduce<Sum>(srr, lds);
     if (threadIdx.x == 0) a.s.part2[(int64_t)c * a.G + blockIdx.x] = srr;
 }
 
@@ -266,12 +214,12 @@ __global__ __launch_bounds__(kThreads) void cg_direction_kernel(CgLaunch a) {
         }
         return;
     }
-    const double rr = row_sum(a.s.part2 + (int64_t)c * a.G, a.G, 1, lds);
+    const double rr = row_reduce<Sum>(a.s.part2 + (int64_t)c * a.G, a.G, 1, lds);
     const T bt = (T)(rr / a.s.rho[slot]);           // ρ > 0: the component is not done
     const T* r = static_cast<const T*>(a.r) + c * a.stride;
     T* p = static_cast<T*>(a.p) + c * a.stride;
     const int64_t nreal = 2 * a.n;
-    CG_FOR_EACH_PACK(T, nreal, i) {
+    NUFFT_FOR_EACH_PACK(T, nreal, i) {
         const int64_t j = i + step__;
         const bool two = j < npacks__;
         Pack<T> r0 = load(r, i), p0 = load(p, i), r1{}, p1{};
@@ -298,27 +246,14 @@ __global__ __launch_bounds__(kThreads) void cg_direction_kernel(CgLaunch a) {
     }
 }
 
-#undef CG_FOR_EACH_PACK
-
 }  // namespace
 
-int cg_workgroups(int dtype, int64_t n, int num_cus) {
-    const int64_t packs = (2 * n) / (dtype == NUFFT_F32 ? 4 : 2);
-    const int64_t need = (packs + 2 * kThreads - 1) / (2 * kThreads);      // two packs per thread and trip
-    const int64_t cap = (int64_t)std::max(num_cus, 1) * 4;                 // 4 workgroups of 4 waves per CU, 32 – 128 B in flight per thread
-    return (int)std::max<int64_t>(1, std::min(need, cap));
-}
+int cg_workgroups(int dtype, int64_t n, int num_cus) { return stream_workgroups((2 * n) / (dtype == NUFFT_F32 ? 4 : 2), num_cus); }
 
 hipError_t launch_cg_residual(const CgLaunch& a, bool warm, hipStream_t stream) {
     const dim3 gr(a.G, a.nc), bl(kThreads);
-    if (a.dtype == NUFFT_F32) {
-        if (warm) hipLaunchKernelGGL((cg_residual_kernel<float, true>), gr, bl, 0, stream, a);
-        else hipLaunchKernelGGL((cg_residual_kernel<float, false>), gr, bl, 0, stream, a);
-    } else {
-        if (warm) hipLaunchKernelGGL((cg_residual_kernel<double, true>), gr, bl, 0, stream, a);
-        else hipLaunchKernelGGL((cg_residual_kernel<double, false>), gr, bl, 0, stream, a);
-    }
-    return hipGetLastError();
+    if (warm) return launch_by_dtype(a.dtype, gr, bl, stream, cg_residual_kernel<float, true>, cg_residual_kernel<double, true>, a);
+    return launch_by_dtype(a.dtype, gr, bl, stream, cg_residual_kernel<float, false>, cg_residual_kernel<double, false>, a);
 }
 
 hipError_t launch_cg_start(const CgLaunch& a, hipStream_t stream) {
@@ -327,24 +262,15 @@ hipError_t launch_cg_start(const CgLaunch& a, hipStream_t stream) {
 }
 
 hipError_t launch_cg_dot(const CgLaunch& a, hipStream_t stream) {
-    const dim3 gr(a.G, a.nc), bl(kThreads);
-    if (a.dtype == NUFFT_F32) hipLaunchKernelGGL((cg_dot_kernel<float>), gr, bl, 0, stream, a);
-    else hipLaunchKernelGGL((cg_dot_kernel<double>), gr, bl, 0, stream, a);
-    return hipGetLastError();
+    return launch_by_dtype(a.dtype, dim3(a.G, a.nc), dim3(kThreads), stream, cg_dot_kernel<float>, cg_dot_kernel<double>, a);
 }
 
 hipError_t launch_cg_update(const CgLaunch& a, hipStream_t stream) {
-    const dim3 gr(a.G, a.nc), bl(kThreads);
-    if (a.dtype == NUFFT_F32) hipLaunchKernelGGL((cg_update_kernel<float>), gr, bl, 0, stream, a);
-    else hipLaunchKernelGGL((cg_update_kernel<double>), gr, bl, 0, stream, a);
-    return hipGetLastError();
+    return launch_by_dtype(a.dtype, dim3(a.G, a.nc), dim3(kThreads), stream, cg_update_kernel<float>, cg_update_kernel<double>, a);
 }
 
 hipError_t launch_cg_direction(const CgLaunch& a, hipStream_t stream) {
-    const dim3 gr(a.G, a.nc), bl(kThreads);
-    if (a.dtype == NUFFT_F32) hipLaunchKernelGGL((cg_direction_kernel<float>), gr, bl, 0, stream, a);
-    else hipLaunchKernelGGL((cg_direction_kernel<double>), gr, bl, 0, stream, a);
-    return hipGetLastError();
+    return launch_by_dtype(a.dtype, dim3(a.G, a.nc), dim3(kThreads), stream, cg_direction_kernel<float>, cg_direction_kernel<double>, a);
 }
 
 }  // namespace nufft

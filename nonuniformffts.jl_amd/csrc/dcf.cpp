@@ -13,9 +13,9 @@
 #include <string>
 
 #include "dcf.h"
-#include "nufft_internal.h"
+#include "host_common.h"
 
-using nufft::set_error;
+using namespace nufft;
 
 struct nufft_dcf {
     nufft_plan* plan = nullptr;       // the internal real-data plan (host-only when the parent is)
@@ -26,79 +26,36 @@ struct nufft_dcf {
     int64_t Np = -1, capacity = 0;
     void* d_v = nullptr;              // T[capacity]
     void* d_part = nullptr;           // double[kDcfMaxGroups][2]
-    void* d_scal = nullptr;           // double res, sum; int32 flag[2], iters, status
+    ScalarMirror scal;                // double res, sum; int32 flag[2], iters, status
     void* d_hist = nullptr;           // double[max_iter]
-    void* h_scal = nullptr;           // pinned mirror of d_scal
     int64_t own_bytes = 0;
 };
 
 namespace {
 
-int fail(int code, const std::string& msg) {
-    set_error(msg);
-    return code;
-}
-
-#define DCF_HIP(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e__ = (expr);                                                               \
-        if (e__ != hipSuccess)                                                                 \
-            return fail(e__ == hipErrorOutOfMemory ? NUFFT_ERR_ALLOC : NUFFT_ERR_HIP,          \
-                        std::string(#expr) + ": " + hipGetErrorString(e__));                   \
-    } while (0)
-
-struct DeviceGuard {
-    int prev = -1;
-    bool active = false;
-    explicit DeviceGuard(int dev) {
-        if (dev >= 0 && hipGetDevice(&prev) == hipSuccess && prev != dev) active = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard() {
-        if (active) (void)hipSetDevice(prev);
-    }
-};
-
-size_t padded(size_t bytes) { return (std::max<size_t>(bytes, 16) + 255) / 256 * 256; }
-size_t real_bytes(const nufft_dcf* s) { return s->dtype == NUFFT_F32 ? 4 : 8; }
 constexpr size_t kScalBytes = 2 * sizeof(double) + 4 * sizeof(int32_t);
-constexpr size_t kPartBytes = (size_t)nufft::kDcfMaxGroups * 2 * sizeof(double);
+constexpr size_t kPartBytes = (size_t)kDcfMaxGroups * 2 * sizeof(double);
 size_t hist_bytes(const nufft_dcf* s) { return (size_t)s->max_iter * sizeof(double); }
-size_t v_bytes(const nufft_dcf* s, int64_t capacity) { return capacity > 0 ? padded((size_t)capacity * real_bytes(s)) : 0; }
+size_t v_bytes(const nufft_dcf* s, int64_t capacity) { return capacity > 0 ? padded((size_t)capacity * real_bytes(s->dtype)) : 0; }
 // what a device object of these parameters and this capacity owns next to its plan
 size_t own_bytes_of(const nufft_dcf* s) { return padded(kPartBytes) + padded(kScalBytes) + padded(hist_bytes(s)) + v_bytes(s, s->capacity); }
 
-int alloc(nufft_dcf* s, void** ptr, size_t bytes) {
-    bytes = padded(bytes);
-    hipError_t e = hipMalloc(ptr, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        *ptr = nullptr;
-        return fail(NUFFT_ERR_ALLOC, "hipMalloc(" + std::to_string(bytes) + ") of a density-compensation buffer: " + hipGetErrorString(e));
-    }
-    s->own_bytes += (int64_t)bytes;
-    return NUFFT_OK;
-}
+int alloc(nufft_dcf* s, void** ptr, size_t bytes) { return alloc_buffer(s->own_bytes, "density-compensation", ptr, bytes); }
 
 void release(nufft_dcf* s) {
     if (!s) return;
     if (s->device >= 0) {
         DeviceGuard g(s->device);
-        for (void* p : {s->d_v, s->d_part, s->d_scal, s->d_hist})
+        for (void* p : {s->d_v, s->d_part, s->d_hist})
             if (p) (void)hipFree(p);
-        if (s->h_scal) (void)hipHostFree(s->h_scal);
+        s->scal.release();
     }
     if (s->plan) nufft_plan_destroy(s->plan);
     delete s;
 }
 
-bool capturing(hipStream_t stream) {
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return st != hipStreamCaptureStatusNone;
-}
-
-nufft::DcfScalars scalars_at(const nufft_dcf* s, void* base) {
-    nufft::DcfScalars k{};
+DcfScalars scalars_at(const nufft_dcf* s, void* base) {
+    DcfScalars k{};
     double* d = static_cast<double*>(base);
     k.res = d;
     k.sum = d + 1;
@@ -109,12 +66,6 @@ nufft::DcfScalars scalars_at(const nufft_dcf* s, void* base) {
     k.history = static_cast<double*>(s->d_hist);
     k.part = static_cast<double*>(s->d_part);
     return k;
-}
-
-int fetch_scalars(nufft_dcf* s, hipStream_t stream) {
-    DCF_HIP(hipMemcpyAsync(s->h_scal, s->d_scal, kScalBytes, hipMemcpyDeviceToHost, stream));
-    DCF_HIP(hipStreamSynchronize(stream));
-    return NUFFT_OK;
 }
 
 int launched(hipError_t e) {
@@ -132,10 +83,8 @@ int nufft_dcf_create(nufft_dcf** out, const nufft_plan* plan, const nufft_dcf_pa
     if (!out || !plan || !params) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
     *out = nullptr;
     nufft_dcf_params p;
-    std::memset(&p, 0, sizeof(p));
-    const size_t known = params->struct_size > 0 ? (size_t)params->struct_size : sizeof(p);
-    if (known < sizeof(p)) return fail(NUFFT_ERR_INVALID_ARG, "nufft_dcf_params.struct_size is smaller than the published layout");
-    std::memcpy(&p, params, sizeof(p));
+    int rc = read_params(p, params, "nufft_dcf_params");
+    if (rc) return rc;
     if (p.max_iter < 1) return fail(NUFFT_ERR_INVALID_ARG, "max_iter must be at least 1");
     if (p.max_iter > (1 << 24)) return fail(NUFFT_ERR_INVALID_ARG, "max_iter beyond 2^24");
     if (p.check_every < 0) return fail(NUFFT_ERR_INVALID_ARG, "check_every must not be negative");
@@ -175,7 +124,7 @@ int nufft_dcf_create(nufft_dcf** out, const nufft_plan* plan, const nufft_dcf_pa
     prm.device = plan->device;
     const std::string options = plan->opts.str();
     prm.options = options.empty() ? nullptr : options.c_str();
-    int rc = nufft_plan_create_ex(&s->plan, &prm);
+    rc = nufft_plan_create_ex(&s->plan, &prm);
     if (rc) {
         const std::string keep = nufft_last_error_message();
         s->plan = nullptr;
@@ -186,19 +135,15 @@ int nufft_dcf_create(nufft_dcf** out, const nufft_plan* plan, const nufft_dcf_pa
 
     if (s->device >= 0) {
         DeviceGuard guard(s->device);
-        if ((rc = alloc(s, &s->d_part, kPartBytes)) || (rc = alloc(s, &s->d_scal, kScalBytes)) || (rc = alloc(s, &s->d_hist, hist_bytes(s)))) {
+        if ((rc = alloc(s, &s->d_part, kPartBytes)) || (rc = alloc(s, &s->d_hist, hist_bytes(s))) ||
+            (rc = s->scal.create(s->own_bytes, "density-compensation", kScalBytes,
+                                 "hipHostMalloc of the host mirror of the density compensation failed"))) {
             const std::string keep = nufft_last_error_message();
             release(s);
             return fail(rc, keep);
         }
-        if (hipHostMalloc(&s->h_scal, kScalBytes, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            s->h_scal = nullptr;
-            release(s);
-            return fail(NUFFT_ERR_ALLOC, "hipHostMalloc of the host mirror of the density compensation failed");
-        }
         // a defined answer from nufft_dcf_get_result / nufft_dcf_history before the first compute
-        if (hipMemset(s->d_scal, 0, kScalBytes) != hipSuccess || hipMemset(s->d_hist, 0xFF, hist_bytes(s)) != hipSuccess ||
+        if (s->scal.zero() != hipSuccess || hipMemset(s->d_hist, 0xFF, hist_bytes(s)) != hipSuccess ||
             hipMemset(s->d_part, 0, kPartBytes) != hipSuccess) {
             (void)hipGetLastError();
             release(s);
@@ -218,8 +163,6 @@ int nufft_dcf_get_info(const nufft_dcf* s, nufft_dcf_info* o) {
     if (!s || !o) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
     nufft_dcf_info i;
     std::memset(&i, 0, sizeof(i));
-    const size_t known = o->struct_size > 0 ? std::min((size_t)o->struct_size, sizeof(i)) : sizeof(i);
-    i.struct_size = (int32_t)known;
     i.ndim = s->D;
     i.dtype = s->dtype;
     i.device = s->device;
@@ -238,7 +181,7 @@ int nufft_dcf_get_info(const nufft_dcf* s, nufft_dcf_info* o) {
     i.num_points = s->Np;
     i.workspace_bytes = s->device >= 0 ? s->own_bytes : (int64_t)own_bytes_of(s);
     i.plan_bytes = s->plan->workspace_bytes;
-    std::memcpy(o, &i, known);
+    write_info(o, i);
     return NUFFT_OK;
 }
 
@@ -253,15 +196,11 @@ int nufft_dcf_set_points(nufft_dcf* s, int64_t np, const void* const* coords, vo
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (np > s->capacity) {
         if (capturing(stream)) return fail(NUFFT_ERR_INVALID_ARG, "nufft_dcf_set_points grows a buffer: not on a capturing stream");
-        DCF_HIP(hipStreamSynchronize(stream));      // an earlier compute may still read v
-        if (s->d_v) {
-            (void)hipFree(s->d_v);
-            s->own_bytes -= (int64_t)v_bytes(s, s->capacity);
-            s->d_v = nullptr;
-        }
+        NUFFT_HIP(hipStreamSynchronize(stream));      // an earlier compute may still read v
+        free_buffer(s->own_bytes, s->d_v, (size_t)s->capacity * real_bytes(s->dtype));
         s->capacity = 0;
         s->Np = -1;
-        const int rc = alloc(s, &s->d_v, (size_t)np * real_bytes(s));
+        const int rc = alloc(s, &s->d_v, (size_t)np * real_bytes(s->dtype));
         if (rc) return rc;
         s->capacity = np;
     }
@@ -269,7 +208,7 @@ int nufft_dcf_set_points(nufft_dcf* s, int64_t np, const void* const* coords, vo
     const int rc = nufft_set_points(s->plan, np, coords, stream);
     if (rc) return rc;
     s->Np = np;
-    s->G = np > 0 ? nufft::dcf_workgroups(s->dtype, np, s->num_cus) : 0;
+    s->G = np > 0 ? dcf_workgroups(s->dtype, np, s->num_cus) : 0;
     return NUFFT_OK;
 }
 
@@ -285,7 +224,7 @@ int nufft_dcf_compute(nufft_dcf* s, void* w, int use_w0, void* stream_) {
     if (s->check_every > 0 && capturing(stream))
         return fail(NUFFT_ERR_INVALID_ARG, "check_every > 0 synchronises the stream: not on a capturing stream (use check_every = 0)");
 
-    nufft::DcfLaunch a{};
+    DcfLaunch a{};
     a.dtype = s->dtype;
     a.G = s->G;
     a.n = s->Np;
@@ -296,14 +235,14 @@ int nufft_dcf_compute(nufft_dcf* s, void* w, int use_w0, void* stream_) {
     a.gamma = std::ldexp(1.0, s->kappa);
     a.max_iter = s->max_iter;
     a.normalize = s->normalize;
-    a.s = scalars_at(s, s->d_scal);
+    a.s = scalars_at(s, s->scal.dev);
 
     s->enqueued = 0;
     const bool warm = use_w0 != 0;
     int rc;
-    if ((rc = launched(nufft::launch_dcf_start(a, warm, stream)))) return rc;
-    if ((rc = launched(nufft::launch_dcf_begin(a, stream)))) return rc;
-    const nufft::DcfScalars host = scalars_at(s, s->h_scal);
+    if ((rc = launched(launch_dcf_start(a, warm, stream)))) return rc;
+    if ((rc = launched(launch_dcf_begin(a, stream)))) return rc;
+    const DcfScalars host = scalars_at(s, s->scal.host);
     const void* in[1] = {w};
     void* outv[1] = {s->d_v};
     for (int k = 0; k < s->max_iter; ++k) {
@@ -315,19 +254,19 @@ int nufft_dcf_compute(nufft_dcf* s, void* w, int use_w0, void* stream_) {
         if ((rc = nufft_fill_zeros(s->plan, stream))) return rc;
         if ((rc = nufft_spread_deferred(s->plan, in, stream))) return rc;
         if ((rc = nufft_interpolate(s->plan, outv, stream))) return rc;
-        if ((rc = launched(nufft::launch_dcf_check(a, stream)))) return rc;
-        if ((rc = launched(nufft::launch_dcf_update(a, stream)))) return rc;
+        if ((rc = launched(launch_dcf_check(a, stream)))) return rc;
+        if ((rc = launched(launch_dcf_update(a, stream)))) return rc;
         s->enqueued = k + 1;
         if (s->check_every > 0 && (k + 1) % s->check_every == 0 && k + 1 < s->max_iter) {
-            if ((rc = fetch_scalars(s, stream))) return rc;
+            if ((rc = s->scal.fetch(stream))) return rc;
             if (host.flag[(k + 1) & 1]) break;
         }
     }
     if (s->normalize == NUFFT_DCF_NORMALIZE_SUM) {
-        if ((rc = launched(nufft::launch_dcf_sum(a, stream)))) return rc;
-        if ((rc = launched(nufft::launch_dcf_scale(a, stream)))) return rc;
+        if ((rc = launched(launch_dcf_sum(a, stream)))) return rc;
+        if ((rc = launched(launch_dcf_scale(a, stream)))) return rc;
     } else if (s->kappa != 0) {
-        if ((rc = launched(nufft::launch_dcf_scale(a, stream)))) return rc;
+        if ((rc = launched(launch_dcf_scale(a, stream)))) return rc;
     }
     return NUFFT_OK;
 }
@@ -338,9 +277,9 @@ int nufft_dcf_get_result(nufft_dcf* s, int32_t* iterations, int32_t* status, dou
     DeviceGuard guard(s->device);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (capturing(stream)) return fail(NUFFT_ERR_INVALID_ARG, "nufft_dcf_get_result synchronises: not on a capturing stream");
-    int rc = fetch_scalars(s, stream);
+    int rc = s->scal.fetch(stream);
     if (rc) return rc;
-    const nufft::DcfScalars host = scalars_at(s, s->h_scal);
+    const DcfScalars host = scalars_at(s, s->scal.host);
     if (iterations) *iterations = host.iters[0];
     if (status) *status = host.status[0];
     if (residual) *residual = host.res[0];
@@ -354,8 +293,8 @@ int nufft_dcf_history(nufft_dcf* s, double* host_out, int64_t capacity, void* st
     DeviceGuard guard(s->device);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (capturing(stream)) return fail(NUFFT_ERR_INVALID_ARG, "nufft_dcf_history synchronises: not on a capturing stream");
-    DCF_HIP(hipMemcpyAsync(host_out, s->d_hist, hist_bytes(s), hipMemcpyDeviceToHost, stream));
-    DCF_HIP(hipStreamSynchronize(stream));
+    NUFFT_HIP(hipMemcpyAsync(host_out, s->d_hist, hist_bytes(s), hipMemcpyDeviceToHost, stream));
+    NUFFT_HIP(hipStreamSynchronize(stream));
     return NUFFT_OK;
 }
 

@@ -1,12 +1,8 @@
 // Kernels of the sample-density compensation iteration (dcf.cpp).
 //
 // The iteration is w <- w / (C w), C = interpolation after spreading (the plan's own kernels, enqueued by dcf.cpp).  What is left for
-// this file are passes over vectors of n reals: 16-byte packs (two Float64 or four Float32), grid-stride, two packs per thread and trip.
-//
-// No workgroup hands anything to another inside a launch and there are no floating-point atomics: a kernel leaves one row of partials
-// per workgroup (plain stores), and every workgroup of the NEXT kernel reduces the rows itself, in one fixed order (thread t takes rows
-// t, t + 256, ...; then the wave shuffles; then four LDS words).  The kernel boundary makes the partials visible.  Sums and maxima are
-// FP64 for both element types.
+// this file are passes over vectors of n reals, with the packs, the loop shape and the fixed-order reduction of the per-workgroup
+// partials of stream_kernels.h (here of maxima too: NaN values are caught by the breakdown test, not by δ).
 //
 // The stopping rule needs δ_k = max |v − 1| of ALL of v before iteration k may divide anything by v, and the breakdown test likewise:
 // that is one kernel boundary inside the iteration, so an iteration has two kernels (check: reads v; update: reads v and w, writes w).
@@ -19,74 +15,16 @@
 
 #include "dcf.h"
 #include "nufft_mi355x.h"
+#include "stream_kernels.h"
 
 namespace nufft {
+using namespace stream;
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-
-template <typename T>
-struct alignas(16) Pack {
-    static constexpr int W = 16 / sizeof(T);
-    T v[W];
-};
-
-struct Sum {
-    __device__ static double op(double a, double b) { return a + b; }
-};
-struct Max {      // fmax: a NaN partial never wins; NaN values are caught by the breakdown test, not by δ
-    __device__ static double op(double a, double b) { return fmax(a, b); }
-};
-
-template <typename Op>
-__device__ __forceinline__ double wave_reduce(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = Op::op(v, __shfl_down(v, off, 64));
-    return v;
-}
-
-// Reduction over the workgroup, returned to every thread.
-template <typename Op>
-__device__ __forceinline__ double block_reduce(double v, double* lds) {
-    v = wave_reduce<Op>(v);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = lds[0];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) t = Op::op(t, lds[w]);
-    __syncthreads();
-    return t;
-}
-
-// Reduction of column `col` of the G rows of partials, in the fixed order described at the top (both identities are 0 here: the sums
-// start empty, the maxima are of non-negative numbers).
-template <typename Op>
-__device__ __forceinline__ double row_reduce(const double* part, int G, int col, double* lds) {
-    double v = 0.0;
-    for (int g = threadIdx.x; g < G; g += kThreads) v = Op::op(v, part[2 * g + col]);
-    return block_reduce<Op>(v, lds);
-}
-
-template <typename T>
-__device__ __forceinline__ Pack<T> load(const T* a, int64_t pack) {
-    return *reinterpret_cast<const Pack<T>*>(a + pack * Pack<T>::W);
-}
-template <typename T>
-__device__ __forceinline__ void store(T* a, int64_t pack, const Pack<T>& v) {
-    *reinterpret_cast<Pack<T>*>(a + pack * Pack<T>::W) = v;
-}
 
 template <typename T>
 __device__ __forceinline__ bool positive_finite(T x) {
     return x > T(0) && x < (T)INFINITY;      // false for NaN
 }
-
-// The loop shape shared by all kernels: whole packs in the loop, the reals behind the last whole pack by one thread afterwards.
-#define DCF_FOR_EACH_PACK(T, n, i)                                                                           \
-    const int64_t npacks__ = (n) / Pack<T>::W;                                                               \
-    const int64_t step__ = (int64_t)gridDim.x * kThreads;                                                    \
-    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < npacks__; i += 2 * step__)
 
 // w = 1 (the state u = w / 2^κ of the all-ones start), or the test of the caller's w0, which is only read
 template <typename T, bool W0>
@@ -98,7 +36,7 @@ __global__ __launch_bounds__(kThreads) void dcf_start_kernel(DcfLaunch a) {
     Pack<T> ones;
 #pragma unroll
     for (int e = 0; e < W; ++e) ones.v[e] = T(1);
-    DCF_FOR_EACH_PACK(T, a.n, i) {
+    NUFFT_FOR_EACH_PACK(T, a.n, i) {
         const int64_t j = i + step__;
         const bool two = j < npacks__;
         if (W0) {
@@ -126,7 +64,7 @@ __global__ __launch_bounds__(kThreads) void dcf_start_kernel(DcfLaunch a) {
 // One workgroup: the scalars before the first iteration, and NaN into the history.
 __global__ __launch_bounds__(kThreads) void dcf_begin_kernel(DcfLaunch a) {
     __shared__ double lds[kWaves];
-    const double bad = row_reduce<Max>(a.s.part, a.G, 1, lds);
+    const double bad = row_reduce<Max>(a.s.part + 1, a.G, 2, lds);
     for (int k = threadIdx.x; k < a.max_iter; k += kThreads) a.s.history[k] = NAN;
     if (threadIdx.x == 0) {
         const int done = bad != 0.0 ? 1 : 0;
@@ -152,7 +90,7 @@ __global__ __launch_bounds__(kThreads) void dcf_check_kernel(DcfLaunch a) {
         dmax = fmax(dmax, fabs((double)x * sc - 1.0));
         bad = positive_finite(x) ? bad : 1.0;
     };
-    DCF_FOR_EACH_PACK(T, a.n, i) {
+    NUFFT_FOR_EACH_PACK(T, a.n, i) {
         const int64_t j = i + step__;
         Pack<T> v0 = load(v, i), v1;
 #pragma unroll
@@ -183,8 +121,8 @@ __global__ __launch_bounds__(kThreads) void dcf_update_kernel(DcfLaunch a) {
         if (first) a.s.flag[next] = 1;
         return;
     }
-    const double delta = row_reduce<Max>(a.s.part, a.G, 0, lds);
-    const bool bad = row_reduce<Max>(a.s.part, a.G, 1, lds) != 0.0;
+    const double delta = row_reduce<Max>(a.s.part, a.G, 2, lds);
+    const bool bad = row_reduce<Max>(a.s.part + 1, a.G, 2, lds) != 0.0;
     const bool conv = !bad && a.k >= 1 && delta <= a.tol;
     if (first) {
         if (a.report && !bad) {
@@ -198,7 +136,7 @@ __global__ __launch_bounds__(kThreads) void dcf_update_kernel(DcfLaunch a) {
     if (bad || conv) return;
     T* w = static_cast<T*>(a.w);
     const T* v = static_cast<const T*>(a.v);
-    DCF_FOR_EACH_PACK(T, a.n, i) {
+    NUFFT_FOR_EACH_PACK(T, a.n, i) {
         const int64_t j = i + step__;
         const bool two = j < npacks__;
         Pack<T> w0 = load(w, i), v0 = load(v, i), w1{}, v1{};
@@ -224,7 +162,7 @@ __global__ __launch_bounds__(kThreads) void dcf_sum_kernel(DcfLaunch a) {
     if (a.s.status[0] == NUFFT_DCF_BREAKDOWN) return;
     const T* w = static_cast<const T*>(a.w);
     double s = 0.0;
-    DCF_FOR_EACH_PACK(T, a.n, i) {
+    NUFFT_FOR_EACH_PACK(T, a.n, i) {
         const int64_t j = i + step__;
         Pack<T> w0 = load(w, i), w1{};
         if (j < npacks__) w1 = load(w, j);
@@ -246,13 +184,13 @@ __global__ __launch_bounds__(kThreads) void dcf_scale_kernel(DcfLaunch a) {
     const bool norm = a.normalize == NUFFT_DCF_NORMALIZE_SUM;
     double total = 1.0;
     if (norm) {
-        total = row_reduce<Sum>(a.s.part, a.G, 0, lds);
+        total = row_reduce<Sum>(a.s.part, a.G, 2, lds);
         if (blockIdx.x == 0 && threadIdx.x == 0) a.s.sum[0] = total;
     }
     const T den = (T)total, mul = (T)a.gamma;
     T* w = static_cast<T*>(a.w);
     auto one = [&](T x) { return norm ? x / den : x * mul; };
-    DCF_FOR_EACH_PACK(T, a.n, i) {
+    NUFFT_FOR_EACH_PACK(T, a.n, i) {
         const int64_t j = i + step__;
         const bool two = j < npacks__;
         Pack<T> w0 = load(w, i), w1{};
@@ -270,24 +208,14 @@ __global__ __launch_bounds__(kThreads) void dcf_scale_kernel(DcfLaunch a) {
         for (int64_t e = npacks__ * W; e < a.n; ++e) w[e] = one(w[e]);
 }
 
-#undef DCF_FOR_EACH_PACK
-
 template <typename KF, typename KD>
 hipError_t launch(const DcfLaunch& a, KF kf, KD kd, hipStream_t stream) {
-    const dim3 gr(a.G), bl(kThreads);
-    if (a.dtype == NUFFT_F32) hipLaunchKernelGGL(kf, gr, bl, 0, stream, a);
-    else hipLaunchKernelGGL(kd, gr, bl, 0, stream, a);
-    return hipGetLastError();
+    return launch_by_dtype(a.dtype, dim3(a.G), dim3(kThreads), stream, kf, kd, a);
 }
 
 }  // namespace
 
-int dcf_workgroups(int dtype, int64_t n, int num_cus) {
-    const int64_t packs = n / (dtype == NUFFT_F32 ? 4 : 2);
-    const int64_t need = (packs + 2 * kThreads - 1) / (2 * kThreads);      // two packs per thread and trip
-    const int64_t cap = std::min<int64_t>((int64_t)std::max(num_cus, 1) * 4, kDcfMaxGroups);   // 4 workgroups of 4 waves per CU
-    return (int)std::max<int64_t>(1, std::min(need, cap));
-}
+int dcf_workgroups(int dtype, int64_t n, int num_cus) { return stream_workgroups(n / (dtype == NUFFT_F32 ? 4 : 2), num_cus, kDcfMaxGroups); }
 
 hipError_t launch_dcf_start(const DcfLaunch& a, bool use_w0, hipStream_t stream) {
     if (use_w0) return launch(a, dcf_start_kernel<float, true>, dcf_start_kernel<double, true>, stream);

@@ -13,38 +13,17 @@
 #include <new>
 #include <string>
 
+#include "host_common.h"
 #include "kernels.h"
-#include "nufft_internal.h"
 
 namespace nufft {
 
 static thread_local std::string g_last_error;
 void set_error(const std::string& msg) { g_last_error = msg; }
 
-static int fail(int code, const std::string& msg) {
-    set_error(msg);
-    return code;
-}
-
-#define NUFFT_HIP(expr)                                                                        \
-    do {                                                                                       \
-        hipError_t e__ = (expr);                                                               \
-        if (e__ != hipSuccess)                                                                 \
-            return nufft::fail(e__ == hipErrorOutOfMemory ? NUFFT_ERR_ALLOC : NUFFT_ERR_HIP,   \
-                               std::string(#expr) + ": " + hipGetErrorString(e__));            \
-    } while (0)
-
-#define NUFFT_ROCFFT(expr)                                                                     \
-    do {                                                                                       \
-        rocfft_status s__ = (expr);                                                            \
-        if (s__ != rocfft_status_success)                                                      \
-            return nufft::fail(NUFFT_ERR_ROCFFT, std::string(#expr) + ": rocfft status " + std::to_string((int)s__)); \
-    } while (0)
-
 static std::once_flag g_rocfft_once;
 
-static size_t real_bytes(const nufft_plan* p) { return p->dtype == NUFFT_F32 ? 4 : 8; }
-static size_t value_bytes(const nufft_plan* p) { return real_bytes(p) * (p->is_complex ? 2 : 1); }
+static size_t value_bytes(const nufft_plan* p) { return real_bytes(p->dtype) * (p->is_complex ? 2 : 1); }
 
 static TileShape make_shape(const nufft::TileShapeHost& h) {
     TileShape t{};
@@ -72,19 +51,6 @@ static Geom make_geom(const nufft_plan* p) {
     g.ip = make_shape(p->tile.ip);
     return g;
 }
-
-struct DeviceGuard {
-    int prev = -1;
-    bool active = false;
-    explicit DeviceGuard(int dev) {
-        if (dev >= 0 && hipGetDevice(&prev) == hipSuccess && prev != dev) {
-            active = hipSetDevice(dev) == hipSuccess;
-        }
-    }
-    ~DeviceGuard() {
-        if (active) (void)hipSetDevice(prev);
-    }
-};
 
 // Every device allocation of a plan goes through here: workspace_bytes and the per-buffer breakdown (nufft_workspace_breakdown) are
 // what the registry holds, so they cannot drift apart.  `name`: the row of DESIGN.md section 3 the buffer belongs to.
@@ -307,7 +273,7 @@ static int build_host(nufft_plan* p, const nufft_params* in) {
     int budget = in->lds_budget_bytes > 0 ? in->lds_budget_bytes : env_int("NUFFT_LDS_BUDGET", kLdsLimit);
     if (budget > kLdsLimit - 256) budget = kLdsLimit - 256;   // small margin for compiler-generated LDS
     const int ncomp = p->is_complex ? 2 : 1;
-    const int rb = (int)real_bytes(p);
+    const int rb = (int)real_bytes(p->dtype);
     int forced_sp[3] = {in->tile_dims[0], in->tile_dims[1], in->tile_dims[2]};
     int forced_ip[3] = {in->interp_tile_dims[0], in->interp_tile_dims[1], in->interp_tile_dims[2]};
     auto env_tile = [](const char* name, int* out) {
@@ -566,7 +532,7 @@ static int build_device(nufft_plan* p) {
     // read); real plans pad their intermediate rows to 128 bytes
     p->spec_row = p->compact_dim1 ? p->Nout[0] : p->Nspec[0];
     if (p->compact_dim1 && !p->is_complex && env_int("NUFFT_FFT_PAD_ROWS", 1) != 0) {
-        const int64_t q = 128 / (int64_t)(2 * real_bytes(p));
+        const int64_t q = 128 / (int64_t)(2 * real_bytes(p->dtype));
         p->spec_row = (p->Nout[0] + q - 1) / q * q;
         if (p->spec_row > p->Nspec[0]) p->spec_row = p->Nout[0];      // (cannot happen for sigma >= 1.25)
     }
@@ -576,7 +542,7 @@ static int build_device(nufft_plan* p) {
         for (int d = 1; d < D; ++d) p->pspec_elems *= p->Nover[d];
     }
     if (!p->is_complex || p->pruned_fft) {
-        if ((rc = dev_alloc(p, &p->d_uhat, (size_t)p->pspec_elems * 2 * real_bytes(p) * p->C, "uhat"))) return rc;
+        if ((rc = dev_alloc(p, &p->d_uhat, (size_t)p->pspec_elems * 2 * real_bytes(p->dtype) * p->C, "uhat"))) return rc;
     }
 
     // bin-sort scratch that does not depend on Np
@@ -677,7 +643,7 @@ static int build_device(nufft_plan* p) {
         }
         if (D == 3) {
             const size_t elems = (size_t)(p->compact_dim1 ? p->spec_row : p->Nout[0]) * p->Nout[1] * p->Nover[2];
-            if ((rc = dev_alloc(p, &p->d_tmp2, elems * 2 * real_bytes(p), "tmp2"))) return rc;
+            if ((rc = dev_alloc(p, &p->d_tmp2, elems * 2 * real_bytes(p->dtype), "tmp2"))) return rc;
         }
     }
 
@@ -721,7 +687,7 @@ static int build_device(nufft_plan* p) {
             if (!p->smarch.eligible && want_halo)
                 p->smarch = smarch_plan(p->dtype, p->is_complex, D, p->M, make_geom(p), other, p->num_cus, p->C, 0, p->smarch_parts);
             if (!p->smarch.eligible || p->smarch.halo != 2) break;
-            const size_t bytes = (size_t)p->smarch.halo_reals * real_bytes(p) * p->C * p->smarch.parts;
+            const size_t bytes = (size_t)p->smarch.halo_reals * real_bytes(p->dtype) * p->C * p->smarch.parts;
             // (NUFFT_TEST_HALO_ALLOC_FAIL=1: the test of this fallback)
             if (!env_int("NUFFT_TEST_HALO_ALLOC_FAIL", 0) && dev_alloc(p, &p->d_smarch_halo, bytes, "ring_side_buffer") == NUFFT_OK) break;
             p->d_smarch_halo = nullptr;
@@ -1014,12 +980,12 @@ static int pruned_forward_fft(nufft_plan* p, hipStream_t stream, bool fuse) {
     if (p->is_complex) {
         int64_t per = 1;
         for (int d = 1; d < p->D; ++d) per *= p->Nover[d];
-        const size_t cb = 2 * real_bytes(p);
+        const size_t cb = 2 * real_bytes(p->dtype);
         for (int c = 0; c < p->C; ++c) {
             const void* in = static_cast<char*>(p->d_us) + (size_t)c * p->grid_elems * cb;
             void* out = static_cast<char*>(p->d_uhat) + (size_t)c * p->pspec_elems * cb;
-            hh.buffer = static_cast<char*>(p->d_smarch_halo) + (size_t)c * p->smarch.parts * p->smarch.halo_reals * real_bytes(p);
-            hh.buffer2 = p->smarch.parts == 2 ? static_cast<const char*>(hh.buffer) + (size_t)p->smarch.halo_reals * real_bytes(p) : nullptr;      // (planar: real parts, then imaginary parts)
+            hh.buffer = static_cast<char*>(p->d_smarch_halo) + (size_t)c * p->smarch.parts * p->smarch.halo_reals * real_bytes(p->dtype);
+            hh.buffer2 = p->smarch.parts == 2 ? static_cast<const char*>(hh.buffer) + (size_t)p->smarch.halo_reals * real_bytes(p->dtype) : nullptr;      // (planar: real parts, then imaginary parts)
             NUFFT_HIP(launch_cplx_lines(p->dtype, p->Nover[0], true, in, out, per, (int)p->Nout[0], p->d_index_map[0], p->d_tw_fw[0], stream,
                                         fuse ? &hh : nullptr));
         }
@@ -1030,7 +996,7 @@ static int pruned_forward_fft(nufft_plan* p, hipStream_t stream, bool fuse) {
         for (int d = 1; d < p->D; ++d) nlines *= p->Nover[d];
         // components are contiguous both in us (Ñ1 reals per line) and in the compact spectrum (N_out1 per line);
         // the per-component offset of the compact spectrum is nlines_per_component * N_out1 <= spec_elems
-        const size_t rb = real_bytes(p);
+        const size_t rb = real_bytes(p->dtype);
         if (p->C == 1) {
             hh.buffer = p->d_smarch_halo;
             NUFFT_HIP(launch_real_lines(p->dtype, p->Nover[0], true, p->d_us, p->d_uhat, nlines, (int)p->Nout[0], (int)p->spec_row, p->d_tw_fw[0], stream,
@@ -1055,7 +1021,7 @@ static int pruned_forward_fft(nufft_plan* p, hipStream_t stream, bool fuse) {
 }
 
 static int pruned_forward_pass(nufft_plan* p, int c, int dim, void* user_out, hipStream_t stream) {
-    const size_t cb = 2 * real_bytes(p);
+    const size_t cb = 2 * real_bytes(p->dtype);
     const int64_t K1 = p->Nout[0];
     const int64_t S1 = p->spec_row;                              // row stride of the dimension-1 spectrum
     // ... and of tmp2: unpadded on the way forward — the last pass would transform the pad columns too (5 % more lines at
@@ -1104,7 +1070,7 @@ static int pruned_forward_pass(nufft_plan* p, int c, int dim, void* user_out, hi
 }
 
 static int pruned_backward_pass(nufft_plan* p, int c, int dim, const void* user_in, hipStream_t stream) {
-    const size_t cb = 2 * real_bytes(p);
+    const size_t cb = 2 * real_bytes(p->dtype);
     const int64_t K1 = p->Nout[0];
     const int64_t S1 = p->spec_row;                              // row stride of the dimension-1 spectrum
     const int64_t T1 = p->compact_dim1 ? p->spec_row : K1;       // ... and of tmp2
@@ -1676,7 +1642,7 @@ static int spread_impl(nufft_plan* p, const void* const* values_in, void* stream
         else
             for (int c = 0; c < p->C; ++c)
                 NUFFT_HIP(launch_gather_values(p->dtype, p->is_complex, p->D, p->d_sorted, p->Np, values_in[c], p->cb_point_weights,
-                                               static_cast<char*>(p->d_vsorted) + (size_t)c * vstride * real_bytes(p), enabled, stream));
+                                               static_cast<char*>(p->d_vsorted) + (size_t)c * vstride * real_bytes(p->dtype), enabled, stream));
         PatchPlan pp{};
         pp.eligible = true;
         pp.npx = p->patch.npx; pp.npy = p->patch.npy; pp.nseg = p->patch.nseg; pp.segl = p->patch.segl;
@@ -1768,7 +1734,7 @@ int nufft_fft_backward(nufft_plan* p, void* stream_) {
     if (p->pruned_fft && p->is_complex) {
         int64_t per = 1;
         for (int d = 1; d < p->D; ++d) per *= p->Nover[d];
-        const size_t cb = 2 * real_bytes(p);
+        const size_t cb = 2 * real_bytes(p->dtype);
         for (int c = 0; c < p->C; ++c) {
             const void* in = static_cast<char*>(p->d_uhat) + (size_t)c * p->pspec_elems * cb;
             void* out = static_cast<char*>(p->d_us) + (size_t)c * p->grid_elems * cb;
@@ -1779,7 +1745,7 @@ int nufft_fft_backward(nufft_plan* p, void* stream_) {
     if (p->pruned_fft && p->compact_dim1) {
         int64_t per = 1;
         for (int d = 1; d < p->D; ++d) per *= p->Nover[d];
-        const size_t rb = real_bytes(p);
+        const size_t rb = real_bytes(p->dtype);
         for (int c = 0; c < p->C; ++c) {
             const void* in = static_cast<char*>(p->d_uhat) + (size_t)c * p->pspec_elems * 2 * rb;
             void* out = static_cast<char*>(p->d_us) + (size_t)c * p->grid_elems * rb;
@@ -1949,7 +1915,7 @@ int nufft_grid_ptr(const nufft_plan* p, int which, int component, void** out_ptr
         *out_ptr = static_cast<char*>(p->d_us) + bytes * component;
         if (out_bytes) *out_bytes = (int64_t)bytes;
     } else if (which == 1 && !p->is_complex) {
-        const size_t bytes = (size_t)p->pspec_elems * 2 * real_bytes(p);      // (the compact spectrum on plans of the library's own FFT passes)
+        const size_t bytes = (size_t)p->pspec_elems * 2 * real_bytes(p->dtype);      // (the compact spectrum on plans of the library's own FFT passes)
         *out_ptr = static_cast<char*>(p->d_uhat) + bytes * component;
         if (out_bytes) *out_bytes = (int64_t)bytes;
     } else {
@@ -1973,7 +1939,7 @@ int nufft_copy_grid(nufft_plan* p, int which, int component, void* dst, int64_t 
     if (component < 0 || component >= p->C) return fail(NUFFT_ERR_INVALID_ARG, "bad argument");
     if (which != 0 && !(which == 1 && !p->is_complex)) return fail(NUFFT_ERR_INVALID_ARG, "which must be 0 (us) or 1 (ûs, real plans only)");
     if (!dst) return fail(NUFFT_ERR_INVALID_ARG, "null destination");
-    const size_t bytes = which == 0 ? (size_t)p->grid_elems * value_bytes(p) : (size_t)p->pspec_elems * 2 * real_bytes(p);
+    const size_t bytes = which == 0 ? (size_t)p->grid_elems * value_bytes(p) : (size_t)p->pspec_elems * 2 * real_bytes(p->dtype);
     if (capacity_bytes < (int64_t)bytes) return fail(NUFFT_ERR_DIM_MISMATCH, "destination buffer too small");
     DeviceGuard guard(p->device);
     hipStream_t stream = static_cast<hipStream_t>(stream_);

@@ -15,11 +15,11 @@
 #include <string>
 #include <vector>
 
+#include "host_common.h"
 #include "kernels.h"
-#include "nufft_internal.h"
 #include "toeplitz.h"
 
-using nufft::set_error;
+using namespace nufft;
 
 struct nufft_toeplitz {
     int dtype = NUFFT_F64, D = 1, C = 1, device = -1, num_cus = 256;
@@ -52,40 +52,6 @@ struct nufft_toeplitz {
 
 namespace {
 
-int fail(int code, const std::string& msg) {
-    set_error(msg);
-    return code;
-}
-
-#define TZ_HIP(expr)                                                                           \
-    do {                                                                                       \
-        hipError_t e__ = (expr);                                                               \
-        if (e__ != hipSuccess)                                                                 \
-            return fail(e__ == hipErrorOutOfMemory ? NUFFT_ERR_ALLOC : NUFFT_ERR_HIP,          \
-                        std::string(#expr) + ": " + hipGetErrorString(e__));                   \
-    } while (0)
-
-#define TZ_ROCFFT(expr)                                                                        \
-    do {                                                                                       \
-        rocfft_status s__ = (expr);                                                            \
-        if (s__ != rocfft_status_success)                                                      \
-            return fail(NUFFT_ERR_ROCFFT, std::string(#expr) + ": rocfft status " + std::to_string((int)s__)); \
-    } while (0)
-
-struct DeviceGuard {
-    int prev = -1;
-    bool active = false;
-    explicit DeviceGuard(int dev) {
-        if (dev >= 0 && hipGetDevice(&prev) == hipSuccess && prev != dev) active = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard() {
-        if (active) (void)hipSetDevice(prev);
-    }
-};
-
-size_t real_bytes(const nufft_toeplitz* t) { return t->dtype == NUFFT_F32 ? 4 : 8; }
-size_t padded(size_t bytes) { return (std::max<size_t>(bytes, 16) + 255) / 256 * 256; }
-
 int64_t grid_cells(const nufft_toeplitz* t) { return t->N2[0] * t->N2[1] * t->N2[2]; }
 int64_t num_modes(const nufft_toeplitz* t) { return t->N[0] * t->N[1] * t->N[2]; }
 
@@ -96,7 +62,7 @@ struct Sizes {
     size_t total() const { return K + tmpA + tmpB + work + maps + twiddles + ones; }
 };
 Sizes sizes_of(const nufft_toeplitz* t) {
-    const size_t rb = real_bytes(t), cb = 2 * rb;
+    const size_t rb = real_bytes(t->dtype), cb = 2 * rb;
     const bool fused = t->path == NUFFT_TOEPLITZ_PATH_FUSED;
     Sizes s{};
     s.K = padded((size_t)grid_cells(t) * rb);
@@ -113,32 +79,14 @@ Sizes sizes_of(const nufft_toeplitz* t) {
     return s;
 }
 
-int alloc(nufft_toeplitz* t, void** ptr, size_t bytes) {
-    bytes = padded(bytes);
-    hipError_t e = hipMalloc(ptr, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        *ptr = nullptr;
-        return fail(NUFFT_ERR_ALLOC, "hipMalloc(" + std::to_string(bytes) + ") of a Toeplitz buffer: " + hipGetErrorString(e));
-    }
-    t->own_bytes += (int64_t)bytes;
-    return NUFFT_OK;
-}
-
-template <typename P>
-void release_buf(nufft_toeplitz* t, P*& ptr, size_t bytes) {
-    if (!ptr) return;
-    (void)hipFree(ptr);
-    t->own_bytes -= (int64_t)padded(bytes);
-    ptr = nullptr;
-}
+int alloc(nufft_toeplitz* t, void** ptr, size_t bytes) { return alloc_buffer(t->own_bytes, "Toeplitz", ptr, bytes); }
 
 template <typename T>
 int upload_real(nufft_toeplitz* t, void** dst, const std::vector<double>& src) {
     std::vector<T> tmp(src.begin(), src.end());
     int rc = alloc(t, dst, tmp.size() * sizeof(T));
     if (rc) return rc;
-    TZ_HIP(hipMemcpy(*dst, tmp.data(), tmp.size() * sizeof(T), hipMemcpyHostToDevice));
+    NUFFT_HIP(hipMemcpy(*dst, tmp.data(), tmp.size() * sizeof(T), hipMemcpyHostToDevice));
     return NUFFT_OK;
 }
 int upload(nufft_toeplitz* t, void** dst, const std::vector<double>& src) {
@@ -147,7 +95,7 @@ int upload(nufft_toeplitz* t, void** dst, const std::vector<double>& src) {
 int upload_i32(nufft_toeplitz* t, int32_t** dst, const std::vector<int32_t>& src) {
     int rc = alloc(t, reinterpret_cast<void**>(dst), src.size() * sizeof(int32_t));
     if (rc) return rc;
-    TZ_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    NUFFT_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     return NUFFT_OK;
 }
 
@@ -170,12 +118,6 @@ void release(nufft_toeplitz* t) {
     delete t;
 }
 
-bool capturing(hipStream_t stream) {
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return st != hipStreamCaptureStatusNone;
-}
-
 nufft::TzGrid grid_of(const nufft_toeplitz* t) {
     nufft::TzGrid g{};
     g.dtype = t->dtype;
@@ -191,7 +133,7 @@ nufft::TzGrid grid_of(const nufft_toeplitz* t) {
 
 int build_device(nufft_toeplitz* t) {
     DeviceGuard guard(t->device);
-    const size_t rb = real_bytes(t), cb = 2 * rb;
+    const size_t rb = real_bytes(t->dtype), cb = 2 * rb;
     const bool fused = t->path == NUFFT_TOEPLITZ_PATH_FUSED;
     int rc;
     if ((rc = alloc(t, &t->d_K, (size_t)grid_cells(t) * rb))) return rc;
@@ -221,17 +163,17 @@ int build_device(nufft_toeplitz* t) {
     size_t lengths[3] = {1, 1, 1};
     for (int d = 0; d < t->D; ++d) lengths[d] = (size_t)t->N2[d];
     const rocfft_precision prec = t->dtype == NUFFT_F32 ? rocfft_precision_single : rocfft_precision_double;
-    TZ_ROCFFT(rocfft_execution_info_create(&t->fft_info));
-    TZ_ROCFFT(rocfft_plan_create(&t->fft_bw, rocfft_placement_inplace, rocfft_transform_type_complex_inverse, prec, (size_t)t->D, lengths, 1, nullptr));
-    TZ_ROCFFT(rocfft_plan_get_work_buffer_size(t->fft_bw, &t->fft_work_bytes));
+    NUFFT_ROCFFT(rocfft_execution_info_create(&t->fft_info));
+    NUFFT_ROCFFT(rocfft_plan_create(&t->fft_bw, rocfft_placement_inplace, rocfft_transform_type_complex_inverse, prec, (size_t)t->D, lengths, 1, nullptr));
+    NUFFT_ROCFFT(rocfft_plan_get_work_buffer_size(t->fft_bw, &t->fft_work_bytes));
     if (!fused) {
         size_t wf = 0;
-        TZ_ROCFFT(rocfft_plan_create(&t->fft_fw, rocfft_placement_inplace, rocfft_transform_type_complex_forward, prec, (size_t)t->D, lengths, 1, nullptr));
-        TZ_ROCFFT(rocfft_plan_get_work_buffer_size(t->fft_fw, &wf));
+        NUFFT_ROCFFT(rocfft_plan_create(&t->fft_fw, rocfft_placement_inplace, rocfft_transform_type_complex_forward, prec, (size_t)t->D, lengths, 1, nullptr));
+        NUFFT_ROCFFT(rocfft_plan_get_work_buffer_size(t->fft_fw, &wf));
         t->fft_work_bytes = std::max(t->fft_work_bytes, wf);
         if (t->fft_work_bytes > 0) {
             if ((rc = alloc(t, &t->d_fft_work, t->fft_work_bytes))) return rc;
-            TZ_ROCFFT(rocfft_execution_info_set_work_buffer(t->fft_info, t->d_fft_work, t->fft_work_bytes));
+            NUFFT_ROCFFT(rocfft_execution_info_set_work_buffer(t->fft_info, t->d_fft_work, t->fft_work_bytes));
         }
     }
     return NUFFT_OK;
@@ -241,11 +183,11 @@ int build_device(nufft_toeplitz* t) {
 // `src` may be `grid` itself.
 int multiplier_from(nufft_toeplitz* t, void* grid, const void* src, hipStream_t stream) {
     const nufft::TzGrid g = grid_of(t);
-    TZ_HIP(nufft::launch_tz_spectrum_load(g, grid, src, t->num_cus, stream));
-    TZ_ROCFFT(rocfft_execution_info_set_stream(t->fft_info, stream));
+    NUFFT_HIP(nufft::launch_tz_spectrum_load(g, grid, src, t->num_cus, stream));
+    NUFFT_ROCFFT(rocfft_execution_info_set_stream(t->fft_info, stream));
     void* io[1] = {grid};
-    TZ_ROCFFT(rocfft_execute(t->fft_bw, io, nullptr, t->fft_info));
-    TZ_HIP(nufft::launch_tz_real_part(g, t->d_K, grid, 1.0 / (double)grid_cells(t), t->num_cus, stream));
+    NUFFT_ROCFFT(rocfft_execute(t->fft_bw, io, nullptr, t->fft_info));
+    NUFFT_HIP(nufft::launch_tz_real_part(g, t->d_K, grid, 1.0 / (double)grid_cells(t), t->num_cus, stream));
     return NUFFT_OK;
 }
 
@@ -257,7 +199,7 @@ struct Scratch {
     explicit Scratch(nufft_toeplitz* tz) : t(tz) {}
     int acquire_grid() {
         if (t->path != NUFFT_TOEPLITZ_PATH_FUSED) { grid = t->d_work; return NUFFT_OK; }
-        return alloc(t, &grid, (size_t)grid_cells(t) * 2 * real_bytes(t));
+        return alloc(t, &grid, (size_t)grid_cells(t) * 2 * real_bytes(t->dtype));
     }
     int acquire_fft_work() {
         if (t->path != NUFFT_TOEPLITZ_PATH_FUSED || t->fft_work_bytes == 0) return NUFFT_OK;
@@ -269,8 +211,8 @@ struct Scratch {
     }
     ~Scratch() {
         if (t->path != NUFFT_TOEPLITZ_PATH_FUSED) return;
-        release_buf(t, grid, (size_t)grid_cells(t) * 2 * real_bytes(t));
-        release_buf(t, fft_work, t->fft_work_bytes);
+        free_buffer(t->own_bytes, grid, (size_t)grid_cells(t) * 2 * real_bytes(t->dtype));
+        free_buffer(t->own_bytes, fft_work, t->fft_work_bytes);
     }
 };
 
@@ -302,7 +244,7 @@ int strided_pass(const nufft_toeplitz* t, int dim, bool forward, const void* in,
         q.in_stride_c = forward ? full_c : pruned_c;
         q.out_stride_c = forward ? pruned_c : full_c;
     }
-    TZ_HIP(nufft::launch_fft_lines(t->dtype, t->N2[dim], forward, q, stream));
+    NUFFT_HIP(nufft::launch_fft_lines(t->dtype, t->N2[dim], forward, q, stream));
     return NUFFT_OK;
 }
 
@@ -314,7 +256,7 @@ int apply_fused(nufft_toeplitz* t, void* out, const void* in, hipStream_t stream
         src = t->d_tmpA;
     }
     if ((rc = strided_pass(t, 1, false, src, t->d_tmpB, stream))) return rc;
-    TZ_HIP(nufft::launch_toeplitz_lines(t->dtype, t->N2[0], t->d_tmpB, t->d_K, t->N2[1] * t->N2[2], (int)t->N[0], t->d_map[0],
+    NUFFT_HIP(nufft::launch_toeplitz_lines(t->dtype, t->N2[0], t->d_tmpB, t->d_K, t->N2[1] * t->N2[2], (int)t->N[0], t->d_map[0],
                                         t->d_tw_fw[0], stream));
     if ((rc = strided_pass(t, 1, true, t->d_tmpB, t->D == 3 ? t->d_tmpA : out, stream))) return rc;
     if (t->D == 3 && (rc = strided_pass(t, 2, true, t->d_tmpA, out, stream))) return rc;
@@ -324,11 +266,11 @@ int apply_fused(nufft_toeplitz* t, void* out, const void* in, hipStream_t stream
 int apply_dense(nufft_toeplitz* t, void* out, const void* in, hipStream_t stream) {
     const nufft::TzGrid g = grid_of(t);
     void* io[1] = {t->d_work};
-    TZ_HIP(nufft::launch_tz_pad(g, t->d_work, in, t->num_cus, stream));
-    TZ_ROCFFT(rocfft_execute(t->fft_bw, io, nullptr, t->fft_info));
-    TZ_HIP(nufft::launch_tz_multiply(g, t->d_work, t->d_K, t->num_cus, stream));
-    TZ_ROCFFT(rocfft_execute(t->fft_fw, io, nullptr, t->fft_info));
-    TZ_HIP(nufft::launch_tz_crop(g, out, t->d_work, t->num_cus, stream));
+    NUFFT_HIP(nufft::launch_tz_pad(g, t->d_work, in, t->num_cus, stream));
+    NUFFT_ROCFFT(rocfft_execute(t->fft_bw, io, nullptr, t->fft_info));
+    NUFFT_HIP(nufft::launch_tz_multiply(g, t->d_work, t->d_K, t->num_cus, stream));
+    NUFFT_ROCFFT(rocfft_execute(t->fft_fw, io, nullptr, t->fft_info));
+    NUFFT_HIP(nufft::launch_tz_crop(g, out, t->d_work, t->num_cus, stream));
     return NUFFT_OK;
 }
 
@@ -405,8 +347,6 @@ int nufft_toeplitz_get_info(const nufft_toeplitz* t, nufft_toeplitz_info* o) {
     if (!t || !o) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
     nufft_toeplitz_info i;
     std::memset(&i, 0, sizeof(i));
-    const size_t known = o->struct_size > 0 ? std::min((size_t)o->struct_size, sizeof(i)) : sizeof(i);
-    i.struct_size = (int32_t)known;
     i.ndim = t->D;
     i.dtype = t->dtype;
     i.ntransforms = t->C;
@@ -415,9 +355,9 @@ int nufft_toeplitz_get_info(const nufft_toeplitz* t, nufft_toeplitz_info* o) {
     i.path = t->path;
     i.has_spectrum = t->has_spectrum;
     for (int d = 0; d < 3; ++d) { i.N[d] = t->N[d]; i.N2[d] = t->N2[d]; }
-    i.multiplier_bytes = grid_cells(t) * (int64_t)real_bytes(t);
+    i.multiplier_bytes = grid_cells(t) * (int64_t)real_bytes(t->dtype);
     i.workspace_bytes = t->device >= 0 ? t->own_bytes + t->build_bytes : (int64_t)sizes_of(t).total();
-    std::memcpy(o, &i, known);
+    write_info(o, i);
     return NUFFT_OK;
 }
 
@@ -425,7 +365,7 @@ int nufft_toeplitz_multiplier_ptr(const nufft_toeplitz* t, void** out_ptr, int64
     if (!t || !out_ptr) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
     if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
     *out_ptr = t->d_K;
-    if (out_bytes) *out_bytes = grid_cells(t) * (int64_t)real_bytes(t);
+    if (out_bytes) *out_bytes = grid_cells(t) * (int64_t)real_bytes(t->dtype);
     return NUFFT_OK;
 }
 
@@ -442,7 +382,7 @@ int nufft_toeplitz_set_spectrum(nufft_toeplitz* t, const void* T_modes, void* st
     int rc;
     if ((rc = s.acquire_grid()) || (rc = s.acquire_fft_work())) return rc;
     if ((rc = multiplier_from(t, s.grid, T_modes, stream))) return rc;
-    TZ_HIP(hipStreamSynchronize(stream));      // the temporaries are freed on return
+    NUFFT_HIP(hipStreamSynchronize(stream));      // the temporaries are freed on return
     t->has_spectrum = true;
     return NUFFT_OK;
 }
@@ -494,7 +434,7 @@ int nufft_toeplitz_set_points(nufft_toeplitz* t, const nufft_params* build, int6
     int rc;
     if ((rc = s.acquire_grid())) return rc;
     void* values = nullptr;
-    const size_t vbytes = (size_t)std::max<int64_t>(np, 1) * 2 * real_bytes(t);
+    const size_t vbytes = (size_t)std::max<int64_t>(np, 1) * 2 * real_bytes(t->dtype);
     if ((rc = alloc(t, &values, vbytes))) return rc;
     nufft_plan* bp = nullptr;
     rc = nufft_plan_create_ex(&bp, &prm);
@@ -516,11 +456,11 @@ int nufft_toeplitz_set_points(nufft_toeplitz* t, const nufft_params* build, int6
     const std::string keep = rc ? nufft_last_error_message() : "";
     if (bp) nufft_plan_destroy(bp);            // before the transform's own work buffer is allocated
     t->build_bytes = 0;
-    release_buf(t, values, vbytes);
+    free_buffer(t->own_bytes, values, vbytes);
     if (rc) return fail(rc, "Toeplitz build (type 1 of the weights on the 2N grid): " + keep);
     if ((rc = s.acquire_fft_work())) return rc;
     if ((rc = multiplier_from(t, s.grid, s.grid, stream))) return rc;
-    TZ_HIP(hipStreamSynchronize(stream));
+    NUFFT_HIP(hipStreamSynchronize(stream));
     t->has_spectrum = true;
     return NUFFT_OK;
 }
@@ -534,7 +474,7 @@ int nufft_toeplitz_apply(nufft_toeplitz* t, void* const* out, const void* const*
         if (!out[c] || !in[c]) return fail(NUFFT_ERR_INVALID_ARG, "null data vector");
     DeviceGuard guard(t->device);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (t->path == NUFFT_TOEPLITZ_PATH_DENSE) TZ_ROCFFT(rocfft_execution_info_set_stream(t->fft_info, stream));
+    if (t->path == NUFFT_TOEPLITZ_PATH_DENSE) NUFFT_ROCFFT(rocfft_execution_info_set_stream(t->fft_info, stream));
     for (int c = 0; c < t->C; ++c) {
         const int rc = t->path == NUFFT_TOEPLITZ_PATH_FUSED ? apply_fused(t, out[c], in[c], stream) : apply_dense(t, out[c], in[c], stream);
         if (rc) return rc;

@@ -10,24 +10,12 @@
 #include <algorithm>
 
 #include "nufft_mi355x.h"
+#include "stream_kernels.h"
 #include "toeplitz.h"
 
 namespace nufft {
+using namespace stream;
 namespace {
-
-constexpr int kThreads = 256;
-
-template <typename T>
-struct alignas(16) Pack {
-    static constexpr int W = 16 / sizeof(T);
-    T v[W];
-};
-
-unsigned grid_for(int64_t chunks, int num_cus) {
-    const int64_t cap = (int64_t)num_cus * 8;      // 8 workgroups of 4 waves per CU: enough bytes in flight for HBM
-    const int64_t need = (chunks + kThreads - 1) / kThreads;
-    return (unsigned)std::max<int64_t>(1, std::min(need, cap));
-}
 
 int64_t cells(const TzGrid& g) { return (int64_t)g.n2[0] * g.n2[1] * g.n2[2]; }
 
@@ -118,50 +106,37 @@ int64_t packs(const TzGrid& g) { return cells(g) / (g.dtype == NUFFT_F32 ? 2 : 1
 
 hipError_t launch_tz_pad(const TzGrid& g, void* grid, const void* u, int num_cus, hipStream_t stream) {
     const int64_t np = packs(g);
-    const dim3 gr(grid_for(np, num_cus)), bl(kThreads);
-    if (g.dtype == NUFFT_F32) hipLaunchKernelGGL((tz_fill_kernel<float, 0>), gr, bl, 0, stream, g, static_cast<float*>(grid), static_cast<const float*>(u), np);
-    else hipLaunchKernelGGL((tz_fill_kernel<double, 0>), gr, bl, 0, stream, g, static_cast<double*>(grid), static_cast<const double*>(u), np);
-    return hipGetLastError();
+    return launch_by_dtype(g.dtype, dim3(grid_for(np, num_cus)), dim3(kThreads), stream, tz_fill_kernel<float, 0>, tz_fill_kernel<double, 0>, g, grid, u, np);
 }
 
 hipError_t launch_tz_spectrum_load(const TzGrid& g, void* grid, const void* T_modes, int num_cus, hipStream_t stream) {
     const int64_t np = packs(g);
-    const dim3 gr(grid_for(np, num_cus)), bl(kThreads);
-    if (g.dtype == NUFFT_F32) hipLaunchKernelGGL((tz_fill_kernel<float, 1>), gr, bl, 0, stream, g, static_cast<float*>(grid), static_cast<const float*>(T_modes), np);
-    else hipLaunchKernelGGL((tz_fill_kernel<double, 1>), gr, bl, 0, stream, g, static_cast<double*>(grid), static_cast<const double*>(T_modes), np);
-    return hipGetLastError();
+    return launch_by_dtype(g.dtype, dim3(grid_for(np, num_cus)), dim3(kThreads), stream, tz_fill_kernel<float, 1>, tz_fill_kernel<double, 1>, g, grid, T_modes,
+                           np);
 }
 
 hipError_t launch_tz_multiply(const TzGrid& g, void* grid, const void* K, int num_cus, hipStream_t stream) {
     const int64_t np = packs(g);
-    const dim3 gr(grid_for(np, num_cus)), bl(kThreads);
-    if (g.dtype == NUFFT_F32) hipLaunchKernelGGL((tz_real_kernel<float, 0>), gr, bl, 0, stream, static_cast<float*>(grid), static_cast<float*>(const_cast<void*>(K)), 1.0f, np);
-    else hipLaunchKernelGGL((tz_real_kernel<double, 0>), gr, bl, 0, stream, static_cast<double*>(grid), static_cast<double*>(const_cast<void*>(K)), 1.0, np);
-    return hipGetLastError();
+    // the scale is a T in the kernel: launch_by_dtype narrows the double for Float32 (1.0 is exact)
+    return launch_by_dtype(g.dtype, dim3(grid_for(np, num_cus)), dim3(kThreads), stream, tz_real_kernel<float, 0>, tz_real_kernel<double, 0>, grid,
+                           const_cast<void*>(K), 1.0, np);
 }
 
 hipError_t launch_tz_real_part(const TzGrid& g, void* K, const void* grid, double scale, int num_cus, hipStream_t stream) {
     const int64_t np = packs(g);
-    const dim3 gr(grid_for(np, num_cus)), bl(kThreads);
-    if (g.dtype == NUFFT_F32) hipLaunchKernelGGL((tz_real_kernel<float, 1>), gr, bl, 0, stream, static_cast<float*>(const_cast<void*>(grid)), static_cast<float*>(K), (float)scale, np);
-    else hipLaunchKernelGGL((tz_real_kernel<double, 1>), gr, bl, 0, stream, static_cast<double*>(const_cast<void*>(grid)), static_cast<double*>(K), scale, np);
-    return hipGetLastError();
+    // `scale` is rounded to Float32 for the Float32 kernel, as (float)scale
+    return launch_by_dtype(g.dtype, dim3(grid_for(np, num_cus)), dim3(kThreads), stream, tz_real_kernel<float, 1>, tz_real_kernel<double, 1>,
+                           const_cast<void*>(grid), K, scale, np);
 }
 
 hipError_t launch_tz_crop(const TzGrid& g, void* out, const void* grid, int num_cus, hipStream_t stream) {
     const int64_t nm = (int64_t)g.nk[0] * g.nk[1] * g.nk[2];
-    const dim3 gr(grid_for(nm, num_cus)), bl(kThreads);
-    if (g.dtype == NUFFT_F32) hipLaunchKernelGGL((tz_crop_kernel<float>), gr, bl, 0, stream, g, static_cast<float*>(out), static_cast<const float*>(grid), nm);
-    else hipLaunchKernelGGL((tz_crop_kernel<double>), gr, bl, 0, stream, g, static_cast<double*>(out), static_cast<const double*>(grid), nm);
-    return hipGetLastError();
+    return launch_by_dtype(g.dtype, dim3(grid_for(nm, num_cus)), dim3(kThreads), stream, tz_crop_kernel<float>, tz_crop_kernel<double>, g, out, grid, nm);
 }
 
 hipError_t launch_tz_weights(int dtype, void* values, const void* weights, int64_t n, int num_cus, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
-    const dim3 gr(grid_for(n, num_cus)), bl(kThreads);
-    if (dtype == NUFFT_F32) hipLaunchKernelGGL((tz_weights_kernel<float>), gr, bl, 0, stream, static_cast<float*>(values), static_cast<const float*>(weights), n);
-    else hipLaunchKernelGGL((tz_weights_kernel<double>), gr, bl, 0, stream, static_cast<double*>(values), static_cast<const double*>(weights), n);
-    return hipGetLastError();
+    return launch_by_dtype(dtype, dim3(grid_for(n, num_cus)), dim3(kThreads), stream, tz_weights_kernel<float>, tz_weights_kernel<double>, values, weights, n);
 }
 
 }  // namespace nufft

@@ -15,10 +15,10 @@
 #include <string>
 #include <vector>
 
-#include "nufft_internal.h"
+#include "host_common.h"
 #include "type3.h"
 
-using nufft::set_error;
+using namespace nufft;
 
 struct nufft_plan3 {
     nufft_plan* sp = nullptr;          // spreading plan: N_over = nf, window of the requested σ and M
@@ -47,30 +47,6 @@ struct nufft_plan3 {
 
 namespace {
 
-int fail(int code, const std::string& msg) {
-    set_error(msg);
-    return code;
-}
-
-#define T3_HIP(expr)                                                                           \
-    do {                                                                                       \
-        hipError_t e__ = (expr);                                                               \
-        if (e__ != hipSuccess)                                                                 \
-            return fail(e__ == hipErrorOutOfMemory ? NUFFT_ERR_ALLOC : NUFFT_ERR_HIP,          \
-                        std::string(#expr) + ": " + hipGetErrorString(e__));                   \
-    } while (0)
-
-struct DeviceGuard {
-    int prev = -1;
-    bool active = false;
-    explicit DeviceGuard(int dev) {
-        if (dev >= 0 && hipGetDevice(&prev) == hipSuccess && prev != dev) active = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceGuard() {
-        if (active) (void)hipSetDevice(prev);
-    }
-};
-
 struct Timer {
     nufft_plan3* p;
     int stage;
@@ -86,34 +62,14 @@ struct Timer {
     }
 };
 
-size_t real_bytes(const nufft_plan3* p) { return p->dtype == NUFFT_F32 ? 4 : 8; }
-
-// Device buffers are padded to whole 16-byte packs of the kernels (type3_kernels.hip) and to 256 bytes.
-int alloc(nufft_plan3* p, void** ptr, size_t bytes) {
-    bytes = (std::max<size_t>(bytes, 16) + 255) / 256 * 256;
-    hipError_t e = hipMalloc(ptr, bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        *ptr = nullptr;
-        return fail(NUFFT_ERR_ALLOC, "hipMalloc(" + std::to_string(bytes) + ") of a type-3 buffer: " + hipGetErrorString(e));
-    }
-    p->own_bytes += (int64_t)bytes;
-    return NUFFT_OK;
-}
-
-void release_buf(nufft_plan3* p, void*& ptr, size_t bytes) {
-    if (!ptr) return;
-    (void)hipFree(ptr);
-    p->own_bytes -= (int64_t)((std::max<size_t>(bytes, 16) + 255) / 256 * 256);
-    ptr = nullptr;
-}
+int alloc(nufft_plan3* p, void** ptr, size_t bytes) { return alloc_buffer(p->own_bytes, "type-3", ptr, bytes); }
 
 size_t src_bytes(const nufft_plan3* p, int64_t n, int which) {      // 0: coordinates, 1: phase, 2: values
-    const size_t rb = real_bytes(p);
+    const size_t rb = real_bytes(p->dtype);
     return which == 0 ? (size_t)n * rb * p->D : which == 1 ? (size_t)n * rb * 2 : (size_t)n * rb * 2 * p->C;
 }
 size_t tgt_bytes(const nufft_plan3* p, int64_t n, int which) {      // 0: θ, 1: post factor
-    const size_t rb = real_bytes(p);
+    const size_t rb = real_bytes(p->dtype);
     return which == 0 ? (size_t)n * rb * p->D : (size_t)n * rb * 2;
 }
 
@@ -121,13 +77,12 @@ void release(nufft_plan3* p) {
     if (!p) return;
     if (p->device >= 0) {
         DeviceGuard g(p->device);
-        release_buf(p, p->d_xr, src_bytes(p, p->src_cap, 0));
-        release_buf(p, p->d_phase, src_bytes(p, p->src_cap, 1));
-        release_buf(p, p->d_cvals, src_bytes(p, p->src_cap, 2));
-        release_buf(p, p->d_theta, tgt_bytes(p, p->tgt_cap, 0));
-        release_buf(p, p->d_post, tgt_bytes(p, p->tgt_cap, 1));
-        void* o = p->d_outside;
-        release_buf(p, o, 16);
+        free_buffer(p->own_bytes, p->d_xr, src_bytes(p, p->src_cap, 0));
+        free_buffer(p->own_bytes, p->d_phase, src_bytes(p, p->src_cap, 1));
+        free_buffer(p->own_bytes, p->d_cvals, src_bytes(p, p->src_cap, 2));
+        free_buffer(p->own_bytes, p->d_theta, tgt_bytes(p, p->tgt_cap, 0));
+        free_buffer(p->own_bytes, p->d_post, tgt_bytes(p, p->tgt_cap, 1));
+        free_buffer(p->own_bytes, p->d_outside, 16);
         for (int s = 0; s < NUFFT3_NUM_STAGES; ++s) {
             if (p->ev_begin[s]) (void)hipEventDestroy(p->ev_begin[s]);
             if (p->ev_end[s]) (void)hipEventDestroy(p->ev_end[s]);
@@ -136,12 +91,6 @@ void release(nufft_plan3* p) {
     if (p->sp) nufft_plan_destroy(p->sp);
     if (p->t2) nufft_plan_destroy(p->t2);
     delete p;
-}
-
-bool capturing(hipStream_t stream) {
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return st != hipStreamCaptureStatusNone;
 }
 
 // Optimal window shape for the requested σ (plan.cpp: build_host, with σ in the plan's precision): the spreading plan's grid is nf,
@@ -166,7 +115,7 @@ int64_t fine_grid(double sigma, int M, double X, double S) {
 // The stages exec_type3 and exec_type3_grad share: premultiply c' = c · phase, then the completing spread of c'; `us` receives the
 // spread grid of every component (the type-2 plan's input spectrum).
 int prephase_and_spread(nufft_plan3* p, const void* const* c_in, std::vector<const void*>& us, hipStream_t stream) {
-    const size_t cb = 2 * real_bytes(p);
+    const size_t cb = 2 * real_bytes(p->dtype);
     std::vector<const void*> cv(p->C);
     for (int c = 0; c < p->C; ++c) cv[c] = static_cast<char*>(p->d_cvals) + (size_t)c * p->Np * cb;
     {
@@ -178,7 +127,7 @@ int prephase_and_spread(nufft_plan3* p, const void* const* c_in, std::vector<con
             m.ncomp = std::min(nufft::kMaxCompPerLaunch, p->C - c0);
             m.factor = p->d_phase;
             for (int i = 0; i < m.ncomp; ++i) { m.in[i] = c_in[c0 + i]; m.out[i] = const_cast<void*>(cv[c0 + i]); }
-            T3_HIP(nufft::launch_t3_multiply(m, p->num_cus, stream));
+            NUFFT_HIP(nufft::launch_t3_multiply(m, p->num_cus, stream));
         }
     }
     int rc;
@@ -279,7 +228,7 @@ int nufft_plan3_create(nufft_plan3** out, const nufft_params* params_in, const n
     {
         double outer = 1.0, inner = 1.0;
         for (int d = 0; d < D; ++d) { outer *= (double)p->nf[d]; inner *= (double)p->inner_nover[d]; }
-        grid_bytes = (outer + inner) * 2.0 * (double)real_bytes(p) * p->C;
+        grid_bytes = (outer + inner) * 2.0 * (double)real_bytes(p->dtype) * p->C;
     }
     const double user_param = prm.kernel_param;
     for (int d = 0; d < D; ++d) p->beta[d] = user_param > 0.0 ? user_param : optimal_param(p->kernel, p->M, p->sigma, p->dtype);
@@ -400,9 +349,9 @@ int nufft_set_points3(nufft_plan3* p, int64_t np, const void* const* x, int64_t 
             return fail(NUFFT_ERR_INVALID_ARG, "nufft_set_points3 would have to grow its buffers on a capturing stream: "
                                                "run it once eagerly with the largest point sets before capturing");
         if (np > p->src_cap) {
-            release_buf(p, p->d_xr, src_bytes(p, p->src_cap, 0));
-            release_buf(p, p->d_phase, src_bytes(p, p->src_cap, 1));
-            release_buf(p, p->d_cvals, src_bytes(p, p->src_cap, 2));
+            free_buffer(p->own_bytes, p->d_xr, src_bytes(p, p->src_cap, 0));
+            free_buffer(p->own_bytes, p->d_phase, src_bytes(p, p->src_cap, 1));
+            free_buffer(p->own_bytes, p->d_cvals, src_bytes(p, p->src_cap, 2));
             p->src_cap = 0;
             if ((rc = alloc(p, &p->d_xr, src_bytes(p, np, 0))) || (rc = alloc(p, &p->d_phase, src_bytes(p, np, 1))) ||
                 (rc = alloc(p, &p->d_cvals, src_bytes(p, np, 2))))
@@ -410,15 +359,15 @@ int nufft_set_points3(nufft_plan3* p, int64_t np, const void* const* x, int64_t 
             p->src_cap = np;
         }
         if (nk > p->tgt_cap) {
-            release_buf(p, p->d_theta, tgt_bytes(p, p->tgt_cap, 0));
-            release_buf(p, p->d_post, tgt_bytes(p, p->tgt_cap, 1));
+            free_buffer(p->own_bytes, p->d_theta, tgt_bytes(p, p->tgt_cap, 0));
+            free_buffer(p->own_bytes, p->d_post, tgt_bytes(p, p->tgt_cap, 1));
             p->tgt_cap = 0;
             if ((rc = alloc(p, &p->d_theta, tgt_bytes(p, nk, 0))) || (rc = alloc(p, &p->d_post, tgt_bytes(p, nk, 1)))) return rc;
             p->tgt_cap = nk;
         }
     }
-    const size_t rb = real_bytes(p);
-    T3_HIP(hipMemsetAsync(p->d_outside, 0, 2 * sizeof(unsigned long long), stream));
+    const size_t rb = real_bytes(p->dtype);
+    NUFFT_HIP(hipMemsetAsync(p->d_outside, 0, 2 * sizeof(unsigned long long), stream));
     if (np > 0) {
         nufft::T3SourceArgs a{};
         a.dtype = p->dtype;
@@ -439,7 +388,7 @@ int nufft_set_points3(nufft_plan3* p, int64_t np, const void* const* x, int64_t 
         }
         {
             Timer tm(p, NUFFT3_STAGE_PREP_SOURCES, stream);
-            T3_HIP(nufft::launch_t3_source_prep(a, p->num_cus, stream));
+            NUFFT_HIP(nufft::launch_t3_source_prep(a, p->num_cus, stream));
         }
         if ((rc = nufft_set_points(p->sp, np, xr, stream))) return rc;
     }
@@ -470,7 +419,7 @@ int nufft_set_points3(nufft_plan3* p, int64_t np, const void* const* x, int64_t 
         }
         {
             Timer tm(p, NUFFT3_STAGE_PREP_TARGETS, stream);
-            T3_HIP(nufft::launch_t3_target_prep(a, p->num_cus, stream));
+            NUFFT_HIP(nufft::launch_t3_target_prep(a, p->num_cus, stream));
         }
         if ((rc = nufft_set_points(p->t2, nk, th, stream))) return rc;
     }
@@ -489,9 +438,9 @@ int nufft_exec_type3(nufft_plan3* p, void* const* f_out, const void* const* c_in
         if (!f_out[c] || (p->Np > 0 && !c_in[c])) return fail(NUFFT_ERR_INVALID_ARG, "null data vector");
     DeviceGuard guard(p->device);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const size_t cb = 2 * real_bytes(p);
+    const size_t cb = 2 * real_bytes(p->dtype);
     if (p->Np == 0) {
-        for (int c = 0; c < p->C; ++c) T3_HIP(hipMemsetAsync(f_out[c], 0, (size_t)p->Nk * cb, stream));
+        for (int c = 0; c < p->C; ++c) NUFFT_HIP(hipMemsetAsync(f_out[c], 0, (size_t)p->Nk * cb, stream));
         return NUFFT_OK;
     }
     std::vector<const void*> us;
@@ -510,7 +459,7 @@ int nufft_exec_type3(nufft_plan3* p, void* const* f_out, const void* const* c_in
             m.ncomp = std::min(nufft::kMaxCompPerLaunch, p->C - c0);
             m.factor = p->d_post;
             for (int i = 0; i < m.ncomp; ++i) { m.in[i] = f_out[c0 + i]; m.out[i] = f_out[c0 + i]; }
-            T3_HIP(nufft::launch_t3_multiply(m, p->num_cus, stream));
+            NUFFT_HIP(nufft::launch_t3_multiply(m, p->num_cus, stream));
         }
     }
     return NUFFT_OK;
@@ -531,11 +480,11 @@ int nufft_exec_type3_grad(nufft_plan3* p, void* const* f_out, void* const* grad_
     }
     DeviceGuard guard(p->device);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    const size_t cb = 2 * real_bytes(p);
+    const size_t cb = 2 * real_bytes(p->dtype);
     if (p->Np == 0) {
         for (int c = 0; c < p->C; ++c) {
-            T3_HIP(hipMemsetAsync(f_out[c], 0, (size_t)p->Nk * cb, stream));
-            for (int d = 0; d < p->D; ++d) T3_HIP(hipMemsetAsync(grad_out[c * p->D + d], 0, (size_t)p->Nk * cb, stream));
+            NUFFT_HIP(hipMemsetAsync(f_out[c], 0, (size_t)p->Nk * cb, stream));
+            for (int d = 0; d < p->D; ++d) NUFFT_HIP(hipMemsetAsync(grad_out[c * p->D + d], 0, (size_t)p->Nk * cb, stream));
         }
         return NUFFT_OK;
     }
@@ -548,7 +497,7 @@ int nufft_exec_type3_grad(nufft_plan3* p, void* const* f_out, void* const* grad_
     }
     {
         Timer tm(p, NUFFT3_STAGE_POSTMULTIPLY, stream);
-        const size_t rb = real_bytes(p);
+        const size_t rb = real_bytes(p->dtype);
         for (int c0 = 0; c0 < p->C; c0 += nufft::kMaxCompPerLaunch) {
             nufft::T3GradArgs g{};
             g.dtype = p->dtype;
@@ -571,7 +520,7 @@ int nufft_exec_type3_grad(nufft_plan3* p, void* const* f_out, void* const* grad_
                 g.f[i] = f_out[c0 + i];
                 for (int d = 0; d < p->D; ++d) g.grad[i][d] = grad_out[(c0 + i) * p->D + d];
             }
-            T3_HIP(nufft::launch_t3_grad_finish(g, p->num_cus, stream));
+            NUFFT_HIP(nufft::launch_t3_grad_finish(g, p->num_cus, stream));
         }
     }
     return NUFFT_OK;
@@ -584,8 +533,8 @@ int nufft_type3_points_outside(nufft_plan3* p, int64_t* sources_out, int64_t* ta
     DeviceGuard guard(p->device);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     unsigned long long h[2] = {0, 0};
-    T3_HIP(hipMemcpyAsync(h, p->d_outside, sizeof(h), hipMemcpyDeviceToHost, stream));
-    T3_HIP(hipStreamSynchronize(stream));
+    NUFFT_HIP(hipMemcpyAsync(h, p->d_outside, sizeof(h), hipMemcpyDeviceToHost, stream));
+    NUFFT_HIP(hipStreamSynchronize(stream));
     if (sources_out) *sources_out = (int64_t)h[0];
     if (targets_out) *targets_out = (int64_t)h[1];
     return NUFFT_OK;
@@ -605,9 +554,9 @@ int nufft_get_stage_times3(nufft_plan3* p, float* ms_out) {
     for (int s = 0; s < NUFFT3_NUM_STAGES; ++s) {
         ms_out[s] = -1.0f;
         if (!p->ev_valid[s]) continue;
-        T3_HIP(hipEventSynchronize(p->ev_end[s]));
+        NUFFT_HIP(hipEventSynchronize(p->ev_end[s]));
         float ms = 0.0f;
-        T3_HIP(hipEventElapsedTime(&ms, p->ev_begin[s], p->ev_end[s]));
+        NUFFT_HIP(hipEventElapsedTime(&ms, p->ev_begin[s], p->ev_end[s]));
         ms_out[s] = ms;
     }
     return NUFFT_OK;

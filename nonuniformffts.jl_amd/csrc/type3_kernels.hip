@@ -9,20 +9,15 @@
 // are stored in the plan's precision.
 #include <hip/hip_runtime.h>
 
+#include "stream_kernels.h"
 #include "type3.h"
 
 namespace nufft {
+using namespace stream;
 namespace {
 
 constexpr double kTwoPi = 6.283185307179586476925286766559;
 constexpr double kPi = 3.1415926535897932384626433832795;
-constexpr int kThreads = 256;
-
-template <typename T>
-struct alignas(16) Pack {
-    static constexpr int W = 16 / sizeof(T);
-    T v[W];
-};
 
 __device__ inline double fold_2pi(double r) { return r - kTwoPi * floor(r * (1.0 / kTwoPi)); }
 
@@ -373,12 +368,6 @@ __global__ __launch_bounds__(kThreads) void t3_grad_finish_kernel(T3GradArgs a, 
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-unsigned grid_for(int64_t chunks, int num_cus) {
-    const int64_t cap = (int64_t)num_cus * 8;      // 8 workgroups of 4 waves per CU: enough bytes in flight for HBM
-    const int64_t need = (chunks + kThreads - 1) / kThreads;
-    return (unsigned)std::max<int64_t>(1, std::min(need, cap));
-}
-
 }  // namespace
 
 hipError_t launch_t3_source_prep(const T3SourceArgs& a, int num_cus, hipStream_t stream) {
@@ -387,20 +376,11 @@ hipError_t launch_t3_source_prep(const T3SourceArgs& a, int num_cus, hipStream_t
     for (int d = 0; d < a.D; ++d) vec &= aligned16(a.x[d]);
     const int W = a.dtype == NUFFT_F32 ? 4 : 2;
     const dim3 grid(grid_for((a.n + W - 1) / W, num_cus)), block(kThreads);
-    if (a.dtype == NUFFT_F32) {
-        switch (a.D) {
-            case 1: hipLaunchKernelGGL((t3_source_prep_kernel<float, 1>), grid, block, 0, stream, a, vec); break;
-            case 2: hipLaunchKernelGGL((t3_source_prep_kernel<float, 2>), grid, block, 0, stream, a, vec); break;
-            default: hipLaunchKernelGGL((t3_source_prep_kernel<float, 3>), grid, block, 0, stream, a, vec); break;
-        }
-    } else {
-        switch (a.D) {
-            case 1: hipLaunchKernelGGL((t3_source_prep_kernel<double, 1>), grid, block, 0, stream, a, vec); break;
-            case 2: hipLaunchKernelGGL((t3_source_prep_kernel<double, 2>), grid, block, 0, stream, a, vec); break;
-            default: hipLaunchKernelGGL((t3_source_prep_kernel<double, 3>), grid, block, 0, stream, a, vec); break;
-        }
+    switch (a.D) {
+        case 1: return launch_by_dtype(a.dtype, grid, block, stream, t3_source_prep_kernel<float, 1>, t3_source_prep_kernel<double, 1>, a, vec);
+        case 2: return launch_by_dtype(a.dtype, grid, block, stream, t3_source_prep_kernel<float, 2>, t3_source_prep_kernel<double, 2>, a, vec);
+        default: return launch_by_dtype(a.dtype, grid, block, stream, t3_source_prep_kernel<float, 3>, t3_source_prep_kernel<double, 3>, a, vec);
     }
-    return hipGetLastError();
 }
 
 hipError_t launch_t3_target_prep(const T3TargetArgs& a, int num_cus, hipStream_t stream) {
@@ -409,20 +389,11 @@ hipError_t launch_t3_target_prep(const T3TargetArgs& a, int num_cus, hipStream_t
     for (int d = 0; d < a.D; ++d) vec &= aligned16(a.s[d]);
     const int W = a.dtype == NUFFT_F32 ? 4 : 2;
     const dim3 grid(grid_for((a.n + W - 1) / W, num_cus)), block(kThreads);
-    if (a.dtype == NUFFT_F32) {
-        switch (a.D) {
-            case 1: hipLaunchKernelGGL((t3_target_prep_kernel<float, 1>), grid, block, 0, stream, a, vec); break;
-            case 2: hipLaunchKernelGGL((t3_target_prep_kernel<float, 2>), grid, block, 0, stream, a, vec); break;
-            default: hipLaunchKernelGGL((t3_target_prep_kernel<float, 3>), grid, block, 0, stream, a, vec); break;
-        }
-    } else {
-        switch (a.D) {
-            case 1: hipLaunchKernelGGL((t3_target_prep_kernel<double, 1>), grid, block, 0, stream, a, vec); break;
-            case 2: hipLaunchKernelGGL((t3_target_prep_kernel<double, 2>), grid, block, 0, stream, a, vec); break;
-            default: hipLaunchKernelGGL((t3_target_prep_kernel<double, 3>), grid, block, 0, stream, a, vec); break;
-        }
+    switch (a.D) {
+        case 1: return launch_by_dtype(a.dtype, grid, block, stream, t3_target_prep_kernel<float, 1>, t3_target_prep_kernel<double, 1>, a, vec);
+        case 2: return launch_by_dtype(a.dtype, grid, block, stream, t3_target_prep_kernel<float, 2>, t3_target_prep_kernel<double, 2>, a, vec);
+        default: return launch_by_dtype(a.dtype, grid, block, stream, t3_target_prep_kernel<float, 3>, t3_target_prep_kernel<double, 3>, a, vec);
     }
-    return hipGetLastError();
 }
 
 hipError_t launch_t3_multiply(const T3MultArgs& a, int num_cus, hipStream_t stream) {
@@ -431,29 +402,27 @@ hipError_t launch_t3_multiply(const T3MultArgs& a, int num_cus, hipStream_t stre
     for (int c = 0; c < a.ncomp; ++c) vec &= (aligned16(a.in[c]) && aligned16(a.out[c])) ? 1 : 0;
     const int W = a.dtype == NUFFT_F32 ? 2 : 1;
     const dim3 grid(grid_for((a.n + W - 1) / W, std::max(1, num_cus / a.ncomp)), a.ncomp), block(kThreads);
-    if (a.dtype == NUFFT_F32) hipLaunchKernelGGL((t3_multiply_kernel<float>), grid, block, 0, stream, a, vec);
-    else hipLaunchKernelGGL((t3_multiply_kernel<double>), grid, block, 0, stream, a, vec);
-    return hipGetLastError();
+    return launch_by_dtype(a.dtype, grid, block, stream, t3_multiply_kernel<float>, t3_multiply_kernel<double>, a, vec);
 }
 
 namespace {
 
-template <typename T, int D>
-void launch_grad_finish_t(const T3GradArgs& a, dim3 grid, hipStream_t stream, int vec_theta, int vec_io) {
+template <int D>
+hipError_t launch_grad_finish_d(const T3GradArgs& a, dim3 grid, hipStream_t stream, int vec_theta, int vec_io) {
     const dim3 block(kThreads);
     switch (a.kernel) {
         case NUFFT_KERNEL_BACKWARDS_KAISER_BESSEL:
-            hipLaunchKernelGGL((t3_grad_finish_kernel<T, D, NUFFT_KERNEL_BACKWARDS_KAISER_BESSEL>), grid, block, 0, stream, a, vec_theta, vec_io);
-            break;
+            return launch_by_dtype(a.dtype, grid, block, stream, t3_grad_finish_kernel<float, D, NUFFT_KERNEL_BACKWARDS_KAISER_BESSEL>,
+                                   t3_grad_finish_kernel<double, D, NUFFT_KERNEL_BACKWARDS_KAISER_BESSEL>, a, vec_theta, vec_io);
         case NUFFT_KERNEL_KAISER_BESSEL:
-            hipLaunchKernelGGL((t3_grad_finish_kernel<T, D, NUFFT_KERNEL_KAISER_BESSEL>), grid, block, 0, stream, a, vec_theta, vec_io);
-            break;
+            return launch_by_dtype(a.dtype, grid, block, stream, t3_grad_finish_kernel<float, D, NUFFT_KERNEL_KAISER_BESSEL>,
+                                   t3_grad_finish_kernel<double, D, NUFFT_KERNEL_KAISER_BESSEL>, a, vec_theta, vec_io);
         case NUFFT_KERNEL_GAUSSIAN:
-            hipLaunchKernelGGL((t3_grad_finish_kernel<T, D, NUFFT_KERNEL_GAUSSIAN>), grid, block, 0, stream, a, vec_theta, vec_io);
-            break;
+            return launch_by_dtype(a.dtype, grid, block, stream, t3_grad_finish_kernel<float, D, NUFFT_KERNEL_GAUSSIAN>,
+                                   t3_grad_finish_kernel<double, D, NUFFT_KERNEL_GAUSSIAN>, a, vec_theta, vec_io);
         default:
-            hipLaunchKernelGGL((t3_grad_finish_kernel<T, D, NUFFT_KERNEL_BSPLINE>), grid, block, 0, stream, a, vec_theta, vec_io);
-            break;
+            return launch_by_dtype(a.dtype, grid, block, stream, t3_grad_finish_kernel<float, D, NUFFT_KERNEL_BSPLINE>,
+                                   t3_grad_finish_kernel<double, D, NUFFT_KERNEL_BSPLINE>, a, vec_theta, vec_io);
     }
 }
 
@@ -469,20 +438,11 @@ hipError_t launch_t3_grad_finish(const T3GradArgs& a, int num_cus, hipStream_t s
     }
     const int W = a.dtype == NUFFT_F32 ? 4 : 2;
     const dim3 grid(grid_for((a.n + W - 1) / W, std::max(1, num_cus / a.ncomp)), a.ncomp);
-    if (a.dtype == NUFFT_F32) {
-        switch (a.D) {
-            case 1: launch_grad_finish_t<float, 1>(a, grid, stream, vec_theta, vec_io); break;
-            case 2: launch_grad_finish_t<float, 2>(a, grid, stream, vec_theta, vec_io); break;
-            default: launch_grad_finish_t<float, 3>(a, grid, stream, vec_theta, vec_io); break;
-        }
-    } else {
-        switch (a.D) {
-            case 1: launch_grad_finish_t<double, 1>(a, grid, stream, vec_theta, vec_io); break;
-            case 2: launch_grad_finish_t<double, 2>(a, grid, stream, vec_theta, vec_io); break;
-            default: launch_grad_finish_t<double, 3>(a, grid, stream, vec_theta, vec_io); break;
-        }
+    switch (a.D) {
+        case 1: return launch_grad_finish_d<1>(a, grid, stream, vec_theta, vec_io);
+        case 2: return launch_grad_finish_d<2>(a, grid, stream, vec_theta, vec_io);
+        default: return launch_grad_finish_d<3>(a, grid, stream, vec_theta, vec_io);
     }
-    return hipGetLastError();
 }
 
 }  // namespace nufft

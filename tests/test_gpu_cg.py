@@ -170,6 +170,53 @@ def test_converged_solve(Z, Ns, fftshift, path, C):
         sol.close()
 
 
+@pytest.mark.parametrize("Z,Ns,path,C,a,cond_bound", [("c128", (512, 512), "fused", 1, 0.2, 5.07), ("c64", (1024, 512), "dense", 2, 0.2, 5.07),
+                                                      ("c64", (128, 64, 64), "fused", 2, 0.15, 6.14)])
+def test_more_workgroups_than_threads(Z, Ns, path, C, a, cond_bound):
+    """More rows of per-workgroup partials than threads in a workgroup (262144 packs per component: 512 workgroups), so the next kernel's
+    fixed-order reduction takes its strided part (thread t adds rows t, t + 256, ...), for C = 2 in the [C][G][2] layout beyond one stride.
+
+    The operator gets the analytic spectrum T[d] = Π_dim a^|d_dim|: the coefficients of a product of Poisson kernels, whose symbol
+    Π (1 − a²) / (1 − 2a cos θ + a²) lies in [((1 − a) / (1 + a))^D, ((1 + a) / (1 − a))^D], so G is positive definite with
+    cond <= 1.5^4 = 5.0625 in 2-D at a = 0.2.  Five iterations against the reference under the bars of test_fixed_iteration_count, and
+    two solves of the same inputs equal bit for bit.  (1024, 512) runs the dense path: the fused passes stop at lines of 2N = 1024
+    cells, and no fused 2-D ComplexF32 system has more than 256 workgroups.  (128, 64, 64) is the fused ComplexF32 system of the same
+    size; a = 0.15 keeps its cond <= (1.15 / 0.85)^6 = 6.133 under the file's limit of 7 (0.2 would give 11.4 in 3-D)."""
+    from nufft_pkg import nufft
+    T, Zc, bar, _ = _dt(Z)
+    D = len(Ns)
+    cond = ((1 + a) / (1 - a)) ** (2 * D)
+    assert cond <= cond_bound <= 7, cond
+    spec = np.ones([2 * n for n in reversed(Ns)])
+    for dim, n in enumerate(Ns):                                               # dimension dim is axis D − 1 − dim
+        shape = [1] * D
+        shape[D - 1 - dim] = 2 * n
+        spec = spec * (a ** np.abs(np.asarray(R.modes(2 * n)).astype(np.float64))).reshape(shape)
+    spec = spec.astype(np.complex128)
+    plan = nufft.PlanNUFFT(Zc, Ns, backend=nufft.ROCBackend(0), ntransforms=C)
+    op = nufft.ToeplitzOperator(plan)
+    assert op.path == path, (Ns, path, op.path)
+    op.set_spectrum(_dev(spec, Zc))
+    plan.close()
+    K = R.multiplier(Ns, spec).real
+    apply = lambda p: R.apply(Ns, K, np.asarray(p).astype(np.complex128))     # noqa: E731
+    rng = np.random.default_rng(4 * sum(Ns))
+    bs = [(rng.standard_normal(Ns[::-1]) + 1j * rng.standard_normal(Ns[::-1])).astype(Zc) for _ in range(C)]
+    sol = nufft.ToeplitzCG(op, maxiter=5, rtol=0.0, lam=0.0)
+    assert sol.info().workgroups > 256, sol.info().workgroups
+    xs, iters, status, hist = _solve(sol, bs, C)
+    assert iters == (5,) * C and status == ("max_iter",) * C and hist.shape == (6, C)
+    for c in range(C):
+        ref = CG.cg(apply, bs[c], lam=0.0, rtol=0.0, max_iter=5, dtype=Zc)
+        ex, eh = R.rel(xs[c], ref["x"]), R.rel(hist[:, c], ref["history"])
+        print(f"{sol.info().workgroups} workgroups {Z} N={Ns} {path} c={c}: x {ex:.3e}, history {eh:.3e} (bar {10 * bar:g})")
+        assert ex <= 10 * bar and eh <= 10 * bar
+    xs2, iters2, status2, hist2 = _solve(sol, bs, C)
+    assert iters2 == iters and status2 == status and _same(hist, hist2) and all(_same(u, v) for u, v in zip(xs, xs2))
+    sol.close()
+    op.close()
+
+
 @pytest.mark.parametrize("Z,Ns", [("c128", (48,)), ("c64", (48,)), ("c128", (15, 9)), ("c64", (15, 9))])
 def test_converged_solve_clustered_points(Z, Ns):
     from nufft_pkg import nufft

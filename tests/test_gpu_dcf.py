@@ -168,6 +168,23 @@ def test_parity_with_the_reference_after_ten_iterations(nufft, Z, Ns, M, kernel,
     assert (i.num_points, i.iterations_enqueued) == (Np, 10) and i.capacity >= Np and i.plan_bytes > 0
 
 
+@pytest.mark.parametrize("Z,Np", [("f64", 300001), ("f32", 600003)])
+def test_more_workgroups_than_threads(nufft, Z, Np):
+    """150000 packs (293 workgroups) and a tail of one / three reals: more rows of partials than threads in a workgroup, so the fixed-order
+    reduction of the next kernel takes its strided part (thread t reduces rows t, t + 256, ...)."""
+    Ns = (65536,)
+    dc, oplan, T = make(nufft, Z, Ns, maxiter=3, tol=0.0, normalize="sum")
+    xs = coords(points("uniform", 1, Np, seed=Np), T)
+    ref = D.pipe_menon(oplan, xs, max_iter=3)
+    w, its, status, _, hist = run(dc, xs)
+    assert dc.info().workgroups > 256, dc.info().workgroups
+    ew, eh = rel(w, ref["w"]), hist_dev(hist, ref["history"])
+    print(f"DCF {dc.info().workgroups} workgroups {Z} Np={Np}: w {ew:.3e} history {eh:.3e} (bars {BAR_W[T]:g}, {BAR_H[T]:g})")
+    assert (its, status) == (3, "max_iter") and ref["iterations"] == 3
+    assert ew <= BAR_W[T] and eh <= BAR_H[T], (ew, eh)
+    assert abs(float(w.astype(np.float64).sum()) - 1.0) <= 8 * np.finfo(T).eps
+
+
 @pytest.mark.parametrize("M", [4, 8])
 def test_float32_three_dimensions_do_not_overflow(nufft, M):
     """C 1 is about 1e45 (M = 4) in the reference's formulation: the device runs on w / 2^κ.  Without normalisation the true weights
