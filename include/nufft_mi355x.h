@@ -483,12 +483,49 @@ int nufft_toeplitz_set_spectrum(nufft_toeplitz* tz, const void* T_modes, void* s
 int nufft_toeplitz_set_points(nufft_toeplitz* tz, const nufft_params* build_params, int64_t num_points, const void* const* coords,
                               const void* weights, void* stream);
 /* out[c] = G in[c], c < ntransforms: device arrays complex(T)[N_out...] in the plan's mode order (fftshift plans work unchanged);
- * out[c] may equal in[c].  Allocates nothing, does not synchronise, is hipGraph-capture safe.  Refusals, all before anything is
+ * out[c] may equal in[c] (not while coil maps are set, see below).  Allocates nothing, does not synchronise, is hipGraph-capture safe.  Refusals, all before anything is
  * enqueued: a host-only object NUFFT_ERR_NO_DEVICE, no spectrum yet NUFFT_ERR_NO_POINTS, a null table or vector NUFFT_ERR_INVALID_ARG. */
 int nufft_toeplitz_apply(nufft_toeplitz* tz, void* const* out, const void* const* in, void* stream);
 /* Device pointer and bytes of K (inspection and tests). */
 int nufft_toeplitz_multiplier_ptr(const nufft_toeplitz* tz, void** out_ptr, int64_t* out_bytes);
 int64_t nufft_sizeof_toeplitz_info(void);
+
+/* ---- Coil sensitivity maps in the Toeplitz normal operator: SENSE --- */
+/* A multi-coil acquisition solves with  G_S û = Σ_c conj(S_c) ⊙ G (S_c ⊙ û),  c < ncoils,  S_c complex maps on the uniform side.
+ * Added after the Toeplitz section under the same rule: detect by symbol (dlsym nufft_toeplitz_set_maps); NUFFT_MI355X_VERSION and
+ * nufft_toeplitz_info are unchanged.
+ *
+ * maps[c]: device arrays complex(T)[N...] laid out like the arrays of nufft_toeplitz_apply, 16-byte aligned.  The operator BORROWS
+ * them: the host table is copied, the device data is not (32 coils at 256³ are 8.6 GB).  They must stay valid, and hold their values,
+ * until the next nufft_toeplitz_set_maps, nufft_toeplitz_clear_maps or nufft_toeplitz_destroy.  The same maps serve every component
+ * of an ntransforms operator.  Independent of nufft_toeplitz_set_spectrum / _set_points: any order, either redone without the other.
+ * Refusals: a null table or ncoils outside 1 ... 1024 NUFFT_ERR_INVALID_ARG; then a host-only object NUFFT_ERR_NO_DEVICE; then a null
+ * or not 16-byte aligned entry NUFFT_ERR_INVALID_ARG.
+ *
+ * With maps set nufft_toeplitz_apply computes G_S per component: the coils run in index order on the caller's stream, coil 0 writes
+ * out[c], coils >= 1 read it and add — no atomics, so two runs and a graph replay give the same bits; it still allocates nothing
+ * and does not synchronise.  out[c] == in[c'] for any c, c' is then refused (NUFFT_ERR_INVALID_ARG): coil 0's store would destroy
+ * the input of coil 1.  Without maps nothing changes, in place included.
+ *
+ * Routes: on the fused path S_c multiplies where the first pruned pass loads the caller's array and conj(S_c) where the last one
+ * stores into it (no extra pass); on the dense path the pad and crop kernels do the same.  The option
+ * NUFFT_TOEPLITZ_MAPS_INPASS=0 of the plan's options string (read at nufft_toeplitz_create) makes the fused path run
+ * nufft_coil_expand into one N^D scratch array, the plain in-place apply on it, and a combine that adds into out[c]; the scratch
+ * array is allocated by nufft_toeplitz_set_maps (never on a capturing stream in this mode), counted in workspace_bytes and freed by
+ * nufft_toeplitz_clear_maps.  `stream` is otherwise unused: the call enqueues nothing. */
+int nufft_toeplitz_set_maps(nufft_toeplitz* tz, int32_t ncoils, const void* const* maps, void* stream);
+/* Back to the plain operator G; idempotent. */
+int nufft_toeplitz_clear_maps(nufft_toeplitz* tz);
+/* 0 without maps. */
+int32_t nufft_toeplitz_num_coils(const nufft_toeplitz* tz);
+/* The forward model's and the right-hand side's coil passes, on `n` complex(T) elements (dtype: NUFFT_F32 / NUFFT_F64 = the real type;
+ * n >= 0, an odd count of ComplexF32 elements included); every pointer 16-byte aligned; ncoils in 1 ... 1024; tables on the host.
+ *   expand:   out[c] = S_c ⊙ in
+ *   combine:  out = Σ_c conj(S_c) ⊙ in[c], summed in coil order in registers: one pass reads every array once and no partial result
+ *             goes through memory (up to 64 coils; beyond, the running sum passes through `out` once per 64 coils, same order).
+ * Both allocate nothing and do not synchronise. */
+int nufft_coil_expand(int dtype, int64_t n, int32_t ncoils, void* const* out, const void* const* maps, const void* in, int device, void* stream);
+int nufft_coil_combine(int dtype, int64_t n, int32_t ncoils, void* out, const void* const* maps, const void* const* in, int device, void* stream);
 
 /* ---- Conjugate gradients on the Toeplitz normal operator --------- */
 /* Solves (G + λ I) x_c = b_c for every component c < ntransforms independently (G is block-diagonal over components: each has its

@@ -210,6 +210,11 @@ SYMBOLS = {
     "nufft_toeplitz_apply": (C.c_int, [_P, _PP, _PP, _P]),
     "nufft_toeplitz_multiplier_ptr": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int64)]),
     "nufft_sizeof_toeplitz_info": (C.c_int64, []),
+    "nufft_toeplitz_set_maps": (C.c_int, [_P, C.c_int32, _PP, _P]),
+    "nufft_toeplitz_clear_maps": (C.c_int, [_P]),
+    "nufft_toeplitz_num_coils": (C.c_int32, [_P]),
+    "nufft_coil_expand": (C.c_int, [C.c_int, C.c_int64, C.c_int32, _PP, _PP, _P, C.c_int, _P]),
+    "nufft_coil_combine": (C.c_int, [C.c_int, C.c_int64, C.c_int32, _P, _PP, _PP, C.c_int, _P]),
     "nufft_cg_create": (C.c_int, [C.POINTER(_P), _P, C.POINTER(NufftCgParams)]),
     "nufft_cg_destroy": (C.c_int, [_P]),
     "nufft_cg_solve": (C.c_int, [_P, _PP, _PP, C.c_int, _P]),

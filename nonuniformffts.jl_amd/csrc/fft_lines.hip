@@ -119,6 +119,8 @@ struct FftLineArgs {
     const void* twiddle;      // complex<T>[N]: exp(SIGN 2πi m / N)
     double scale;             // extra scalar factor (normfactor)
     const void* mult;         // optional T[]: real multiplier indexed like the pruned side (uniform callback), or null
+    const void* cmap;         // CMAP kernels: complex<T>[] indexed like the pruned side (a coil sensitivity map)
+    int accumulate;           // CMAP, forward: the store adds to what `out` holds (uniform per launch)
     // rows: a = r * row_a + k1 enumerates rows r of row_a columns of which k1 < row_valid exist; the row strides of the two
     // sides differ (intermediates pad their rows to 128 bytes, the caller's array does not).  row_a = 0: no row structure.
     int row_a, row_valid, row_in, row_out;
@@ -217,7 +219,9 @@ __device__ __forceinline__ void fft_line(typename Cplx2<T>::type* line, const ty
 #endif
 // FWD: full input (N along j), pruned output (nk along k').  BWD: pruned input, full output.
 // MULT: a real multiplier array (uniform callback menu) is applied on the pruned side.
-template <typename T, int N, bool FWD, int TA, bool MULT>
+// CMAP: a complex array S on the pruned side (the Toeplitz operator's coil maps): backward multiplies the kept modes by S while they are
+// loaded, forward multiplies them by conj(S) while they are stored and, with a.accumulate, adds what `out` already holds.
+template <typename T, int N, bool FWD, int TA, bool MULT, bool CMAP = false>
 __global__ __launch_bounds__(TA * kWave) void fft_lines_kernel(FftLineArgs a) {
     using C = typename Cplx2<T>::type;
     constexpr int LINE = N + (N >> 4) + 1;            // padded line length (elements)
@@ -237,6 +241,8 @@ __global__ __launch_bounds__(TA * kWave) void fft_lines_kernel(FftLineArgs a) {
     const T* fk = static_cast<const T*>(a.fk);
     const T scale = (T)a.scale;
     const T* mult = static_cast<const T*>(a.mult);
+    [[maybe_unused]] const C* cmap = nullptr;
+    if constexpr (CMAP) cmap = static_cast<const C*>(a.cmap) + (int64_t)c * (FWD ? a.out_stride_c : a.in_stride_c);
     // this thread's column (NT is a multiple of TA: e % TA is the same in every loop below)
     const int64_t acol = a0 + tid % TA;
     bool cvalid = acol < a.a_total;
@@ -301,11 +307,16 @@ __global__ __launch_bounds__(TA * kWave) void fft_lines_kernel(FftLineArgs a) {
             const int ai = tid % TA;
             for (int k0 = tid / TA; k0 < a.nk; k0 += 4 * kWave) {
                 C v[4];
+                [[maybe_unused]] C sv[CMAP ? 4 : 1];
 #pragma unroll
                 for (int b = 0; b < 4; ++b) {
                     const int k = k0 + b * kWave;
                     v[b].x = T(0); v[b].y = T(0);
                     if (k < a.nk) v[b] = in[in_col + (int64_t)k * a.in_stride_j];
+                    if constexpr (CMAP) {
+                        sv[b].x = T(0); sv[b].y = T(0);
+                        if (k < a.nk) sv[b] = cmap[in_col + (int64_t)k * a.in_stride_j];
+                    }
                 }
 #pragma unroll
                 for (int b = 0; b < 4; ++b) {
@@ -314,6 +325,7 @@ __global__ __launch_bounds__(TA * kWave) void fft_lines_kernel(FftLineArgs a) {
                         T f = fa[fidx] * fk[k] * scale;
                         if constexpr (MULT) f *= mult[in_col + (int64_t)k * a.in_stride_j];
                         v[b].x *= f; v[b].y *= f;
+                        if constexpr (CMAP) v[b] = cmul(v[b], sv[b]);
                         lines[ai * LINE + lpad(a.map[k])] = v[b];
                     }
                 }
@@ -336,7 +348,40 @@ __global__ __launch_bounds__(TA * kWave) void fft_lines_kernel(FftLineArgs a) {
     if constexpr (FWD) __builtin_amdgcn_s_setprio(0);
 #endif
 
-    if (FWD) {
+    if constexpr (FWD && CMAP) {
+        // the map and (coils >= 1) the running output of four kept modes are in flight per thread before the first is used, as in the
+        // backward load: element by element the store would wait for two dependent HBM reads each
+        if (cvalid) {
+            const int ai = tid % TA;
+            const bool acc = a.accumulate != 0;
+            for (int k0 = tid / TA; k0 < a.nk; k0 += 4 * kWave) {
+                C s[4], o[4];
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    const int k = k0 + b * kWave;
+                    s[b].x = T(0); s[b].y = T(0); o[b] = s[b];
+                    if (k < a.nk) {
+                        const int64_t off = out_col + (int64_t)k * a.out_stride_j;
+                        s[b] = cmap[off];
+                        if (acc) o[b] = out[off];
+                    }
+                }
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    const int k = k0 + b * kWave;
+                    if (k < a.nk) {
+                        C v = lines[ai * LINE + lpad(a.map[k])];
+                        const T f = fa[fidx] * fk[k] * scale;
+                        v.x *= f; v.y *= f;
+                        s[b].y = -s[b].y;
+                        v = cmul(v, s[b]);
+                        if (acc) v = cadd(o[b], v);
+                        out[out_col + (int64_t)k * a.out_stride_j] = v;
+                    }
+                }
+            }
+        }
+    } else if (FWD) {
         for (int e = tid; e < TA * a.nk; e += NT) {
             const int ai = e % TA, k = e / TA;
             if (cvalid) {
@@ -822,7 +867,7 @@ hipError_t launch_cplx_lines(int dtype, int64_t n, bool forward, const void* in,
     return forward ? launch_cplx_t<double, true>((int)n, a, stream) : launch_cplx_t<double, false>((int)n, a, stream);
 }
 
-template <typename T, int N, bool FWD, bool MULT>
+template <typename T, int N, bool FWD, bool MULT, bool CMAP = false>
 static hipError_t launch_n_m(const FftLineArgs& a, hipStream_t stream) {
     using C = typename Cplx2<T>::type;
     constexpr int LINE = N + (N >> 4) + 1;
@@ -835,7 +880,7 @@ static hipError_t launch_n_m(const FftLineArgs& a, hipStream_t stream) {
     constexpr int TA = (sizeof(C) * (16 * LINE + N) <= NUFFT_FFT_LDS_LIMIT) ? 16 : ((sizeof(C) * (8 * LINE + N) <= NUFFT_FFT_LDS_LIMIT) ? 8 : 4);
     static_assert(sizeof(C) * (size_t)(TA * LINE + N) <= kFftLdsLimit, "line buffers exceed the 160 KiB of LDS");
     const size_t lds = sizeof(C) * (size_t)(TA * LINE + N);
-    auto fn = fft_lines_kernel<T, N, FWD, TA, MULT>;
+    auto fn = fft_lines_kernel<T, N, FWD, TA, MULT, CMAP>;
     // the attribute is per device: remember which devices of this process have it (plans may live on several)
     static std::atomic<unsigned long long> prepared{0};
     int dev = 0;
@@ -854,6 +899,7 @@ static hipError_t launch_n_m(const FftLineArgs& a, hipStream_t stream) {
 
 template <typename T, int N, bool FWD>
 static hipError_t launch_n(const FftLineArgs& a, hipStream_t stream) {
+    if (a.cmap) return a.mult ? hipErrorInvalidValue : launch_n_m<T, N, FWD, false, true>(a, stream);
     return a.mult ? launch_n_m<T, N, FWD, true>(a, stream) : launch_n_m<T, N, FWD, false>(a, stream);
 }
 
@@ -880,6 +926,7 @@ hipError_t launch_fft_lines(int dtype, int64_t n, bool forward, const FftLinePas
     a.out_stride_j = p.out_stride_j; a.out_stride_c = p.out_stride_c;
     a.nc = p.nc; a.nk = p.nk; a.map = p.map; a.fa = p.fa; a.ka = p.ka; a.fk = p.fk;
     a.twiddle = p.twiddle; a.scale = p.scale; a.mult = p.mult;
+    a.cmap = p.cmap; a.accumulate = p.accumulate ? 1 : 0;
     a.row_a = p.row_a; a.row_valid = p.row_valid; a.row_in = p.row_in; a.row_out = p.row_out;
     if (dtype == NUFFT_F32) return forward ? launch_t<float, true>((int)n, a, stream) : launch_t<float, false>((int)n, a, stream);
     return forward ? launch_t<double, true>((int)n, a, stream) : launch_t<double, false>((int)n, a, stream);

@@ -240,6 +240,8 @@ struct FftLinePass {
     double scale;
     const void* mult;                       // optional T[...]: real multiplier indexed like the pruned side, or null
     int row_a = 0, row_valid = 0, row_in = 0, row_out = 0;      // rows of the enumeration and their strides on both sides (0: none)
+    const void* cmap = nullptr;             // optional complex<T>[...] on the pruned side: backward times S at the load, forward times
+    bool accumulate = false;                // conj(S) at the store, added to what `out` holds when `accumulate` (not with mult)
 };
 bool fft_lines_supported(int dtype, int64_t n);
 bool real_lines_supported(int dtype, int64_t n);

@@ -5,6 +5,10 @@
 //   G û = crop(forwardDFT_{2N}(K ⊙ backwardDFT_{2N}(pad(û)))).
 // The fused path runs pad + backward transform and forward transform + crop as the pruned line passes of fft_lines.hip (kept modes
 // in, full line out and back) with the multiply inside the dimension-1 kernel; the dense path runs rocFFT on a (2N)^D grid.
+//
+// With coil sensitivity maps S_c set the same apply computes G_S û = Σ_c conj(S_c) ⊙ G (S_c ⊙ û), coil after
+// coil in stream order: S_c multiplies where the first pass loads the caller's array, conj(S_c) where the last pass stores into it,
+// and coils >= 1 add to what coil 0 stored.
 #include <hip/hip_runtime.h>
 #include <rocfft/rocfft.h>
 
@@ -48,6 +52,10 @@ struct nufft_toeplitz {
     size_t fft_work_bytes = 0;
     int64_t own_bytes = 0, build_bytes = 0;
     bool has_spectrum = false;
+    // coil sensitivity maps: borrowed device pointers, the host table is the operator's
+    std::vector<const void*> coil_maps;
+    bool maps_inpass = true;                           // fused: the maps ride in the outermost passes (false: expand / apply / combine)
+    void* d_coil = nullptr;                            // fused, streaming route: complex<T>[N_1, N_2, N_3], held while maps are set
 };
 
 namespace {
@@ -109,7 +117,7 @@ void release(nufft_toeplitz* t) {
             if (t->d_tw_fw[d]) (void)hipFree(t->d_tw_fw[d]);
             if (t->d_tw_bw[d]) (void)hipFree(t->d_tw_bw[d]);
         }
-        for (void* p : {t->d_ones, t->d_K, t->d_tmpA, t->d_tmpB, t->d_work, t->d_fft_work})
+        for (void* p : {t->d_ones, t->d_K, t->d_tmpA, t->d_tmpB, t->d_work, t->d_fft_work, t->d_coil})
             if (p) (void)hipFree(p);
         if (t->fft_bw) (void)rocfft_plan_destroy(t->fft_bw);
         if (t->fft_fw) (void)rocfft_plan_destroy(t->fft_fw);
@@ -217,7 +225,9 @@ struct Scratch {
 };
 
 // One pruned strided pass of the fused apply along dimension `dim` (1 or 2, zero-based): backward = kept modes in, full line out.
-int strided_pass(const nufft_toeplitz* t, int dim, bool forward, const void* in, void* out, hipStream_t stream) {
+// `smap` (the outermost pass only: its pruned side is the caller's array): the coil's map, see FftLinePass::cmap.
+int strided_pass(const nufft_toeplitz* t, int dim, bool forward, const void* in, void* out, hipStream_t stream, const void* smap = nullptr,
+                 bool accumulate = false) {
     // pruned side: N_dim kept modes; full side: 2 N_dim.  Columns: dimension 1 (and 2 for the pass along dimension 3) of the KEPT
     // modes; the outer index of the pass along dimension 2 of a 3-D grid is the full dimension 3.
     nufft::FftLinePass q{};
@@ -230,6 +240,8 @@ int strided_pass(const nufft_toeplitz* t, int dim, bool forward, const void* in,
     q.fk = t->d_ones;
     q.scale = 1.0;
     q.mult = nullptr;
+    q.cmap = smap;
+    q.accumulate = accumulate;
     const int64_t N1 = t->N[0];
     if (dim == 2) {
         q.a_total = q.a_out = N1 * t->N[1];
@@ -248,31 +260,54 @@ int strided_pass(const nufft_toeplitz* t, int dim, bool forward, const void* in,
     return NUFFT_OK;
 }
 
-int apply_fused(nufft_toeplitz* t, void* out, const void* in, hipStream_t stream) {
+// smap != null: out (+)= conj(S) ⊙ G (S ⊙ in), the map inside the two passes that touch the caller's arrays
+int apply_fused(nufft_toeplitz* t, void* out, const void* in, hipStream_t stream, const void* smap = nullptr, bool accumulate = false) {
     int rc;
     const void* src = in;
     if (t->D == 3) {
-        if ((rc = strided_pass(t, 2, false, in, t->d_tmpA, stream))) return rc;
+        if ((rc = strided_pass(t, 2, false, in, t->d_tmpA, stream, smap))) return rc;
         src = t->d_tmpA;
     }
-    if ((rc = strided_pass(t, 1, false, src, t->d_tmpB, stream))) return rc;
+    if ((rc = strided_pass(t, 1, false, src, t->d_tmpB, stream, t->D == 3 ? nullptr : smap))) return rc;
     NUFFT_HIP(nufft::launch_toeplitz_lines(t->dtype, t->N2[0], t->d_tmpB, t->d_K, t->N2[1] * t->N2[2], (int)t->N[0], t->d_map[0],
                                         t->d_tw_fw[0], stream));
-    if ((rc = strided_pass(t, 1, true, t->d_tmpB, t->D == 3 ? t->d_tmpA : out, stream))) return rc;
-    if (t->D == 3 && (rc = strided_pass(t, 2, true, t->d_tmpA, out, stream))) return rc;
-    return NUFFT_OK;
+    if (t->D == 3) {
+        if ((rc = strided_pass(t, 1, true, t->d_tmpB, t->d_tmpA, stream))) return rc;
+        return strided_pass(t, 2, true, t->d_tmpA, out, stream, smap, accumulate);
+    }
+    return strided_pass(t, 1, true, t->d_tmpB, out, stream, smap, accumulate);
 }
 
-int apply_dense(nufft_toeplitz* t, void* out, const void* in, hipStream_t stream) {
+int apply_dense(nufft_toeplitz* t, void* out, const void* in, hipStream_t stream, const void* smap = nullptr, bool accumulate = false) {
     const nufft::TzGrid g = grid_of(t);
     void* io[1] = {t->d_work};
-    NUFFT_HIP(nufft::launch_tz_pad(g, t->d_work, in, t->num_cus, stream));
+    if (smap) NUFFT_HIP(nufft::launch_tz_pad_map(g, t->d_work, in, smap, t->num_cus, stream));
+    else NUFFT_HIP(nufft::launch_tz_pad(g, t->d_work, in, t->num_cus, stream));
     NUFFT_ROCFFT(rocfft_execute(t->fft_bw, io, nullptr, t->fft_info));
     NUFFT_HIP(nufft::launch_tz_multiply(g, t->d_work, t->d_K, t->num_cus, stream));
     NUFFT_ROCFFT(rocfft_execute(t->fft_fw, io, nullptr, t->fft_info));
-    NUFFT_HIP(nufft::launch_tz_crop(g, out, t->d_work, t->num_cus, stream));
+    if (smap) NUFFT_HIP(nufft::launch_tz_crop_map(g, out, t->d_work, smap, accumulate, t->num_cus, stream));
+    else NUFFT_HIP(nufft::launch_tz_crop(g, out, t->d_work, t->num_cus, stream));
     return NUFFT_OK;
 }
+
+// One coil of G_S: out (+)= conj(S) ⊙ G (S ⊙ in).  The streaming route of the fused path expands into d_coil, runs the plain apply
+// in place on it and combines into out.
+int apply_coil(nufft_toeplitz* t, void* out, const void* in, const void* smap, bool accumulate, hipStream_t stream) {
+    if (t->path == NUFFT_TOEPLITZ_PATH_DENSE) return apply_dense(t, out, in, stream, smap, accumulate);
+    if (t->maps_inpass) return apply_fused(t, out, in, stream, smap, accumulate);
+    void* outs[1] = {t->d_coil};
+    const void* maps[1] = {smap};
+    const void* ins[1] = {t->d_coil};
+    NUFFT_HIP(nufft::launch_coil_expand(t->dtype, num_modes(t), 1, outs, maps, in, t->num_cus, stream));
+    if (int rc = apply_fused(t, t->d_coil, t->d_coil, stream)) return rc;
+    NUFFT_HIP(nufft::launch_coil_combine(t->dtype, num_modes(t), 1, out, maps, ins, accumulate, t->num_cus, stream));
+    return NUFFT_OK;
+}
+
+size_t coil_scratch_bytes(const nufft_toeplitz* t) { return (size_t)num_modes(t) * 2 * real_bytes(t->dtype); }
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -306,6 +341,7 @@ int nufft_toeplitz_create(nufft_toeplitz** out, const nufft_plan* plan) {
     t->options = plan->opts.str();
     nufft::set_current_options(&plan->opts);
     bool fused = plan->D >= 2 && nufft::option_int("NUFFT_TOEPLITZ_FUSED", 1) != 0;
+    t->maps_inpass = nufft::option_int("NUFFT_TOEPLITZ_MAPS_INPASS", 1) != 0;
     for (int d = 0; d < 3; ++d) {
         const bool in = d < plan->D;
         t->N[d] = in ? plan->N[d] : 1;
@@ -475,10 +511,91 @@ int nufft_toeplitz_apply(nufft_toeplitz* t, void* const* out, const void* const*
     DeviceGuard guard(t->device);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (t->path == NUFFT_TOEPLITZ_PATH_DENSE) NUFFT_ROCFFT(rocfft_execution_info_set_stream(t->fft_info, stream));
+    const int ncoils = (int)t->coil_maps.size();
+    if (ncoils > 0) {       // coil 0 stores into out[c] what coil 1 still has to read from in[c']
+        for (int c = 0; c < t->C; ++c)
+            for (int c2 = 0; c2 < t->C; ++c2)
+                if (out[c] == in[c2])
+                    return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_apply with coil maps set: an output array is also an input array");
+    }
     for (int c = 0; c < t->C; ++c) {
-        const int rc = t->path == NUFFT_TOEPLITZ_PATH_FUSED ? apply_fused(t, out[c], in[c], stream) : apply_dense(t, out[c], in[c], stream);
+        int rc = NUFFT_OK;
+        if (ncoils == 0) rc = t->path == NUFFT_TOEPLITZ_PATH_FUSED ? apply_fused(t, out[c], in[c], stream) : apply_dense(t, out[c], in[c], stream);
+        for (int s = 0; s < ncoils && !rc; ++s) rc = apply_coil(t, out[c], in[c], t->coil_maps[(size_t)s], s > 0, stream);
         if (rc) return rc;
     }
+    return NUFFT_OK;
+}
+
+int nufft_toeplitz_set_maps(nufft_toeplitz* t, int32_t ncoils, const void* const* maps, void* stream_) {
+    if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    if (!maps) return fail(NUFFT_ERR_INVALID_ARG, "null table of coil maps");
+    if (ncoils < 1 || ncoils > 1024) return fail(NUFFT_ERR_INVALID_ARG, "the number of coils must lie in 1 ... 1024");
+    if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
+    for (int32_t c = 0; c < ncoils; ++c) {
+        if (!maps[c]) return fail(NUFFT_ERR_INVALID_ARG, "null coil map");
+        if (!aligned16(maps[c])) return fail(NUFFT_ERR_INVALID_ARG, "coil maps must be 16-byte aligned");
+    }
+    if (t->path == NUFFT_TOEPLITZ_PATH_FUSED && !t->maps_inpass && !t->d_coil) {
+        DeviceGuard guard(t->device);
+        if (capturing(static_cast<hipStream_t>(stream_)))
+            return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_set_maps allocates on the streaming route: not on a capturing stream");
+        if (int rc = alloc(t, &t->d_coil, coil_scratch_bytes(t))) return rc;
+    }
+    t->coil_maps.assign(maps, maps + ncoils);
+    return NUFFT_OK;
+}
+
+int nufft_toeplitz_clear_maps(nufft_toeplitz* t) {
+    if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    t->coil_maps.clear();
+    if (t->d_coil) {
+        DeviceGuard guard(t->device);
+        free_buffer(t->own_bytes, t->d_coil, coil_scratch_bytes(t));      // hipFree waits for the applies in flight
+    }
+    return NUFFT_OK;
+}
+
+int32_t nufft_toeplitz_num_coils(const nufft_toeplitz* t) { return t ? (int32_t)t->coil_maps.size() : 0; }
+
+namespace {
+int coil_args(int dtype, int64_t n, int32_t ncoils, const void* const* a, const void* const* b, const void* single) {
+    if (dtype != NUFFT_F32 && dtype != NUFFT_F64) return fail(NUFFT_ERR_INVALID_ARG, "dtype must be NUFFT_F32 or NUFFT_F64");
+    if (n < 0) return fail(NUFFT_ERR_INVALID_ARG, "negative number of elements");
+    if (ncoils < 1 || ncoils > 1024) return fail(NUFFT_ERR_INVALID_ARG, "the number of coils must lie in 1 ... 1024");
+    if (!a || !b) return fail(NUFFT_ERR_INVALID_ARG, "null table");
+    if (n == 0) return NUFFT_OK;
+    if (!single || !aligned16(single)) return fail(NUFFT_ERR_INVALID_ARG, "null or not 16-byte aligned array");
+    for (int32_t c = 0; c < ncoils; ++c)
+        if (!a[c] || !b[c] || !aligned16(a[c]) || !aligned16(b[c])) return fail(NUFFT_ERR_INVALID_ARG, "null or not 16-byte aligned coil array");
+    return NUFFT_OK;
+}
+
+int device_cus(int device, int* num_cus) {
+    NUFFT_HIP(hipDeviceGetAttribute(num_cus, hipDeviceAttributeMultiprocessorCount, device));
+    return NUFFT_OK;
+}
+}  // namespace
+
+int nufft_coil_expand(int dtype, int64_t n, int32_t ncoils, void* const* out, const void* const* maps, const void* in, int device, void* stream) {
+    if (device < 0) return fail(NUFFT_ERR_NO_DEVICE, "nufft_coil_expand needs a device");
+    if (int rc = coil_args(dtype, n, ncoils, out, maps, in)) return rc;
+    if (n == 0) return NUFFT_OK;
+    DeviceGuard guard(device);
+    int cus = 256;
+    if (int rc = device_cus(device, &cus)) return rc;
+    NUFFT_HIP(nufft::launch_coil_expand(dtype, n, ncoils, out, maps, in, cus, static_cast<hipStream_t>(stream)));
+    return NUFFT_OK;
+}
+
+int nufft_coil_combine(int dtype, int64_t n, int32_t ncoils, void* out, const void* const* maps, const void* const* in, int device, void* stream) {
+    if (device < 0) return fail(NUFFT_ERR_NO_DEVICE, "nufft_coil_combine needs a device");
+    if (int rc = coil_args(dtype, n, ncoils, maps, in, out)) return rc;
+    if (n == 0) return NUFFT_OK;
+    DeviceGuard guard(device);
+    int cus = 256;
+    if (int rc = device_cus(device, &cus)) return rc;
+    NUFFT_HIP(nufft::launch_coil_combine(dtype, n, ncoils, out, maps, in, false, cus, static_cast<hipStream_t>(stream)));
     return NUFFT_OK;
 }
 

@@ -29,6 +29,25 @@ hipError_t launch_tz_real_part(const TzGrid& g, void* K, const void* grid, doubl
 // values = weights + 0 i (complex<T>[n] from T[n]; weights = null: ones)
 hipError_t launch_tz_weights(int dtype, void* values, const void* weights, int64_t n, int num_cus, hipStream_t stream);
 
+// The multi-coil operator.  smap: the coil's sensitivity map, complex<T> laid out like û.
+// grid = zero-padded S ⊙ û
+hipError_t launch_tz_pad_map(const TzGrid& g, void* grid, const void* u, const void* smap, int num_cus, hipStream_t stream);
+// out = conj(S) ⊙ (grid at the kept modes), added to what out holds when `accumulate`
+hipError_t launch_tz_crop_map(const TzGrid& g, void* out, const void* grid, const void* smap, bool accumulate, int num_cus, hipStream_t stream);
+
+// Coil expand and combine over n complex elements (host tables of device pointers, passed to the kernel by value kCoilChunk coils at a
+// time).  expand: out[c] = S_c ⊙ in.  combine: out = Σ_c conj(S_c) ⊙ in[c] in coil order in registers, started from what out holds
+// when `accumulate`; beyond kCoilChunk coils the running sum passes through `out` once per chunk, in the same order.
+constexpr int kCoilChunk = 64;
+struct CoilTable {
+    const void* maps[kCoilChunk];
+    void* data[kCoilChunk];
+};
+hipError_t launch_coil_expand(int dtype, int64_t n, int ncoils, void* const* out, const void* const* maps, const void* in, int num_cus,
+                              hipStream_t stream);
+hipError_t launch_coil_combine(int dtype, int64_t n, int ncoils, void* out, const void* const* maps, const void* const* in, bool accumulate,
+                               int num_cus, hipStream_t stream);
+
 // Dimension 1 of the fused apply, in place: per contiguous line of k1 kept modes, backward FFT of length n (= 2 k1), times the
 // line of K, forward FFT, kept modes stored back.  data: complex<T>[nlines][k1]; K: T[nlines][n]; twiddle: exp(-2πi m / n).
 bool toeplitz_lines_supported(int dtype, int64_t n);

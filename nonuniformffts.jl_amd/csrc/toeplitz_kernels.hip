@@ -1,6 +1,7 @@
 // Streaming kernels of the Toeplitz normal operator (toeplitz.cpp): the pad / multiply / crop of the dense
 // apply, and the two passes around the dense transform that builds the multiplier K (load with the Nyquist planes zeroed, real
-// part with the normalisation), plus the real-to-complex copy of the weights.
+// part with the normalisation), plus the real-to-complex copy of the weights, and the coil passes of the multi-coil operator
+// (DESIGN.md section 19): the pad and crop with a sensitivity map, and coil expand / combine over whole arrays.
 //
 // All of them are HBM-bound and in the style of type3_kernels.hip: a thread moves whole 16-byte packs of the embedding grid (one
 // ComplexF64 or two ComplexF32 cells; rows of 2 N_1 cells are even, so a pack never crosses a row), grid-stride loops over a grid
@@ -19,9 +20,10 @@ namespace {
 
 int64_t cells(const TzGrid& g) { return (int64_t)g.n2[0] * g.n2[1] * g.n2[2]; }
 
-// MODE 0: grid = zero-padded û (gather through inv);  MODE 1: grid = T with the Nyquist planes zeroed
+// MODE 0: grid = zero-padded û (gather through inv);  MODE 1: grid = T with the Nyquist planes zeroed;
+// MODE 2: grid = zero-padded S ⊙ û (smap: the coil's sensitivity map, laid out like û)
 template <typename T, int MODE>
-__global__ __launch_bounds__(kThreads) void tz_fill_kernel(TzGrid g, T* grid, const T* src, int64_t npacks) {
+__global__ __launch_bounds__(kThreads) void tz_fill_kernel(TzGrid g, T* grid, const T* src, int64_t npacks, const T* smap) {
     constexpr int CW = Pack<T>::W / 2;          // cells per pack
     for (int64_t q = (int64_t)blockIdx.x * kThreads + threadIdx.x; q < npacks; q += (int64_t)gridDim.x * kThreads) {
         const int64_t cell = q * CW;
@@ -29,7 +31,7 @@ __global__ __launch_bounds__(kThreads) void tz_fill_kernel(TzGrid g, T* grid, co
         const int64_t r = cell / g.n2[0];
         const int j2 = (int)(r % g.n2[1]), j3 = (int)(r / g.n2[1]);
         Pack<T> pk;
-        if (MODE == 0) {
+        if (MODE == 0 || MODE == 2) {
             const int k2 = g.inv[1][j2], k3 = g.inv[2][j3];
 #pragma unroll
             for (int w = 0; w < CW; ++w) {
@@ -39,6 +41,12 @@ __global__ __launch_bounds__(kThreads) void tz_fill_kernel(TzGrid g, T* grid, co
                     const int64_t s = k1 + (int64_t)g.nk[0] * (k2 + (int64_t)g.nk[1] * k3);
                     re = src[2 * s];
                     im = src[2 * s + 1];
+                    if constexpr (MODE == 2) {
+                        const T sr = smap[2 * s], si = smap[2 * s + 1];
+                        const T pr = re * sr - im * si;
+                        im = re * si + im * sr;
+                        re = pr;
+                    }
                 }
                 pk.v[2 * w] = re;
                 pk.v[2 * w + 1] = im;
@@ -77,15 +85,29 @@ __global__ __launch_bounds__(kThreads) void tz_real_kernel(T* grid, T* K, T scal
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(kThreads) void tz_crop_kernel(TzGrid g, T* out, const T* grid, int64_t nmodes) {
+// SMAP: out = conj(S) ⊙ (grid at the kept modes), added to what out holds when `accumulate`
+template <typename T, bool SMAP>
+__global__ __launch_bounds__(kThreads) void tz_crop_kernel(TzGrid g, T* out, const T* grid, int64_t nmodes, const T* smap, int accumulate) {
     typedef T T2 __attribute__((ext_vector_type(2)));
     for (int64_t s = (int64_t)blockIdx.x * kThreads + threadIdx.x; s < nmodes; s += (int64_t)gridDim.x * kThreads) {
         const int k1 = (int)(s % g.nk[0]);
         const int64_t r = s / g.nk[0];
         const int k2 = (int)(r % g.nk[1]), k3 = (int)(r / g.nk[1]);
         const int64_t cell = g.map[0][k1] + (int64_t)g.n2[0] * (g.map[1][k2] + (int64_t)g.n2[1] * g.map[2][k3]);
-        reinterpret_cast<T2*>(out)[s] = reinterpret_cast<const T2*>(grid)[cell];
+        if constexpr (SMAP) {
+            const T2 v = reinterpret_cast<const T2*>(grid)[cell], m = reinterpret_cast<const T2*>(smap)[s];
+            T2 r;
+            r.x = v.x * m.x + v.y * m.y;
+            r.y = v.y * m.x - v.x * m.y;
+            if (accumulate) {
+                const T2 o = reinterpret_cast<const T2*>(out)[s];
+                r.x = o.x + r.x;
+                r.y = o.y + r.y;
+            }
+            reinterpret_cast<T2*>(out)[s] = r;
+        } else {
+            reinterpret_cast<T2*>(out)[s] = reinterpret_cast<const T2*>(grid)[cell];
+        }
     }
 }
 
@@ -102,17 +124,86 @@ __global__ __launch_bounds__(kThreads) void tz_weights_kernel(T* values, const T
 
 int64_t packs(const TzGrid& g) { return cells(g) / (g.dtype == NUFFT_F32 ? 2 : 1); }
 
+// Coil expand (EXPAND: data[c] = S_c ⊙ x for every coil of the table) and combine (y = Σ_c conj(S_c) ⊙ data[c], summed in coil order in
+// registers, started from what y holds when `accumulate`), over n complex elements in 16-byte packs; the ComplexF32 element behind the
+// last pack of an odd n is left to one thread.  Each array is read once and written once per launch.
+template <typename T, bool EXPAND>
+__global__ __launch_bounds__(kThreads) void coil_kernel(CoilTable tab, int ncoils, T* y, const T* x, int64_t n, int accumulate) {
+    constexpr int CW = Pack<T>::W / 2;          // elements per pack
+    const int64_t npacks = n / CW;
+    for (int64_t q = (int64_t)blockIdx.x * kThreads + threadIdx.x; q < npacks; q += (int64_t)gridDim.x * kThreads) {
+        if constexpr (EXPAND) {
+            const Pack<T> v = load(x, q);
+            for (int c = 0; c < ncoils; ++c) {
+                const Pack<T> m = load(static_cast<const T*>(tab.maps[c]), q);
+                Pack<T> r;
+#pragma unroll
+                for (int w = 0; w < CW; ++w) {
+                    r.v[2 * w] = v.v[2 * w] * m.v[2 * w] - v.v[2 * w + 1] * m.v[2 * w + 1];
+                    r.v[2 * w + 1] = v.v[2 * w] * m.v[2 * w + 1] + v.v[2 * w + 1] * m.v[2 * w];
+                }
+                store(static_cast<T*>(tab.data[c]), q, r);
+            }
+        } else {
+            Pack<T> acc;
+#pragma unroll
+            for (int w = 0; w < 2 * CW; ++w) acc.v[w] = T(0);
+            if (accumulate) acc = load(static_cast<const T*>(y), q);
+            for (int c = 0; c < ncoils; ++c) {
+                const Pack<T> m = load(static_cast<const T*>(tab.maps[c]), q);
+                const Pack<T> v = load(static_cast<const T*>(tab.data[c]), q);
+#pragma unroll
+                for (int w = 0; w < CW; ++w) {
+                    acc.v[2 * w] += v.v[2 * w] * m.v[2 * w] + v.v[2 * w + 1] * m.v[2 * w + 1];
+                    acc.v[2 * w + 1] += v.v[2 * w + 1] * m.v[2 * w] - v.v[2 * w] * m.v[2 * w + 1];
+                }
+            }
+            store(y, q, acc);
+        }
+    }
+    if (CW > 1 && (n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+        const int64_t e = 2 * (n - 1);
+        if constexpr (EXPAND) {
+            const T vr = x[e], vi = x[e + 1];
+            for (int c = 0; c < ncoils; ++c) {
+                const T* m = static_cast<const T*>(tab.maps[c]);
+                T* d = static_cast<T*>(tab.data[c]);
+                d[e] = vr * m[e] - vi * m[e + 1];
+                d[e + 1] = vr * m[e + 1] + vi * m[e];
+            }
+        } else {
+            T ar = T(0), ai = T(0);
+            if (accumulate) { ar = y[e]; ai = y[e + 1]; }
+            for (int c = 0; c < ncoils; ++c) {
+                const T* m = static_cast<const T*>(tab.maps[c]);
+                const T* d = static_cast<const T*>(tab.data[c]);
+                ar += d[e] * m[e] + d[e + 1] * m[e + 1];
+                ai += d[e + 1] * m[e] - d[e] * m[e + 1];
+            }
+            y[e] = ar;
+            y[e + 1] = ai;
+        }
+    }
+}
+
 }  // namespace
 
 hipError_t launch_tz_pad(const TzGrid& g, void* grid, const void* u, int num_cus, hipStream_t stream) {
     const int64_t np = packs(g);
-    return launch_by_dtype(g.dtype, dim3(grid_for(np, num_cus)), dim3(kThreads), stream, tz_fill_kernel<float, 0>, tz_fill_kernel<double, 0>, g, grid, u, np);
+    return launch_by_dtype(g.dtype, dim3(grid_for(np, num_cus)), dim3(kThreads), stream, tz_fill_kernel<float, 0>, tz_fill_kernel<double, 0>, g, grid, u, np,
+                           nullptr);
+}
+
+hipError_t launch_tz_pad_map(const TzGrid& g, void* grid, const void* u, const void* smap, int num_cus, hipStream_t stream) {
+    const int64_t np = packs(g);
+    return launch_by_dtype(g.dtype, dim3(grid_for(np, num_cus)), dim3(kThreads), stream, tz_fill_kernel<float, 2>, tz_fill_kernel<double, 2>, g, grid, u, np,
+                           smap);
 }
 
 hipError_t launch_tz_spectrum_load(const TzGrid& g, void* grid, const void* T_modes, int num_cus, hipStream_t stream) {
     const int64_t np = packs(g);
     return launch_by_dtype(g.dtype, dim3(grid_for(np, num_cus)), dim3(kThreads), stream, tz_fill_kernel<float, 1>, tz_fill_kernel<double, 1>, g, grid, T_modes,
-                           np);
+                           np, nullptr);
 }
 
 hipError_t launch_tz_multiply(const TzGrid& g, void* grid, const void* K, int num_cus, hipStream_t stream) {
@@ -131,7 +222,44 @@ hipError_t launch_tz_real_part(const TzGrid& g, void* K, const void* grid, doubl
 
 hipError_t launch_tz_crop(const TzGrid& g, void* out, const void* grid, int num_cus, hipStream_t stream) {
     const int64_t nm = (int64_t)g.nk[0] * g.nk[1] * g.nk[2];
-    return launch_by_dtype(g.dtype, dim3(grid_for(nm, num_cus)), dim3(kThreads), stream, tz_crop_kernel<float>, tz_crop_kernel<double>, g, out, grid, nm);
+    return launch_by_dtype(g.dtype, dim3(grid_for(nm, num_cus)), dim3(kThreads), stream, tz_crop_kernel<float, false>, tz_crop_kernel<double, false>, g, out, grid,
+                           nm, nullptr, 0);
+}
+
+hipError_t launch_tz_crop_map(const TzGrid& g, void* out, const void* grid, const void* smap, bool accumulate, int num_cus, hipStream_t stream) {
+    const int64_t nm = (int64_t)g.nk[0] * g.nk[1] * g.nk[2];
+    return launch_by_dtype(g.dtype, dim3(grid_for(nm, num_cus)), dim3(kThreads), stream, tz_crop_kernel<float, true>, tz_crop_kernel<double, true>, g, out, grid,
+                           nm, smap, accumulate ? 1 : 0);
+}
+
+hipError_t launch_coil_expand(int dtype, int64_t n, int ncoils, void* const* out, const void* const* maps, const void* in, int num_cus,
+                              hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    const int64_t np = n / (dtype == NUFFT_F32 ? 2 : 1);
+    for (int c0 = 0; c0 < ncoils; c0 += kCoilChunk) {
+        CoilTable tab{};
+        const int nc = std::min(kCoilChunk, ncoils - c0);
+        for (int c = 0; c < nc; ++c) { tab.maps[c] = maps[c0 + c]; tab.data[c] = out[c0 + c]; }
+        hipError_t e = launch_by_dtype(dtype, dim3(grid_for(np, num_cus)), dim3(kThreads), stream, coil_kernel<float, true>, coil_kernel<double, true>, tab, nc,
+                                       nullptr, in, n, 0);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_coil_combine(int dtype, int64_t n, int ncoils, void* out, const void* const* maps, const void* const* in, bool accumulate,
+                               int num_cus, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    const int64_t np = n / (dtype == NUFFT_F32 ? 2 : 1);
+    for (int c0 = 0; c0 < ncoils; c0 += kCoilChunk) {
+        CoilTable tab{};
+        const int nc = std::min(kCoilChunk, ncoils - c0);
+        for (int c = 0; c < nc; ++c) { tab.maps[c] = maps[c0 + c]; tab.data[c] = const_cast<void*>(in[c0 + c]); }
+        hipError_t e = launch_by_dtype(dtype, dim3(grid_for(np, num_cus)), dim3(kThreads), stream, coil_kernel<float, false>, coil_kernel<double, false>, tab,
+                                       nc, out, nullptr, n, (accumulate || c0 > 0) ? 1 : 0);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t launch_tz_weights(int dtype, void* values, const void* weights, int64_t n, int num_cus, hipStream_t stream) {

@@ -8,6 +8,9 @@ so after one build per point set it is applied with FFTs of size 2N alone, at a 
 
     op = ToeplitzOperator(plan).set_points(points, weights)
     g = op(u)                      # = exec_type1(w * exec_type2(u)) up to the accuracy of one NUFFT
+
+With coil sensitivity maps (``op.set_maps(maps)``, parallel MRI) the same ``apply`` computes ``Σ_c conj(S_c) ⊙ G (S_c ⊙ û)``;
+``coil_expand`` / ``coil_combine`` are the coil passes of the forward model and of the right-hand side.
 """
 from __future__ import annotations
 
@@ -40,12 +43,18 @@ class ToeplitzOperator:
         self.ndim = plan.ndim
         self.ntransforms = plan.ntransforms
         self._kernel, self._evalmode = plan.kernel, plan.kernel_evalmode
+        self._maps = ()
 
     def close(self):
         h = getattr(self, "_handle", None)
         if h is not None and h.value:
             lib.nufft_toeplitz_destroy(h)
             self._handle = C.c_void_p()
+        self._maps = ()
+
+    def _require_open(self):
+        if not self._handle.value:
+            raise ValueError("the ToeplitzOperator is closed")
 
     def __del__(self):
         try:
@@ -151,6 +160,42 @@ class ToeplitzOperator:
         _check(lib.nufft_toeplitz_set_points(self._handle, build, n, _ptr_table(points), wptr, self._stream()))
         return self
 
+    def set_maps(self, maps) -> "ToeplitzOperator":
+        """Coil sensitivity maps ``S_c``: a contiguous complex tensor of shape ``(ncoils, *plan.shape)`` or a sequence of ``plan.shape``
+        tensors.  From here on ``apply`` computes ``Σ_c conj(S_c) ⊙ G (S_c ⊙ u)`` for every component.  The library borrows the device
+        arrays: this object keeps references to them, and their values must not change while they are set.  Slices of a stacked tensor
+        that are not 16-byte aligned (an odd element count in ComplexF32) are copied to their own allocations."""
+        self._require_gpu()
+        self._require_open()
+        if isinstance(maps, torch.Tensor):
+            if maps.dim() != self.ndim + 1:
+                raise DimensionMismatch(f"wrong dimensions of the coil maps (expected tensor shape (ncoils, {', '.join(map(str, self.shape))}), "
+                                        f"got {tuple(maps.shape)})")
+            if not maps.is_contiguous():
+                raise ValueError("coil maps must be contiguous")
+            maps = tuple(maps[c] for c in range(maps.shape[0]))
+        else:
+            maps = tuple(maps)
+        if len(maps) < 1:
+            raise ValueError("at least one coil map is needed")
+        _check_coil_arrays(maps, self.device, self.Z, self.shape, "coil maps")
+        maps = _aligned(maps)
+        _check(lib.nufft_toeplitz_set_maps(self._handle, len(maps), _ptr_table(maps), self._stream()))
+        self._maps = maps
+        return self
+
+    def clear_maps(self) -> "ToeplitzOperator":
+        """Back to the plain operator ``G``."""
+        self._require_open()
+        _check(lib.nufft_toeplitz_clear_maps(self._handle))
+        self._maps = ()
+        return self
+
+    @property
+    def ncoils(self) -> int:
+        """Number of coil maps set (0: the plain operator)."""
+        return int(lib.nufft_toeplitz_num_coils(self._handle)) if self._handle.value else 0
+
     def _check_uniform(self, us: Sequence[torch.Tensor], what: str):
         if len(us) != self.ntransforms:
             raise DimensionMismatch(f"wrong amount of {what} arrays (expected a tuple of {self.ntransforms} arrays)")
@@ -166,8 +211,9 @@ class ToeplitzOperator:
 
     def apply(self, u, out=None):
         """``out = G u`` for every component; ``u``: a tensor of ``plan.shape`` or a tuple of ntransforms such tensors; ``out`` may be
-        ``u``.  Returns ``out``."""
+        ``u`` unless coil maps are set (coil 0's store would destroy the input of coil 1).  Returns ``out``."""
         self._require_gpu()
+        self._require_open()
         single = isinstance(u, torch.Tensor)
         u_t = (u,) if single else tuple(u)
         self._check_uniform(u_t, "input")
@@ -177,6 +223,8 @@ class ToeplitzOperator:
         else:
             out_t = (out,) if isinstance(out, torch.Tensor) else tuple(out)
             self._check_uniform(out_t, "output")
+            if self._maps and any(o is v or o.data_ptr() == v.data_ptr() for o in out_t for v in u_t):
+                raise ValueError("with coil maps set the output must not be the input")
         _check(lib.nufft_toeplitz_apply(self._handle, _ptr_table(out_t), _ptr_table(u_t), self._stream()))
         return out
 
@@ -213,4 +261,87 @@ class ToeplitzOperator:
     def __repr__(self):
         i = self.info()
         return (f"ToeplitzOperator of a {self.ndim}-dimensional {self.Z} plan, N = {tuple(int(i.N[d]) for d in range(self.ndim))}, "
-                f"{self.path} path, {i.workspace_bytes / 1e6:.1f} MB")
+                f"{self.path} path, {f'{self.ncoils} coil maps, ' if self.ncoils else ''}{i.workspace_bytes / 1e6:.1f} MB")
+
+
+def _check_coil_arrays(arrays, device, Z, shape, what):
+    """The checks of ``_check_uniform`` (same exception types) for a sequence of coil arrays."""
+    for a in arrays:
+        if not isinstance(a, torch.Tensor) or a.device != device:
+            raise ValueError(f"{what} must be torch tensors on {device}")
+        if a.dtype != Z:
+            raise ValueError(f"{what} must have element type {Z} (got {a.dtype})")
+        if tuple(a.shape) != tuple(shape):
+            raise DimensionMismatch(f"wrong dimensions of {what} (expected tensor shape {tuple(shape)}, got {tuple(a.shape)})")
+        if not a.is_contiguous():
+            raise ValueError(f"{what} must be contiguous")
+
+
+def _aligned(arrays):
+    """The arrays themselves where they are 16-byte aligned, own copies where not (slices of a stacked tensor with an odd element
+    count in ComplexF32)."""
+    return tuple(a if a.data_ptr() % 16 == 0 else a.clone() for a in arrays)
+
+
+def _coil_list(maps, what="coil maps"):
+    if isinstance(maps, torch.Tensor):
+        if maps.dim() < 1 or not maps.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous stacked tensor or a sequence of tensors")
+        return tuple(maps[c] for c in range(maps.shape[0]))
+    return tuple(maps)
+
+
+def _coil_setup(maps, x):
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or not x.is_complex():
+        raise ValueError("expected a complex torch tensor on a GPU")
+    if x.dtype not in (torch.complex64, torch.complex128):
+        raise ValueError(f"unsupported element type {x.dtype}")
+    maps = _coil_list(maps)
+    if len(maps) < 1:
+        raise ValueError("at least one coil map is needed")
+    _check_coil_arrays(maps, x.device, x.dtype, x.shape, "coil maps")
+    return maps, (_lib.F32 if x.dtype == torch.complex64 else _lib.F64), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+
+
+def coil_expand(maps, x, out=None):
+    """``out[c] = S_c ⊙ x``: ``maps`` a stacked tensor ``(ncoils, *x.shape)`` or a sequence of tensors shaped like ``x``; ``out`` likewise
+    (None: a new stacked tensor, returned)."""
+    if not isinstance(x, torch.Tensor) or not x.is_contiguous():
+        raise ValueError("the input must be a contiguous torch tensor")
+    maps, dtype, stream = _coil_setup(maps, x)
+    if out is None:
+        out = torch.empty((len(maps),) + tuple(x.shape), dtype=x.dtype, device=x.device)
+    outs = _coil_list(out, "outputs")
+    if len(outs) != len(maps):
+        raise DimensionMismatch(f"wrong amount of output arrays (expected {len(maps)})")
+    _check_coil_arrays(outs, x.device, x.dtype, x.shape, "outputs")
+    work = _aligned(outs)          # a misaligned slice is written through an aligned copy
+    maps_a, xin = _aligned(maps), _aligned((x,))[0]
+    _check(lib.nufft_coil_expand(dtype, x.numel(), len(maps), _ptr_table(work), _ptr_table(maps_a), C.c_void_p(xin.data_ptr()), x.device.index or 0,
+                                 stream))
+    for o, w in zip(outs, work):
+        if o is not w:
+            o.copy_(w)
+    return out
+
+
+def coil_combine(maps, a, out=None):
+    """``out = Σ_c conj(S_c) ⊙ a[c]``, summed in coil order; ``maps`` and ``a``: stacked tensors or sequences of equally shaped tensors."""
+    arrs = _coil_list(a, "inputs")
+    if len(arrs) < 1:
+        raise ValueError("at least one coil is needed")
+    maps, dtype, stream = _coil_setup(maps, arrs[0])
+    if len(arrs) != len(maps):
+        raise DimensionMismatch(f"wrong amount of input arrays (expected {len(maps)})")
+    x = arrs[0]
+    _check_coil_arrays(arrs, x.device, x.dtype, x.shape, "inputs")
+    if out is None:
+        out = torch.empty_like(x)
+    _check_coil_arrays((out,), x.device, x.dtype, x.shape, "the output")
+    work = _aligned((out,))[0]
+    maps_a, arrs_a = _aligned(maps), _aligned(arrs)      # held until the call is enqueued: a freed copy's memory would be handed out again
+    _check(lib.nufft_coil_combine(dtype, x.numel(), len(maps), C.c_void_p(work.data_ptr()), _ptr_table(maps_a), _ptr_table(arrs_a),
+                                  x.device.index or 0, stream))
+    if work is not out:
+        out.copy_(work)
+    return out
