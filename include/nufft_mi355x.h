@@ -527,6 +527,58 @@ int32_t nufft_toeplitz_num_coils(const nufft_toeplitz* tz);
 int nufft_coil_expand(int dtype, int64_t n, int32_t ncoils, void* const* out, const void* const* maps, const void* in, int device, void* stream);
 int nufft_coil_combine(int dtype, int64_t n, int32_t ncoils, void* out, const void* const* maps, const void* const* in, int device, void* stream);
 
+/* ---- Coupled components in the Toeplitz normal operator: subspace models --- */
+/* A subspace / low-rank model mixes the K = ntransforms components at the samples,  y_j = Σ_a φ_a(j) (A û_a)_j,  φ ∈ C^{K × Np}  (a
+ * temporal basis, or the temporal interpolators of time-segmented off-resonance correction).  Its normal operator is a K × K block
+ * operator whose blocks are Toeplitz:
+ *     (G_Φ û)_a = Σ_b A^H diag(w ⊙ conj(φ_a) ⊙ φ_b) A û_b = Σ_b Toeplitz(T_ab) û_b,     T_ab = Σ_j w_j conj(φ_a(j)) φ_b(j) exp(−i d·x_j).
+ * With the Nyquist planes of every T_ab zeroed, K_ab = backwardDFT_{2N}(T_ab) / Π 2N_d satisfies K_ba = conj(K_ab) and K_aa is real:
+ * the object holds K real grids (the diagonal) and K (K − 1) / 2 complex grids (the pairs a < b), each real(T) / complex(T)[2N_1, 2N_2,
+ * 2N_3], and applies K_ab for a < b and its conjugate for a > b.  Pair order everywhere is row-major over a <= b:
+ * idx(a, b) = a K − a (a − 1) / 2 + (b − a).  1 <= K <= 16 (more: NUFFT_ERR_UNSUPPORTED).
+ * Added after the SENSE section under the same rule: detect by symbol (dlsym nufft_toeplitz_set_points_coupled);
+ * NUFFT_MI355X_VERSION and nufft_toeplitz_info are unchanged.
+ *
+ * The first coupled build allocates the multipliers (K² real grids' worth) and K intermediates — fused: complex[N_1, 2N_2, 2N_3] each,
+ * dense: complex[(2N)^D] each — all counted in workspace_bytes; they are kept across coupled builds and freed by the next
+ * nufft_toeplitz_set_points / _set_spectrum, which return the operator to independent components, bit for bit, or by
+ * nufft_toeplitz_destroy.  No coupled build runs on a capturing stream (NUFFT_ERR_INVALID_ARG).
+ *
+ * While a coupled build is in force nufft_toeplitz_apply computes out[a] = Σ_b Toeplitz(T_ab) in[b]: per component the strided passes
+ * of the fused path (or pad + rocFFT of the dense path) into its own intermediate, ONE kernel that applies the K × K block to every
+ * cell (fused: inside the dimension-1 kernel, where a wave holds the K lines of a line id in LDS between their backward and forward
+ * transforms; dense: a streaming kernel over the K grids), and the passes back.  Every output depends on every input: out[a] == in[b]
+ * for any a, b is refused (NUFFT_ERR_INVALID_ARG), with or without coil maps.  With coil maps G_{S,Φ} û = Σ_c conj(S_c) ⊙ G_Φ (S_c ⊙ û),
+ * the same maps for every component, coils in index order, coil 0 stores and coils >= 1 add — no atomics: two runs and a graph replay
+ * give the same bits.  The apply still allocates nothing and does not synchronise.
+ *
+ * Fused path: the K lines of 2 N_1 cells (plus 1/16 padding) and the twiddle table must fit the 160 KiB of LDS of one wave's workgroup —
+ * K <= 8 at 2 N_1 <= 512 always does; otherwise the coupled build returns NUFFT_ERR_UNSUPPORTED and names the option
+ * NUFFT_TOEPLITZ_FUSED=0 (the path is decided at creation and never switched silently).  On the route NUFFT_TOEPLITZ_MAPS_INPASS=0
+ * nufft_toeplitz_set_maps on a coupled operator, and a coupled build while maps are set, return NUFFT_ERR_UNSUPPORTED.
+ *
+ * nufft_cg_solve on an operator with a coupled build in force treats the K components as ONE system: Re<p, q>, |p|², |r|² and |b|² are
+ * summed over all components (the per-workgroup partial sums are contiguous over components and reduced in one fixed order, so runs
+ * and graph replays still agree bit for bit), with one α, one β, one done flag and one breakdown test; nufft_cg_get_result and
+ * nufft_cg_history report the same iterations, status and residual for every component.  Uncoupled operators keep their
+ * per-component scalars.
+ *
+ * Refusals of the two builds, in order: a null object or table NUFFT_ERR_INVALID_ARG; a host-only object NUFFT_ERR_NO_DEVICE; a null
+ * (or, basis: not 16-byte aligned) entry NUFFT_ERR_INVALID_ARG; the limits above NUFFT_ERR_UNSUPPORTED; a capturing stream. */
+/* basis: host table of K device pointers complex(T)[num_points], 16-byte aligned, only read during the call.  The internal 2N plan is
+ * created once, its points are set once, and it runs one type 1 per pair a <= b of the weights w_j conj(φ_a(j)) φ_b(j); each result
+ * becomes a multiplier (real part for a = b, complex for a < b) before the next pair runs.  Peak memory: the internal plan, one (2N)^D
+ * complex grid and rocFFT's work buffer on top of what the operator holds.  Other arguments as nufft_toeplitz_set_points. */
+int nufft_toeplitz_set_points_coupled(nufft_toeplitz* tz, const nufft_params* build_params, int64_t num_points, const void* const* coords,
+                                      const void* weights, const void* const* basis, void* stream);
+/* T_pairs: host table of K (K + 1) / 2 device pointers, T_ab on the 2N mode set as for nufft_toeplitz_set_spectrum, in pair order.  Any
+ * Hermitian family (T_ba(d) = conj(T_ab(−d))) is admitted, not only the rank-one form that _set_points_coupled builds. */
+int nufft_toeplitz_set_spectra_coupled(nufft_toeplitz* tz, const void* const* T_pairs, void* stream);
+/* K while a coupled build is in force, else 0. */
+int32_t nufft_toeplitz_num_coupled(const nufft_toeplitz* tz);
+/* Device pointer and bytes of K_ab, 0 <= a <= b < K (inspection and tests): real(T) for a = b, complex(T) for a < b. */
+int nufft_toeplitz_multiplier_pair_ptr(const nufft_toeplitz* tz, int32_t a, int32_t b, void** out_ptr, int64_t* out_bytes);
+
 /* ---- Conjugate gradients on the Toeplitz normal operator --------- */
 /* Solves (G + λ I) x_c = b_c for every component c < ntransforms independently (G is block-diagonal over components: each has its
  * own scalars), G = what a nufft_toeplitz object applies, λ >= 0 real.  With b = nufft_exec_type1(w ⊙ y) this is the weighted,

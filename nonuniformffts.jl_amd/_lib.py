@@ -213,6 +213,10 @@ SYMBOLS = {
     "nufft_toeplitz_set_maps": (C.c_int, [_P, C.c_int32, _PP, _P]),
     "nufft_toeplitz_clear_maps": (C.c_int, [_P]),
     "nufft_toeplitz_num_coils": (C.c_int32, [_P]),
+    "nufft_toeplitz_set_points_coupled": (C.c_int, [_P, C.POINTER(NufftParams), C.c_int64, _PP, _P, _PP, _P]),
+    "nufft_toeplitz_set_spectra_coupled": (C.c_int, [_P, _PP, _P]),
+    "nufft_toeplitz_num_coupled": (C.c_int32, [_P]),
+    "nufft_toeplitz_multiplier_pair_ptr": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(_P), C.POINTER(C.c_int64)]),
     "nufft_coil_expand": (C.c_int, [C.c_int, C.c_int64, C.c_int32, _PP, _PP, _P, C.c_int, _P]),
     "nufft_coil_combine": (C.c_int, [C.c_int, C.c_int64, C.c_int32, _P, _PP, _PP, C.c_int, _P]),
     "nufft_cg_create": (C.c_int, [C.POINTER(_P), _P, C.POINTER(NufftCgParams)]),

@@ -26,7 +26,9 @@ class ToeplitzCG:
     ``check_every=0`` enqueues all ``maxiter`` iterations without synchronising (components that reached ``rtol`` are frozen on the
     device; legal inside ``torch.cuda.graph``); ``check_every=k`` lets the host look at the done flags every ``k`` iterations and stop
     early.  Both return the same bits.  The solver keeps ``op`` alive; ``op.set_points`` / ``set_spectrum`` between two solves is
-    allowed and changes ``G``."""
+    allowed and changes ``G``.  On a coupled operator (``op.set_points(..., basis=)`` / ``op.set_spectra``) the components are ONE system:
+    one α, one β and one stopping test from sums over all components; ``iterations``, ``status``, ``residual`` and ``history()`` then
+    report the same values for every component."""
 
     def __init__(self, op: ToeplitzOperator, maxiter: int = 50, rtol: float = 1e-6, lam: float = 0.0, check_every: int = 0):
         if not isinstance(op, ToeplitzOperator):

@@ -219,6 +219,7 @@ int nufft_cg_solve(nufft_cg* s, void* const* x, const void* const* b, int use_x0
     a.rtol = s->rtol;
     a.max_iter = s->max_iter;
     a.it = 0;
+    a.joint = nufft_toeplitz_num_coupled(s->tz) > 0 ? 1 : 0;      // coupled components are one system: one α, one β, one done flag
     a.s = scalars_at(s, s->scal.dev);
 
     s->enqueued = 0;

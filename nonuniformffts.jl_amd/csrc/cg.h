@@ -38,6 +38,9 @@ struct CgLaunch {
     double lambda, rtol;
     int max_iter;
     int it;                  // iteration number, 1-based (parity = it & 1)
+    int joint;               // the operator couples its components: they are ONE system — the partial-sum rows
+                             // are reduced over all C * G entries from component 0's row (part1 / part2 are contiguous over
+                             // components), every component reads the scalars of slot 0 and writes the same values to its own
     CgScalars s;
 };
 

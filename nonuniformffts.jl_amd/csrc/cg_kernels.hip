@@ -7,6 +7,11 @@
 // A component whose done flag is set is frozen: its workgroups leave after reading the flag.  The first workgroup of the last
 // kernel of an iteration writes the scalars of the next one into the other parity slot (every workgroup of that kernel still reads
 // the current slot); for a frozen component it only carries flag and ρ over.
+//
+// Joint mode (CgLaunch::joint: the operator couples its components): the components are one system.  The
+// partial-sum rows of all components are contiguous, so every reduction runs over C * G entries from component 0's row, in the same
+// fixed order; every component reads the scalars of slot 0 — all components then take the same decisions — and writes the values it
+// computed, the same in every component, to its own slot, which is what the host reads.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -88,9 +93,10 @@ __global__ __launch_bounds__(kThreads) void cg_residual_kernel(CgLaunch a) {
 __global__ __launch_bounds__(kThreads) void cg_start_kernel(CgLaunch a) {
     __shared__ double lds[kWaves];
     const int c = a.c0 + blockIdx.y;
-    const double* row = a.s.part1 + (int64_t)c * a.G * 2;
-    const double rr = row_reduce<Sum>(row, a.G, 2, lds);
-    const double bb = row_reduce<Sum>(row + 1, a.G, 2, lds);
+    const int GR = a.joint ? a.C * a.G : a.G;      // joint: one sum over all components
+    const double* row = a.s.part1 + (int64_t)(a.joint ? 0 : c) * a.G * 2;
+    const double rr = row_reduce<Sum>(row, GR, 2, lds);
+    const double bb = row_reduce<Sum>(row + 1, GR, 2, lds);
     for (int it = 1 + threadIdx.x; it <= a.max_iter; it += kThreads) a.s.history[(int64_t)it * a.C + c] = NAN;
     if (threadIdx.x == 0) {
         const int done = rr <= a.rtol * a.rtol * bb ? 1 : 0;
@@ -113,7 +119,7 @@ __global__ __launch_bounds__(kThreads) void cg_dot_kernel(CgLaunch a) {
     __shared__ double lds[kWaves];
     constexpr int W = Pack<T>::W;
     const int c = a.c0 + blockIdx.y;
-    if (a.s.flag[(a.it & 1) * a.C + c]) return;
+    if (a.s.flag[(a.it & 1) * a.C + (a.joint ? 0 : c)]) return;
     const T* p = static_cast<const T*>(a.p) + c * a.stride;
     const T* q = static_cast<const T*>(a.q) + c * a.stride;
     const int64_t nreal = 2 * a.n;
@@ -154,11 +160,12 @@ __global__ __launch_bounds__(kThreads) void cg_update_kernel(CgLaunch a) {
     __shared__ double lds[kWaves];
     constexpr int W = Pack<T>::W;
     const int c = a.c0 + blockIdx.y;
-    const int slot = (a.it & 1) * a.C + c;
+    const int sc = a.joint ? 0 : c, GR = a.joint ? a.C * a.G : a.G;
+    const int slot = (a.it & 1) * a.C + sc;
     if (a.s.flag[slot]) return;
-    const double* row = a.s.part1 + (int64_t)c * a.G * 2;
-    const double pq = row_reduce<Sum>(row, a.G, 2, lds);
-    const double pp = row_reduce<Sum>(row + 1, a.G, 2, lds);
+    const double* row = a.s.part1 + (int64_t)sc * a.G * 2;
+    const double pq = row_reduce<Sum>(row, GR, 2, lds);
+    const double pp = row_reduce<Sum>(row + 1, GR, 2, lds);
     const double gamma = pq + a.lambda * pp;
     const bool bad = !(gamma > 0.0) || !isfinite(gamma);      // the same bits in every workgroup: they all leave, or none does
     if (blockIdx.x == 0 && threadIdx.x == 0) a.s.brk[c] = bad ? 1 : 0;
@@ -203,9 +210,10 @@ __global__ __launch_bounds__(kThreads) void cg_direction_kernel(CgLaunch a) {
     __shared__ double lds[kWaves];
     constexpr int W = Pack<T>::W;
     const int c = a.c0 + blockIdx.y;
-    const int slot = (a.it & 1) * a.C + c, next = ((a.it + 1) & 1) * a.C + c;
+    const int sc = a.joint ? 0 : c, GR = a.joint ? a.C * a.G : a.G;
+    const int slot = (a.it & 1) * a.C + sc, next = ((a.it + 1) & 1) * a.C + c;
     const bool first = blockIdx.x == 0 && threadIdx.x == 0;
-    const bool frozen = a.s.flag[slot] != 0, bad = !frozen && a.s.brk[c] != 0;
+    const bool frozen = a.s.flag[slot] != 0, bad = !frozen && a.s.brk[sc] != 0;
     if (frozen || bad) {
         if (first) {
             a.s.flag[next] = 1;
@@ -214,7 +222,7 @@ __global__ __launch_bounds__(kThreads) void cg_direction_kernel(CgLaunch a) {
         }
         return;
     }
-    const double rr = row_reduce<Sum>(a.s.part2 + (int64_t)c * a.G, a.G, 1, lds);
+    const double rr = row_reduce<Sum>(a.s.part2 + (int64_t)sc * a.G, GR, 1, lds);
     const T bt = (T)(rr / a.s.rho[slot]);           // ρ > 0: the component is not done
     const T* r = static_cast<const T*>(a.r) + c * a.stride;
     T* p = static_cast<T*>(a.p) + c * a.stride;
@@ -235,7 +243,7 @@ __global__ __launch_bounds__(kThreads) void cg_direction_kernel(CgLaunch a) {
     }
     if (first) {
         for (int64_t e = npacks__ * W; e < nreal; ++e) p[e] = r[e] + bt * p[e];
-        const double bb = a.s.beta0[c];
+        const double bb = a.s.beta0[sc];
         const int done = rr <= a.rtol * a.rtol * bb ? 1 : 0;
         a.s.rho[next] = rr;
         a.s.flag[next] = done;

@@ -9,6 +9,10 @@
 // With coil sensitivity maps S_c set the same apply computes G_S û = Σ_c conj(S_c) ⊙ G (S_c ⊙ û), coil after
 // coil in stream order: S_c multiplies where the first pass loads the caller's array, conj(S_c) where the last pass stores into it,
 // and coils >= 1 add to what coil 0 stored.
+//
+// With a coupled build the C components are one block operator, out[a] = Σ_b Toeplitz(T_ab) in[b]: the halves of
+// the apply before and after the multiply run per component into C intermediates, and one kernel applies the C × C block of
+// multipliers (C real grids K_aa, C (C − 1) / 2 complex grids K_ab, a < b; K_ba = conj(K_ab)) to every cell in between.
 #include <hip/hip_runtime.h>
 #include <rocfft/rocfft.h>
 
@@ -56,6 +60,12 @@ struct nufft_toeplitz {
     std::vector<const void*> coil_maps;
     bool maps_inpass = true;                           // fused: the maps ride in the outermost passes (false: expand / apply / combine)
     void* d_coil = nullptr;                            // fused, streaming route: complex<T>[N_1, N_2, N_3], held while maps are set
+    // coupled components: the C × C block multiplier and one intermediate per component, held from the first
+    // coupled build to the next uncoupled one
+    bool coupled = false;
+    void* d_kd = nullptr;                              // T[C][2N_1, 2N_2, 2N_3]: the diagonal blocks K_aa
+    void* d_kc = nullptr;                              // complex<T>[C (C − 1) / 2][2N_1, 2N_2, 2N_3]: K_ab, a < b, row-major
+    void* d_grids = nullptr;                           // fused: C arrays like d_tmpB; dense: C arrays like d_work
 };
 
 namespace {
@@ -89,6 +99,33 @@ Sizes sizes_of(const nufft_toeplitz* t) {
 
 int alloc(nufft_toeplitz* t, void** ptr, size_t bytes) { return alloc_buffer(t->own_bytes, "Toeplitz", ptr, bytes); }
 
+// The buffers of a coupled build: C real and C (C − 1) / 2 complex multiplier grids, and C intermediates (each padded on its own:
+// the components of d_grids are grid_stride complex elements apart).
+size_t coupled_kd_bytes(const nufft_toeplitz* t) { return (size_t)t->C * (size_t)grid_cells(t) * real_bytes(t->dtype); }
+size_t coupled_kc_bytes(const nufft_toeplitz* t) { return (size_t)(t->C * (t->C - 1) / 2) * (size_t)grid_cells(t) * 2 * real_bytes(t->dtype); }
+size_t coupled_grid_stride(const nufft_toeplitz* t) {
+    const size_t cb = 2 * real_bytes(t->dtype);
+    const size_t n = t->path == NUFFT_TOEPLITZ_PATH_FUSED ? (size_t)(t->N[0] * t->N2[1] * t->N2[2]) : (size_t)grid_cells(t);
+    return padded(n * cb) / cb;
+}
+size_t coupled_grids_bytes(const nufft_toeplitz* t) { return (size_t)t->C * coupled_grid_stride(t) * 2 * real_bytes(t->dtype); }
+
+int acquire_coupled(nufft_toeplitz* t) {
+    int rc;
+    if (!t->d_kd && (rc = alloc(t, &t->d_kd, coupled_kd_bytes(t)))) return rc;
+    if (!t->d_kc && t->C > 1 && (rc = alloc(t, &t->d_kc, coupled_kc_bytes(t)))) return rc;
+    if (!t->d_grids && (rc = alloc(t, &t->d_grids, coupled_grids_bytes(t)))) return rc;
+    return NUFFT_OK;
+}
+
+// Back to independent components (hipFree waits for the applies in flight).
+void drop_coupled(nufft_toeplitz* t) {
+    t->coupled = false;
+    free_buffer(t->own_bytes, t->d_kd, coupled_kd_bytes(t));
+    free_buffer(t->own_bytes, t->d_kc, coupled_kc_bytes(t));
+    free_buffer(t->own_bytes, t->d_grids, coupled_grids_bytes(t));
+}
+
 template <typename T>
 int upload_real(nufft_toeplitz* t, void** dst, const std::vector<double>& src) {
     std::vector<T> tmp(src.begin(), src.end());
@@ -117,7 +154,7 @@ void release(nufft_toeplitz* t) {
             if (t->d_tw_fw[d]) (void)hipFree(t->d_tw_fw[d]);
             if (t->d_tw_bw[d]) (void)hipFree(t->d_tw_bw[d]);
         }
-        for (void* p : {t->d_ones, t->d_K, t->d_tmpA, t->d_tmpB, t->d_work, t->d_fft_work, t->d_coil})
+        for (void* p : {t->d_ones, t->d_K, t->d_tmpA, t->d_tmpB, t->d_work, t->d_fft_work, t->d_coil, t->d_kd, t->d_kc, t->d_grids})
             if (p) (void)hipFree(p);
         if (t->fft_bw) (void)rocfft_plan_destroy(t->fft_bw);
         if (t->fft_fw) (void)rocfft_plan_destroy(t->fft_fw);
@@ -199,6 +236,25 @@ int multiplier_from(nufft_toeplitz* t, void* grid, const void* src, hipStream_t 
     return NUFFT_OK;
 }
 
+// The multiplier of the pair a <= b of a coupled operator from the spectrum T_ab, as multiplier_from: the scaled real part for a = b
+// (K_aa is real), the scaled complex value for a < b.
+int multiplier_pair_from(nufft_toeplitz* t, void* grid, const void* src, int a, int b, hipStream_t stream) {
+    const nufft::TzGrid g = grid_of(t);
+    const size_t rb = real_bytes(t->dtype);
+    NUFFT_HIP(nufft::launch_tz_spectrum_load(g, grid, src, t->num_cus, stream));
+    NUFFT_ROCFFT(rocfft_execution_info_set_stream(t->fft_info, stream));
+    void* io[1] = {grid};
+    NUFFT_ROCFFT(rocfft_execute(t->fft_bw, io, nullptr, t->fft_info));
+    const double scale = 1.0 / (double)grid_cells(t);
+    if (a == b) {
+        NUFFT_HIP(nufft::launch_tz_real_part(g, static_cast<char*>(t->d_kd) + (size_t)a * (size_t)grid_cells(t) * rb, grid, scale, t->num_cus, stream));
+    } else {
+        void* kc = static_cast<char*>(t->d_kc) + (size_t)nufft::coupled_offdiag_index(a, b, t->C) * (size_t)grid_cells(t) * 2 * rb;
+        NUFFT_HIP(nufft::launch_tz_complex_part(g, kc, grid, scale, t->num_cus, stream));
+    }
+    return NUFFT_OK;
+}
+
 // The fused path's temporaries of set_spectrum / set_points: the (2N)^D complex grid and rocFFT's work buffer.
 struct Scratch {
     nufft_toeplitz* t;
@@ -261,21 +317,30 @@ int strided_pass(const nufft_toeplitz* t, int dim, bool forward, const void* in,
 }
 
 // smap != null: out (+)= conj(S) ⊙ G (S ⊙ in), the map inside the two passes that touch the caller's arrays
-int apply_fused(nufft_toeplitz* t, void* out, const void* in, hipStream_t stream, const void* smap = nullptr, bool accumulate = false) {
+// the strided passes before (in -> tmpB) and after (tmpB -> out) the dimension-1 kernel; tmpB: complex<T>[N_1, 2N_2, 2N_3]
+int fused_backward(nufft_toeplitz* t, void* tmpB, const void* in, hipStream_t stream, const void* smap) {
     int rc;
     const void* src = in;
     if (t->D == 3) {
         if ((rc = strided_pass(t, 2, false, in, t->d_tmpA, stream, smap))) return rc;
         src = t->d_tmpA;
     }
-    if ((rc = strided_pass(t, 1, false, src, t->d_tmpB, stream, t->D == 3 ? nullptr : smap))) return rc;
-    NUFFT_HIP(nufft::launch_toeplitz_lines(t->dtype, t->N2[0], t->d_tmpB, t->d_K, t->N2[1] * t->N2[2], (int)t->N[0], t->d_map[0],
-                                        t->d_tw_fw[0], stream));
+    return strided_pass(t, 1, false, src, tmpB, stream, t->D == 3 ? nullptr : smap);
+}
+int fused_forward(nufft_toeplitz* t, void* out, const void* tmpB, hipStream_t stream, const void* smap, bool accumulate) {
+    int rc;
     if (t->D == 3) {
-        if ((rc = strided_pass(t, 1, true, t->d_tmpB, t->d_tmpA, stream))) return rc;
+        if ((rc = strided_pass(t, 1, true, tmpB, t->d_tmpA, stream))) return rc;
         return strided_pass(t, 2, true, t->d_tmpA, out, stream, smap, accumulate);
     }
-    return strided_pass(t, 1, true, t->d_tmpB, out, stream, smap, accumulate);
+    return strided_pass(t, 1, true, tmpB, out, stream, smap, accumulate);
+}
+
+int apply_fused(nufft_toeplitz* t, void* out, const void* in, hipStream_t stream, const void* smap = nullptr, bool accumulate = false) {
+    if (int rc = fused_backward(t, t->d_tmpB, in, stream, smap)) return rc;
+    NUFFT_HIP(nufft::launch_toeplitz_lines(t->dtype, t->N2[0], t->d_tmpB, t->d_K, t->N2[1] * t->N2[2], (int)t->N[0], t->d_map[0],
+                                        t->d_tw_fw[0], stream));
+    return fused_forward(t, out, t->d_tmpB, stream, smap, accumulate);
 }
 
 int apply_dense(nufft_toeplitz* t, void* out, const void* in, hipStream_t stream, const void* smap = nullptr, bool accumulate = false) {
@@ -302,6 +367,87 @@ int apply_coil(nufft_toeplitz* t, void* out, const void* in, const void* smap, b
     NUFFT_HIP(nufft::launch_coil_expand(t->dtype, num_modes(t), 1, outs, maps, in, t->num_cus, stream));
     if (int rc = apply_fused(t, t->d_coil, t->d_coil, stream)) return rc;
     NUFFT_HIP(nufft::launch_coil_combine(t->dtype, num_modes(t), 1, out, maps, ins, accumulate, t->num_cus, stream));
+    return NUFFT_OK;
+}
+
+// One coil (or the plain operator, smap = null) of the coupled apply: out[a] (+)= conj(S) ⊙ Σ_b Toeplitz(T_ab) (S ⊙ in[b]).  All C
+// backward halves first, each into its own intermediate, then the block multiply across them, then the C forward halves.
+int apply_coupled(nufft_toeplitz* t, void* const* out, const void* const* in, const void* smap, bool accumulate, hipStream_t stream) {
+    const size_t stride = coupled_grid_stride(t), cb = 2 * real_bytes(t->dtype);
+    auto grid_at = [&](int c) { return static_cast<void*>(static_cast<char*>(t->d_grids) + (size_t)c * stride * cb); };
+    const bool fused = t->path == NUFFT_TOEPLITZ_PATH_FUSED;
+    const nufft::TzGrid g = grid_of(t);
+    int rc;
+    for (int b = 0; b < t->C; ++b) {
+        if (fused) {
+            if ((rc = fused_backward(t, grid_at(b), in[b], stream, smap))) return rc;
+            continue;
+        }
+        void* io[1] = {grid_at(b)};
+        if (smap) NUFFT_HIP(nufft::launch_tz_pad_map(g, io[0], in[b], smap, t->num_cus, stream));
+        else NUFFT_HIP(nufft::launch_tz_pad(g, io[0], in[b], t->num_cus, stream));
+        NUFFT_ROCFFT(rocfft_execute(t->fft_bw, io, nullptr, t->fft_info));
+    }
+    if (fused)
+        NUFFT_HIP(nufft::launch_toeplitz_lines_coupled(t->dtype, t->N2[0], t->C, t->d_grids, (int64_t)stride, t->d_kd, t->d_kc, t->N2[1] * t->N2[2],
+                                                    (int)t->N[0], t->d_map[0], t->d_tw_fw[0], stream));
+    else
+        NUFFT_HIP(nufft::launch_tz_multiply_coupled(g, t->d_grids, (int64_t)stride, t->C, t->d_kd, t->d_kc, t->num_cus, stream));
+    for (int a = 0; a < t->C; ++a) {
+        if (fused) {
+            if ((rc = fused_forward(t, out[a], grid_at(a), stream, smap, accumulate))) return rc;
+            continue;
+        }
+        void* io[1] = {grid_at(a)};
+        NUFFT_ROCFFT(rocfft_execute(t->fft_fw, io, nullptr, t->fft_info));
+        if (smap) NUFFT_HIP(nufft::launch_tz_crop_map(g, out[a], io[0], smap, accumulate, t->num_cus, stream));
+        else NUFFT_HIP(nufft::launch_tz_crop(g, out[a], io[0], t->num_cus, stream));
+    }
+    return NUFFT_OK;
+}
+
+// What every coupled build checks before it touches the device, in the order of the header.
+int coupled_refusals(const nufft_toeplitz* t, const char* fn) {
+    if (t->C > nufft::kMaxCoupled)
+        return fail(NUFFT_ERR_UNSUPPORTED, std::string(fn) + ": at most " + std::to_string(nufft::kMaxCoupled) + " coupled components (ntransforms)");
+    if (t->path == NUFFT_TOEPLITZ_PATH_FUSED && !nufft::toeplitz_lines_coupled_supported(t->dtype, t->N2[0], t->C))
+        return fail(NUFFT_ERR_UNSUPPORTED, std::string(fn) + ": the " + std::to_string(t->C) + " lines of 2 N_1 = " + std::to_string(t->N2[0]) +
+                                               " cells of a line id do not fit the LDS of one wave of the fused dimension-1 kernel; create the "
+                                               "operator from a plan with the option NUFFT_TOEPLITZ_FUSED=0 (the dense path)");
+    if (t->path == NUFFT_TOEPLITZ_PATH_FUSED && !t->maps_inpass && !t->coil_maps.empty())
+        return fail(NUFFT_ERR_UNSUPPORTED, std::string(fn) + ": coil maps on the route NUFFT_TOEPLITZ_MAPS_INPASS=0 do not combine with coupled components");
+    return NUFFT_OK;
+}
+
+// The internal 2N plan's parameters: the parent plan's window unless `build` overrides it (nufft_toeplitz_set_points).
+int build_plan_params(const nufft_toeplitz* t, const nufft_params* build, nufft_params& prm) {
+    std::memset(&prm, 0, sizeof(prm));
+    prm.struct_size = (int32_t)sizeof(prm);
+    prm.dtype = t->dtype;
+    prm.is_complex = 1;
+    prm.ndim = t->D;
+    for (int d = 0; d < t->D; ++d) prm.N[d] = t->N2[d];
+    prm.half_support = t->M;
+    prm.sigma = t->sigma_req;
+    prm.kernel = t->kernel;
+    prm.evalmode = t->evalmode;
+    prm.ntransforms = 1;
+    prm.fftshift = 0;
+    prm.point_transform = t->point_transform;
+    prm.device = t->device;
+    prm.options = t->options.empty() ? nullptr : t->options.c_str();
+    if (build) {        // the caller's window for the build: half_support and sigma where set, kernel / kernel_param / evalmode verbatim
+        nufft_params b;
+        std::memset(&b, 0, sizeof(b));
+        const size_t known = build->struct_size > 0 ? (size_t)build->struct_size : offsetof(nufft_params, kernel_param_dim);
+        if (known < offsetof(nufft_params, kernel_param_dim)) return fail(NUFFT_ERR_INVALID_ARG, "nufft_params.struct_size is smaller than any published layout");
+        std::memcpy(&b, build, std::min(known, sizeof(b)));
+        if (b.half_support > 0) prm.half_support = b.half_support;
+        if (b.sigma > 0) prm.sigma = b.sigma;
+        prm.kernel = b.kernel;
+        prm.kernel_param = b.kernel_param;
+        prm.evalmode = b.evalmode;
+    }
     return NUFFT_OK;
 }
 
@@ -414,6 +560,7 @@ int nufft_toeplitz_set_spectrum(nufft_toeplitz* t, const void* T_modes, void* st
     if (capturing(stream))
         return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_set_spectrum allocates and synchronises: not on a capturing stream");
     t->has_spectrum = false;
+    drop_coupled(t);
     Scratch s(t);
     int rc;
     if ((rc = s.acquire_grid()) || (rc = s.acquire_fft_work())) return rc;
@@ -436,35 +583,10 @@ int nufft_toeplitz_set_points(nufft_toeplitz* t, const nufft_params* build, int6
     if (capturing(stream))
         return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_set_points builds and destroys a plan: not on a capturing stream");
     t->has_spectrum = false;
+    drop_coupled(t);
 
     nufft_params prm;
-    std::memset(&prm, 0, sizeof(prm));
-    prm.struct_size = (int32_t)sizeof(prm);
-    prm.dtype = t->dtype;
-    prm.is_complex = 1;
-    prm.ndim = t->D;
-    for (int d = 0; d < t->D; ++d) prm.N[d] = t->N2[d];
-    prm.half_support = t->M;
-    prm.sigma = t->sigma_req;
-    prm.kernel = t->kernel;
-    prm.evalmode = t->evalmode;
-    prm.ntransforms = 1;
-    prm.fftshift = 0;
-    prm.point_transform = t->point_transform;
-    prm.device = t->device;
-    prm.options = t->options.empty() ? nullptr : t->options.c_str();
-    if (build) {        // the caller's window for the build: half_support and sigma where set, kernel / kernel_param / evalmode verbatim
-        nufft_params b;
-        std::memset(&b, 0, sizeof(b));
-        const size_t known = build->struct_size > 0 ? (size_t)build->struct_size : offsetof(nufft_params, kernel_param_dim);
-        if (known < offsetof(nufft_params, kernel_param_dim)) return fail(NUFFT_ERR_INVALID_ARG, "nufft_params.struct_size is smaller than any published layout");
-        std::memcpy(&b, build, std::min(known, sizeof(b)));
-        if (b.half_support > 0) prm.half_support = b.half_support;
-        if (b.sigma > 0) prm.sigma = b.sigma;
-        prm.kernel = b.kernel;
-        prm.kernel_param = b.kernel_param;
-        prm.evalmode = b.evalmode;
-    }
+    if (int prc = build_plan_params(t, build, prm)) return prc;
 
     Scratch s(t);
     int rc;
@@ -501,6 +623,112 @@ int nufft_toeplitz_set_points(nufft_toeplitz* t, const nufft_params* build, int6
     return NUFFT_OK;
 }
 
+int nufft_toeplitz_set_spectra_coupled(nufft_toeplitz* t, const void* const* T_pairs, void* stream_) {
+    if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    if (!T_pairs) return fail(NUFFT_ERR_INVALID_ARG, "null table of spectra");
+    if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
+    const int npairs = t->C * (t->C + 1) / 2;
+    for (int p = 0; p < npairs; ++p)
+        if (!T_pairs[p]) return fail(NUFFT_ERR_INVALID_ARG, "null spectrum");
+    int rc;
+    if ((rc = coupled_refusals(t, "nufft_toeplitz_set_spectra_coupled"))) return rc;
+    DeviceGuard guard(t->device);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (capturing(stream))
+        return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_set_spectra_coupled allocates and synchronises: not on a capturing stream");
+    t->has_spectrum = false;
+    t->coupled = false;
+    if ((rc = acquire_coupled(t))) return rc;
+    Scratch s(t);
+    if ((rc = s.acquire_grid()) || (rc = s.acquire_fft_work())) return rc;
+    for (int a = 0, p = 0; a < t->C; ++a)
+        for (int b = a; b < t->C; ++b, ++p)
+            if ((rc = multiplier_pair_from(t, s.grid, T_pairs[p], a, b, stream))) return rc;
+    NUFFT_HIP(hipStreamSynchronize(stream));      // the temporaries are freed on return
+    t->coupled = true;
+    t->has_spectrum = true;
+    return NUFFT_OK;
+}
+
+int nufft_toeplitz_set_points_coupled(nufft_toeplitz* t, const nufft_params* build, int64_t np, const void* const* coords, const void* weights,
+                                      const void* const* basis, void* stream_) {
+    if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    if (!basis) return fail(NUFFT_ERR_INVALID_ARG, "null table of basis functions");
+    if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
+    if (np < 0) return fail(NUFFT_ERR_INVALID_ARG, "negative number of points");
+    if (!coords) return fail(NUFFT_ERR_INVALID_ARG, "null coordinate table");
+    for (int d = 0; d < t->D; ++d)
+        if (np > 0 && !coords[d]) return fail(NUFFT_ERR_INVALID_ARG, "null coordinate vector");
+    for (int c = 0; c < t->C; ++c)
+        if (np > 0 && (!basis[c] || !aligned16(basis[c]))) return fail(NUFFT_ERR_INVALID_ARG, "null or not 16-byte aligned basis function");
+    int rc;
+    if ((rc = coupled_refusals(t, "nufft_toeplitz_set_points_coupled"))) return rc;
+    DeviceGuard guard(t->device);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (capturing(stream))
+        return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_set_points_coupled builds and destroys a plan: not on a capturing stream");
+    t->has_spectrum = false;
+    t->coupled = false;
+    nufft_params prm;
+    if ((rc = build_plan_params(t, build, prm))) return rc;
+    if ((rc = acquire_coupled(t))) return rc;
+
+    Scratch s(t);
+    // (the transform's own work buffer lives next to the plan here: every pair is transformed while the plan exists)
+    if ((rc = s.acquire_grid()) || (rc = s.acquire_fft_work())) return rc;
+    void* values = nullptr;
+    const size_t vbytes = (size_t)std::max<int64_t>(np, 1) * 2 * real_bytes(t->dtype);
+    if ((rc = alloc(t, &values, vbytes))) return rc;
+    nufft_plan* bp = nullptr;
+    rc = nufft_plan_create_ex(&bp, &prm);
+    if (rc == NUFFT_OK) {
+        t->build_bytes = bp->workspace_bytes;
+        rc = nufft_set_points(bp, np, coords, stream);      // once for all pairs
+        t->build_bytes = bp->workspace_bytes;
+    }
+    bool in_type1 = true;
+    for (int a = 0; a < t->C && rc == NUFFT_OK; ++a)
+        for (int b = a; b < t->C && rc == NUFFT_OK; ++b) {
+            in_type1 = true;
+            hipError_t e = nufft::launch_tz_pair_weights(t->dtype, values, weights, basis[a], basis[b], np, t->num_cus, stream);
+            if (e != hipSuccess) rc = fail(NUFFT_ERR_HIP, std::string("launch_tz_pair_weights: ") + hipGetErrorString(e));
+            if (rc == NUFFT_OK) {
+                void* outs[1] = {s.grid};
+                const void* ins[1] = {values};
+                rc = nufft_exec_type1(bp, outs, ins, stream);
+            }
+            in_type1 = false;
+            if (rc == NUFFT_OK) rc = multiplier_pair_from(t, s.grid, s.grid, a, b, stream);
+        }
+    if (rc == NUFFT_OK && hipStreamSynchronize(stream) != hipSuccess) rc = fail(NUFFT_ERR_HIP, "hipStreamSynchronize failed");
+    const std::string keep = rc ? nufft_last_error_message() : "";
+    if (bp) nufft_plan_destroy(bp);
+    t->build_bytes = 0;
+    free_buffer(t->own_bytes, values, vbytes);
+    if (rc) return fail(rc, (in_type1 ? "coupled Toeplitz build (type 1 of a pair's weights on the 2N grid): " : "coupled Toeplitz build: ") + keep);
+    t->coupled = true;
+    t->has_spectrum = true;
+    return NUFFT_OK;
+}
+
+int32_t nufft_toeplitz_num_coupled(const nufft_toeplitz* t) { return t && t->coupled ? (int32_t)t->C : 0; }
+
+int nufft_toeplitz_multiplier_pair_ptr(const nufft_toeplitz* t, int32_t a, int32_t b, void** out_ptr, int64_t* out_bytes) {
+    if (!t || !out_ptr) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
+    if (!t->coupled) return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_multiplier_pair_ptr: no coupled build is in force");
+    if (a < 0 || b < a || b >= t->C) return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_multiplier_pair_ptr: the pair must satisfy 0 <= a <= b < ntransforms");
+    const int64_t rb = (int64_t)real_bytes(t->dtype);
+    if (a == b) {
+        *out_ptr = static_cast<char*>(t->d_kd) + a * grid_cells(t) * rb;
+        if (out_bytes) *out_bytes = grid_cells(t) * rb;
+    } else {
+        *out_ptr = static_cast<char*>(t->d_kc) + nufft::coupled_offdiag_index(a, b, t->C) * grid_cells(t) * 2 * rb;
+        if (out_bytes) *out_bytes = grid_cells(t) * 2 * rb;
+    }
+    return NUFFT_OK;
+}
+
 int nufft_toeplitz_apply(nufft_toeplitz* t, void* const* out, const void* const* in, void* stream_) {
     if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
     if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
@@ -512,11 +740,17 @@ int nufft_toeplitz_apply(nufft_toeplitz* t, void* const* out, const void* const*
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (t->path == NUFFT_TOEPLITZ_PATH_DENSE) NUFFT_ROCFFT(rocfft_execution_info_set_stream(t->fft_info, stream));
     const int ncoils = (int)t->coil_maps.size();
-    if (ncoils > 0) {       // coil 0 stores into out[c] what coil 1 still has to read from in[c']
+    if (ncoils > 0 || t->coupled) {       // coil 0 stores into out[c] what coil 1 still has to read from in[c']; coupled: every output needs every input
         for (int c = 0; c < t->C; ++c)
             for (int c2 = 0; c2 < t->C; ++c2)
                 if (out[c] == in[c2])
-                    return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_apply with coil maps set: an output array is also an input array");
+                    return fail(NUFFT_ERR_INVALID_ARG, ncoils > 0 ? "nufft_toeplitz_apply with coil maps set: an output array is also an input array"
+                                                                  : "nufft_toeplitz_apply on coupled components: an output array is also an input array");
+    }
+    if (t->coupled) {
+        int rc = ncoils == 0 ? apply_coupled(t, out, in, nullptr, false, stream) : NUFFT_OK;
+        for (int s = 0; s < ncoils && !rc; ++s) rc = apply_coupled(t, out, in, t->coil_maps[(size_t)s], s > 0, stream);
+        return rc;
     }
     for (int c = 0; c < t->C; ++c) {
         int rc = NUFFT_OK;
@@ -536,6 +770,8 @@ int nufft_toeplitz_set_maps(nufft_toeplitz* t, int32_t ncoils, const void* const
         if (!maps[c]) return fail(NUFFT_ERR_INVALID_ARG, "null coil map");
         if (!aligned16(maps[c])) return fail(NUFFT_ERR_INVALID_ARG, "coil maps must be 16-byte aligned");
     }
+    if (t->coupled && t->path == NUFFT_TOEPLITZ_PATH_FUSED && !t->maps_inpass)
+        return fail(NUFFT_ERR_UNSUPPORTED, "nufft_toeplitz_set_maps: coil maps on the route NUFFT_TOEPLITZ_MAPS_INPASS=0 do not combine with coupled components");
     if (t->path == NUFFT_TOEPLITZ_PATH_FUSED && !t->maps_inpass && !t->d_coil) {
         DeviceGuard guard(t->device);
         if (capturing(static_cast<hipStream_t>(stream_)))

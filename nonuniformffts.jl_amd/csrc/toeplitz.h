@@ -54,4 +54,23 @@ bool toeplitz_lines_supported(int dtype, int64_t n);
 hipError_t launch_toeplitz_lines(int dtype, int64_t n, void* data, const void* K, int64_t nlines, int k1, const int32_t* map,
                                  const void* twiddle, hipStream_t stream);
 
+// Coupled components.  The K × K block multiplier is stored as K real grids (the diagonal, `kd`:
+// T[K][cells]) and K (K − 1) / 2 complex grids (`kc`: complex<T>[pairs a < b, row-major][cells]); K_ba = conj(K_ab).
+constexpr int kMaxCoupled = 16;
+inline int coupled_offdiag_index(int a, int b, int K) { return a * (K - 1) - a * (a - 1) / 2 + (b - a - 1); }      // a < b
+// values[j] = w_j conj(φ_a(j)) φ_b(j)  (complex<T>[n]; weights = null: ones; φ 16-byte aligned)
+hipError_t launch_tz_pair_weights(int dtype, void* values, const void* weights, const void* phi_a, const void* phi_b, int64_t n, int num_cus,
+                                  hipStream_t stream);
+// Kc = scale * grid  (complex, same shape: the multiplier of a pair a < b)
+hipError_t launch_tz_complex_part(const TzGrid& g, void* Kc, const void* grid, double scale, int num_cus, hipStream_t stream);
+// grids[a] = Σ_b K_ab ⊙ grids[b] per cell, in place; grids: K complex grids `grid_stride` complex elements apart
+hipError_t launch_tz_multiply_coupled(const TzGrid& g, void* grids, int64_t grid_stride, int K, const void* kd, const void* kc, int num_cus,
+                                      hipStream_t stream);
+// Dimension 1 of the fused apply for K coupled components, in place: one wave owns the K lines of a line id (data: K arrays
+// complex<T>[nlines][k1], `data_stride` complex elements apart), transforms them backward, applies the block multiplier per cell and
+// transforms them forward inside LDS.  _supported: the K lines of length n fit the LDS of one wave.
+bool toeplitz_lines_coupled_supported(int dtype, int64_t n, int K);
+hipError_t launch_toeplitz_lines_coupled(int dtype, int64_t n, int K, void* data, int64_t data_stride, const void* kd, const void* kc,
+                                         int64_t nlines, int k1, const int32_t* map, const void* twiddle, hipStream_t stream);
+
 }  // namespace nufft

@@ -122,6 +122,87 @@ __global__ __launch_bounds__(kThreads) void tz_weights_kernel(T* values, const T
     }
 }
 
+// Coupled components.  values[j] = w_j conj(φ_a(j)) φ_b(j): the weights of the type 1 that builds T_ab.
+// The complex arrays pass as 2n reals in 16-byte packs, two per thread and trip; the weights are read element by element.
+template <typename T>
+__global__ __launch_bounds__(kThreads) void tz_pair_weights_kernel(T* values, const T* weights, const T* pa, const T* pb, int64_t n) {
+    constexpr int W = Pack<T>::W, CW = W / 2;
+    auto one = [&](T ar, T ai, T br, T bi, int64_t j, T& re, T& im) {
+        const T w = weights ? weights[j] : T(1);
+        re = w * (ar * br + ai * bi);
+        im = w * (ar * bi - ai * br);
+    };
+    auto pack = [&](int64_t i) {
+        const Pack<T> a = load(pa, i), b = load(pb, i);
+        Pack<T> r;
+#pragma unroll
+        for (int w = 0; w < CW; ++w) one(a.v[2 * w], a.v[2 * w + 1], b.v[2 * w], b.v[2 * w + 1], i * CW + w, r.v[2 * w], r.v[2 * w + 1]);
+        store(values, i, r);
+    };
+    NUFFT_FOR_EACH_PACK(T, 2 * n, i) {
+        pack(i);
+        if (i + step__ < npacks__) pack(i + step__);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (int64_t j = npacks__ * CW; j < n; ++j) one(pa[2 * j], pa[2 * j + 1], pb[2 * j], pb[2 * j + 1], j, values[2 * j], values[2 * j + 1]);
+}
+
+// Kc = scale * grid (complex): the multiplier of a pair a < b, the sibling of tz_real_kernel's MODE 1
+template <typename T>
+__global__ __launch_bounds__(kThreads) void tz_complex_part_kernel(const T* grid, T* K, T scale, int64_t npacks) {
+    for (int64_t q = (int64_t)blockIdx.x * kThreads + threadIdx.x; q < npacks; q += (int64_t)gridDim.x * kThreads) {
+        Pack<T> pk = load(grid, q);
+#pragma unroll
+        for (int w = 0; w < Pack<T>::W; ++w) pk.v[w] *= scale;
+        store(K, q, pk);
+    }
+}
+
+// grids[a] = Σ_b K_ab ⊙ grids[b] per cell, in place: a thread holds the K packs of its cells, so every grid and every multiplier
+// grid is read once.  KT: the compile-time bound of the run-time K (the register arrays).  kd: T[K][cells]; kc: complex<T>[pairs a < b,
+// row-major][cells]; the pair (b, a), b < a, applies conjugated.
+template <typename T, int KT>
+__global__ __launch_bounds__(kThreads) void tz_multiply_coupled_kernel(T* grids, int64_t stride, int K, const T* kd, const T* kc, int64_t ncells,
+                                                                       int64_t npacks) {
+    constexpr int CW = Pack<T>::W / 2;
+    for (int64_t q = (int64_t)blockIdx.x * kThreads + threadIdx.x; q < npacks; q += (int64_t)gridDim.x * kThreads) {
+        const int64_t cell = q * CW;
+        Pack<T> v[KT], acc[KT];
+#pragma unroll
+        for (int a = 0; a < KT; ++a) {
+            if (a < K) {
+                v[a] = load(grids + a * stride, q);
+#pragma unroll
+                for (int w = 0; w < CW; ++w) {
+                    const T d = kd[a * ncells + cell + w];
+                    acc[a].v[2 * w] = d * v[a].v[2 * w];
+                    acc[a].v[2 * w + 1] = d * v[a].v[2 * w + 1];
+                }
+            }
+        }
+#pragma unroll
+        for (int a = 0; a < KT; ++a) {
+#pragma unroll
+            for (int b = a + 1; b < KT; ++b) {
+                if (b < K) {
+                    const Pack<T> k = load(kc + 2 * (int64_t)(a * (K - 1) - a * (a - 1) / 2 + (b - a - 1)) * ncells, q);
+#pragma unroll
+                    for (int w = 0; w < CW; ++w) {
+                        const T kr = k.v[2 * w], ki = k.v[2 * w + 1];
+                        acc[a].v[2 * w] += kr * v[b].v[2 * w] - ki * v[b].v[2 * w + 1];
+                        acc[a].v[2 * w + 1] += kr * v[b].v[2 * w + 1] + ki * v[b].v[2 * w];
+                        acc[b].v[2 * w] += kr * v[a].v[2 * w] + ki * v[a].v[2 * w + 1];
+                        acc[b].v[2 * w + 1] += kr * v[a].v[2 * w + 1] - ki * v[a].v[2 * w];
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int a = 0; a < KT; ++a)
+            if (a < K) store(grids + a * stride, q, acc[a]);
+    }
+}
+
 int64_t packs(const TzGrid& g) { return cells(g) / (g.dtype == NUFFT_F32 ? 2 : 1); }
 
 // Coil expand (EXPAND: data[c] = S_c ⊙ x for every coil of the table) and combine (y = Σ_c conj(S_c) ⊙ data[c], summed in coil order in
@@ -260,6 +341,31 @@ hipError_t launch_coil_combine(int dtype, int64_t n, int ncoils, void* out, cons
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+hipError_t launch_tz_pair_weights(int dtype, void* values, const void* weights, const void* phi_a, const void* phi_b, int64_t n, int num_cus,
+                                  hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    const int64_t np = (2 * n) / (dtype == NUFFT_F32 ? 4 : 2);
+    return launch_by_dtype(dtype, dim3(stream_workgroups(np, num_cus)), dim3(kThreads), stream, tz_pair_weights_kernel<float>,
+                           tz_pair_weights_kernel<double>, values, weights, phi_a, phi_b, n);
+}
+
+hipError_t launch_tz_complex_part(const TzGrid& g, void* Kc, const void* grid, double scale, int num_cus, hipStream_t stream) {
+    const int64_t np = packs(g);
+    return launch_by_dtype(g.dtype, dim3(grid_for(np, num_cus)), dim3(kThreads), stream, tz_complex_part_kernel<float>, tz_complex_part_kernel<double>,
+                           grid, Kc, scale, np);
+}
+
+hipError_t launch_tz_multiply_coupled(const TzGrid& g, void* grids, int64_t grid_stride, int K, const void* kd, const void* kc, int num_cus,
+                                      hipStream_t stream) {
+    if (K < 1 || K > kMaxCoupled) return hipErrorInvalidValue;
+    const int64_t np = packs(g), nc = cells(g), stride = 2 * grid_stride;
+    const dim3 gr(grid_for(np, num_cus)), bl(kThreads);
+    if (K <= 2) return launch_by_dtype(g.dtype, gr, bl, stream, tz_multiply_coupled_kernel<float, 2>, tz_multiply_coupled_kernel<double, 2>, grids, stride, K, kd, kc, nc, np);
+    if (K <= 4) return launch_by_dtype(g.dtype, gr, bl, stream, tz_multiply_coupled_kernel<float, 4>, tz_multiply_coupled_kernel<double, 4>, grids, stride, K, kd, kc, nc, np);
+    if (K <= 8) return launch_by_dtype(g.dtype, gr, bl, stream, tz_multiply_coupled_kernel<float, 8>, tz_multiply_coupled_kernel<double, 8>, grids, stride, K, kd, kc, nc, np);
+    return launch_by_dtype(g.dtype, gr, bl, stream, tz_multiply_coupled_kernel<float, 16>, tz_multiply_coupled_kernel<double, 16>, grids, stride, K, kd, kc, nc, np);
 }
 
 hipError_t launch_tz_weights(int dtype, void* values, const void* weights, int64_t n, int num_cus, hipStream_t stream) {

@@ -11,6 +11,10 @@ so after one build per point set it is applied with FFTs of size 2N alone, at a 
 
 With coil sensitivity maps (``op.set_maps(maps)``, parallel MRI) the same ``apply`` computes ``Σ_c conj(S_c) ⊙ G (S_c ⊙ û)``;
 ``coil_expand`` / ``coil_combine`` are the coil passes of the forward model and of the right-hand side.
+
+Coupled components (subspace models, ``y_j = Σ_a φ_a(j) (A û_a)_j``): ``op.set_points(points, weights, basis=phi)`` with ``phi`` of shape
+``(ntransforms, Np)`` makes ``apply`` the block operator ``(G_Φ u)_a = Σ_b A^H diag(w conj(φ_a) φ_b) A u_b`` and ``solve`` / ``ToeplitzCG``
+one joint system; a plain ``set_points`` / ``set_spectrum`` returns to independent components.
 """
 from __future__ import annotations
 
@@ -101,11 +105,74 @@ class ToeplitzOperator:
         _check(lib.nufft_toeplitz_set_spectrum(self._handle, C.c_void_p(T.data_ptr()), self._stream()))
         return self
 
-    def set_points(self, points, weights: Optional[torch.Tensor] = None, *, m=None, sigma: Optional[float] = None,
-                   σ: Optional[float] = None, kernel=None, kernel_evalmode=None) -> "ToeplitzOperator":
+    @staticmethod
+    def pair_index(a: int, b: int, K: int) -> int:
+        """Position of the pair ``a <= b`` in the row-major order over ``a <= b`` that ``set_spectra`` uses."""
+        if not 0 <= a <= b < K:
+            raise ValueError(f"the pair must satisfy 0 <= a <= b < {K}")
+        return a * K - a * (a - 1) // 2 + (b - a)
+
+    @property
+    def coupled(self) -> bool:
+        """True while a coupled build (``set_points(..., basis=)`` / ``set_spectra``) is in force."""
+        return bool(self._handle.value) and lib.nufft_toeplitz_num_coupled(self._handle) > 0
+
+    def set_spectra(self, T) -> "ToeplitzOperator":
+        """The coupled counterpart of ``set_spectrum``: ``T`` of shape ``(K (K + 1) / 2, *padded_shape)`` or a sequence of that many
+        ``padded_shape`` tensors, ``T[pair_index(a, b, K)] = T_ab`` on the mode set of a 2N plan, ``K = ntransforms``.  Only read."""
+        K = self.ntransforms
+        npairs = K * (K + 1) // 2
+        if isinstance(T, torch.Tensor):
+            if T.dim() != self.ndim + 1 or T.shape[0] != npairs:
+                raise DimensionMismatch(f"wrong dimensions of the spectra (expected tensor shape ({npairs}, ...) for {K} components, "
+                                        f"got {tuple(T.shape)})")
+            if not T.is_contiguous():
+                raise ValueError("the spectra must be contiguous")
+            T = tuple(T[p] for p in range(npairs))
+        else:
+            T = tuple(T)
+            if len(T) != npairs:
+                raise DimensionMismatch(f"wrong amount of spectra (expected {npairs} for {K} components, got {len(T)})")
+        self._require_gpu()
+        self._require_open()
+        _check_coil_arrays(T, self.device, self.Z, self.padded_shape, "the spectra")
+        _check(lib.nufft_toeplitz_set_spectra_coupled(self._handle, _ptr_table(T), self._stream()))
+        return self
+
+    def _basis_rows(self, basis):
+        """``basis`` as a ``(K, Np)`` tensor: a vector counts as one row where ``ntransforms == 1``."""
+        K = self.ntransforms
+        if not isinstance(basis, torch.Tensor):
+            raise ValueError("basis must be a torch tensor of shape (ntransforms, Np)")
+        if basis.dim() == 1 and K == 1:
+            basis = basis[None]
+        if basis.dim() != 2 or basis.shape[0] != K:
+            raise DimensionMismatch(f"wrong dimensions of the basis (expected {K} rows of Np values, got tensor shape {tuple(basis.shape)})")
+        return basis
+
+    def _check_basis(self, basis, n):
+        """``basis`` (from ``_basis_rows``) as a tuple of K aligned ``(Np,)`` tensors (the exception types of ``_check_uniform``)."""
+        K = self.ntransforms
+        if basis.device != self.device:
+            raise ValueError(f"basis must be a torch tensor on {self.device}")
+        if basis.dtype != self.Z:
+            raise ValueError(f"basis must have element type {self.Z} (got {basis.dtype})")
+        if basis.shape[1] != n:
+            raise DimensionMismatch(f"wrong length of the basis (expected {n} points, got {basis.shape[1]})")
+        if not basis.is_contiguous():
+            raise ValueError("basis must be contiguous")
+        return _aligned(tuple(basis[a] for a in range(K)))
+
+    def set_points(self, points, weights: Optional[torch.Tensor] = None, *, basis: Optional[torch.Tensor] = None, m=None,
+                   sigma: Optional[float] = None, σ: Optional[float] = None, kernel=None, kernel_evalmode=None) -> "ToeplitzOperator":
         """Builds the multiplier from ``points`` (what ``set_points`` of the plan accepts) and real ``weights`` (None = ones) with an
         internal plan of 2N modes that is destroyed before the call returns (it is large while it lives: 17 GB at 256³, σ = 2,
-        ComplexF64).  ``m`` / ``sigma`` / ``kernel`` / ``kernel_evalmode`` override the parent plan's window for this build."""
+        ComplexF64).  ``m`` / ``sigma`` / ``kernel`` / ``kernel_evalmode`` override the parent plan's window for this build.
+
+        ``basis``: a contiguous complex tensor ``(ntransforms, Np)`` of the plan's element type (a ``(Np,)`` vector when
+        ``ntransforms == 1``): the components are then coupled, ``(G u)_a = Σ_b A^H diag(w conj(φ_a) φ_b) A u_b``."""
+        if basis is not None:
+            basis = self._basis_rows(basis)        # the component count needs no device
         self._require_gpu()
         if isinstance(points, torch.Tensor):
             if points.dim() == 1:
@@ -157,6 +224,10 @@ class ToeplitzOperator:
             prm.kernel_param = 0.0 if kparam is None else float(kparam)
             prm.evalmode = _lib.EVAL_DIRECT if isinstance(mode, Direct) else _lib.EVAL_FAST_APPROXIMATION
             build = C.byref(prm)
+        if basis is not None:
+            rows = self._check_basis(basis, n)
+            _check(lib.nufft_toeplitz_set_points_coupled(self._handle, build, n, _ptr_table(points), wptr, _ptr_table(rows), self._stream()))
+            return self
         _check(lib.nufft_toeplitz_set_points(self._handle, build, n, _ptr_table(points), wptr, self._stream()))
         return self
 
@@ -225,6 +296,8 @@ class ToeplitzOperator:
             self._check_uniform(out_t, "output")
             if self._maps and any(o is v or o.data_ptr() == v.data_ptr() for o in out_t for v in u_t):
                 raise ValueError("with coil maps set the output must not be the input")
+            if self.coupled and any(o is v or o.data_ptr() == v.data_ptr() for o in out_t for v in u_t):
+                raise ValueError("on coupled components the output must not be the input: every output depends on every input")
         _check(lib.nufft_toeplitz_apply(self._handle, _ptr_table(out_t), _ptr_table(u_t), self._stream()))
         return out
 
@@ -242,16 +315,35 @@ class ToeplitzOperator:
             sol.close()
         return out
 
-    def multiplier(self) -> torch.Tensor:
+    def multiplier(self, a: Optional[int] = None, b: Optional[int] = None) -> torch.Tensor:
         """The real multiplier ``K`` (shape ``padded_shape``): a view of the device array the operator holds — valid while the
-        operator lives, rewritten by the next ``set_points`` / ``set_spectrum``; ``.clone()`` it to keep it."""
+        operator lives, rewritten by the next ``set_points`` / ``set_spectrum``; ``.clone()`` it to keep it.
+
+        On a coupled operator ``multiplier(a, b)`` is the block ``K_ab``: a real view for ``a == b``, a complex view for ``a < b``
+        (``K_ba = conj(K_ab)``: ``a > b`` raises), freed by the next uncoupled build."""
         self._require_gpu()
+        self._require_open()
         ptr, nbytes = C.c_void_p(), C.c_int64()
-        _check(lib.nufft_toeplitz_multiplier_ptr(self._handle, C.byref(ptr), C.byref(nbytes)))
+        if (a is None) != (b is None):
+            raise ValueError("multiplier() takes no component or the pair (a, b)")
+        if a is None and self.coupled:
+            raise ValueError("a coupled operator has a block of multipliers: ask for multiplier(a, b) with a <= b")
+        if a is not None:
+            if not self.coupled:
+                raise ValueError("multiplier(a, b) needs a coupled build (set_points(..., basis=) or set_spectra)")
+            if not 0 <= a < self.ntransforms or not 0 <= b < self.ntransforms:
+                raise ValueError(f"components must lie in 0 ... {self.ntransforms - 1}")
+            if a > b:
+                raise ValueError("only the pairs a <= b are stored: multiplier(b, a) is the conjugate of multiplier(a, b)")
+            _check(lib.nufft_toeplitz_multiplier_pair_ptr(self._handle, a, b, C.byref(ptr), C.byref(nbytes)))
+        else:
+            _check(lib.nufft_toeplitz_multiplier_ptr(self._handle, C.byref(ptr), C.byref(nbytes)))
         shape = self.padded_shape
+        real = a is None or a == b
+        typestr = ("<f4" if self.T == torch.float32 else "<f8") if real else ("<c8" if self.T == torch.float32 else "<c16")
 
         class _View:       # the array-interface protocol: torch wraps the pointer without copying
-            __cuda_array_interface__ = {"shape": shape, "typestr": "<f4" if self.T == torch.float32 else "<f8",
+            __cuda_array_interface__ = {"shape": shape, "typestr": typestr,
                                         "data": (int(ptr.value), False), "version": 2, "strides": None}
 
         k = torch.as_tensor(_View(), device=self.device)
@@ -261,7 +353,7 @@ class ToeplitzOperator:
     def __repr__(self):
         i = self.info()
         return (f"ToeplitzOperator of a {self.ndim}-dimensional {self.Z} plan, N = {tuple(int(i.N[d]) for d in range(self.ndim))}, "
-                f"{self.path} path, {f'{self.ncoils} coil maps, ' if self.ncoils else ''}{i.workspace_bytes / 1e6:.1f} MB")
+                f"{self.path} path, {'coupled components, ' if self.coupled else ''}{f'{self.ncoils} coil maps, ' if self.ncoils else ''}{i.workspace_bytes / 1e6:.1f} MB")
 
 
 def _check_coil_arrays(arrays, device, Z, shape, what):
