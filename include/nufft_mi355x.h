@@ -654,6 +654,90 @@ int nufft_cg_history(nufft_cg* cg, double* host_out, int64_t capacity, void* str
 int64_t nufft_sizeof_cg_params(void);
 int64_t nufft_sizeof_cg_info(void);
 
+/* ---- Preconditioner: T. Chan's optimal circulant for the Toeplitz normal operator ---- */
+/* G is multi-level Toeplitz over the array indices of a component (for fftshift = 0 after a cyclic rotation of rows and columns,
+ * which leaves a circulant unchanged: the same object serves both layouts).  C = argmin over circulants of ‖C − G‖_F has the
+ * eigenvalues e = Re diag(F G F^H) / n, F the unnormalised N-point DFT over the array indices, n = Π N_d; they follow from the
+ * operator's multiplier alone (Fejér-weighted fold of its generating sequence and one N-point transform).  The object applies
+ *
+ *     M⁻¹ r = d ⊙ F⁻¹( m ⊙ F( d ⊙ r ) ),      m_q = 1 / max(e_q + μ, floor · max_q(e_q + μ))
+ *
+ * to every component: Hermitian and positive definite.  d is an optional real positive array shaped like a component (none: the two
+ * multiplies are skipped).  If the operator has coil maps set when the preconditioner is created or updated, d = (Σ_c |S_c|²)^(−1/2)
+ * (the sum floored at 1e-3 of its maximum) is computed into an array the object owns and μ = λ / mean(Σ_c |S_c|²); otherwise μ = λ.
+ * nufft_precond_set_scaling replaces d by a caller's array (borrowed; NULL: none) and leaves μ as it is.
+ *
+ * Two paths, chosen at creation from the shape alone and independent of the operator's own path: FUSED (2-D and 3-D, every N_d one
+ * of the line lengths 64 ... 1024 of the library's own FFT passes, unless the plan carries NUFFT_TOEPLITZ_FUSED=0): strided line
+ * passes and one in-LDS kernel along dimension 1; DENSE: rocFFT forward, one multiply, rocFFT backward on one scratch array.
+ *
+ * Added after ABI 104 without changing NUFFT_MI355X_VERSION: detect by symbol (dlsym nufft_precond_create) and compare
+ * nufft_sizeof_precond_params() / nufft_sizeof_precond_info() with your own. */
+typedef struct nufft_precond nufft_precond; /* opaque */
+
+enum { NUFFT_PRECOND_PATH_DENSE = 0, NUFFT_PRECOND_PATH_FUSED = 1 };
+enum { NUFFT_PRECOND_SCALING_NONE = 0, NUFFT_PRECOND_SCALING_MAPS = 1, NUFFT_PRECOND_SCALING_CALLER = 2 };
+
+typedef struct nufft_precond_params {
+    int32_t struct_size;     /* sizeof(nufft_precond_params) of the caller's header (0 = this layout)                              */
+    int32_t reserved;        /* 0                                                                                                  */
+    double lambda;           /* the λ of the system (G + λ I) that is preconditioned: >= 0, finite                                 */
+    double floor;            /* > 0, finite; 0 is NOT a default here: pass 1e-6                                                    */
+} nufft_precond_params;
+
+typedef struct nufft_precond_info {
+    int32_t struct_size;     /* sizeof(nufft_precond_info) of the caller's header, set before the call (0 = this layout)           */
+    int32_t ndim, dtype, ntransforms, device;
+    int32_t path;            /* NUFFT_PRECOND_PATH_*                                                                               */
+    int32_t scaling;         /* NUFFT_PRECOND_SCALING_*                                                                            */
+    int32_t reserved;
+    int64_t N[3];
+    double lambda, mu, floor;
+    double max_e, min_e;     /* of the eigenvalues e of the last build (before μ and the floor)                                    */
+    int64_t multiplier_bytes;/* m: one real per mode                                                                               */
+    int64_t workspace_bytes; /* device bytes owned at rest                                                                         */
+} nufft_precond_info;
+
+/* Builds m from the operator's current multiplier on the default stream: allocates temporaries (a complex (2N)^D grid and rocFFT's work
+ * buffers), synchronises and frees them before returning — like nufft_toeplitz_set_spectrum the build is not capturable
+ * (nufft_precond_update, which takes a stream, refuses a capturing one).  The object keeps the POINTER `tz`: the operator must outlive it.  Refusals, in order: null arguments, lambda < 0, floor <= 0
+ * or non-finite values NUFFT_ERR_INVALID_ARG; a host-only operator NUFFT_ERR_NO_DEVICE; no spectrum yet NUFFT_ERR_NO_POINTS; a coupled
+ * build in force NUFFT_ERR_UNSUPPORTED (a block preconditioner is not built); an operator whose e + μ is nowhere positive
+ * NUFFT_ERR_INVALID_ARG. */
+int nufft_precond_create(nufft_precond** out, nufft_toeplitz* tz, const nufft_precond_params* params);
+int nufft_precond_destroy(nufft_precond* pc);
+/* Rebuilds m (and the scaling from coil maps) after the operator's spectrum or maps changed; same rules as the build in _create. */
+int nufft_precond_update(nufft_precond* pc, void* stream);
+/* d: real(T)[N...] on the device, 16-byte aligned, positive, borrowed until replaced; NULL: no scaling. */
+int nufft_precond_set_scaling(nufft_precond* pc, const void* d);
+/* out[c] = M⁻¹ in[c] for every component; complex(T)[N...], 16-byte aligned; out[c] may be in[c].  Allocates nothing, does not
+ * synchronise, hipGraph-capture safe. */
+int nufft_precond_apply(nufft_precond* pc, void* const* out, const void* const* in, void* stream);
+int nufft_precond_get_info(const nufft_precond* pc, nufft_precond_info* out);
+/* Device pointers (inspection and tests): m, real(T)[N...] with 1 / Π N_d folded in; the scaling d in force (NULL: none). */
+int nufft_precond_multiplier_ptr(const nufft_precond* pc, void** out_ptr, int64_t* out_bytes);
+int nufft_precond_scaling_ptr(const nufft_precond* pc, void** out_ptr, int64_t* out_bytes);
+int64_t nufft_sizeof_precond_params(void);
+int64_t nufft_sizeof_precond_info(void);
+
+/* Preconditioned CG: with a preconditioner set, nufft_cg_solve runs
+ *
+ *     r = b − (G + λ) x0     z = M⁻¹ r     p = z     ρ_z = Re<r, z>     ρ = ‖r‖²     β0 = ‖b‖²
+ *     for it = 1 ... max_iter:
+ *         q = G p                                                         nufft_toeplitz_apply
+ *         γ = Re<p, q> + λ ‖p‖²                                           cg_dot_kernel
+ *         α = ρ_z / γ;  x += α p;  r −= α (q + λ p);  ρ' = ‖r‖²           pcg_update_kernel
+ *         z = M⁻¹ r                                                       nufft_precond_apply
+ *         ρ_z' = Re<r, z>                                                 cg_dot_kernel on (r, z)
+ *         done from ρ';  p = z + (ρ_z'/ρ_z) p;  ρ_z = ρ_z';  ρ = ρ'       pcg_direction_kernel
+ *
+ * with the stopping test, residual and history of the plain solver (‖r‖ / ‖b‖), its freeze rule, fixed-order sums and capture rules;
+ * NUFFT_CG_BREAKDOWN also when ρ_z is not positive and finite while the component is not done.  One more array per component (z),
+ * allocated by this call (not on a capturing stream).  pc = NULL returns to the plain solver, which enqueues exactly what it did
+ * before this entry point existed.  The preconditioner must have been created for the solver's operator (else
+ * NUFFT_ERR_INVALID_ARG) and must outlive the solver or be cleared first. */
+int nufft_cg_set_preconditioner(nufft_cg* cg, nufft_precond* pc);
+
 /* ---- Sample-density compensation weights ------------------------ */
 /* The weights w_j of nufft_exec_type1_cb / nufft_toeplitz_set_points for a point set, by the fixed-point iteration of Pipe & Menon
  * (MRM 41, 1999; NFFT.jl: sdc).  C is interpolation after spreading on the fine grid of a REAL-data plan with the parent plan's window:

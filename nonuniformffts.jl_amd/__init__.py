@@ -19,6 +19,7 @@ from .nfft_interface import NFFTPlan, plan_nfft  # noqa: F401
 from .type3 import PlanNUFFT3, exec_type3, exec_type3_grad, set_points3  # noqa: F401
 from .toeplitz import ToeplitzOperator, coil_combine, coil_expand  # noqa: F401
 from .cg import ToeplitzCG  # noqa: F401
+from .precond import ToeplitzPreconditioner  # noqa: F401
 from .dcf import DensityCompensation, density_weights  # noqa: F401
 from . import autograd  # noqa: F401
 
@@ -29,6 +30,6 @@ __all__ = [
     "NFFTPlan", "plan_nfft",
     "PlanNUFFT3", "set_points3", "exec_type3", "exec_type3_grad",
     "exec_type2_grad", "interpolate_grad", "autograd",
-    "ToeplitzOperator", "ToeplitzCG", "coil_expand", "coil_combine",
+    "ToeplitzOperator", "ToeplitzCG", "ToeplitzPreconditioner", "coil_expand", "coil_combine",
     "DensityCompensation", "density_weights",
 ]

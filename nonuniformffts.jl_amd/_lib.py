@@ -126,6 +126,25 @@ CG_MAX_ITER, CG_CONVERGED, CG_BREAKDOWN = 0, 1, 2
 CG_STATUS_NAMES = {CG_MAX_ITER: "max_iter", CG_CONVERGED: "converged", CG_BREAKDOWN: "breakdown"}
 
 
+class NufftPrecondParams(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("reserved", C.c_int32), ("lambda_", C.c_double), ("floor", C.c_double),
+    ]
+
+
+class NufftPrecondInfo(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("ndim", C.c_int32), ("dtype", C.c_int32), ("ntransforms", C.c_int32), ("device", C.c_int32),
+        ("path", C.c_int32), ("scaling", C.c_int32), ("reserved", C.c_int32),
+        ("N", C.c_int64 * 3), ("lambda_", C.c_double), ("mu", C.c_double), ("floor", C.c_double),
+        ("max_e", C.c_double), ("min_e", C.c_double), ("multiplier_bytes", C.c_int64), ("workspace_bytes", C.c_int64),
+    ]
+
+
+PRECOND_PATH_DENSE, PRECOND_PATH_FUSED = 0, 1
+PRECOND_SCALING_NONE, PRECOND_SCALING_MAPS, PRECOND_SCALING_CALLER = 0, 1, 2
+
+
 class NufftDcfParams(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int32), ("max_iter", C.c_int32), ("check_every", C.c_int32), ("normalize", C.c_int32),
@@ -227,6 +246,17 @@ SYMBOLS = {
     "nufft_cg_history": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int64, _P]),
     "nufft_sizeof_cg_params": (C.c_int64, []),
     "nufft_sizeof_cg_info": (C.c_int64, []),
+    "nufft_precond_create": (C.c_int, [C.POINTER(_P), _P, C.POINTER(NufftPrecondParams)]),
+    "nufft_precond_destroy": (C.c_int, [_P]),
+    "nufft_precond_update": (C.c_int, [_P, _P]),
+    "nufft_precond_set_scaling": (C.c_int, [_P, _P]),
+    "nufft_precond_apply": (C.c_int, [_P, _PP, _PP, _P]),
+    "nufft_precond_get_info": (C.c_int, [_P, C.POINTER(NufftPrecondInfo)]),
+    "nufft_precond_multiplier_ptr": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int64)]),
+    "nufft_precond_scaling_ptr": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int64)]),
+    "nufft_sizeof_precond_params": (C.c_int64, []),
+    "nufft_sizeof_precond_info": (C.c_int64, []),
+    "nufft_cg_set_preconditioner": (C.c_int, [_P, _P]),
     "nufft_dcf_create": (C.c_int, [C.POINTER(_P), _P, C.POINTER(NufftDcfParams)]),
     "nufft_dcf_destroy": (C.c_int, [_P]),
     "nufft_dcf_set_points": (C.c_int, [_P, C.c_int64, _PP, _P]),
@@ -265,7 +295,8 @@ def _load():
     for name, mirror in (("nufft_sizeof_params", NufftParams), ("nufft_sizeof_info", NufftInfo),
                          ("nufft_sizeof_type3_params", NufftType3Params), ("nufft_sizeof_info3", NufftInfo3),
                          ("nufft_sizeof_toeplitz_info", NufftToeplitzInfo), ("nufft_sizeof_cg_params", NufftCgParams),
-                         ("nufft_sizeof_cg_info", NufftCgInfo), ("nufft_sizeof_dcf_params", NufftDcfParams),
+                         ("nufft_sizeof_cg_info", NufftCgInfo), ("nufft_sizeof_precond_params", NufftPrecondParams),
+                         ("nufft_sizeof_precond_info", NufftPrecondInfo), ("nufft_sizeof_dcf_params", NufftDcfParams),
                          ("nufft_sizeof_dcf_info", NufftDcfInfo)):
         if getattr(lib, name)() != C.sizeof(mirror):
             raise ImportError(f"{LIB_PATH}: {name}() = {getattr(lib, name)()} but the ctypes mirror has {C.sizeof(mirror)} bytes "

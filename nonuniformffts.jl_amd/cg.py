@@ -7,6 +7,9 @@ only: argument checks, pointers, and reading the outcome back.
     sol = ToeplitzCG(op, maxiter=50, rtol=1e-6, lam=0.0)
     x = sol.solve(b)
     sol.iterations, sol.status, sol.residual, sol.history()
+
+``precond=ToeplitzPreconditioner(op, lam=...)`` makes it preconditioned CG: the same stopping rule on ``‖r‖ / ‖b‖``, one
+apply of ``M⁻¹`` more per iteration and one more array per component.
 """
 from __future__ import annotations
 
@@ -28,9 +31,12 @@ class ToeplitzCG:
     early.  Both return the same bits.  The solver keeps ``op`` alive; ``op.set_points`` / ``set_spectrum`` between two solves is
     allowed and changes ``G``.  On a coupled operator (``op.set_points(..., basis=)`` / ``op.set_spectra``) the components are ONE system:
     one α, one β and one stopping test from sums over all components; ``iterations``, ``status``, ``residual`` and ``history()`` then
-    report the same values for every component."""
+    report the same values for every component.
 
-    def __init__(self, op: ToeplitzOperator, maxiter: int = 50, rtol: float = 1e-6, lam: float = 0.0, check_every: int = 0):
+    ``precond``: a :class:`ToeplitzPreconditioner` built for ``op`` (kept alive by the solver) or None; ``set_preconditioner`` changes it
+    between two solves.  Without one the solver enqueues exactly what it always did."""
+
+    def __init__(self, op: ToeplitzOperator, maxiter: int = 50, rtol: float = 1e-6, lam: float = 0.0, check_every: int = 0, precond=None):
         if not isinstance(op, ToeplitzOperator):
             raise ValueError("ToeplitzCG takes a ToeplitzOperator")
         for name, v in (("maxiter", maxiter), ("check_every", check_every)):
@@ -44,6 +50,28 @@ class ToeplitzCG:
         _check(lib.nufft_cg_create(C.byref(self._handle), op._handle, C.byref(prm)))
         self.op = op
         self.maxiter, self.rtol, self.lam, self.check_every = maxiter, float(rtol), float(lam), check_every
+        self.precond = None
+        if precond is not None:
+            try:
+                self.set_preconditioner(precond)
+            except Exception:
+                self.close()
+                raise
+
+    def set_preconditioner(self, precond) -> "ToeplitzCG":
+        """``precond``: a :class:`ToeplitzPreconditioner` created for this solver's operator, or None for plain CG."""
+        from .precond import ToeplitzPreconditioner
+        self._require_open(check_precond=False)
+        if precond is None:
+            _check(lib.nufft_cg_set_preconditioner(self._handle, None))
+            self.precond = None
+            return self
+        if not isinstance(precond, ToeplitzPreconditioner):
+            raise ValueError("precond must be a ToeplitzPreconditioner or None")
+        precond._require_open()
+        _check(lib.nufft_cg_set_preconditioner(self._handle, precond._handle))
+        self.precond = precond
+        return self
 
     def close(self):
         h = getattr(self, "_handle", None)
@@ -57,12 +85,14 @@ class ToeplitzCG:
         except Exception:
             pass
 
-    def _require_open(self):
+    def _require_open(self, check_precond=True):
         """The library keeps a pointer to the operator: refuse to follow it once either object has been closed."""
         if not self._handle.value:
             raise ValueError("this ToeplitzCG has been closed")
         if not self.op._handle.value:
             raise ValueError("the ToeplitzOperator of this solver has been closed: the operator must outlive the solver")
+        if check_precond and self.precond is not None and not self.precond._handle.value:
+            raise ValueError("the ToeplitzPreconditioner of this solver has been closed: clear it with set_preconditioner(None) first")
 
     def info(self) -> _lib.NufftCgInfo:
         self._require_open()
@@ -130,4 +160,5 @@ class ToeplitzCG:
     def __repr__(self):
         i = self.info()
         return (f"ToeplitzCG on a {self.op.ndim}-dimensional {self.op.Z} operator, maxiter = {self.maxiter}, rtol = {self.rtol:g}, "
-                f"lam = {self.lam:g}, check_every = {self.check_every}, {i.workspace_bytes / 1e6:.1f} MB")
+                f"lam = {self.lam:g}, check_every = {self.check_every}, {'preconditioned, ' if self.precond is not None else ''}"
+                f"{i.workspace_bytes / 1e6:.1f} MB")

@@ -2,6 +2,9 @@
 //
 // The host side only enqueues: per iteration one nufft_toeplitz_apply (unchanged) and the three kernels of cg_kernels.hip.  Every
 // scalar lives on the device; with check_every > 0 the host looks at the done flags now and then, and at nothing else.
+//
+// With a preconditioner set (nufft_cg_set_preconditioner) an iteration is the apply, the dot kernel, pcg_update_kernel,
+// the preconditioner's apply, the dot kernel on (r, z) and pcg_direction_kernel; without one, exactly the launches above.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,6 +16,7 @@
 
 #include "cg.h"
 #include "host_common.h"
+#include "precond.h"
 
 using namespace nufft;
 
@@ -26,16 +30,19 @@ struct nufft_cg {
     void* d_r = nullptr;
     void* d_p = nullptr;
     void* d_q = nullptr;
+    void* d_z = nullptr;              // with a preconditioner: z = M⁻¹ r
+    nufft_precond* pc = nullptr;      // borrowed
     void* d_part = nullptr;           // double[C][G][2] + double[C][G]
-    ScalarMirror scal;                // double rho[2][C], beta0[C], res[C]; int32 flag[2][C], brk[C], iters[C], status[C]
+    ScalarMirror scal;                // double rho[2][C], beta0[C], res[C], rhoz[2][C]; int32 flag[2][C], brk[C], iters[C], status[C]
     void* d_hist = nullptr;           // double[max_iter + 1][C]
     int64_t array_bytes = 0, own_bytes = 0;
     std::vector<void*> ptab, qtab;    // the pointer tables nufft_toeplitz_apply takes
+    std::vector<void*> rtab, ztab;    // ... and nufft_precond_apply
 };
 
 namespace {
 
-size_t scal_bytes(const nufft_cg* s) { return (size_t)s->C * (4 * sizeof(double) + 5 * sizeof(int32_t)); }
+size_t scal_bytes(const nufft_cg* s) { return (size_t)s->C * (6 * sizeof(double) + 5 * sizeof(int32_t)); }
 size_t part_bytes(const nufft_cg* s) { return (size_t)s->C * s->G * 3 * sizeof(double); }
 size_t hist_bytes(const nufft_cg* s) { return (size_t)(s->max_iter + 1) * s->C * sizeof(double); }
 
@@ -45,7 +52,7 @@ void release(nufft_cg* s) {
     if (!s) return;
     if (s->device >= 0) {
         DeviceGuard g(s->device);
-        for (void* p : {s->d_r, s->d_p, s->d_q, s->d_part, s->d_hist})
+        for (void* p : {s->d_r, s->d_p, s->d_q, s->d_z, s->d_part, s->d_hist})
             if (p) (void)hipFree(p);
         s->scal.release();
     }
@@ -59,7 +66,8 @@ CgScalars scalars_at(const nufft_cg* s, void* base) {
     k.rho = d;
     k.beta0 = d + 2 * C;
     k.res = d + 3 * C;
-    int32_t* i = reinterpret_cast<int32_t*>(d + 4 * C);
+    k.rhoz = d + 4 * C;
+    int32_t* i = reinterpret_cast<int32_t*>(d + 6 * C);
     k.flag = i;
     k.brk = i + 2 * C;
     k.iters = i + 3 * C;
@@ -153,6 +161,7 @@ int nufft_cg_create(nufft_cg** out, nufft_toeplitz* tz, const nufft_cg_params* p
     for (int c = 0; c < s->C; ++c) {
         s->ptab.push_back(static_cast<char*>(s->d_p) + (size_t)c * comp);
         s->qtab.push_back(static_cast<char*>(s->d_q) + (size_t)c * comp);
+        s->rtab.push_back(static_cast<char*>(s->d_r) + (size_t)c * comp);
     }
     *out = s;
     return NUFFT_OK;
@@ -160,6 +169,25 @@ int nufft_cg_create(nufft_cg** out, nufft_toeplitz* tz, const nufft_cg_params* p
 
 int nufft_cg_destroy(nufft_cg* cg) {
     release(cg);
+    return NUFFT_OK;
+}
+
+int nufft_cg_set_preconditioner(nufft_cg* s, nufft_precond* pc) {
+    if (!s) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    if (!pc) {
+        s->pc = nullptr;
+        return NUFFT_OK;
+    }
+    if (nufft::precond_operator(pc) != s->tz)
+        return fail(NUFFT_ERR_INVALID_ARG, "the preconditioner was created for another operator (element type, shape and ntransforms follow the operator)");
+    if (!s->d_z) {
+        DeviceGuard guard(s->device);
+        const size_t comp = (size_t)s->stride * real_bytes(s->dtype);
+        if (int rc = alloc(s, &s->d_z, (size_t)s->C * comp)) return rc;
+        for (int c = 0; c < s->C; ++c) s->ztab.push_back(static_cast<char*>(s->d_z) + (size_t)c * comp);
+        s->array_bytes += (int64_t)s->C * (int64_t)comp;
+    }
+    s->pc = pc;
     return NUFFT_OK;
 }
 
@@ -221,6 +249,10 @@ int nufft_cg_solve(nufft_cg* s, void* const* x, const void* const* b, int use_x0
     a.it = 0;
     a.joint = nufft_toeplitz_num_coupled(s->tz) > 0 ? 1 : 0;      // coupled components are one system: one α, one β, one done flag
     a.s = scalars_at(s, s->scal.dev);
+    if (s->pc) {
+        if (a.joint) return fail(NUFFT_ERR_UNSUPPORTED, "the operator couples its components: the preconditioner does not apply (clear it with nufft_cg_set_preconditioner(cg, NULL))");
+        a.z = s->d_z;
+    }
 
     s->enqueued = 0;
     const bool warm = use_x0 != 0;
@@ -228,12 +260,29 @@ int nufft_cg_solve(nufft_cg* s, void* const* x, const void* const* b, int use_x0
     if ((rc = for_batches(s, a, x, b, [&](const CgLaunch& l) { return launch_cg_residual(l, warm, stream); }))) return rc;
     if ((rc = for_batches(s, a, x, b, [&](const CgLaunch& l) { return launch_cg_start(l, stream); }))) return rc;
     const CgScalars host = scalars_at(s, s->scal.host);
+    // z = M⁻¹ r, the partials of Re<r, z> (the dot kernel with p = r, q = z) and the direction kernel: the tail of a preconditioned
+    // iteration, and with it = 0 the start of the solve
+    auto precondition = [&]() -> int {
+        int prc = nufft_precond_apply(s->pc, s->ztab.data(), s->rtab.data(), stream);
+        if (prc) return prc;
+        CgLaunch d = a;
+        d.p = s->d_r;
+        d.q = s->d_z;
+        if ((prc = for_batches(s, d, x, nullptr, [&](const CgLaunch& l) { return launch_cg_dot(l, stream); }))) return prc;
+        return for_batches(s, a, x, nullptr, [&](const CgLaunch& l) { return launch_pcg_direction(l, stream); });
+    };
+    if (s->pc && (rc = precondition())) return rc;
     for (int it = 1; it <= s->max_iter; ++it) {
         a.it = it;
         if ((rc = nufft_toeplitz_apply(s->tz, s->qtab.data(), s->ptab.data(), stream))) return rc;
         if ((rc = for_batches(s, a, x, nullptr, [&](const CgLaunch& l) { return launch_cg_dot(l, stream); }))) return rc;
-        if ((rc = for_batches(s, a, x, nullptr, [&](const CgLaunch& l) { return launch_cg_update(l, stream); }))) return rc;
-        if ((rc = for_batches(s, a, x, nullptr, [&](const CgLaunch& l) { return launch_cg_direction(l, stream); }))) return rc;
+        if (s->pc) {
+            if ((rc = for_batches(s, a, x, nullptr, [&](const CgLaunch& l) { return launch_pcg_update(l, stream); }))) return rc;
+            if ((rc = precondition())) return rc;
+        } else {
+            if ((rc = for_batches(s, a, x, nullptr, [&](const CgLaunch& l) { return launch_cg_update(l, stream); }))) return rc;
+            if ((rc = for_batches(s, a, x, nullptr, [&](const CgLaunch& l) { return launch_cg_direction(l, stream); }))) return rc;
+        }
         s->enqueued = it;
         if (s->check_every > 0 && it % s->check_every == 0 && it < s->max_iter) {
             if ((rc = s->scal.fetch(stream))) return rc;

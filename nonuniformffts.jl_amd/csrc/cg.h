@@ -15,6 +15,7 @@ struct CgScalars {
     double* rho;        // [2][C]   ‖r‖²
     double* beta0;      // [C]      ‖b‖²
     double* res;        // [C]      sqrt(rho / beta0) after the last iteration that changed the component
+    double* rhoz;       // [2][C]   Re<r, z> (preconditioned solves only), double-buffered like rho
     double* history;    // [max_iter + 1][C]
     int32_t* flag;      // [2][C]   done (frozen)
     int32_t* brk;       // [C]      written by the update kernel of this iteration: γ was not positive and finite
@@ -33,6 +34,7 @@ struct CgLaunch {
     void* r;                 // own arrays, component c at + c * stride
     void* p;
     void* q;
+    void* z;                 // (preconditioned solves only) z = M⁻¹ r
     void* x[kCgBatch];       // the caller's arrays of components c0 ... c0 + nc − 1
     const void* b[kCgBatch]; // (initial residual only)
     double lambda, rtol;
@@ -52,6 +54,12 @@ hipError_t launch_cg_start(const CgLaunch& a, hipStream_t stream);
 hipError_t launch_cg_dot(const CgLaunch& a, hipStream_t stream);
 hipError_t launch_cg_update(const CgLaunch& a, hipStream_t stream);
 hipError_t launch_cg_direction(const CgLaunch& a, hipStream_t stream);
+
+// The preconditioned iteration: the dot kernel, α = ρ_z / γ in the update, the preconditioner's apply, the dot
+// kernel again on (r, z) (launch_cg_dot with p = r, q = z: Re<r, z> lands where Re<p, q> did), and the direction kernel
+// p = z + (ρ_z'/ρ_z) p, which also takes the stopping decision from the update's ‖r‖².  it = 0: the start (p = z, ρ_z = Re<r, z>).
+hipError_t launch_pcg_update(const CgLaunch& a, hipStream_t stream);
+hipError_t launch_pcg_direction(const CgLaunch& a, hipStream_t stream);
 
 // workgroups per component for n complex elements of `dtype` on a device with num_cus compute units
 int cg_workgroups(int dtype, int64_t n, int num_cus);

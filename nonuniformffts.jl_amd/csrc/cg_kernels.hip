@@ -254,6 +254,116 @@ __global__ __launch_bounds__(kThreads) void cg_direction_kernel(CgLaunch a) {
     }
 }
 
+// The preconditioned iteration.  Kernel 2': as cg_update_kernel with α = ρ_z / γ, ρ_z = Re<r, z> of the iteration before.
+template <typename T>
+__global__ __launch_bounds__(kThreads) void pcg_update_kernel(CgLaunch a) {
+    __shared__ double lds[kWaves];
+    constexpr int W = Pack<T>::W;
+    const int c = a.c0 + blockIdx.y;
+    const int slot = (a.it & 1) * a.C + c;
+    if (a.s.flag[slot]) return;
+    const double* row = a.s.part1 + (int64_t)c * a.G * 2;
+    const double pq = row_reduce<Sum>(row, a.G, 2, lds);
+    const double pp = row_reduce<Sum>(row + 1, a.G, 2, lds);
+    const double gamma = pq + a.lambda * pp;
+    const bool bad = !(gamma > 0.0) || !isfinite(gamma);      // the same bits in every workgroup: they all leave, or none does
+    if (blockIdx.x == 0 && threadIdx.x == 0) a.s.brk[c] = bad ? 1 : 0;
+    if (bad) return;
+    const T al = (T)(a.s.rhoz[slot] / gamma), lam = (T)a.lambda;
+    T* x = static_cast<T*>(a.x[blockIdx.y]);
+    T* r = static_cast<T*>(a.r) + c * a.stride;
+    const T* p = static_cast<const T*>(a.p) + c * a.stride;
+    const T* q = static_cast<const T*>(a.q) + c * a.stride;
+    const int64_t nreal = 2 * a.n;
+    double srr = 0.0;
+    auto one = [&](T& xv, T& rv, T pv, T qv) {
+        xv += al * pv;
+        rv -= al * (qv + lam * pv);
+        srr += (double)rv * (double)rv;
+    };
+    NUFFT_FOR_EACH_PACK(T, nreal, i) {
+        const int64_t j = i + step__;
+        const bool two = j < npacks__;
+        Pack<T> x0 = load(x, i), r0 = load(r, i), p0 = load(p, i), q0 = load(q, i), x1{}, r1{}, p1{}, q1{};
+        if (two) { x1 = load(x, j); r1 = load(r, j); p1 = load(p, j); q1 = load(q, j); }
+#pragma unroll
+        for (int w = 0; w < W; ++w) one(x0.v[w], r0.v[w], p0.v[w], q0.v[w]);
+        store(x, i, x0);
+        store(r, i, r0);
+        if (two) {
+#pragma unroll
+            for (int w = 0; w < W; ++w) one(x1.v[w], r1.v[w], p1.v[w], q1.v[w]);
+            store(x, j, x1);
+            store(r, j, r1);
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (int64_t e = npacks__ * W; e < nreal; ++e) one(x[e], r[e], p[e], q[e]);
+    srr = block_reduce<Sum>(srr, lds);
+    if (threadIdx.x == 0) a.s.part2[(int64_t)c * a.G + blockIdx.x] = srr;
+}
+
+// Kernel 3': ρ' = ‖r‖² from the update's partials (the stopping test and the history, as in cg_direction_kernel), ρ_z' = Re<r, z> from the
+// dot kernel's partials on (r, z);  p = z + (ρ_z'/ρ_z) p;  the first workgroup writes the scalars of the next iteration.  it = 0 is the
+// start of a solve: p = z, ρ and the done flag are those cg_start_kernel left in both slots.  A ρ_z' that is not positive and finite while
+// the component is not done is a breakdown (M⁻¹ is positive definite: it means r or m is not finite): p stays, the component freezes.
+template <typename T>
+__global__ __launch_bounds__(kThreads) void pcg_direction_kernel(CgLaunch a) {
+    __shared__ double lds[kWaves];
+    constexpr int W = Pack<T>::W;
+    const int c = a.c0 + blockIdx.y;
+    const int slot = (a.it & 1) * a.C + c, next = ((a.it + 1) & 1) * a.C + c;
+    const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+    const bool start = a.it == 0;
+    const bool frozen = a.s.flag[slot] != 0, bad = !frozen && !start && a.s.brk[c] != 0;
+    if (frozen || bad) {
+        if (first) {
+            a.s.flag[next] = 1;
+            a.s.rho[next] = a.s.rho[slot];
+            a.s.rhoz[next] = start ? 0.0 : a.s.rhoz[slot];
+            if (bad) a.s.status[c] = NUFFT_CG_BREAKDOWN;
+        }
+        return;
+    }
+    const double rr = start ? a.s.rho[slot] : row_reduce<Sum>(a.s.part2 + (int64_t)c * a.G, a.G, 1, lds);
+    const double rz = row_reduce<Sum>(a.s.part1 + (int64_t)c * a.G * 2, a.G, 2, lds);
+    const double bb = a.s.beta0[c];
+    const int done = rr <= a.rtol * a.rtol * bb ? 1 : 0;      // (start: not done, or the component would be frozen)
+    const bool broke = !done && (!(rz > 0.0) || !isfinite(rz));
+    if (first) {
+        a.s.rho[next] = rr;
+        a.s.rhoz[next] = rz;
+        a.s.flag[next] = done || broke ? 1 : 0;
+        if (!start) {
+            a.s.res[c] = relative(rr, bb);
+            a.s.history[(int64_t)a.it * a.C + c] = relative(rr, bb);
+            a.s.iters[c] = a.it;
+        }
+        a.s.status[c] = broke ? NUFFT_CG_BREAKDOWN : (done ? NUFFT_CG_CONVERGED : NUFFT_CG_MAX_ITER);
+    }
+    if (broke) return;
+    const T bt = start ? T(0) : (T)(rz / a.s.rhoz[slot]);      // ρ_z > 0: checked when it was written
+    const T* z = static_cast<const T*>(a.z) + c * a.stride;
+    T* p = static_cast<T*>(a.p) + c * a.stride;
+    const int64_t nreal = 2 * a.n;
+    NUFFT_FOR_EACH_PACK(T, nreal, i) {
+        const int64_t j = i + step__;
+        const bool two = j < npacks__;
+        Pack<T> z0 = load(z, i), p0 = load(p, i), z1{}, p1{};
+        if (two) { z1 = load(z, j); p1 = load(p, j); }
+#pragma unroll
+        for (int w = 0; w < W; ++w) p0.v[w] = start ? z0.v[w] : z0.v[w] + bt * p0.v[w];
+        store(p, i, p0);
+        if (two) {
+#pragma unroll
+            for (int w = 0; w < W; ++w) p1.v[w] = start ? z1.v[w] : z1.v[w] + bt * p1.v[w];
+            store(p, j, p1);
+        }
+    }
+    if (first)
+        for (int64_t e = npacks__ * W; e < nreal; ++e) p[e] = start ? z[e] : z[e] + bt * p[e];
+}
+
 }  // namespace
 
 int cg_workgroups(int dtype, int64_t n, int num_cus) { return stream_workgroups((2 * n) / (dtype == NUFFT_F32 ? 4 : 2), num_cus); }
@@ -279,6 +389,14 @@ hipError_t launch_cg_update(const CgLaunch& a, hipStream_t stream) {
 
 hipError_t launch_cg_direction(const CgLaunch& a, hipStream_t stream) {
     return launch_by_dtype(a.dtype, dim3(a.G, a.nc), dim3(kThreads), stream, cg_direction_kernel<float>, cg_direction_kernel<double>, a);
+}
+
+hipError_t launch_pcg_update(const CgLaunch& a, hipStream_t stream) {
+    return launch_by_dtype(a.dtype, dim3(a.G, a.nc), dim3(kThreads), stream, pcg_update_kernel<float>, pcg_update_kernel<double>, a);
+}
+
+hipError_t launch_pcg_direction(const CgLaunch& a, hipStream_t stream) {
+    return launch_by_dtype(a.dtype, dim3(a.G, a.nc), dim3(kThreads), stream, pcg_direction_kernel<float>, pcg_direction_kernel<double>, a);
 }
 
 }  // namespace nufft

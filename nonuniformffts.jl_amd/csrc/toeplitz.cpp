@@ -457,6 +457,8 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 
 }  // namespace
 
+const std::vector<const void*>& nufft::toeplitz_coil_maps(const nufft_toeplitz* t) { return t->coil_maps; }
+
 extern "C" {
 
 int64_t nufft_sizeof_toeplitz_info(void) { return (int64_t)sizeof(nufft_toeplitz_info); }

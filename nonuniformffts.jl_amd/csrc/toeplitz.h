@@ -4,8 +4,14 @@
 
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <vector>
+
+#include "nufft_mi355x.h"
 
 namespace nufft {
+
+// The coil maps set on an operator (borrowed device pointers, in coil order; empty: none) — for the preconditioner (precond.cpp).
+const std::vector<const void*>& toeplitz_coil_maps(const ::nufft_toeplitz* t);
 
 // The embedding grid: n2[d] = 2 N_d cells (dimension 1 fastest), the plan's nk[d] = N_d modes sit at map[d][k'] (= k mod 2 N_d);
 // inv[d][j] is the kept index at cell j or -1.  Unused dimensions have n2 = nk = 1 and one-entry maps.

@@ -1,0 +1,162 @@
+"""T. Chan's optimal circulant preconditioner of a :class:`ToeplitzOperator`, above the C ABI's ``nufft_precond_*`` entry points.
+
+``G`` is multi-level Toeplitz, so the circulant ``C`` closest to it in the Frobenius norm has its eigenvalues ``e`` in the DFT basis of size
+N (not 2N), and they follow from the operator's own multiplier — the points are not needed again.  The object applies
+
+    M⁻¹ r = d ⊙ F⁻¹( m ⊙ F( d ⊙ r ) ),      m = 1 / max(e + μ, floor · max(e + μ))
+
+(DESIGN.md §21).  Plumbing only: every array operation runs in the library.
+
+    pc = ToeplitzPreconditioner(op, lam=lam)
+    x = op.solve(b, lam=lam, rtol=1e-6, maxiter=200, precond=pc)
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import torch
+
+from . import _lib
+from ._lib import lib
+from .plan import _check, _ptr_table, DimensionMismatch
+from .toeplitz import ToeplitzOperator
+
+_PATHS = {_lib.PRECOND_PATH_DENSE: "dense", _lib.PRECOND_PATH_FUSED: "fused"}
+
+
+class ToeplitzPreconditioner:
+    """``ToeplitzPreconditioner(op, lam=0.0, floor=1e-6)``: built from the multiplier ``op`` holds now (``op.set_points`` /
+    ``set_spectrum`` first); ``update()`` rebuilds it after the operator's spectrum or coil maps changed.  ``lam`` is the λ of the system
+    ``(G + λ I)`` it preconditions.  With coil maps set on ``op`` the scaling ``d = (Σ_c |S_c|²)^(-1/2)`` is computed and owned here and
+    ``μ = λ / mean(Σ_c |S_c|²)``; ``set_scaling(d)`` passes another ``d``.  Coupled operators (``basis=``) are refused.
+
+    ``path`` is ``"fused"`` (2-D and 3-D shapes whose every ``N_d`` is one of the library's line lengths 64 … 1024) or ``"dense"``
+    (rocFFT); it does not depend on the operator's own path — a 48 × 40 operator is fused while its preconditioner is dense.  Building
+    allocates temporaries and synchronises (not inside ``torch.cuda.graph``); ``apply`` allocates nothing and is capturable.  The object
+    keeps ``op`` alive."""
+
+    def __init__(self, op: ToeplitzOperator, lam: float = 0.0, floor: float = 1e-6):
+        if not isinstance(op, ToeplitzOperator):
+            raise ValueError("ToeplitzPreconditioner takes a ToeplitzOperator")
+        op._require_open()
+        prm = _lib.NufftPrecondParams()
+        prm.struct_size = C.sizeof(_lib.NufftPrecondParams)
+        prm.lambda_, prm.floor = float(lam), float(floor)
+        self._handle = C.c_void_p()
+        self._d = None
+        if op.device is not None:
+            torch.cuda.current_stream(op.device).synchronize()      # the build runs on the default stream
+        _check(lib.nufft_precond_create(C.byref(self._handle), op._handle, C.byref(prm)))
+        self.op = op
+        self.lam, self.floor = float(lam), float(floor)
+
+    def close(self):
+        h = getattr(self, "_handle", None)
+        if h is not None and h.value:
+            lib.nufft_precond_destroy(h)
+            self._handle = C.c_void_p()
+        self._d = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _require_open(self):
+        if not self._handle.value:
+            raise ValueError("this ToeplitzPreconditioner has been closed")
+        if not self.op._handle.value:
+            raise ValueError("the ToeplitzOperator of this preconditioner has been closed: the operator must outlive it")
+
+    def info(self) -> _lib.NufftPrecondInfo:
+        self._require_open()
+        out = _lib.NufftPrecondInfo()
+        out.struct_size = C.sizeof(_lib.NufftPrecondInfo)
+        _check(lib.nufft_precond_get_info(self._handle, C.byref(out)))
+        return out
+
+    @property
+    def path(self) -> str:
+        return _PATHS[self.info().path]
+
+    def update(self) -> "ToeplitzPreconditioner":
+        """Rebuilds ``m`` (and the scaling from coil maps) from what the operator holds now."""
+        self._require_open()
+        _check(lib.nufft_precond_update(self._handle, self.op._stream()))
+        if self.info().scaling != _lib.PRECOND_SCALING_CALLER:
+            self._d = None
+        return self
+
+    def set_scaling(self, d: Optional[torch.Tensor]) -> "ToeplitzPreconditioner":
+        """``d``: a real positive tensor of ``plan.shape`` with the operator's accuracy (borrowed: this object keeps a reference and its
+        values must not change while it is set); ``None``: no scaling."""
+        self._require_open()
+        op = self.op
+        if d is None:
+            _check(lib.nufft_precond_set_scaling(self._handle, None))
+            self._d = None
+            return self
+        if not isinstance(d, torch.Tensor) or d.device != op.device:
+            raise ValueError(f"the scaling must be a torch tensor on {op.device}")
+        if d.dtype != op.T:
+            raise ValueError(f"the scaling must be real with the operator's accuracy ({op.T}; got {d.dtype})")
+        if tuple(d.shape) != tuple(op.shape):
+            raise DimensionMismatch(f"wrong dimensions of the scaling (expected tensor shape {tuple(op.shape)}, got {tuple(d.shape)})")
+        if not d.is_contiguous():
+            raise ValueError("the scaling must be contiguous")
+        if d.data_ptr() % 16:
+            d = d.clone()
+        _check(lib.nufft_precond_set_scaling(self._handle, C.c_void_p(d.data_ptr())))
+        self._d = d
+        return self
+
+    def apply(self, r, out=None):
+        """``out = M⁻¹ r`` for every component; ``r``: a tensor of ``plan.shape`` or a tuple of ntransforms such tensors; ``out`` may
+        be ``r``.  Returns ``out``."""
+        self._require_open()
+        op = self.op
+        single = isinstance(r, torch.Tensor)
+        r_t = (r,) if single else tuple(r)
+        op._check_uniform(r_t, "input")
+        if out is None:
+            out_t = tuple(torch.empty_like(v) for v in r_t)
+            out = out_t[0] if single else out_t
+        else:
+            out_t = (out,) if isinstance(out, torch.Tensor) else tuple(out)
+            op._check_uniform(out_t, "output")
+        _check(lib.nufft_precond_apply(self._handle, _ptr_table(out_t), _ptr_table(r_t), op._stream()))
+        return out
+
+    __call__ = apply
+
+    def _view(self, ptr, nbytes):
+        shape = tuple(self.op.shape)
+        typestr = "<f4" if self.op.T == torch.float32 else "<f8"
+
+        class _View:       # the array-interface protocol: torch wraps the pointer without copying
+            __cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (int(ptr.value), False), "version": 2, "strides": None}
+
+        t = torch.as_tensor(_View(), device=self.op.device)
+        assert t.numel() * t.element_size() == nbytes.value
+        return t
+
+    def multiplier(self) -> torch.Tensor:
+        """``m`` (shape ``plan.shape``, real, ``1 / Π N_d`` folded in): a view of the device array, rewritten by ``update()``."""
+        self._require_open()
+        ptr, nbytes = C.c_void_p(), C.c_int64()
+        _check(lib.nufft_precond_multiplier_ptr(self._handle, C.byref(ptr), C.byref(nbytes)))
+        return self._view(ptr, nbytes)
+
+    def scaling(self) -> Optional[torch.Tensor]:
+        """The scaling ``d`` in force (a view; ``None``: no scaling)."""
+        self._require_open()
+        ptr, nbytes = C.c_void_p(), C.c_int64()
+        _check(lib.nufft_precond_scaling_ptr(self._handle, C.byref(ptr), C.byref(nbytes)))
+        return self._view(ptr, nbytes) if ptr.value else None
+
+    def __repr__(self):
+        i = self.info()
+        return (f"ToeplitzPreconditioner of a {self.op.ndim}-dimensional {self.op.Z} operator, {self.path} path, lam = {self.lam:g}, "
+                f"mu = {i.mu:g}, floor = {self.floor:g}, e in [{i.min_e:g}, {i.max_e:g}], {i.workspace_bytes / 1e6:.1f} MB")
