@@ -693,7 +693,7 @@ typedef struct nufft_precond_info {
     int32_t reserved;
     int64_t N[3];
     double lambda, mu, floor;
-    double max_e, min_e;     /* of the eigenvalues e of the last build (before μ and the floor)                                    */
+    double max_e, min_e;     /* of the eigenvalues e of the last build (before μ and the floor); block object: of the E_aa(q)      */
     int64_t multiplier_bytes;/* m: one real per mode                                                                               */
     int64_t workspace_bytes; /* device bytes owned at rest                                                                         */
 } nufft_precond_info;
@@ -702,11 +702,13 @@ typedef struct nufft_precond_info {
  * buffers), synchronises and frees them before returning — like nufft_toeplitz_set_spectrum the build is not capturable
  * (nufft_precond_update, which takes a stream, refuses a capturing one).  The object keeps the POINTER `tz`: the operator must outlive it.  Refusals, in order: null arguments, lambda < 0, floor <= 0
  * or non-finite values NUFFT_ERR_INVALID_ARG; a host-only operator NUFFT_ERR_NO_DEVICE; no spectrum yet NUFFT_ERR_NO_POINTS; a coupled
- * build in force NUFFT_ERR_UNSUPPORTED (a block preconditioner is not built); an operator whose e + μ is nowhere positive
- * NUFFT_ERR_INVALID_ARG. */
+ * build in force NUFFT_ERR_UNSUPPORTED (this entry point builds the scalar object: nufft_precond_create_block builds the block one); an
+ * operator whose e + μ is nowhere positive NUFFT_ERR_INVALID_ARG. */
 int nufft_precond_create(nufft_precond** out, nufft_toeplitz* tz, const nufft_precond_params* params);
 int nufft_precond_destroy(nufft_precond* pc);
-/* Rebuilds m (and the scaling from coil maps) after the operator's spectrum or maps changed; same rules as the build in _create. */
+/* Rebuilds m (and the scaling from coil maps) after the operator's spectrum or maps changed; same rules as the build in _create.  A scalar
+ * object whose operator has become coupled, and a block object whose operator is no longer coupled with the same K, are refused
+ * (NUFFT_ERR_UNSUPPORTED). */
 int nufft_precond_update(nufft_precond* pc, void* stream);
 /* d: real(T)[N...] on the device, 16-byte aligned, positive, borrowed until replaced; NULL: no scaling. */
 int nufft_precond_set_scaling(nufft_precond* pc, const void* d);
@@ -714,11 +716,52 @@ int nufft_precond_set_scaling(nufft_precond* pc, const void* d);
  * synchronise, hipGraph-capture safe. */
 int nufft_precond_apply(nufft_precond* pc, void* const* out, const void* const* in, void* stream);
 int nufft_precond_get_info(const nufft_precond* pc, nufft_precond_info* out);
-/* Device pointers (inspection and tests): m, real(T)[N...] with 1 / Π N_d folded in; the scaling d in force (NULL: none). */
+/* Device pointers (inspection and tests): m, real(T)[N...] with 1 / Π N_d folded in (a block object has no m: NUFFT_ERR_UNSUPPORTED, see
+ * nufft_precond_block_ptr); the scaling d in force (NULL: none). */
 int nufft_precond_multiplier_ptr(const nufft_precond* pc, void** out_ptr, int64_t* out_bytes);
 int nufft_precond_scaling_ptr(const nufft_precond* pc, void** out_ptr, int64_t* out_bytes);
 int64_t nufft_sizeof_precond_params(void);
 int64_t nufft_sizeof_precond_info(void);
+
+/* Block-circulant preconditioner of a COUPLED operator (nufft_toeplitz_set_points_coupled / _set_spectra_coupled).
+ * G_Φ has the blocks Toeplitz(T_ab); the block circulant closest to it in the Frobenius norm replaces every block by its own optimal
+ * circulant, so E_ab = DFT_N(fold(T_ab)) per stored pair a <= b, with T_ab = forwardDFT_2N(K_ab) from the operator's own multiplier
+ * grids (no pass over the points): complex for a < b, E_aa real, E_ba = conj(E_ab) cell by cell.  For every mode q, E(q) is a K × K
+ * Hermitian positive semi-definite matrix.  The object applies, the K components being ONE vector,
+ *
+ *     (M⁻¹ r)_a = d ⊙ F⁻¹( Σ_b B_ab ⊙ F(d ⊙ r_b) ),      B(q) = (E(q) + shift · I)⁻¹ / n,
+ *     shift = max(μ, floor · s),      s = max_{q,a} E_aa(q) + μ,
+ *
+ * with μ and d exactly as in the scalar object.  The floor is a SHIFT here, not a clamp: a clamp needs the eigen-decomposition of every
+ * cell, whereas the shift moves every eigenvalue of E(q) + μ I up by at most floor · s (by nothing while μ >= floor · s) and keeps B(q)
+ * Hermitian positive definite.  B(q) is formed per cell by a Cholesky factorisation and a triangular inverse in FP64 whatever the
+ * element type, and stored in T.  A pivot that is not finite or not above shift / 4 — in exact arithmetic every pivot is >= shift, so
+ * only round-off in E does that — is floored at shift / 4; nufft_precond_floored_cells counts the cells where that happened in the
+ * last build.  B is stored like the operator's multipliers: K real grids (the diagonal) and K (K − 1) / 2 complex grids (the pairs
+ * a < b, row-major), N^D cells each, 1 / n folded in.
+ *
+ * nufft_precond_apply, _update, _set_scaling, _get_info, _scaling_ptr and _destroy take a block object.  Every out[a] depends on every
+ * in[b]; out[a] == in[a] is still allowed: all K inputs pass into K scratch arrays the object owns before any output is written.
+ * Capture-safe, allocates nothing, no atomics: two runs and a graph replay give the same bits.  The fused path needs, on top of the
+ * scalar object's conditions, the K lines of N_1 cells of one wave to fit LDS (K tiered 2, 4, 8, 16 as in the operator); where they
+ * do not, the object takes the dense path silently.  In nufft_precond_info of a block object multiplier_bytes is the total over all
+ * blocks, and max_e / min_e are the extreme DIAGONAL entries E_aa(q): they bound λ_max(E) from below and λ_min(E) from above.
+ *
+ * nufft_cg_solve accepts a block object on a coupled operator (one ρ_z, one γ, one done flag: the joint mode of the plain solver) and
+ * refuses a scalar object there, and a block object whose operator no longer couples the same K (NUFFT_ERR_UNSUPPORTED).
+ *
+ * Added without changing NUFFT_MI355X_VERSION, nufft_precond_params or nufft_precond_info: detect by symbol (dlsym
+ * nufft_precond_create_block). */
+/* As nufft_precond_create, same parameters, validations in the same order; requires a coupled build in force (else
+ * NUFFT_ERR_UNSUPPORTED, naming nufft_precond_create). */
+int nufft_precond_create_block(nufft_precond** out, nufft_toeplitz* tz, const nufft_precond_params* params);
+/* K for a block object, else 0. */
+int32_t nufft_precond_num_coupled(const nufft_precond* pc);
+/* Device pointer and bytes of B_ab, 0 <= a <= b < K (inspection and tests): real(T) for a = b, complex(T) for a < b; a > b
+ * NUFFT_ERR_INVALID_ARG (B_ba = conj(B_ab)); a scalar object NUFFT_ERR_UNSUPPORTED. */
+int nufft_precond_block_ptr(const nufft_precond* pc, int32_t a, int32_t b, void** out_ptr, int64_t* out_bytes);
+/* Cells of the last build where a Cholesky pivot was floored (0 for a scalar object, -1 for NULL). */
+int64_t nufft_precond_floored_cells(const nufft_precond* pc);
 
 /* Preconditioned CG: with a preconditioner set, nufft_cg_solve runs
  *

@@ -256,6 +256,10 @@ SYMBOLS = {
     "nufft_precond_scaling_ptr": (C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_int64)]),
     "nufft_sizeof_precond_params": (C.c_int64, []),
     "nufft_sizeof_precond_info": (C.c_int64, []),
+    "nufft_precond_create_block": (C.c_int, [C.POINTER(_P), _P, C.POINTER(NufftPrecondParams)]),
+    "nufft_precond_num_coupled": (C.c_int32, [_P]),
+    "nufft_precond_block_ptr": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(_P), C.POINTER(C.c_int64)]),
+    "nufft_precond_floored_cells": (C.c_int64, [_P]),
     "nufft_cg_set_preconditioner": (C.c_int, [_P, _P]),
     "nufft_dcf_create": (C.c_int, [C.POINTER(_P), _P, C.POINTER(NufftDcfParams)]),
     "nufft_dcf_destroy": (C.c_int, [_P]),

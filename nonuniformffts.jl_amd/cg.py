@@ -9,7 +9,8 @@ only: argument checks, pointers, and reading the outcome back.
     sol.iterations, sol.status, sol.residual, sol.history()
 
 ``precond=ToeplitzPreconditioner(op, lam=...)`` makes it preconditioned CG: the same stopping rule on ``‖r‖ / ‖b‖``, one
-apply of ``M⁻¹`` more per iteration and one more array per component.
+apply of ``M⁻¹`` more per iteration and one more array per component.  A coupled operator takes the block preconditioner
+``ToeplitzPreconditioner(op, lam=..., block=True)`` and is refused with the scalar one.
 """
 from __future__ import annotations
 

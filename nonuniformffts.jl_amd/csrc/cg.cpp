@@ -3,7 +3,7 @@
 // The host side only enqueues: per iteration one nufft_toeplitz_apply (unchanged) and the three kernels of cg_kernels.hip.  Every
 // scalar lives on the device; with check_every > 0 the host looks at the done flags now and then, and at nothing else.
 //
-// With a preconditioner set (nufft_cg_set_preconditioner) an iteration is the apply, the dot kernel, pcg_update_kernel,
+// With a preconditioner set (nufft_cg_set_preconditioner, DESIGN.md sections 21 and 22) an iteration is the apply, the dot kernel, pcg_update_kernel,
 // the preconditioner's apply, the dot kernel on (r, z) and pcg_direction_kernel; without one, exactly the launches above.
 #include <hip/hip_runtime.h>
 
@@ -250,7 +250,13 @@ int nufft_cg_solve(nufft_cg* s, void* const* x, const void* const* b, int use_x0
     a.joint = nufft_toeplitz_num_coupled(s->tz) > 0 ? 1 : 0;      // coupled components are one system: one α, one β, one done flag
     a.s = scalars_at(s, s->scal.dev);
     if (s->pc) {
-        if (a.joint) return fail(NUFFT_ERR_UNSUPPORTED, "the operator couples its components: the preconditioner does not apply (clear it with nufft_cg_set_preconditioner(cg, NULL))");
+        // a coupled operator takes the block preconditioner created for its K, independent components the scalar one
+        const int K = nufft_toeplitz_num_coupled(s->tz);
+        if (nufft_precond_num_coupled(s->pc) != K)
+            return fail(NUFFT_ERR_UNSUPPORTED, K > 0 ? "the operator couples its components: the preconditioner must be a block preconditioner created for this coupling "
+                                                       "(nufft_precond_create_block; clear the one set with nufft_cg_set_preconditioner(cg, NULL))"
+                                                     : "the block preconditioner was created for a coupled operator, and the operator no longer couples its components "
+                                                       "(clear it with nufft_cg_set_preconditioner(cg, NULL))");
         a.z = s->d_z;
     }
 

@@ -254,17 +254,18 @@ __global__ __launch_bounds__(kThreads) void cg_direction_kernel(CgLaunch a) {
     }
 }
 
-// The preconditioned iteration.  Kernel 2': as cg_update_kernel with α = ρ_z / γ, ρ_z = Re<r, z> of the iteration before.
+// The preconditioned iteration (joint mode as in the plain kernels, for the block preconditioner of section 22).  Kernel 2': as cg_update_kernel with α = ρ_z / γ, ρ_z = Re<r, z> of the iteration before.
 template <typename T>
 __global__ __launch_bounds__(kThreads) void pcg_update_kernel(CgLaunch a) {
     __shared__ double lds[kWaves];
     constexpr int W = Pack<T>::W;
     const int c = a.c0 + blockIdx.y;
-    const int slot = (a.it & 1) * a.C + c;
+    const int sc = a.joint ? 0 : c, GR = a.joint ? a.C * a.G : a.G;
+    const int slot = (a.it & 1) * a.C + sc;
     if (a.s.flag[slot]) return;
-    const double* row = a.s.part1 + (int64_t)c * a.G * 2;
-    const double pq = row_reduce<Sum>(row, a.G, 2, lds);
-    const double pp = row_reduce<Sum>(row + 1, a.G, 2, lds);
+    const double* row = a.s.part1 + (int64_t)sc * a.G * 2;
+    const double pq = row_reduce<Sum>(row, GR, 2, lds);
+    const double pp = row_reduce<Sum>(row + 1, GR, 2, lds);
     const double gamma = pq + a.lambda * pp;
     const bool bad = !(gamma > 0.0) || !isfinite(gamma);      // the same bits in every workgroup: they all leave, or none does
     if (blockIdx.x == 0 && threadIdx.x == 0) a.s.brk[c] = bad ? 1 : 0;
@@ -312,10 +313,11 @@ __global__ __launch_bounds__(kThreads) void pcg_direction_kernel(CgLaunch a) {
     __shared__ double lds[kWaves];
     constexpr int W = Pack<T>::W;
     const int c = a.c0 + blockIdx.y;
-    const int slot = (a.it & 1) * a.C + c, next = ((a.it + 1) & 1) * a.C + c;
+    const int sc = a.joint ? 0 : c, GR = a.joint ? a.C * a.G : a.G;
+    const int slot = (a.it & 1) * a.C + sc, next = ((a.it + 1) & 1) * a.C + c;
     const bool first = blockIdx.x == 0 && threadIdx.x == 0;
     const bool start = a.it == 0;
-    const bool frozen = a.s.flag[slot] != 0, bad = !frozen && !start && a.s.brk[c] != 0;
+    const bool frozen = a.s.flag[slot] != 0, bad = !frozen && !start && a.s.brk[sc] != 0;
     if (frozen || bad) {
         if (first) {
             a.s.flag[next] = 1;
@@ -325,9 +327,9 @@ __global__ __launch_bounds__(kThreads) void pcg_direction_kernel(CgLaunch a) {
         }
         return;
     }
-    const double rr = start ? a.s.rho[slot] : row_reduce<Sum>(a.s.part2 + (int64_t)c * a.G, a.G, 1, lds);
-    const double rz = row_reduce<Sum>(a.s.part1 + (int64_t)c * a.G * 2, a.G, 2, lds);
-    const double bb = a.s.beta0[c];
+    const double rr = start ? a.s.rho[slot] : row_reduce<Sum>(a.s.part2 + (int64_t)sc * a.G, GR, 1, lds);
+    const double rz = row_reduce<Sum>(a.s.part1 + (int64_t)sc * a.G * 2, GR, 2, lds);
+    const double bb = a.s.beta0[sc];
     const int done = rr <= a.rtol * a.rtol * bb ? 1 : 0;      // (start: not done, or the component would be frozen)
     const bool broke = !done && (!(rz > 0.0) || !isfinite(rz));
     if (first) {

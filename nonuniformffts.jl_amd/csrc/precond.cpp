@@ -9,6 +9,10 @@
 // operator): backward strided passes of fft_lines.hip along dimensions 3 and 2 (unpruned: all N modes kept, identity map, unit
 // factors; d rides on the first load), precond_lines_kernel along dimension 1, forward strided passes along 2 and 3 (d on the last
 // store).  The dense path runs rocFFT on one scratch array.
+//
+// Block object (nufft_precond_create_block): the same build per stored pair of a coupled operator's multipliers
+// gives the K (K + 1) / 2 grids E_ab, pc_block_invert_kernel turns them into B = (E + shift I)⁻¹ / n in place, and the apply runs the
+// passes above per component around ONE kernel that applies the K × K block of every cell (precond_block_kernels.hip).
 #include <hip/hip_runtime.h>
 #include <rocfft/rocfft.h>
 
@@ -33,8 +37,17 @@ struct nufft_precond {
     int64_t n = 1;                         // modes per component
     int path = NUFFT_PRECOND_PATH_DENSE;
     double lambda = 0.0, mu = 0.0, floor = 1e-6, max_e = 0.0, min_e = 0.0;
-    void* d_m = nullptr;                   // T[N_1, N_2, N_3]
-    void* d_scratch = nullptr;             // complex<T>[N_1, N_2, N_3]: shared by all components
+    void* d_m = nullptr;                   // T[N_1, N_2, N_3] (scalar object)
+    void* d_scratch = nullptr;             // complex<T>[N_1, N_2, N_3]: shared by all components; block object: K of them, sstride apart
+    // block object
+    int K = 0;                             // coupled components (0: the scalar object)
+    int64_t pitch = 0;                     // cells between two grids of B: n rounded up to whole 16-byte packs of reals
+    int64_t sstride = 0;                   // complex elements between two scratch arrays
+    void* d_bd = nullptr;                  // T[K][pitch]: B_aa
+    void* d_bc = nullptr;                  // complex<T>[K (K − 1) / 2][pitch]: B_ab, a < b, row-major
+    double* d_cnt = nullptr;               // double[Gc]: partial counts of floored cells
+    int Gc = 1;
+    int64_t floored = 0;
     void* d_own_d = nullptr;               // T[N...]: the scaling from coil maps
     const void* d_scaling = nullptr;       // in force: d_own_d, a caller's array, or null
     int scaling = NUFFT_PRECOND_SCALING_NONE;
@@ -66,7 +79,8 @@ void release(nufft_precond* p) {
             if (p->d_tw_fw[d]) (void)hipFree(p->d_tw_fw[d]);
             if (p->d_tw_bw[d]) (void)hipFree(p->d_tw_bw[d]);
         }
-        for (void* q : {p->d_m, p->d_scratch, p->d_own_d, static_cast<void*>(p->d_part), p->d_ones, static_cast<void*>(p->d_iota), p->d_fft_work})
+        for (void* q : {p->d_m, p->d_scratch, p->d_own_d, static_cast<void*>(p->d_part), p->d_ones, static_cast<void*>(p->d_iota), p->d_fft_work, p->d_bd,
+                        p->d_bc, static_cast<void*>(p->d_cnt)})
             if (q) (void)hipFree(q);
         if (p->fft_fw) (void)rocfft_plan_destroy(p->fft_fw);
         if (p->fft_bw) (void)rocfft_plan_destroy(p->fft_bw);
@@ -92,9 +106,20 @@ int build_device(nufft_precond* p) {
     const size_t rb = real_bytes(p->dtype), cb = 2 * rb;
     const bool fused = p->path == NUFFT_PRECOND_PATH_FUSED;
     int rc;
-    if ((rc = alloc(p, &p->d_m, (size_t)p->n * rb)) || (rc = alloc(p, &p->d_scratch, (size_t)p->n * cb))) return rc;
     p->G = pc_workgroups(p->n, p->num_cus);
-    if ((rc = alloc(p, reinterpret_cast<void**>(&p->d_part), (size_t)p->G * 2 * sizeof(double)))) return rc;
+    if (p->K > 0) {
+        const size_t K = (size_t)p->K;
+        p->pitch = (p->n + 3) / 4 * 4;
+        p->sstride = (p->n + 1) / 2 * 2;
+        p->Gc = pc_block_invert_workgroups(p->n, p->K, p->num_cus);
+        if ((rc = alloc(p, &p->d_bd, K * (size_t)p->pitch * rb)) || (rc = alloc(p, &p->d_scratch, K * (size_t)p->sstride * cb)) ||
+            (rc = alloc(p, reinterpret_cast<void**>(&p->d_cnt), (size_t)p->Gc * sizeof(double))))
+            return rc;
+        if (K > 1 && (rc = alloc(p, &p->d_bc, K * (K - 1) / 2 * (size_t)p->pitch * cb))) return rc;
+    } else if ((rc = alloc(p, &p->d_m, (size_t)p->n * rb)) || (rc = alloc(p, &p->d_scratch, (size_t)p->n * cb))) {
+        return rc;
+    }
+    if ((rc = alloc(p, reinterpret_cast<void**>(&p->d_part), (size_t)std::max(p->K, 1) * p->G * 2 * sizeof(double)))) return rc;
     if (fused) {
         int64_t nmax = 1;
         for (int d = 0; d < p->D; ++d) {
@@ -157,6 +182,19 @@ struct BuildScratch {
     }
 };
 
+// The scalar object serves independent components, the block object the K coupled components it was created for.
+int check_coupling(const nufft_precond* p) {
+    const int K = nufft_toeplitz_num_coupled(p->tz);
+    if (p->K == 0 && K > 0)
+        return fail(NUFFT_ERR_UNSUPPORTED, "the operator couples its components: nufft_precond_create builds the preconditioner of independent components; a "
+                                           "coupled operator takes the block preconditioner of nufft_precond_create_block (Python: block=True)");
+    if (p->K > 0 && K != p->K)
+        return fail(NUFFT_ERR_UNSUPPORTED, K > 0 ? "the block preconditioner was created for another number of coupled components: create a new one"
+                                                 : "nufft_precond_create_block needs a coupled build in force (nufft_toeplitz_set_points_coupled / "
+                                                   "_set_spectra_coupled); independent components take nufft_precond_create");
+    return NUFFT_OK;
+}
+
 // d = (Σ_c |S_c|²)^(−1/2) from the operator's maps, and the mean of the sum (for μ)
 int scaling_from_maps(nufft_precond* p, const std::vector<const void*>& maps, double& mean, hipStream_t stream) {
     int rc;
@@ -185,13 +223,9 @@ int build(nufft_precond* p, hipStream_t stream) {
     if (rc) return rc;
     if (!ti.has_spectrum)
         return fail(NUFFT_ERR_NO_POINTS, "nufft_toeplitz_set_spectrum or nufft_toeplitz_set_points must be called before the preconditioner is built");
-    if (nufft_toeplitz_num_coupled(p->tz) > 0)
-        return fail(NUFFT_ERR_UNSUPPORTED, "the operator couples its components: a block preconditioner for coupled operators is not built");
+    if ((rc = check_coupling(p))) return rc;
     if (capturing(stream))
         return fail(NUFFT_ERR_INVALID_ARG, "the build of a preconditioner allocates and synchronises: not on a capturing stream");
-    void* K = nullptr;
-    if ((rc = nufft_toeplitz_multiplier_ptr(p->tz, &K, nullptr))) return rc;
-
     const size_t cb = 2 * real_bytes(p->dtype);
     const int64_t cells2 = ti.N2[0] * ti.N2[1] * ti.N2[2];
     BuildScratch s(p);
@@ -228,31 +262,59 @@ int build(nufft_precond* p, hipStream_t stream) {
         p->scaling = NUFFT_PRECOND_SCALING_NONE;
     }
 
-    // T = forwardDFT_2N(K);  c = fold(T);  e = Re DFT_N(c)
+    // per multiplier grid: T = forwardDFT_2N(K);  c = fold(T);  E = DFT_N(c), left in d_scratch.  The scalar object has one real grid; the
+    // block object one per stored pair a <= b (complex for a < b), through the one (2N)^D temporary.  The diagonal keeps Re E.
     PcGrid g{};
     g.dtype = p->dtype;
     g.D = p->D;
     for (int d = 0; d < 3; ++d) g.n[d] = (int)p->N[d];
-    NUFFT_HIP(launch_pc_embed(p->dtype, s.grid, K, cells2, p->num_cus, stream));
-    void* io2[1] = {s.grid};
-    NUFFT_ROCFFT(rocfft_execute(s.plan2, io2, nullptr, s.info2));
-    NUFFT_HIP(launch_pc_fold(g, p->d_scratch, s.grid, p->num_cus, stream));
-    void* io[1] = {p->d_scratch};
-    NUFFT_ROCFFT(rocfft_execute(p->fft_fw, io, nullptr, p->fft_info));
-    NUFFT_HIP(launch_pc_eigen(p->dtype, p->d_m, p->d_scratch, p->n, p->d_part, p->G, stream));
-    std::vector<double> part((size_t)p->G * 2);
+    const size_t rb = real_bytes(p->dtype);
+    const int rows = std::max(p->K, 1);
+    for (int a = 0; a < rows; ++a)
+        for (int b = a; b < rows; ++b) {
+            void* K = nullptr;
+            if ((rc = p->K > 0 ? nufft_toeplitz_multiplier_pair_ptr(p->tz, a, b, &K, nullptr) : nufft_toeplitz_multiplier_ptr(p->tz, &K, nullptr))) return rc;
+            if (a == b) NUFFT_HIP(launch_pc_embed(p->dtype, s.grid, K, cells2, p->num_cus, stream));
+            else NUFFT_HIP(hipMemcpyAsync(s.grid, K, s.grid_bytes, hipMemcpyDeviceToDevice, stream));
+            void* io2[1] = {s.grid};
+            NUFFT_ROCFFT(rocfft_execute(s.plan2, io2, nullptr, s.info2));
+            NUFFT_HIP(launch_pc_fold(g, p->d_scratch, s.grid, p->num_cus, stream));
+            void* io[1] = {p->d_scratch};
+            NUFFT_ROCFFT(rocfft_execute(p->fft_fw, io, nullptr, p->fft_info));
+            if (a == b) {
+                void* e = p->K > 0 ? static_cast<char*>(p->d_bd) + (size_t)a * p->pitch * rb : p->d_m;
+                NUFFT_HIP(launch_pc_eigen(p->dtype, e, p->d_scratch, p->n, p->d_part + (size_t)a * p->G * 2, p->G, stream));
+            } else {
+                void* e = static_cast<char*>(p->d_bc) + (size_t)coupled_offdiag_index(a, b, p->K) * p->pitch * cb;
+                NUFFT_HIP(hipMemcpyAsync(e, p->d_scratch, (size_t)p->n * cb, hipMemcpyDeviceToDevice, stream));
+            }
+        }
+    std::vector<double> part((size_t)rows * p->G * 2);
     NUFFT_HIP(hipMemcpyAsync(part.data(), p->d_part, part.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
     NUFFT_HIP(hipStreamSynchronize(stream));
     double hi = -INFINITY, lo = -INFINITY;
-    for (int w = 0; w < p->G; ++w) {
-        hi = std::max(hi, part[2 * (size_t)w]);
-        lo = std::max(lo, part[2 * (size_t)w + 1]);
+    for (size_t w = 0; w < (size_t)rows * p->G; ++w) {
+        hi = std::max(hi, part[2 * w]);
+        lo = std::max(lo, part[2 * w + 1]);
     }
     p->max_e = hi;
     p->min_e = -lo;
     p->mu = mu;
     if (!std::isfinite(hi) || !(hi + mu > 0.0))
         return fail(NUFFT_ERR_INVALID_ARG, "the eigenvalues of the circulant plus mu are nowhere positive (a zero operator with lambda = 0?): nothing to invert");
+    if (p->K > 0) {
+        // the floor as a shift: every eigenvalue of E(q) + shift I is at least shift, so is every Cholesky pivot in exact arithmetic
+        const double shift = std::max(mu, p->floor * (hi + mu));
+        NUFFT_HIP(launch_pc_block_invert(p->dtype, p->d_bd, p->d_bc, p->K, p->n, p->pitch, shift, kPcPivotFraction * shift, (double)p->n, p->d_cnt,
+                                         p->Gc, stream));
+        std::vector<double> cnt((size_t)p->Gc);
+        NUFFT_HIP(hipMemcpyAsync(cnt.data(), p->d_cnt, cnt.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+        NUFFT_HIP(hipStreamSynchronize(stream));      // the temporaries are freed on return
+        double total = 0.0;
+        for (double c : cnt) total += c;
+        p->floored = (int64_t)total;
+        return NUFFT_OK;
+    }
     NUFFT_HIP(launch_pc_invert(p->dtype, p->d_m, p->n, mu, p->floor * (hi + mu), (double)p->n, p->num_cus, stream));
     NUFFT_HIP(hipStreamSynchronize(stream));      // the temporaries are freed on return
     return NUFFT_OK;
@@ -313,16 +375,48 @@ int apply_dense(nufft_precond* p, void* out, const void* in, hipStream_t stream)
     return NUFFT_OK;
 }
 
-}  // namespace
+// The block object: every input passes into its own scratch array before the one kernel that mixes them, and only then is any output
+// written — out[a] may be in[a].
+int apply_block(nufft_precond* p, void* const* out, const void* const* in, hipStream_t stream) {
+    int rc;
+    const size_t sb = (size_t)p->sstride * 2 * real_bytes(p->dtype);
+    auto scratch = [&](int a) { return static_cast<void*>(static_cast<char*>(p->d_scratch) + (size_t)a * sb); };
+    if (p->path == NUFFT_PRECOND_PATH_DENSE) {
+        for (int b = 0; b < p->K; ++b) {
+            void* io[1] = {scratch(b)};
+            NUFFT_HIP(launch_pc_scale(p->dtype, io[0], in[b], p->d_scaling, p->n, p->num_cus, stream));
+            NUFFT_ROCFFT(rocfft_execute(p->fft_fw, io, nullptr, p->fft_info));
+        }
+        NUFFT_HIP(launch_pc_block_multiply(p->dtype, p->d_scratch, p->sstride, p->K, p->d_bd, p->d_bc, p->n, p->pitch, p->num_cus, stream));
+        for (int a = 0; a < p->K; ++a) {
+            void* io[1] = {scratch(a)};
+            NUFFT_ROCFFT(rocfft_execute(p->fft_bw, io, nullptr, p->fft_info));
+            NUFFT_HIP(launch_pc_scale(p->dtype, out[a], io[0], p->d_scaling, p->n, p->num_cus, stream));
+        }
+        return NUFFT_OK;
+    }
+    for (int b = 0; b < p->K; ++b) {
+        void* s = scratch(b);
+        if (p->D == 3) {
+            if ((rc = strided_pass(p, 2, false, in[b], s, p->d_scaling, stream)) || (rc = strided_pass(p, 1, false, s, s, nullptr, stream))) return rc;
+        } else if ((rc = strided_pass(p, 1, false, in[b], s, p->d_scaling, stream))) {
+            return rc;
+        }
+    }
+    NUFFT_HIP(launch_precond_block_lines(p->dtype, p->N[0], p->K, p->d_scratch, p->sstride, p->d_bd, p->d_bc, (int)p->N[1], (int)p->N[2], p->d_tw_fw[0],
+                                         stream));
+    for (int a = 0; a < p->K; ++a) {
+        void* s = scratch(a);
+        if (p->D == 3) {
+            if ((rc = strided_pass(p, 1, true, s, s, nullptr, stream)) || (rc = strided_pass(p, 2, true, s, out[a], p->d_scaling, stream))) return rc;
+        } else if ((rc = strided_pass(p, 1, true, s, out[a], p->d_scaling, stream))) {
+            return rc;
+        }
+    }
+    return NUFFT_OK;
+}
 
-const nufft_toeplitz* nufft::precond_operator(const nufft_precond* pc) { return pc ? pc->tz : nullptr; }
-
-extern "C" {
-
-int64_t nufft_sizeof_precond_params(void) { return (int64_t)sizeof(nufft_precond_params); }
-int64_t nufft_sizeof_precond_info(void) { return (int64_t)sizeof(nufft_precond_info); }
-
-int nufft_precond_create(nufft_precond** out, nufft_toeplitz* tz, const nufft_precond_params* params) {
+int create(nufft_precond** out, nufft_toeplitz* tz, const nufft_precond_params* params, bool block) {
     if (!out || !tz || !params) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
     *out = nullptr;
     nufft_precond_params prm;
@@ -345,6 +439,15 @@ int nufft_precond_create(nufft_precond** out, nufft_toeplitz* tz, const nufft_pr
     p->device = ti.device;
     p->lambda = prm.lambda;
     p->floor = prm.floor;
+    if (block) {      // the arrays are sized by K: the refusals of the build that depend on the operator's state come first, in its order
+        p->K = ti.ntransforms;
+        if (!ti.has_spectrum) rc = fail(NUFFT_ERR_NO_POINTS, "nufft_toeplitz_set_spectrum or nufft_toeplitz_set_points must be called before the preconditioner is built");
+        else rc = check_coupling(p);
+        if (rc) {
+            delete p;
+            return rc;
+        }
+    }
     // the operator's dense path on a shape its fused path supports is the plan's option NUFFT_TOEPLITZ_FUSED=0, which this object honours
     bool op_fusable = ti.ndim >= 2;
     bool fused = ti.ndim >= 2;
@@ -355,6 +458,8 @@ int nufft_precond_create(nufft_precond** out, nufft_toeplitz* tz, const nufft_pr
         fused = fused && fft_lines_supported(ti.dtype, ti.N[d]) && precond_lines_supported(ti.dtype, ti.N[d]);
     }
     if (op_fusable && ti.path == NUFFT_TOEPLITZ_PATH_DENSE) fused = false;
+    // the K lines of one wave must fit LDS; where they do not, the dense path serves (the operator refuses such a build instead)
+    if (block && !precond_block_lines_supported(ti.dtype, ti.N[0], p->K)) fused = false;
     p->n = p->N[0] * p->N[1] * p->N[2];
     p->path = fused ? NUFFT_PRECOND_PATH_FUSED : NUFFT_PRECOND_PATH_DENSE;
 
@@ -370,6 +475,19 @@ int nufft_precond_create(nufft_precond** out, nufft_toeplitz* tz, const nufft_pr
     *out = p;
     return NUFFT_OK;
 }
+
+}  // namespace
+
+const nufft_toeplitz* nufft::precond_operator(const nufft_precond* pc) { return pc ? pc->tz : nullptr; }
+
+extern "C" {
+
+int64_t nufft_sizeof_precond_params(void) { return (int64_t)sizeof(nufft_precond_params); }
+int64_t nufft_sizeof_precond_info(void) { return (int64_t)sizeof(nufft_precond_info); }
+
+int nufft_precond_create(nufft_precond** out, nufft_toeplitz* tz, const nufft_precond_params* params) { return create(out, tz, params, false); }
+
+int nufft_precond_create_block(nufft_precond** out, nufft_toeplitz* tz, const nufft_precond_params* params) { return create(out, tz, params, true); }
 
 int nufft_precond_destroy(nufft_precond* pc) {
     release(pc);
@@ -401,6 +519,7 @@ int nufft_precond_apply(nufft_precond* pc, void* const* out, const void* const* 
     DeviceGuard guard(pc->device);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (pc->path == NUFFT_PRECOND_PATH_DENSE) NUFFT_ROCFFT(rocfft_execution_info_set_stream(pc->fft_info, stream));
+    if (pc->K > 0) return apply_block(pc, out, in, stream);
     for (int c = 0; c < pc->C; ++c) {
         const int rc = pc->path == NUFFT_PRECOND_PATH_FUSED ? apply_fused(pc, out[c], in[c], stream) : apply_dense(pc, out[c], in[c], stream);
         if (rc) return rc;
@@ -424,7 +543,7 @@ int nufft_precond_get_info(const nufft_precond* pc, nufft_precond_info* o) {
     i.floor = pc->floor;
     i.max_e = pc->max_e;
     i.min_e = pc->min_e;
-    i.multiplier_bytes = pc->n * (int64_t)real_bytes(pc->dtype);
+    i.multiplier_bytes = (pc->K > 0 ? (int64_t)pc->K * pc->K : 1) * pc->n * (int64_t)real_bytes(pc->dtype);
     i.workspace_bytes = pc->own_bytes;
     write_info(o, i);
     return NUFFT_OK;
@@ -432,6 +551,7 @@ int nufft_precond_get_info(const nufft_precond* pc, nufft_precond_info* o) {
 
 int nufft_precond_multiplier_ptr(const nufft_precond* pc, void** out_ptr, int64_t* out_bytes) {
     if (!pc || !out_ptr) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    if (pc->K > 0) return fail(NUFFT_ERR_UNSUPPORTED, "a block preconditioner has no single multiplier: ask nufft_precond_block_ptr for B_ab");
     *out_ptr = pc->d_m;
     if (out_bytes) *out_bytes = pc->n * (int64_t)real_bytes(pc->dtype);
     return NUFFT_OK;
@@ -441,6 +561,25 @@ int nufft_precond_scaling_ptr(const nufft_precond* pc, void** out_ptr, int64_t* 
     if (!pc || !out_ptr) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
     *out_ptr = const_cast<void*>(pc->d_scaling);
     if (out_bytes) *out_bytes = pc->d_scaling ? pc->n * (int64_t)real_bytes(pc->dtype) : 0;
+    return NUFFT_OK;
+}
+
+int32_t nufft_precond_num_coupled(const nufft_precond* pc) { return pc ? (int32_t)pc->K : 0; }
+
+int64_t nufft_precond_floored_cells(const nufft_precond* pc) { return pc ? pc->floored : -1; }
+
+int nufft_precond_block_ptr(const nufft_precond* pc, int32_t a, int32_t b, void** out_ptr, int64_t* out_bytes) {
+    if (!pc || !out_ptr) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    if (pc->K == 0) return fail(NUFFT_ERR_UNSUPPORTED, "nufft_precond_block_ptr: not a block preconditioner (nufft_precond_multiplier_ptr returns m)");
+    if (a < 0 || b < a || b >= pc->K) return fail(NUFFT_ERR_INVALID_ARG, "nufft_precond_block_ptr: the pair must satisfy 0 <= a <= b < K (B_ba = conj(B_ab))");
+    const int64_t rb = (int64_t)real_bytes(pc->dtype);
+    if (a == b) {
+        *out_ptr = static_cast<char*>(pc->d_bd) + a * pc->pitch * rb;
+        if (out_bytes) *out_bytes = pc->n * rb;
+    } else {
+        *out_ptr = static_cast<char*>(pc->d_bc) + coupled_offdiag_index(a, b, pc->K) * pc->pitch * 2 * rb;
+        if (out_bytes) *out_bytes = pc->n * 2 * rb;
+    }
     return NUFFT_OK;
 }
 

@@ -37,6 +37,26 @@ hipError_t launch_pc_coil_scaling(int dtype, void* d, int64_t n, double floor, i
 bool precond_lines_supported(int dtype, int64_t n);
 hipError_t launch_precond_lines(int dtype, int64_t n, void* data, const void* m, int n2, int n3, const void* twiddle, hipStream_t stream);
 
+// The block preconditioner of a coupled operator (precond_block_kernels.hip).  B is stored like the operator's
+// multipliers: `bd` T[K][pitch] (the diagonal blocks, real) and `bc` complex<T>[pairs a < b, row-major][pitch]; B_ba = conj(B_ab).  A grid
+// has n cells; pitch >= n keeps every grid 16-byte aligned (the fused path has pitch = n).
+constexpr double kPcPivotFraction = 0.25;      // a Cholesky pivot below this fraction of the shift is floored there
+// E -> B = (E + shift I)⁻¹ / count per cell, in place on the K (K + 1) / 2 grids: FP64 Cholesky and triangular inverse; part[g] = cells of
+// wave g where a pivot was floored at `pivot_floor` (double[G]: whole numbers).  G = pc_block_invert_workgroups(...)
+int pc_block_invert_workgroups(int64_t n, int K, int num_cus);
+hipError_t launch_pc_block_invert(int dtype, void* bd, void* bc, int K, int64_t n, int64_t pitch, double shift, double pivot_floor, double count,
+                                  double* part,
+                                  int G, hipStream_t stream);
+// data[a] = Σ_b B_ab ⊙ data[b] per cell, in place; data: K arrays complex<T>[n], `data_stride` complex elements apart (dense path)
+hipError_t launch_pc_block_multiply(int dtype, void* data, int64_t data_stride, int K, const void* bd, const void* bc, int64_t n, int64_t pitch,
+                                    int num_cus, hipStream_t stream);
+// Dimension 1 of the fused apply for K coupled components, in place: one wave owns the K lines of a line id (data: K arrays
+// complex<T>[nlines][n], `data_stride` complex elements apart) — K backward FFTs, the block of B at the negated frequencies per cell, K
+// forward FFTs, all inside LDS.  _supported: the K lines of length n fit the LDS of one wave.
+bool precond_block_lines_supported(int dtype, int64_t n, int K);
+hipError_t launch_precond_block_lines(int dtype, int64_t n, int K, void* data, int64_t data_stride, const void* bd, const void* bc, int n2, int n3,
+                                      const void* twiddle, hipStream_t stream);
+
 // The operator a preconditioner was built for (the solver refuses one built for another).
 const ::nufft_toeplitz* precond_operator(const ::nufft_precond* pc);
 

@@ -5,7 +5,12 @@ N (not 2N), and they follow from the operator's own multiplier — the points ar
 
     M⁻¹ r = d ⊙ F⁻¹( m ⊙ F( d ⊙ r ) ),      m = 1 / max(e + μ, floor · max(e + μ))
 
-(DESIGN.md §21).  Plumbing only: every array operation runs in the library.
+(DESIGN.md §21).  On a coupled operator (``op.set_points(..., basis=)`` / ``op.set_spectra``) ``block=True`` builds the block-circulant
+preconditioner of the K × K block system: per mode ``q`` the Hermitian matrix ``E(q)`` of the blocks' optimal circulants, and
+
+    (M⁻¹ r)_a = d ⊙ F⁻¹( Σ_b B_ab ⊙ F( d ⊙ r_b ) ),      B(q) = (E(q) + shift I)⁻¹ / n,   shift = max(μ, floor · (max_{q,a} E_aa(q) + μ)).
+
+Plumbing only: every array operation runs in the library.
 
     pc = ToeplitzPreconditioner(op, lam=lam)
     x = op.solve(b, lam=lam, rtol=1e-6, maxiter=200, precond=pc)
@@ -29,14 +34,17 @@ class ToeplitzPreconditioner:
     """``ToeplitzPreconditioner(op, lam=0.0, floor=1e-6)``: built from the multiplier ``op`` holds now (``op.set_points`` /
     ``set_spectrum`` first); ``update()`` rebuilds it after the operator's spectrum or coil maps changed.  ``lam`` is the λ of the system
     ``(G + λ I)`` it preconditions.  With coil maps set on ``op`` the scaling ``d = (Σ_c |S_c|²)^(-1/2)`` is computed and owned here and
-    ``μ = λ / mean(Σ_c |S_c|²)``; ``set_scaling(d)`` passes another ``d``.  Coupled operators (``basis=``) are refused.
+    ``μ = λ / mean(Σ_c |S_c|²)``; ``set_scaling(d)`` passes another ``d``.  A coupled operator (``basis=``) takes ``block=True`` — the
+    components are then ONE vector: ``apply`` takes and returns a tuple of K arrays, ``block(a, b)`` returns ``B_ab``, ``floor`` is a shift
+    of every cell's eigenvalues instead of a clamp, and ``floored_cells`` counts the cells whose Cholesky pivot had to be floored (round-off
+    in ``E``; 0 on any reasonable system) — and is refused with ``block=False``, as an uncoupled one is with ``block=True``.
 
     ``path`` is ``"fused"`` (2-D and 3-D shapes whose every ``N_d`` is one of the library's line lengths 64 … 1024) or ``"dense"``
     (rocFFT); it does not depend on the operator's own path — a 48 × 40 operator is fused while its preconditioner is dense.  Building
     allocates temporaries and synchronises (not inside ``torch.cuda.graph``); ``apply`` allocates nothing and is capturable.  The object
     keeps ``op`` alive."""
 
-    def __init__(self, op: ToeplitzOperator, lam: float = 0.0, floor: float = 1e-6):
+    def __init__(self, op: ToeplitzOperator, lam: float = 0.0, floor: float = 1e-6, block: bool = False):
         if not isinstance(op, ToeplitzOperator):
             raise ValueError("ToeplitzPreconditioner takes a ToeplitzOperator")
         op._require_open()
@@ -47,7 +55,8 @@ class ToeplitzPreconditioner:
         self._d = None
         if op.device is not None:
             torch.cuda.current_stream(op.device).synchronize()      # the build runs on the default stream
-        _check(lib.nufft_precond_create(C.byref(self._handle), op._handle, C.byref(prm)))
+        create = lib.nufft_precond_create_block if block else lib.nufft_precond_create
+        _check(create(C.byref(self._handle), op._handle, C.byref(prm)))
         self.op = op
         self.lam, self.floor = float(lam), float(floor)
 
@@ -81,8 +90,20 @@ class ToeplitzPreconditioner:
     def path(self) -> str:
         return _PATHS[self.info().path]
 
+    @property
+    def coupled(self) -> int:
+        """K for a block preconditioner (``block=True``), else 0."""
+        self._require_open()
+        return int(lib.nufft_precond_num_coupled(self._handle))
+
+    @property
+    def floored_cells(self) -> int:
+        """Cells of the last build whose Cholesky pivot was floored (a block preconditioner; 0 otherwise)."""
+        self._require_open()
+        return int(lib.nufft_precond_floored_cells(self._handle))
+
     def update(self) -> "ToeplitzPreconditioner":
-        """Rebuilds ``m`` (and the scaling from coil maps) from what the operator holds now."""
+        """Rebuilds ``m`` — a block preconditioner: ``B`` — (and the scaling from coil maps) from what the operator holds now."""
         self._require_open()
         _check(lib.nufft_precond_update(self._handle, self.op._stream()))
         if self.info().scaling != _lib.PRECOND_SCALING_CALLER:
@@ -114,7 +135,7 @@ class ToeplitzPreconditioner:
 
     def apply(self, r, out=None):
         """``out = M⁻¹ r`` for every component; ``r``: a tensor of ``plan.shape`` or a tuple of ntransforms such tensors; ``out`` may
-        be ``r``.  Returns ``out``."""
+        be ``r``.  A block preconditioner takes the tuple of its K components as one vector.  Returns ``out``."""
         self._require_open()
         op = self.op
         single = isinstance(r, torch.Tensor)
@@ -131,9 +152,9 @@ class ToeplitzPreconditioner:
 
     __call__ = apply
 
-    def _view(self, ptr, nbytes):
+    def _view(self, ptr, nbytes, real=True):
         shape = tuple(self.op.shape)
-        typestr = "<f4" if self.op.T == torch.float32 else "<f8"
+        typestr = ("<f4" if self.op.T == torch.float32 else "<f8") if real else ("<c8" if self.op.T == torch.float32 else "<c16")
 
         class _View:       # the array-interface protocol: torch wraps the pointer without copying
             __cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (int(ptr.value), False), "version": 2, "strides": None}
@@ -149,6 +170,14 @@ class ToeplitzPreconditioner:
         _check(lib.nufft_precond_multiplier_ptr(self._handle, C.byref(ptr), C.byref(nbytes)))
         return self._view(ptr, nbytes)
 
+    def block(self, a: int, b: int) -> torch.Tensor:
+        """``B_ab`` of a block preconditioner (shape ``plan.shape``, ``1 / Π N_d`` folded in): a real view for ``a == b``, a complex view
+        for ``a < b`` (``B_ba = conj(B_ab)``: ``a > b`` raises), rewritten by ``update()``."""
+        self._require_open()
+        ptr, nbytes = C.c_void_p(), C.c_int64()
+        _check(lib.nufft_precond_block_ptr(self._handle, int(a), int(b), C.byref(ptr), C.byref(nbytes)))
+        return self._view(ptr, nbytes, real=a == b)
+
     def scaling(self) -> Optional[torch.Tensor]:
         """The scaling ``d`` in force (a view; ``None``: no scaling)."""
         self._require_open()
@@ -158,5 +187,5 @@ class ToeplitzPreconditioner:
 
     def __repr__(self):
         i = self.info()
-        return (f"ToeplitzPreconditioner of a {self.op.ndim}-dimensional {self.op.Z} operator, {self.path} path, lam = {self.lam:g}, "
+        return (f"{'Block ' if self.coupled else ''}ToeplitzPreconditioner of a {self.op.ndim}-dimensional {self.op.Z} operator, {self.path} path, lam = {self.lam:g}, "
                 f"mu = {i.mu:g}, floor = {self.floor:g}, e in [{i.min_e:g}, {i.max_e:g}], {i.workspace_bytes / 1e6:.1f} MB")
