@@ -876,6 +876,167 @@ int nufft_dcf_history(nufft_dcf* dcf, double* host_out, int64_t capacity, void* 
 int64_t nufft_sizeof_dcf_params(void);
 int64_t nufft_sizeof_dcf_info(void);
 
+/* ---- Wavelet transform with its proximal map -------------------- */
+/* Orthogonal periodic wavelets of 2 taps (Haar) and 4 taps (Daubechies, two vanishing moments) on arrays laid out like those of
+ * nufft_toeplitz_apply: complex(T)[N...], T the plan's precision, ntransforms components, D = 1, 2, 3.  One analysis stage along an axis
+ * of length n is
+ *
+ *     lo[i] = Σ_k h[k] a[(2i + k) mod n]      hi[i] = Σ_k g[k] a[(2i + k) mod n]      g[k] = (−1)^k h[L − 1 − k],  i < n / 2
+ *
+ * (filter coefficients: FP64 constants cast to T), applied separably; every level recurses on the low-pass corner, and the output is
+ * the Mallat layout in one array of the input's shape: along every axis the approximation of the deepest level sits at [0, N_d / 2^L),
+ * the details of level l at [N_d / 2^l, N_d / 2^(l − 1)).  The transform is orthogonal: the inverse is its transpose.  It acts on the
+ * array AS STORED, periodic in the storage index.  A periodic transform of L levels commutes with cyclic shifts by multiples of 2^L, so
+ * fftshift = 1 and fftshift = 0 plans (whose storage orders differ by a shift of N_d / 2) give the same proximal map whenever 2^(L + 1)
+ * divides every N_d; otherwise the two orders differ only in which pixels are paired.
+ *
+ * One launch per level handles all D dimensions of a tile in LDS (a level reads its sub-box once and writes it once); the levels pass
+ * their low-pass corner through two scratch arrays the object owns (n / 2^D and n / 4^D elements per component), never in place.
+ * forward, inverse and shrink allocate nothing, do not synchronise and are hipGraph-capture safe; no atomics: two runs give the same
+ * bits.  The object keeps scratch and partial sums: one call at a time per object.
+ *
+ * Added after ABI 104 without changing NUFFT_MI355X_VERSION: detect by symbol (dlsym nufft_wavelet_create) and compare
+ * nufft_sizeof_wavelet_params() / nufft_sizeof_wavelet_info() with your own. */
+typedef struct nufft_wavelet nufft_wavelet; /* opaque */
+
+enum { NUFFT_WAVELET_HAAR = 0, NUFFT_WAVELET_DB2 = 1 };
+
+typedef struct nufft_wavelet_params {
+    int32_t struct_size;     /* sizeof(nufft_wavelet_params) of the caller's header (0 = this layout)                              */
+    int32_t wavelet;         /* NUFFT_WAVELET_*                                                                                    */
+    int32_t levels;          /* L >= 1                                                                                             */
+    int32_t reserved;        /* 0                                                                                                  */
+} nufft_wavelet_params;
+
+typedef struct nufft_wavelet_info {
+    int32_t struct_size;     /* sizeof(nufft_wavelet_info) of the caller's header, set before the call (0 = this layout)           */
+    int32_t ndim, dtype, ntransforms, device;
+    int32_t wavelet;         /* NUFFT_WAVELET_*                                                                                    */
+    int32_t taps;            /* 2 or 4                                                                                             */
+    int32_t levels;
+    int64_t N[3];            /* 1 beyond ndim                                                                                      */
+    int64_t scratch_bytes;   /* the two low-pass scratch arrays of all components                                                  */
+    int64_t workspace_bytes; /* device bytes owned: scratch_bytes + partial sums                                                   */
+} nufft_wavelet_info;
+
+/* Takes element type, shape, ntransforms and device from the plan; the plan is not kept.  Refusals, in order: null arguments, a
+ * struct_size smaller than the published layout NUFFT_ERR_INVALID_ARG; a real-data plan NUFFT_ERR_UNSUPPORTED (as
+ * nufft_toeplitz_create); an unknown wavelet, levels < 1, an N_d that is no multiple of 2^levels, DB2 with N_d / 2^levels < 2 (every
+ * level's input must be at least one filter long) NUFFT_ERR_INVALID_ARG; a host-only plan NUFFT_ERR_NO_DEVICE. */
+int nufft_wavelet_create(nufft_wavelet** out, const nufft_plan* plan, const nufft_wavelet_params* params);
+/* The same from a Toeplitz operator (the operator is not kept). */
+int nufft_wavelet_create_for_operator(nufft_wavelet** out, const nufft_toeplitz* tz, const nufft_wavelet_params* params);
+int nufft_wavelet_destroy(nufft_wavelet* w);
+/* Static facts and sizes; does not synchronise. */
+int nufft_wavelet_get_info(const nufft_wavelet* w, nufft_wavelet_info* out);
+/* out[c] = W in[c] (Mallat layout) for every component; host tables of ntransforms device pointers, 16-byte aligned.  in is only read.
+ * Refusals, before anything is enqueued: a null table or vector, a pointer that is not 16-byte aligned, out[c] overlapping any in[c']
+ * (a level reads its sub-box while other tiles store into it) or another out[c'] NUFFT_ERR_INVALID_ARG. */
+int nufft_wavelet_forward(nufft_wavelet* w, void* const* out, const void* const* in, void* stream);
+/* out[c] = W^H in[c]; same rules. */
+int nufft_wavelet_inverse(nufft_wavelet* w, void* const* out, const void* const* in, void* stream);
+/* The forward transform whose detail coefficients are soft-thresholded where they are stored: c <- c · max(1 − t[c'] / |c|, 0) with the
+ * threshold t[c'] of the coefficient's component (HOST array of ntransforms values, finite and >= 0, read during the call); the
+ * approximation band of the deepest level is never thresholded, and t = 0 stores exactly what nufft_wavelet_forward stores.
+ * l1_out_device (device, double[ntransforms], may be NULL): Σ |stored detail coefficient| per component, FP64, summed in one fixed
+ * order.  With inverse this is the proximal map of t ‖D W x‖₁: x <- W^H shrink(W x, t); ADMM's x-update is nufft_cg_solve with
+ * lambda = ρ and a starting guess. */
+int nufft_wavelet_shrink(nufft_wavelet* w, void* const* out, const void* const* in, const double* t, double* l1_out_device, void* stream);
+int64_t nufft_sizeof_wavelet_params(void);
+int64_t nufft_sizeof_wavelet_info(void);
+
+/* ---- Largest eigenvalue of the Toeplitz normal operator ---------- */
+/* Power iteration on whatever nufft_toeplitz_apply currently computes (plain, with coil maps, coupled):
+ *
+ *     v = v0;  repeat iters times:  g = G v;  ρ = Re<v, g> / <v, v>;  v = g / ‖g‖
+ *
+ * out_host[c], c < ntransforms: the FP64 Rayleigh quotient ρ of the LAST apply — a lower bound of λ_max(G).  Uncoupled components give
+ * one value each; coupled components are one vector (sums over all components) and every entry receives the same value.  <v, v> = 0
+ * gives 0.  v0: host table of ntransforms device pointers, complex(T)[N...], 16-byte aligned, only read.  Sums are FP64 in one fixed
+ * order.  Allocates two arrays per component for the duration of the call, synchronises `stream` and frees them: refused on a
+ * capturing stream.  Refusals: null arguments, iters < 1, a null or misaligned vector, a capturing stream NUFFT_ERR_INVALID_ARG; a
+ * host-only operator NUFFT_ERR_NO_DEVICE; no spectrum yet NUFFT_ERR_NO_POINTS.  Added without changing NUFFT_MI355X_VERSION. */
+int nufft_toeplitz_max_eigenvalue(nufft_toeplitz* tz, const void* const* v0, int32_t iters, double* out_host, void* stream);
+
+/* ---- FISTA with an l1-wavelet prior on the Toeplitz normal operator ---- */
+/* Minimises, for every component c (coupled components: jointly, the quadratic term coupling them),
+ *
+ *     ½ <x, (G + μ I) x> − Re<b, x> + Σ_c l1_c ‖D W x_c‖₁
+ *
+ * G what the nufft_toeplitz object applies, W the wavelet transform above, D the projection on its detail bands, by the accelerated
+ * proximal-gradient iteration of Beck & Teboulle (2009) with the fixed step τ.  Start: t_1 = 1, z = x = x0 (or 0).
+ *
+ *     for it = 1 ... max_iter:
+ *         q = G z                                                          nufft_toeplitz_apply
+ *         v = z − τ (q + μ z − b)                                          fista_gradient_kernel, in place over q
+ *         c = shrink(W v, τ l1)                                            one launch per level, threshold and ‖·‖₁ partials on store
+ *         x⁺ = W^H c;  z = x⁺ + ((t_it − 1) / t_it+1) (x⁺ − x);  x = x⁺    one launch per level, the step on the last level's store
+ *         change = ‖x⁺ − x‖ / ‖x⁺‖ (0 when both are 0)                     fista_decide_kernel
+ *         done ← change <= tol, or change not finite (NUFFT_FISTA_BREAKDOWN)
+ *
+ * t_it+1 = (1 + sqrt(1 + 4 t_it²)) / 2 depends on the iteration number only: the host passes the factor as a kernel argument.  The
+ * iteration converges for τ <= 1 / (λ_max(G) + μ) (nufft_toeplitz_max_eigenvalue).  A component that is done is FROZEN: no kernel writes
+ * its x, z or scalars again.  Uncoupled operators stop per component; a coupled operator is one system with one change and one flag,
+ * reported identically for every component.  Sums and scalars are FP64, formed without atomics in one fixed order: two runs, and a
+ * replayed hipGraph, give the same bits.
+ *
+ * check_every = 0: all max_iter iterations are enqueued without synchronising or allocating (hipGraph-capture safe).
+ * check_every = k > 0: after every k iterations the host reads the done flags and stops enqueuing once every component is done.
+ *                  Refused on a capturing stream.  Both modes return bit-identical x, iteration counts and history.
+ *
+ * Added after ABI 104 without changing NUFFT_MI355X_VERSION: detect by symbol (dlsym nufft_fista_create) and compare
+ * nufft_sizeof_fista_params() / nufft_sizeof_fista_info() with your own. */
+typedef struct nufft_fista nufft_fista; /* opaque */
+
+enum { NUFFT_FISTA_MAX_ITER = 0,   /* max_iter iterations ran without reaching tol */
+       NUFFT_FISTA_CONVERGED = 1,  /* change <= tol                                */
+       NUFFT_FISTA_BREAKDOWN = 2   /* change not finite: the component was frozen  */ };
+
+typedef struct nufft_fista_params {
+    int32_t struct_size;     /* sizeof(nufft_fista_params) of the caller's header (0 = this layout)                                */
+    int32_t max_iter;        /* 1 ... 2^24                                                                                         */
+    int32_t check_every;     /* 0, or the number of iterations between two looks at the done flags                                 */
+    int32_t wavelet;         /* NUFFT_WAVELET_*                                                                                    */
+    int32_t levels;          /* of the wavelet transform                                                                           */
+    int32_t reserved;        /* 0                                                                                                  */
+    double tol;              /* >= 0, finite; 0 = run max_iter iterations unless x stops changing exactly                          */
+    double step;             /* τ > 0, finite                                                                                      */
+    double l1;               /* >= 0, finite: the weight of every component until nufft_fista_set_l1                               */
+    double lambda;           /* the Tikhonov μ: >= 0, finite                                                                       */
+} nufft_fista_params;
+
+typedef struct nufft_fista_info {
+    int32_t struct_size;     /* sizeof(nufft_fista_info) of the caller's header, set before the call (0 = this layout)             */
+    int32_t ntransforms, dtype, max_iter, check_every, wavelet, levels;
+    int32_t iterations_enqueued; /* by the last nufft_fista_solve (check_every > 0 stops early); -1 before the first               */
+    double tol, step, lambda;
+    int64_t array_bytes;     /* z, q / v, c: 3 arrays per component                                                                */
+    int64_t workspace_bytes; /* device bytes owned: array_bytes + the wavelet object's scratch and partials + partial sums + scalars
+                                + history                                                                                          */
+} nufft_fista_info;
+
+/* Allocates z, q, c (3 arrays per component), a wavelet object for the operator's shape, partial sums, scalars and history on the
+ * operator's device.  The solver keeps the POINTER `tz`: the operator must outlive it; nufft_toeplitz_set_points / _set_spectrum on it
+ * between two solves is allowed.  Refusals: null arguments, max_iter < 1 or > 2^24, check_every < 0, tol < 0, l1 < 0, lambda < 0,
+ * step <= 0 or non-finite values, and whatever nufft_wavelet_create refuses for the shape NUFFT_ERR_INVALID_ARG; a host-only operator
+ * NUFFT_ERR_NO_DEVICE (after the argument checks). */
+int nufft_fista_create(nufft_fista** out, nufft_toeplitz* tz, const nufft_fista_params* params);
+int nufft_fista_destroy(nufft_fista* f);
+/* One weight per component (host array, count = ntransforms, each finite and >= 0) for the following solves. */
+int nufft_fista_set_l1(nufft_fista* f, const double* l1, int64_t count);
+/* x_inout[c], b[c] as in nufft_cg_solve, with the same refusals.  use_x0 = 0: start from zero. */
+int nufft_fista_solve(nufft_fista* f, void* const* x_inout, const void* const* b, int use_x0, void* stream);
+/* Static facts and sizes; does not synchronise. */
+int nufft_fista_get_info(const nufft_fista* f, nufft_fista_info* out);
+/* Per-component outcome of the last solve: iterations that changed the component, NUFFT_FISTA_* status, the last change.  Each output
+ * may be NULL; `capacity` entries each, at least ntransforms.  Synchronises `stream` (never a capturing one). */
+int nufft_fista_get_result(nufft_fista* f, int32_t* iterations, int32_t* status, double* change, int64_t capacity, void* stream);
+/* host_out[max_iter][ntransforms][2]: row it − 1 holds the change and ‖D W x‖₁ of every component after iteration it (a coupled operator:
+ * the joint values); NaN where the iteration did not change the component.  Synchronises `stream`. */
+int nufft_fista_history(nufft_fista* f, double* host_out, int64_t capacity, void* stream);
+int64_t nufft_sizeof_fista_params(void);
+int64_t nufft_sizeof_fista_info(void);
+
 /* ---- misc ----------------------------------------------------------------------------- */
 /* sizeof(nufft_params) / sizeof(nufft_info) of the library build: a binding that mirrors the structs by hand
  * (ctypes, Julia) compares them with its own layout before the first call. */

@@ -145,6 +145,42 @@ PRECOND_PATH_DENSE, PRECOND_PATH_FUSED = 0, 1
 PRECOND_SCALING_NONE, PRECOND_SCALING_MAPS, PRECOND_SCALING_CALLER = 0, 1, 2
 
 
+class NufftWaveletParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("wavelet", C.c_int32), ("levels", C.c_int32), ("reserved", C.c_int32)]
+
+
+class NufftWaveletInfo(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("ndim", C.c_int32), ("dtype", C.c_int32), ("ntransforms", C.c_int32), ("device", C.c_int32),
+        ("wavelet", C.c_int32), ("taps", C.c_int32), ("levels", C.c_int32),
+        ("N", C.c_int64 * 3), ("scratch_bytes", C.c_int64), ("workspace_bytes", C.c_int64),
+    ]
+
+
+WAVELET_HAAR, WAVELET_DB2 = 0, 1
+WAVELET_IDS = {"haar": WAVELET_HAAR, "db2": WAVELET_DB2}
+
+
+class NufftFistaParams(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("max_iter", C.c_int32), ("check_every", C.c_int32), ("wavelet", C.c_int32),
+        ("levels", C.c_int32), ("reserved", C.c_int32),
+        ("tol", C.c_double), ("step", C.c_double), ("l1", C.c_double), ("lambda_", C.c_double),
+    ]
+
+
+class NufftFistaInfo(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("ntransforms", C.c_int32), ("dtype", C.c_int32), ("max_iter", C.c_int32),
+        ("check_every", C.c_int32), ("wavelet", C.c_int32), ("levels", C.c_int32), ("iterations_enqueued", C.c_int32),
+        ("tol", C.c_double), ("step", C.c_double), ("lambda_", C.c_double), ("array_bytes", C.c_int64), ("workspace_bytes", C.c_int64),
+    ]
+
+
+FISTA_MAX_ITER, FISTA_CONVERGED, FISTA_BREAKDOWN = 0, 1, 2
+FISTA_STATUS_NAMES = {FISTA_MAX_ITER: "max_iter", FISTA_CONVERGED: "converged", FISTA_BREAKDOWN: "breakdown"}
+
+
 class NufftDcfParams(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int32), ("max_iter", C.c_int32), ("check_every", C.c_int32), ("normalize", C.c_int32),
@@ -270,6 +306,25 @@ SYMBOLS = {
     "nufft_dcf_history": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int64, _P]),
     "nufft_sizeof_dcf_params": (C.c_int64, []),
     "nufft_sizeof_dcf_info": (C.c_int64, []),
+    "nufft_wavelet_create": (C.c_int, [C.POINTER(_P), _P, C.POINTER(NufftWaveletParams)]),
+    "nufft_wavelet_create_for_operator": (C.c_int, [C.POINTER(_P), _P, C.POINTER(NufftWaveletParams)]),
+    "nufft_wavelet_destroy": (C.c_int, [_P]),
+    "nufft_wavelet_get_info": (C.c_int, [_P, C.POINTER(NufftWaveletInfo)]),
+    "nufft_wavelet_forward": (C.c_int, [_P, _PP, _PP, _P]),
+    "nufft_wavelet_inverse": (C.c_int, [_P, _PP, _PP, _P]),
+    "nufft_wavelet_shrink": (C.c_int, [_P, _PP, _PP, C.POINTER(C.c_double), _P, _P]),
+    "nufft_sizeof_wavelet_params": (C.c_int64, []),
+    "nufft_sizeof_wavelet_info": (C.c_int64, []),
+    "nufft_toeplitz_max_eigenvalue": (C.c_int, [_P, _PP, C.c_int32, C.POINTER(C.c_double), _P]),
+    "nufft_fista_create": (C.c_int, [C.POINTER(_P), _P, C.POINTER(NufftFistaParams)]),
+    "nufft_fista_destroy": (C.c_int, [_P]),
+    "nufft_fista_set_l1": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int64]),
+    "nufft_fista_solve": (C.c_int, [_P, _PP, _PP, C.c_int, _P]),
+    "nufft_fista_get_info": (C.c_int, [_P, C.POINTER(NufftFistaInfo)]),
+    "nufft_fista_get_result": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int64, _P]),
+    "nufft_fista_history": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int64, _P]),
+    "nufft_sizeof_fista_params": (C.c_int64, []),
+    "nufft_sizeof_fista_info": (C.c_int64, []),
     "nufft_sizeof_params": (C.c_int64, []),
     "nufft_sizeof_info": (C.c_int64, []),
     "nufft_strerror": (C.c_char_p, [C.c_int]),
@@ -301,7 +356,9 @@ def _load():
                          ("nufft_sizeof_toeplitz_info", NufftToeplitzInfo), ("nufft_sizeof_cg_params", NufftCgParams),
                          ("nufft_sizeof_cg_info", NufftCgInfo), ("nufft_sizeof_precond_params", NufftPrecondParams),
                          ("nufft_sizeof_precond_info", NufftPrecondInfo), ("nufft_sizeof_dcf_params", NufftDcfParams),
-                         ("nufft_sizeof_dcf_info", NufftDcfInfo)):
+                         ("nufft_sizeof_dcf_info", NufftDcfInfo), ("nufft_sizeof_wavelet_params", NufftWaveletParams),
+                         ("nufft_sizeof_wavelet_info", NufftWaveletInfo), ("nufft_sizeof_fista_params", NufftFistaParams),
+                         ("nufft_sizeof_fista_info", NufftFistaInfo)):
         if getattr(lib, name)() != C.sizeof(mirror):
             raise ImportError(f"{LIB_PATH}: {name}() = {getattr(lib, name)()} but the ctypes mirror has {C.sizeof(mirror)} bytes "
                               "(include/nufft_mi355x.h and _lib.py disagree)")

@@ -1,0 +1,151 @@
+"""FISTA with an l1-wavelet prior on a :class:`ToeplitzOperator`, above the C ABI's ``nufft_fista_*`` entry points.
+
+    min_x  ½⟨x, (G + lam I) x⟩ − Re⟨b, x⟩ + Σ_c l1_c ‖D W x_c‖₁
+
+``W`` an orthogonal periodic wavelet transform, ``D`` the projection on its detail bands.  The whole loop runs in the library: per
+iteration one apply of the operator, one streaming kernel, one kernel per wavelet level each way and one decision kernel, every scalar
+on the device.  Plumbing only: argument checks, pointers, and reading the outcome back.
+
+    sol = ToeplitzFISTA(op, wavelet="db2", levels=3, l1=1e-3, maxiter=100, tol=1e-4)
+    x = sol.solve(b)
+    sol.iterations, sol.status, sol.change, sol.history()
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from . import _lib
+from ._lib import lib
+from .plan import DimensionMismatch, _check, _ptr_table
+from .toeplitz import ToeplitzOperator
+from .wavelet import _wavelet_id
+
+
+class ToeplitzFISTA:
+    """``ToeplitzFISTA(op, wavelet="db2", levels=3, l1=0.0, step=None, lam=0.0, maxiter=100, tol=1e-4, check_every=0)``.
+
+    ``l1``: a scalar or one weight per component.  ``lam``: the Tikhonov weight (named as in :class:`ToeplitzCG`).  ``step``: the step
+    ``τ``; None computes ``1 / (1.05 · max(op.max_eigenvalue()) + lam)`` once, here (the operator then needs its spectrum already).
+    ``check_every=0`` enqueues all ``maxiter`` iterations without synchronising (components whose relative change reached ``tol`` are
+    frozen on the device; legal inside ``torch.cuda.graph``); ``check_every=k`` lets the host stop early.  Both return the same bits.
+    The solver keeps ``op`` alive; ``op.set_points`` / ``set_spectrum`` between two solves is allowed.  On a coupled operator the
+    components are one system: one change and one stopping test, reported identically for every component."""
+
+    def __init__(self, op: ToeplitzOperator, wavelet: str = "db2", levels: int = 3, l1=0.0, step=None, lam: float = 0.0,
+                 maxiter: int = 100, tol: float = 1e-4, check_every: int = 0):
+        if not isinstance(op, ToeplitzOperator):
+            raise ValueError("ToeplitzFISTA takes a ToeplitzOperator")
+        for name, v in (("maxiter", maxiter), ("check_every", check_every), ("levels", levels)):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError(f"{name} must be an integer")
+        l1s = [float(l1)] * op.ntransforms if isinstance(l1, (int, float)) else [float(v) for v in l1]
+        if len(l1s) != op.ntransforms:
+            raise DimensionMismatch(f"wrong amount of l1 weights (expected {op.ntransforms})")
+        wid = _wavelet_id(wavelet)
+        if step is None:
+            op._require_gpu()
+            step = 1.0 / (1.05 * max(op.max_eigenvalue()) + float(lam))
+        prm = _lib.NufftFistaParams()
+        prm.struct_size = C.sizeof(_lib.NufftFistaParams)
+        prm.max_iter, prm.check_every, prm.wavelet, prm.levels = maxiter, check_every, wid, levels
+        prm.tol, prm.step, prm.l1, prm.lambda_ = float(tol), float(step), l1s[0], float(lam)
+        self._handle = C.c_void_p()
+        _check(lib.nufft_fista_create(C.byref(self._handle), op._handle, C.byref(prm)))
+        self.op = op
+        self.wavelet, self.levels, self.l1, self.step, self.lam = wavelet, levels, tuple(l1s), float(step), float(lam)
+        self.maxiter, self.tol, self.check_every = maxiter, float(tol), check_every
+        try:
+            _check(lib.nufft_fista_set_l1(self._handle, (C.c_double * len(l1s))(*l1s), len(l1s)))
+        except Exception:
+            self.close()
+            raise
+
+    def close(self):
+        h = getattr(self, "_handle", None)
+        if h is not None and h.value:
+            lib.nufft_fista_destroy(h)
+            self._handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _require_open(self):
+        """The library keeps a pointer to the operator: refuse to follow it once either object has been closed."""
+        if not self._handle.value:
+            raise ValueError("this ToeplitzFISTA has been closed")
+        if not self.op._handle.value:
+            raise ValueError("the ToeplitzOperator of this solver has been closed: the operator must outlive the solver")
+
+    def info(self) -> _lib.NufftFistaInfo:
+        self._require_open()
+        out = _lib.NufftFistaInfo()
+        out.struct_size = C.sizeof(_lib.NufftFistaInfo)
+        _check(lib.nufft_fista_get_info(self._handle, C.byref(out)))
+        return out
+
+    def solve(self, b, x0=None, out=None):
+        """``b``: a tensor of ``plan.shape`` or a tuple of ntransforms such tensors (only read).  ``x0``: starting guess (None = zero);
+        ``out``: where the solution goes (may be ``x0``; None = new tensors; never ``b``).  Returns ``out``."""
+        self._require_open()
+        op = self.op
+        op._require_gpu()
+        single = isinstance(b, torch.Tensor)
+        b_t = (b,) if single else tuple(b)
+        op._check_uniform(b_t, "right-hand side")
+        if out is None:
+            out_t = tuple(torch.empty_like(v) for v in b_t)
+            out = out_t[0] if single else out_t
+        else:
+            out_t = (out,) if isinstance(out, torch.Tensor) else tuple(out)
+            op._check_uniform(out_t, "output")
+        if x0 is not None:
+            x0_t = (x0,) if isinstance(x0, torch.Tensor) else tuple(x0)
+            op._check_uniform(x0_t, "starting guess")
+            for o, g in zip(out_t, x0_t):
+                if o.data_ptr() != g.data_ptr():
+                    o.copy_(g)
+        _check(lib.nufft_fista_solve(self._handle, _ptr_table(out_t), _ptr_table(b_t), 0 if x0 is None else 1, op._stream()))
+        return out
+
+    def _result(self):
+        self._require_open()
+        n = self.op.ntransforms
+        it, st, ch = (C.c_int32 * n)(), (C.c_int32 * n)(), (C.c_double * n)()
+        _check(lib.nufft_fista_get_result(self._handle, it, st, ch, n, self.op._stream()))
+        return list(it), list(st), list(ch)
+
+    @property
+    def iterations(self):
+        """Per component: iterations that changed it (synchronises the current stream)."""
+        return tuple(self._result()[0])
+
+    @property
+    def status(self):
+        """Per component: ``"converged"``, ``"max_iter"`` or ``"breakdown"`` (a relative change that is not finite)."""
+        return tuple(_lib.FISTA_STATUS_NAMES[s] for s in self._result()[1])
+
+    @property
+    def change(self):
+        """Per component: ``‖x⁺ − x‖ / ‖x⁺‖`` of the last iteration that changed it."""
+        return tuple(self._result()[2])
+
+    def history(self) -> torch.Tensor:
+        """``[max(iterations), ntransforms, 2]`` (host, float64): relative change and ``‖D W x‖₁`` after every iteration; NaN where an
+        iteration did not change the component."""
+        self._require_open()
+        n = self.op.ntransforms
+        buf = (C.c_double * (self.maxiter * n * 2))()
+        _check(lib.nufft_fista_history(self._handle, buf, len(buf), self.op._stream()))
+        rows = max(self.iterations)
+        return torch.tensor(list(buf), dtype=torch.float64).reshape(self.maxiter, n, 2)[:rows].clone()
+
+    def __repr__(self):
+        i = self.info()
+        return (f"ToeplitzFISTA on a {self.op.ndim}-dimensional {self.op.Z} operator, {self.wavelet!r} x {self.levels} levels, "
+                f"step = {self.step:g}, lam = {self.lam:g}, maxiter = {self.maxiter}, tol = {self.tol:g}, check_every = {self.check_every}, "
+                f"{i.workspace_bytes / 1e6:.1f} MB")

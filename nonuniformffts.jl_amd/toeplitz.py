@@ -315,6 +315,25 @@ class ToeplitzOperator:
             sol.close()
         return out
 
+    def max_eigenvalue(self, iters: int = 30, v0=None):
+        """The Rayleigh quotient ``<v, G v> / <v, v>`` (float64) after ``iters`` applies of a power iteration on what ``apply`` computes
+        now (plain, with coil maps, coupled): a lower bound of ``λmax``, one value per component as a tuple (coupled components are one
+        vector: the same value for each).  ``v0``: start vectors like the input of ``apply`` (None: a seeded ``torch.randn``).
+        Synchronises the current stream; not inside a graph capture."""
+        self._require_gpu()
+        self._require_open()
+        if isinstance(iters, bool) or not isinstance(iters, int):
+            raise ValueError("iters must be an integer")
+        if v0 is None:
+            gen = torch.Generator(device=self.device).manual_seed(0)
+            v_t = tuple(torch.randn(self.shape, dtype=self.Z, device=self.device, generator=gen) for _ in range(self.ntransforms))
+        else:
+            v_t = (v0,) if isinstance(v0, torch.Tensor) else tuple(v0)
+            self._check_uniform(v_t, "start vector")
+        out = (C.c_double * self.ntransforms)()
+        _check(lib.nufft_toeplitz_max_eigenvalue(self._handle, _ptr_table(v_t), iters, out, self._stream()))
+        return tuple(out)
+
     def multiplier(self, a: Optional[int] = None, b: Optional[int] = None) -> torch.Tensor:
         """The real multiplier ``K`` (shape ``padded_shape``): a view of the device array the operator holds — valid while the
         operator lives, rewritten by the next ``set_points`` / ``set_spectrum``; ``.clone()`` it to keep it.
