@@ -1037,6 +1037,93 @@ int nufft_fista_history(nufft_fista* f, double* host_out, int64_t capacity, void
 int64_t nufft_sizeof_fista_params(void);
 int64_t nufft_sizeof_fista_info(void);
 
+/* ---- Locally low-rank proximal map ------------------------------- */
+/* The K = ntransforms arrays x_a (complex(T)[N...], as those of nufft_toeplitz_apply) are cut into spatial blocks of b_1 x ... x b_D
+ * cells; storage index i_d belongs to block floor(((i_d − s_d) mod N_d) / b_d), s the cyclic shift, 0 <= s_d < b_d.  Like the wavelet
+ * transform the map acts on the arrays AS STORED and is periodic in the storage index.  Every block gives a B x K Casorati matrix M
+ * (B = Π b_d, column a = the block's cells of x_a), and the map is singular-value soft-thresholding of every M,
+ *
+ *     prox_{t ‖·‖_*}(M) = U max(Σ − t, 0) V^H,
+ *
+ * computed without an SVD of M:  H = M^H M (K x K, accumulated in FP64 for both element types, one fixed order);  H = V Λ V^H by cyclic
+ * complex Jacobi in FP64 (row-cyclic rotation order; a rotation is skipped when |h_pq|² <= 2^-106 h_pp h_qq or |h_pq| <= 2^-60 trace H;
+ * the sweeps stop after the first one that rotates nothing, at most jacobi_sweeps_max);  σ_i = sqrt(max(λ_i, 0)),
+ * f_i = σ_i > t ? 1 − t / σ_i : 0;  M <- M V diag(f) V^H.  Nothing is divided where σ_i <= t: a zero block stays zero.  K = 1 is block-wise
+ * group shrinkage.  One kernel reads every array once and writes it once; a block's values stay in LDS in between.  No atomics: two
+ * runs and a replayed hipGraph give the same bits.
+ *
+ * Block sides are powers of two, 1 ... 16, each dividing its N_d, with B · K <= 8192.
+ *
+ * Added after ABI 104 without changing NUFFT_MI355X_VERSION: detect by symbol (dlsym nufft_llr_create) and compare
+ * nufft_sizeof_llr_params() / nufft_sizeof_llr_info() with your own. */
+typedef struct nufft_llr nufft_llr; /* opaque */
+
+typedef struct nufft_llr_params {
+    int32_t struct_size;     /* sizeof(nufft_llr_params) of the caller's header (0 = this layout)                                  */
+    int32_t block[3];        /* block sides: powers of two, 1 ... 16, b_d | N_d; 1 beyond ndim                                     */
+    int32_t shifts;          /* 0 / 1: nufft_fista_create_llr draws a new cyclic shift every iteration (ignored by nufft_llr_apply) */
+    int32_t reserved;        /* 0                                                                                                  */
+    uint64_t seed;           /* of the shift sequence                                                                              */
+} nufft_llr_params;
+
+typedef struct nufft_llr_info {
+    int32_t struct_size;     /* sizeof(nufft_llr_info) of the caller's header, set before the call (0 = this layout)               */
+    int32_t ndim, dtype, ntransforms, device;
+    int32_t block[3];
+    int32_t shifts;
+    int64_t N[3];            /* 1 beyond ndim                                                                                      */
+    int64_t blocks;          /* Π N_d / b_d                                                                                        */
+    int64_t workspace_bytes; /* device bytes owned: the partial sums                                                               */
+    int32_t jacobi_sweeps_max;
+    int32_t waves_per_cu;    /* the LDS bound: resident waves per compute unit that the kernel's LDS use admits for this (element
+                                type, K, B).  nufft_llr_apply's variant reaches it; the solver's fused variant needs more registers
+                                and is limited to 20 waves per compute unit where this reads more            */
+} nufft_llr_info;
+
+/* Takes element type, shape, ntransforms and device from the plan; the plan is not kept.  Refusals, in order: null arguments, a
+ * struct_size smaller than the published layout NUFFT_ERR_INVALID_ARG; a real-data plan NUFFT_ERR_UNSUPPORTED; a block side that is no
+ * power of two in 1 ... 16 (or not 1 beyond ndim), shifts not 0 / 1, a b_d that does not divide N_d NUFFT_ERR_INVALID_ARG; more than 16
+ * transforms or B · K > 8192 NUFFT_ERR_UNSUPPORTED; a host-only plan NUFFT_ERR_NO_DEVICE. */
+int nufft_llr_create(nufft_llr** out, const nufft_plan* plan, const nufft_llr_params* params);
+/* The same from a Toeplitz operator (the operator is not kept). */
+int nufft_llr_create_for_operator(nufft_llr** out, const nufft_toeplitz* tz, const nufft_llr_params* params);
+int nufft_llr_destroy(nufft_llr* l);
+/* Static facts and sizes; does not synchronise. */
+int nufft_llr_get_info(const nufft_llr* l, nufft_llr_info* out);
+/* out = prox_{t ‖·‖_LLR}(in) with the given shift (host array of ndim values, 0 <= shift[d] < b_d; NULL = zero shift).  Host tables of
+ * ntransforms device pointers, 16-byte aligned.  out[c] may be exactly in[c] (a block is owned by one workgroup, which stores after it
+ * has loaded); any other overlap between an output and an input or another output is refused.  nuc_out_device (device, double[1], may be
+ * NULL): Σ over all blocks of the kept singular values max(σ_i − t, 0), the LLR norm of the output, FP64, summed in one fixed order.
+ * Allocates nothing, does not synchronise, hipGraph-capture safe; the object keeps the partial sums: one call at a time per object.
+ * Refusals, before anything is enqueued: a null table or vector, a pointer that is not 16-byte aligned, a partial overlap, t < 0 or not
+ * finite, a shift outside [0, b_d) NUFFT_ERR_INVALID_ARG. */
+int nufft_llr_apply(nufft_llr* l, void* const* out, const void* const* in, double t, const int32_t* shift, double* nuc_out_device, void* stream);
+int64_t nufft_sizeof_llr_params(void);
+int64_t nufft_sizeof_llr_info(void);
+
+/* ---- FISTA with a locally low-rank prior ------------------------- */
+/* Minimises  ½ <x, (G + μ I) x> − Re<b, x> + nuc · Σ_blocks ‖M_block(x)‖_*  with the iteration of nufft_fista_create, the proximal map
+ * being the one above with t = τ · nuc.  The prior couples the components: they are ONE system with one change, one flag and one status,
+ * reported identically for every component, whether the operator is coupled or not.  One iteration is
+ *
+ *     q = G z                                                                          nufft_toeplitz_apply
+ *     v = z − τ (q + μ z − b) on load;  x⁺ = prox(v);  z = x⁺ + β (x⁺ − x), x = x⁺ on store    one kernel
+ *     change, done flag, history                                                       the decision kernel
+ *
+ * The solver owns two arrays per component (z, q; nufft_fista_info.array_bytes says so; wavelet and levels read 0).  Reads max_iter,
+ * check_every, tol, step and lambda from `params`; wavelet, levels and l1 must be 0 (NUFFT_ERR_INVALID_ARG otherwise); nuc >= 0, finite.
+ * History column 2 holds Σ_blocks ‖M_block(x⁺)‖_* after the iteration.  nufft_fista_set_l1 on such a solver and nufft_fista_set_nuc on a
+ * wavelet solver return NUFFT_ERR_INVALID_ARG.  Everything else (solve, result, history, capture with check_every = 0, set_points /
+ * set_spectrum between two solves, bit-identical modes) is as for nufft_fista_create.
+ *
+ * llr->shifts = 1: iteration it uses the cyclic shift s(it), which depends on it and llr->seed only:  state_0 = seed;  for it = 1, 2, ...
+ * and d = 1 ... ndim:  state <- state · 6364136223846793005 + 1442695040888963407 (mod 2^64),  s_d = (state >> 33) mod b_d.  The host passes
+ * the shift as kernel arguments.  With shifts the objective changes every iteration and the relative change does not fall to a small
+ * tol (it stalls around 1e-2 ... 7e-2 on small systems): shifts are for tol = 0 and a fixed max_iter. */
+int nufft_fista_create_llr(nufft_fista** out, nufft_toeplitz* tz, const nufft_fista_params* params, const nufft_llr_params* llr, double nuc);
+/* The weight of the LLR prior for the following solves (>= 0, finite). */
+int nufft_fista_set_nuc(nufft_fista* f, double nuc);
+
 /* ---- misc ----------------------------------------------------------------------------- */
 /* sizeof(nufft_params) / sizeof(nufft_info) of the library build: a binding that mirrors the structs by hand
  * (ctypes, Julia) compares them with its own layout before the first call. */

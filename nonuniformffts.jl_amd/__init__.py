@@ -21,6 +21,7 @@ from .toeplitz import ToeplitzOperator, coil_combine, coil_expand  # noqa: F401
 from .cg import ToeplitzCG  # noqa: F401
 from .precond import ToeplitzPreconditioner  # noqa: F401
 from .wavelet import WaveletTransform  # noqa: F401
+from .llr import LocallyLowRank  # noqa: F401
 from .fista import ToeplitzFISTA  # noqa: F401
 from .dcf import DensityCompensation, density_weights  # noqa: F401
 from . import autograd  # noqa: F401
@@ -33,6 +34,6 @@ __all__ = [
     "PlanNUFFT3", "set_points3", "exec_type3", "exec_type3_grad",
     "exec_type2_grad", "interpolate_grad", "autograd",
     "ToeplitzOperator", "ToeplitzCG", "ToeplitzPreconditioner", "coil_expand", "coil_combine",
-    "WaveletTransform", "ToeplitzFISTA",
+    "WaveletTransform", "LocallyLowRank", "ToeplitzFISTA",
     "DensityCompensation", "density_weights",
 ]

@@ -177,6 +177,19 @@ class NufftFistaInfo(C.Structure):
     ]
 
 
+class NufftLlrParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("block", C.c_int32 * 3), ("shifts", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_uint64)]
+
+
+class NufftLlrInfo(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("ndim", C.c_int32), ("dtype", C.c_int32), ("ntransforms", C.c_int32), ("device", C.c_int32),
+        ("block", C.c_int32 * 3), ("shifts", C.c_int32),
+        ("N", C.c_int64 * 3), ("blocks", C.c_int64), ("workspace_bytes", C.c_int64),
+        ("jacobi_sweeps_max", C.c_int32), ("waves_per_cu", C.c_int32),
+    ]
+
+
 FISTA_MAX_ITER, FISTA_CONVERGED, FISTA_BREAKDOWN = 0, 1, 2
 FISTA_STATUS_NAMES = {FISTA_MAX_ITER: "max_iter", FISTA_CONVERGED: "converged", FISTA_BREAKDOWN: "breakdown"}
 
@@ -325,6 +338,15 @@ SYMBOLS = {
     "nufft_fista_history": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int64, _P]),
     "nufft_sizeof_fista_params": (C.c_int64, []),
     "nufft_sizeof_fista_info": (C.c_int64, []),
+    "nufft_llr_create": (C.c_int, [C.POINTER(_P), _P, C.POINTER(NufftLlrParams)]),
+    "nufft_llr_create_for_operator": (C.c_int, [C.POINTER(_P), _P, C.POINTER(NufftLlrParams)]),
+    "nufft_llr_destroy": (C.c_int, [_P]),
+    "nufft_llr_get_info": (C.c_int, [_P, C.POINTER(NufftLlrInfo)]),
+    "nufft_llr_apply": (C.c_int, [_P, _PP, _PP, C.c_double, C.POINTER(C.c_int32), _P, _P]),
+    "nufft_sizeof_llr_params": (C.c_int64, []),
+    "nufft_sizeof_llr_info": (C.c_int64, []),
+    "nufft_fista_create_llr": (C.c_int, [C.POINTER(_P), _P, C.POINTER(NufftFistaParams), C.POINTER(NufftLlrParams), C.c_double]),
+    "nufft_fista_set_nuc": (C.c_int, [_P, C.c_double]),
     "nufft_sizeof_params": (C.c_int64, []),
     "nufft_sizeof_info": (C.c_int64, []),
     "nufft_strerror": (C.c_char_p, [C.c_int]),
@@ -358,7 +380,8 @@ def _load():
                          ("nufft_sizeof_precond_info", NufftPrecondInfo), ("nufft_sizeof_dcf_params", NufftDcfParams),
                          ("nufft_sizeof_dcf_info", NufftDcfInfo), ("nufft_sizeof_wavelet_params", NufftWaveletParams),
                          ("nufft_sizeof_wavelet_info", NufftWaveletInfo), ("nufft_sizeof_fista_params", NufftFistaParams),
-                         ("nufft_sizeof_fista_info", NufftFistaInfo)):
+                         ("nufft_sizeof_fista_info", NufftFistaInfo), ("nufft_sizeof_llr_params", NufftLlrParams),
+                         ("nufft_sizeof_llr_info", NufftLlrInfo)):
         if getattr(lib, name)() != C.sizeof(mirror):
             raise ImportError(f"{LIB_PATH}: {name}() = {getattr(lib, name)()} but the ctypes mirror has {C.sizeof(mirror)} bytes "
                               "(include/nufft_mi355x.h and _lib.py disagree)")

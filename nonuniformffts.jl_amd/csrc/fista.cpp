@@ -4,6 +4,9 @@
 // levels (threshold and ‖·‖₁ partials on store), its synthesis levels (the momentum step and the partials of ‖x⁺ − x‖², ‖x⁺‖² on the
 // last level's store) and the decision kernel.  Every scalar lives on the device; with check_every > 0 the host looks at the done flags
 // now and then, and at nothing else.
+//
+// With the locally low-rank prior (nufft_fista_create_llr) an iteration is the apply, llr.h's kernel (gradient
+// step on load, proximal map, momentum step on store) and the decision kernel of one joint system; the wavelet path is untouched by it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,6 +18,7 @@
 
 #include "fista.h"
 #include "host_common.h"
+#include "llr.h"
 #include "wavelet.h"
 
 using namespace nufft;
@@ -22,6 +26,8 @@ using namespace nufft;
 struct nufft_fista {
     nufft_toeplitz* tz = nullptr;
     nufft_wavelet* wav = nullptr;
+    nufft_llr* llr = nullptr;         // the locally low-rank prior instead of the wavelet one
+    double nuc = 0.0;
     int dtype = NUFFT_F64, C = 1, device = -1, num_cus = 256, G = 1, G0 = 1;
     int max_iter = 1, check_every = 0, enqueued = -1, wavelet = 0, levels = 1;
     double tol = 0.0, step = 1.0, lambda = 0.0;
@@ -45,6 +51,7 @@ size_t hist_bytes(const nufft_fista* s) { return (size_t)s->max_iter * s->C * 2 
 void release(nufft_fista* s) {
     if (!s) return;
     if (s->wav) (void)nufft_wavelet_destroy(s->wav);
+    if (s->llr) (void)nufft_llr_destroy(s->llr);
     if (s->device >= 0) {
         DeviceGuard g(s->device);
         for (void* p : {s->d_z, s->d_q, s->d_c, s->d_mom, s->d_hist})
@@ -89,16 +96,8 @@ int for_batches(const nufft_fista* s, FistaLaunch& a, void* const* x, const void
 
 bool weight_ok(double v) { return std::isfinite(v) && v >= 0.0; }
 
-}  // namespace
-
-extern "C" {
-
-int64_t nufft_sizeof_fista_params(void) { return (int64_t)sizeof(nufft_fista_params); }
-int64_t nufft_sizeof_fista_info(void) { return (int64_t)sizeof(nufft_fista_info); }
-
-int nufft_fista_create(nufft_fista** out, nufft_toeplitz* tz, const nufft_fista_params* params) {
-    if (!out || !tz || !params) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
-    *out = nullptr;
+// nufft_fista_create (lp null) and nufft_fista_create_llr
+int create(nufft_fista** out, nufft_toeplitz* tz, const nufft_fista_params* params, const nufft_llr_params* lp, double nuc) {
     nufft_toeplitz_info ti;
     std::memset(&ti, 0, sizeof(ti));
     ti.struct_size = (int32_t)sizeof(ti);
@@ -112,6 +111,9 @@ int nufft_fista_create(nufft_fista** out, nufft_toeplitz* tz, const nufft_fista_
     if (!weight_ok(p.tol)) return fail(NUFFT_ERR_INVALID_ARG, "tol must be finite and not negative");
     if (!weight_ok(p.l1)) return fail(NUFFT_ERR_INVALID_ARG, "l1 must be finite and not negative");
     if (!weight_ok(p.lambda)) return fail(NUFFT_ERR_INVALID_ARG, "lambda must be finite and not negative");
+    if (lp && (p.wavelet != 0 || p.levels != 0 || p.l1 != 0.0))
+        return fail(NUFFT_ERR_INVALID_ARG, "wavelet, levels and l1 must be 0 for the locally low-rank prior");
+    if (lp && !weight_ok(nuc)) return fail(NUFFT_ERR_INVALID_ARG, "nuc must be finite and not negative");
     if (!std::isfinite(p.step) || !(p.step > 0.0))
         return fail(NUFFT_ERR_INVALID_ARG, "step must be finite and positive (1 / (lambda_max + lambda): nufft_toeplitz_max_eigenvalue)");
 
@@ -122,10 +124,13 @@ int nufft_fista_create(nufft_fista** out, nufft_toeplitz* tz, const nufft_fista_
     wp.struct_size = (int32_t)sizeof(wp);
     wp.wavelet = p.wavelet;
     wp.levels = p.levels;
-    if ((rc = wavelet_create_geometry(&s->wav, ti.dtype, ti.ndim, ti.N, ti.ntransforms, ti.device, &wp))) {      // host-only: refused here
+    rc = lp ? llr_create_geometry(&s->llr, ti.dtype, ti.ndim, ti.N, ti.ntransforms, ti.device, lp)
+            : wavelet_create_geometry(&s->wav, ti.dtype, ti.ndim, ti.N, ti.ntransforms, ti.device, &wp);      // host-only: refused here
+    if (rc) {
         delete s;
         return rc;
     }
+    s->nuc = nuc;
     s->tz = tz;
     s->dtype = ti.dtype;
     s->C = ti.ntransforms;
@@ -142,17 +147,17 @@ int nufft_fista_create(nufft_fista** out, nufft_toeplitz* tz, const nufft_fista_
     s->n = ti.N[0] * ti.N[1] * ti.N[2];
     const size_t rb = real_bytes(s->dtype), comp = padded((size_t)s->n * 2 * rb);
     s->stride = (int64_t)(comp / rb);
-    s->array_bytes = 3 * (int64_t)s->C * (int64_t)comp;
+    s->array_bytes = (lp ? 2 : 3) * (int64_t)s->C * (int64_t)comp;      // the locally low-rank kernel needs no coefficient array
 
     DeviceGuard guard(s->device);
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device) == hipSuccess && cus > 0) s->num_cus = cus;
     else (void)hipGetLastError();
     s->G = fista_workgroups(s->dtype, s->n, s->num_cus);
-    s->G0 = wavelet_level0_workgroups(s->wav);
+    s->G0 = lp ? 1 : wavelet_level0_workgroups(s->wav);
     auto alloc = [&](void** ptr, size_t bytes) { return alloc_buffer(s->own_bytes, "FISTA", ptr, bytes); };
-    if ((rc = alloc(&s->d_z, (size_t)s->C * comp)) || (rc = alloc(&s->d_q, (size_t)s->C * comp)) || (rc = alloc(&s->d_c, (size_t)s->C * comp)) ||
-        (rc = alloc(&s->d_mom, (size_t)s->C * s->G0 * 2 * sizeof(double))) || (rc = alloc(&s->d_hist, hist_bytes(s))) ||
+    if ((rc = alloc(&s->d_z, (size_t)s->C * comp)) || (rc = alloc(&s->d_q, (size_t)s->C * comp)) ||
+        (!lp && ((rc = alloc(&s->d_c, (size_t)s->C * comp)) || (rc = alloc(&s->d_mom, (size_t)s->C * s->G0 * 2 * sizeof(double))))) || (rc = alloc(&s->d_hist, hist_bytes(s))) ||
         (rc = s->scal.create(s->own_bytes, "FISTA", scal_bytes(s), "hipHostMalloc of the solver's host mirror failed"))) {
         const std::string keep = nufft_last_error_message();
         release(s);
@@ -167,9 +172,79 @@ int nufft_fista_create(nufft_fista** out, nufft_toeplitz* tz, const nufft_fista_
     for (int c = 0; c < s->C; ++c) {
         s->ztab.push_back(static_cast<char*>(s->d_z) + (size_t)c * comp);
         s->qtab.push_back(static_cast<char*>(s->d_q) + (size_t)c * comp);
-        s->ctab.push_back(static_cast<char*>(s->d_c) + (size_t)c * comp);
+        if (s->d_c) s->ctab.push_back(static_cast<char*>(s->d_c) + (size_t)c * comp);
     }
     *out = s;
+    return NUFFT_OK;
+}
+
+// One solve with the locally low-rank prior: the components are one system.
+int solve_llr(nufft_fista* s, FistaLaunch& a, void* const* x, const void* const* b, hipStream_t stream) {
+    int rc;
+    LlrLaunch l = llr_launch_template(s->llr);
+    l.mode = LLR_FISTA;
+    l.t = s->step * s->nuc;
+    l.z = s->d_z;
+    l.q = s->d_q;
+    l.stride = s->stride;
+    l.step = s->step;
+    l.lambda = s->lambda;
+    l.flag = a.s.flag;
+    for (int c = 0; c < s->C; ++c) {
+        l.in[c] = b[c];
+        l.out[c] = x[c];
+    }
+    const int64_t G = llr_workgroups(l);
+    const FistaScalars host = scalars_at(s, s->scal.host);
+    uint64_t state = llr_seed(s->llr);
+    double t = 1.0;
+    for (int it = 1; it <= s->max_iter; ++it) {
+        a.it = it;
+        const double t_next = 0.5 * (1.0 + std::sqrt(1.0 + 4.0 * t * t));
+        l.beta = (t - 1.0) / t_next;
+        t = t_next;
+        if (llr_shifts(s->llr))
+            for (int d = 0; d < l.D; ++d) {
+                state = state * 6364136223846793005ull + 1442695040888963407ull;
+                l.shift[d] = (int)((state >> 33) % (uint64_t)llr_block_side(s->llr, d));
+            }
+        if ((rc = nufft_toeplitz_apply(s->tz, s->qtab.data(), s->ztab.data(), stream))) return rc;                        // q = G z
+        hipError_t e = launch_llr(l, stream);
+        if (e == hipSuccess) e = launch_fista_decide_llr(a, l.part, G, stream);
+        if (e != hipSuccess) return fail(NUFFT_ERR_HIP, std::string("launch of a FISTA kernel: ") + hipGetErrorString(e));
+        s->enqueued = it;
+        if (s->check_every > 0 && it % s->check_every == 0 && it < s->max_iter) {
+            if ((rc = s->scal.fetch(stream))) return rc;
+            if (host.flag[0] != 0) break;
+        }
+    }
+    return NUFFT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t nufft_sizeof_fista_params(void) { return (int64_t)sizeof(nufft_fista_params); }
+int64_t nufft_sizeof_fista_info(void) { return (int64_t)sizeof(nufft_fista_info); }
+
+int nufft_fista_create(nufft_fista** out, nufft_toeplitz* tz, const nufft_fista_params* params) {
+    if (!out || !tz || !params) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    return create(out, tz, params, nullptr, 0.0);
+}
+
+int nufft_fista_create_llr(nufft_fista** out, nufft_toeplitz* tz, const nufft_fista_params* params, const nufft_llr_params* llr, double nuc) {
+    if (!out || !tz || !params || !llr) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    return create(out, tz, params, llr, nuc);
+}
+
+int nufft_fista_set_nuc(nufft_fista* s, double nuc) {
+    if (!s) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    if (!s->llr) return fail(NUFFT_ERR_INVALID_ARG, "nufft_fista_set_nuc on a solver with the wavelet prior (nufft_fista_set_l1)");
+    if (!weight_ok(nuc)) return fail(NUFFT_ERR_INVALID_ARG, "nuc must be finite and not negative");
+    s->nuc = nuc;
     return NUFFT_OK;
 }
 
@@ -180,6 +255,7 @@ int nufft_fista_destroy(nufft_fista* f) {
 
 int nufft_fista_set_l1(nufft_fista* s, const double* l1, int64_t count) {
     if (!s || !l1) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    if (s->llr) return fail(NUFFT_ERR_INVALID_ARG, "nufft_fista_set_l1 on a solver with the locally low-rank prior (nufft_fista_set_nuc)");
     if (count != s->C) return fail(NUFFT_ERR_INVALID_ARG, "count must be ntransforms");
     for (int c = 0; c < s->C; ++c)
         if (!weight_ok(l1[c])) return fail(NUFFT_ERR_INVALID_ARG, "l1 must be finite and not negative");
@@ -189,10 +265,20 @@ int nufft_fista_set_l1(nufft_fista* s, const double* l1, int64_t count) {
 
 int nufft_fista_get_info(const nufft_fista* s, nufft_fista_info* o) {
     if (!s || !o) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
-    nufft_wavelet_info wi;
-    std::memset(&wi, 0, sizeof(wi));
-    wi.struct_size = (int32_t)sizeof(wi);
-    if (int rc = nufft_wavelet_get_info(s->wav, &wi)) return rc;
+    int64_t prior_bytes = 0;
+    if (s->llr) {
+        nufft_llr_info li;
+        std::memset(&li, 0, sizeof(li));
+        li.struct_size = (int32_t)sizeof(li);
+        if (int rc = nufft_llr_get_info(s->llr, &li)) return rc;
+        prior_bytes = li.workspace_bytes;
+    } else {
+        nufft_wavelet_info wi;
+        std::memset(&wi, 0, sizeof(wi));
+        wi.struct_size = (int32_t)sizeof(wi);
+        if (int rc = nufft_wavelet_get_info(s->wav, &wi)) return rc;
+        prior_bytes = wi.workspace_bytes;
+    }
     nufft_fista_info i;
     std::memset(&i, 0, sizeof(i));
     i.ntransforms = s->C;
@@ -206,7 +292,7 @@ int nufft_fista_get_info(const nufft_fista* s, nufft_fista_info* o) {
     i.step = s->step;
     i.lambda = s->lambda;
     i.array_bytes = s->array_bytes;
-    i.workspace_bytes = s->own_bytes + wi.workspace_bytes;
+    i.workspace_bytes = s->own_bytes + prior_bytes;
     write_info(o, i);
     return NUFFT_OK;
 }
@@ -251,13 +337,14 @@ int nufft_fista_solve(nufft_fista* s, void* const* x, const void* const* b, int 
     a.joint = nufft_toeplitz_num_coupled(s->tz) > 0 ? 1 : 0;
     a.mom_part = static_cast<const double*>(s->d_mom);
     a.G0 = s->G0;
-    a.l1_part = wavelet_partials(s->wav, &a.P);
+    if (s->wav) a.l1_part = wavelet_partials(s->wav, &a.P);
     a.s = scalars_at(s, s->scal.dev);
     for (int c = 0; c < s->C; ++c) s->thr[c] = s->step * s->l1[c];
 
     s->enqueued = 0;
     const bool warm = use_x0 != 0;
     if ((rc = for_batches(s, a, x, b, [&](const FistaLaunch& l) { return launch_fista_start(l, warm, stream); }))) return rc;
+    if (s->llr) return solve_llr(s, a, x, b, stream);
     const FistaScalars host = scalars_at(s, s->scal.host);
     double t = 1.0;
     for (int it = 1; it <= s->max_iter; ++it) {

@@ -46,6 +46,8 @@ hipError_t launch_fista_start(const FistaLaunch& a, bool warm, hipStream_t strea
 hipError_t launch_fista_gradient(const FistaLaunch& a, hipStream_t stream);
 // the decision of iteration a.it from the partial sums
 hipError_t launch_fista_decide(const FistaLaunch& a, hipStream_t stream);
+// the same for a solver with the locally low-rank prior (one system): part[G][3] of llr.h's kernel, the outcome stored for all a.C components
+hipError_t launch_fista_decide_llr(const FistaLaunch& a, const double* part, int64_t G, hipStream_t stream);
 int fista_workgroups(int dtype, int64_t n, int num_cus);
 
 // Power iteration (nufft_toeplitz_max_eigenvalue): v, g are the solver's own arrays (component c at + c * stride reals).

@@ -110,6 +110,35 @@ __global__ __launch_bounds__(kThreads) void fista_decide_kernel(FistaLaunch a) {
     }
 }
 
+// The decision of a solver with the locally low-rank prior: ONE system whatever the operator, so one workgroup sums the rows
+// part[g][3] (‖x⁺ − x‖², ‖x⁺‖², Σ kept singular values) of the fused kernel's workgroups and stores the same outcome for every component
+__global__ __launch_bounds__(kThreads) void fista_decide_llr_kernel(FistaLaunch a, const double* part, int64_t G) {
+    __shared__ double lds[kWaves];
+    if (a.s.flag[0]) return;
+    double dd = 0.0, xx = 0.0, nuc = 0.0;
+    for (int64_t g = threadIdx.x; g < G; g += kThreads) {
+        dd += part[g * 3];
+        xx += part[g * 3 + 1];
+        nuc += part[g * 3 + 2];
+    }
+    dd = block_reduce<Sum>(dd, lds);
+    xx = block_reduce<Sum>(xx, lds);
+    nuc = block_reduce<Sum>(nuc, lds);
+    if (threadIdx.x == 0) {
+        const double change = (dd == 0.0 && xx == 0.0) ? 0.0 : sqrt(dd / xx);
+        const bool bad = !isfinite(change);
+        const bool done = !bad && change <= a.tol;
+        for (int c = 0; c < a.C; ++c) {
+            a.s.change[c] = change;
+            a.s.history[((int64_t)(a.it - 1) * a.C + c) * 2] = change;
+            a.s.history[((int64_t)(a.it - 1) * a.C + c) * 2 + 1] = nuc;
+            a.s.iters[c] = a.it;
+            a.s.status[c] = bad ? NUFFT_FISTA_BREAKDOWN : (done ? NUFFT_FISTA_CONVERGED : NUFFT_FISTA_MAX_ITER);
+            a.s.flag[c] = bad || done ? 1 : 0;
+        }
+    }
+}
+
 // partial sums of Re<v, g>, <v, v>, <g, g>
 template <typename T>
 __global__ __launch_bounds__(kThreads) void power_dot_kernel(PowerLaunch a) {
@@ -198,6 +227,11 @@ hipError_t launch_fista_gradient(const FistaLaunch& a, hipStream_t stream) {
 
 hipError_t launch_fista_decide(const FistaLaunch& a, hipStream_t stream) {
     hipLaunchKernelGGL(fista_decide_kernel, dim3(1, a.nc), dim3(kThreads), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_fista_decide_llr(const FistaLaunch& a, const double* part, int64_t G, hipStream_t stream) {
+    hipLaunchKernelGGL(fista_decide_llr_kernel, dim3(1), dim3(kThreads), 0, stream, a, part, G);
     return hipGetLastError();
 }
 
