@@ -1124,6 +1124,140 @@ int nufft_fista_create_llr(nufft_fista** out, nufft_toeplitz* tz, const nufft_fi
 /* The weight of the LLR prior for the following solves (>= 0, finite). */
 int nufft_fista_set_nuc(nufft_fista* f, double nuc);
 
+/* ---- Total variation: the periodic difference operator ----------- */
+/* On arrays laid out like those of nufft_toeplitz_apply (complex(T)[N...], ntransforms components, D = 1, 2, 3), AS STORED and periodic
+ * in the storage index:
+ *
+ *     (∇x)_d[i] = x[i + e_d] − x[i]                  d = 1 ... D, indices mod N_d          (D arrays per component)
+ *     (∇ᴴy)[i]  = Σ_d (y_d[i − e_d] − y_d[i])        summed in the order d = 1 ... D
+ *     ‖∇x‖₂,₁   = Σ_i |(∇x)_i|₂,   |(∇x)_i|₂ = sqrt(Σ_d |(∇x)_d[i]|²)                      isotropic: one norm over the D complex differences
+ *
+ * The operator commutes with every cyclic shift, so fftshift = 1 and fftshift = 0 plans give the same prior after reordering, with no
+ * divisibility condition.  A table of "D arrays per component" holds ntransforms · D pointers, y_d of component c at [c · D + (d − 1)].
+ * The calls allocate nothing, do not synchronise and are hipGraph-capture safe; no atomics: two runs give the same bits.  The object
+ * keeps partial sums: one call at a time per object.
+ *
+ * Added after ABI 104 without changing NUFFT_MI355X_VERSION: detect by symbol (dlsym nufft_tv_create) and compare
+ * nufft_sizeof_tv_info() with your own. */
+typedef struct nufft_tv nufft_tv; /* opaque */
+
+typedef struct nufft_tv_info {
+    int32_t struct_size;     /* sizeof(nufft_tv_info) of the caller's header, set before the call (0 = this layout)                */
+    int32_t ndim, dtype, ntransforms, device;
+    int32_t tile[3];         /* cells of a workgroup's tile per dimension (1 beyond ndim)                                          */
+    int64_t N[3];            /* 1 beyond ndim                                                                                      */
+    int64_t workgroups;      /* per component and launch                                                                           */
+    int64_t workspace_bytes; /* device bytes owned: the partial sums                                                               */
+} nufft_tv_info;
+
+/* Takes element type, shape, ntransforms and device from the plan; the plan is not kept.  Refusals, in order: null arguments
+ * NUFFT_ERR_INVALID_ARG; a real-data plan NUFFT_ERR_UNSUPPORTED (as nufft_toeplitz_create); N_1 > 2^30, or more than 2^20 (ndim = 2) /
+ * 2^17 (ndim = 3) cells along dimension 2, or more than 2^18 along dimension 3, or more than 2^31 - 1 workgroups over all components
+ * (tiles of nufft_tv_info.tile cells, times ntransforms) NUFFT_ERR_UNSUPPORTED; a host-only plan NUFFT_ERR_NO_DEVICE. */
+int nufft_tv_create(nufft_tv** out, const nufft_plan* plan);
+/* The same from a Toeplitz operator (the operator is not kept). */
+int nufft_tv_create_for_operator(nufft_tv** out, const nufft_toeplitz* tz);
+int nufft_tv_destroy(nufft_tv* tv);
+/* Static facts and sizes; does not synchronise. */
+int nufft_tv_get_info(const nufft_tv* tv, nufft_tv_info* out);
+/* y_out[c · D + d − 1] = (∇x[c])_d: one subtraction per value, so the result is the correctly rounded difference.  Host tables of device
+ * pointers (ntransforms · D and ntransforms), 16-byte aligned; x is only read.  Refusals, before anything is enqueued: a null table or
+ * vector, a pointer that is not 16-byte aligned, an output overlapping an input (a cell's neighbours are read while other workgroups
+ * store) or another output NUFFT_ERR_INVALID_ARG. */
+int nufft_tv_gradient(nufft_tv* tv, void* const* y_out, const void* const* x, void* stream);
+/* x_out[c] = ∇ᴴ (y[c · D], ..., y[c · D + D − 1]); same rules. */
+int nufft_tv_adjoint(nufft_tv* tv, void* const* x_out, const void* const* y, void* stream);
+/* sums_out_device (device, double[ntransforms]): ‖∇x[c]‖₂,₁ per component.  The differences are formed in T, their squares, the square
+ * root and the sum in FP64, in one fixed order. */
+int nufft_tv_norm(nufft_tv* tv, const void* const* x, double* sums_out_device, void* stream);
+int64_t nufft_sizeof_tv_info(void);
+
+/* ---- Primal-dual solver with a total-variation prior ------------- */
+/* Minimises, for every component c (coupled components: jointly, the quadratic term coupling them),
+ *
+ *     ½ <x, (G + μ I) x> − Re<b, x> + tv_c · Σ_i |(∇x)_i|₂
+ *
+ * G what the nufft_toeplitz object applies, ∇ the periodic forward difference above.  The proximal map of ‖∇x‖₂,₁ has no closed form, so
+ * the iteration is the primal-dual one of Condat (2013) and Vũ (2013) (Chambolle & Pock 2011 with the smooth term taken by its
+ * gradient), with fixed steps τ and σ and one dual array y_d per dimension:
+ *
+ *     start:  x = x0 (or 0),  y_d = 0
+ *     for it = 1 ... max_iter:
+ *         q  = G x                                        nufft_toeplitz_apply
+ *         x⁺ = x − τ (q + μ x − b + ∇ᴴ y)                 tv_primal_kernel: stores x <- x⁺ and q <- x̄ = x⁺ + (x⁺ − x),
+ *                                                         partials of ‖x⁺ − x‖², ‖x⁺‖²
+ *         y  <- P_tv(y + σ ∇x̄)                            tv_dual_kernel, in place: P_t(v)_i = v_i · min(1, t / |v_i|₂);
+ *                                                         partial of Σ_i |(∇x⁺)_i|₂
+ *         change = ‖x⁺ − x‖ / ‖x⁺‖ (0 when both are 0);  history row (change, Σ_i |(∇x⁺)_i|₂)          tv_decide_kernel
+ *         done <- change <= tol, or change not finite (NUFFT_TVPD_BREAKDOWN)
+ *
+ * The iteration converges for 1 / τ − σ ‖∇‖² >= L / 2, L = λ_max(G) + μ.  With ‖∇‖² <= 4 D, τ <= 1 / L (nufft_toeplitz_max_eigenvalue) and
+ * the default σ = 1 / (8 D τ) the left side is 1 / (2 τ) >= L / 2.  Any finite σ > 0 is accepted: the condition is the caller's to keep.
+ * tv_c = 0 leaves y exactly zero: the iteration is then plain gradient descent on (G + μ) x = b.  y restarts at 0 in every solve.
+ *
+ * The primal kernel reads y at neighbours and writes only x[i] and q[i]; the dual kernel reads x̄ and x⁺ at neighbours and writes only
+ * y_d[i]: no launch reads at a neighbour an array it writes.  The solver owns 1 + D arrays per component (q and y_1 ... y_D).  A
+ * component that is done is FROZEN: no kernel writes its x, y or scalars again, and its x is bit-equal to that of a solve of this
+ * component alone.  Uncoupled operators stop per component; a coupled operator is one system with one change and one flag, reported
+ * identically for every component.  Sums and scalars are FP64, formed without atomics in one fixed order: two runs, and a replayed
+ * hipGraph, give the same bits.
+ *
+ * check_every = 0: all max_iter iterations are enqueued without synchronising or allocating (hipGraph-capture safe).
+ * check_every = k > 0: after every k iterations the host reads the done flags and stops enqueuing once every component is done.
+ *                  Refused on a capturing stream.  Both modes return bit-identical x, iteration counts and history.
+ *
+ * Added after ABI 104 without changing NUFFT_MI355X_VERSION: detect by symbol (dlsym nufft_tvpd_create) and compare
+ * nufft_sizeof_tvpd_params() / nufft_sizeof_tvpd_info() with your own. */
+typedef struct nufft_tvpd nufft_tvpd; /* opaque */
+
+enum { NUFFT_TVPD_MAX_ITER = 0,   /* max_iter iterations ran without reaching tol */
+       NUFFT_TVPD_CONVERGED = 1,  /* change <= tol                                */
+       NUFFT_TVPD_BREAKDOWN = 2   /* change not finite: the component was frozen  */ };
+
+typedef struct nufft_tvpd_params {
+    int32_t struct_size;     /* sizeof(nufft_tvpd_params) of the caller's header (0 = this layout)                                 */
+    int32_t max_iter;        /* 1 ... 2^24                                                                                         */
+    int32_t check_every;     /* 0, or the number of iterations between two looks at the done flags                                 */
+    int32_t reserved;        /* 0                                                                                                  */
+    double tol;              /* >= 0, finite; 0 = run max_iter iterations unless x stops changing exactly                          */
+    double step;             /* τ > 0, finite                                                                                      */
+    double sigma;            /* σ > 0, finite; 0 = 1 / (8 ndim τ)                                                                  */
+    double tv;               /* >= 0, finite: the weight of every component until nufft_tvpd_set_tv                                */
+    double lambda;           /* the Tikhonov μ: >= 0, finite                                                                       */
+} nufft_tvpd_params;
+
+typedef struct nufft_tvpd_info {
+    int32_t struct_size;     /* sizeof(nufft_tvpd_info) of the caller's header, set before the call (0 = this layout)              */
+    int32_t ntransforms, dtype, ndim, max_iter, check_every;
+    int32_t iterations_enqueued; /* by the last nufft_tvpd_solve (check_every > 0 stops early); -1 before the first                */
+    int32_t reserved;
+    double tol, step, sigma, lambda;   /* sigma: the value in use                                                                  */
+    int64_t array_bytes;     /* q, y_1 ... y_ndim: 1 + ndim arrays per component                                                   */
+    int64_t workspace_bytes; /* device bytes owned: array_bytes + partial sums + scalars + history                                 */
+} nufft_tvpd_info;
+
+/* Allocates q and y (1 + ndim arrays per component), partial sums, scalars and history on the operator's device.  The solver keeps the
+ * POINTER `tz`: the operator must outlive it; nufft_toeplitz_set_points / _set_spectrum on it between two solves is allowed.  Refusals:
+ * null arguments, max_iter < 1 or > 2^24, check_every < 0, tol < 0, tv < 0, lambda < 0, sigma < 0, step <= 0 or non-finite values
+ * NUFFT_ERR_INVALID_ARG; whatever nufft_tv_create refuses for the shape; a host-only operator NUFFT_ERR_NO_DEVICE (after the argument
+ * checks). */
+int nufft_tvpd_create(nufft_tvpd** out, nufft_toeplitz* tz, const nufft_tvpd_params* params);
+int nufft_tvpd_destroy(nufft_tvpd* s);
+/* One weight per component (host array, count = ntransforms, each finite and >= 0) for the following solves. */
+int nufft_tvpd_set_tv(nufft_tvpd* s, const double* weights, int64_t count);
+/* x_inout[c], b[c] as in nufft_cg_solve, with the same refusals (x overlapping b among them).  use_x0 = 0: start from zero. */
+int nufft_tvpd_solve(nufft_tvpd* s, void* const* x_inout, const void* const* b, int use_x0, void* stream);
+/* Static facts and sizes; does not synchronise. */
+int nufft_tvpd_get_info(const nufft_tvpd* s, nufft_tvpd_info* out);
+/* Per-component outcome of the last solve: iterations that changed the component, NUFFT_TVPD_* status, the last change.  Each output
+ * may be NULL; `capacity` entries each, at least ntransforms.  Synchronises `stream` (never a capturing one). */
+int nufft_tvpd_get_result(nufft_tvpd* s, int32_t* iterations, int32_t* status, double* change, int64_t capacity, void* stream);
+/* host_out[max_iter][ntransforms][2]: row it − 1 holds the change and Σ_i |(∇x)_i|₂ of every component after iteration it (a coupled
+ * operator: the joint values); NaN where the iteration did not change the component.  Synchronises `stream`. */
+int nufft_tvpd_history(nufft_tvpd* s, double* host_out, int64_t capacity, void* stream);
+int64_t nufft_sizeof_tvpd_params(void);
+int64_t nufft_sizeof_tvpd_info(void);
+
 /* ---- misc ----------------------------------------------------------------------------- */
 /* sizeof(nufft_params) / sizeof(nufft_info) of the library build: a binding that mirrors the structs by hand
  * (ctypes, Julia) compares them with its own layout before the first call. */

@@ -23,6 +23,7 @@ from .precond import ToeplitzPreconditioner  # noqa: F401
 from .wavelet import WaveletTransform  # noqa: F401
 from .llr import LocallyLowRank  # noqa: F401
 from .fista import ToeplitzFISTA  # noqa: F401
+from .tv import ToeplitzTV, TotalVariation  # noqa: F401
 from .dcf import DensityCompensation, density_weights  # noqa: F401
 from . import autograd  # noqa: F401
 
@@ -34,6 +35,6 @@ __all__ = [
     "PlanNUFFT3", "set_points3", "exec_type3", "exec_type3_grad",
     "exec_type2_grad", "interpolate_grad", "autograd",
     "ToeplitzOperator", "ToeplitzCG", "ToeplitzPreconditioner", "coil_expand", "coil_combine",
-    "WaveletTransform", "LocallyLowRank", "ToeplitzFISTA",
+    "WaveletTransform", "LocallyLowRank", "ToeplitzFISTA", "TotalVariation", "ToeplitzTV",
     "DensityCompensation", "density_weights",
 ]

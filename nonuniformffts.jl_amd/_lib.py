@@ -194,6 +194,34 @@ FISTA_MAX_ITER, FISTA_CONVERGED, FISTA_BREAKDOWN = 0, 1, 2
 FISTA_STATUS_NAMES = {FISTA_MAX_ITER: "max_iter", FISTA_CONVERGED: "converged", FISTA_BREAKDOWN: "breakdown"}
 
 
+class NufftTvInfo(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("ndim", C.c_int32), ("dtype", C.c_int32), ("ntransforms", C.c_int32), ("device", C.c_int32),
+        ("tile", C.c_int32 * 3),
+        ("N", C.c_int64 * 3), ("workgroups", C.c_int64), ("workspace_bytes", C.c_int64),
+    ]
+
+
+class NufftTvpdParams(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("max_iter", C.c_int32), ("check_every", C.c_int32), ("reserved", C.c_int32),
+        ("tol", C.c_double), ("step", C.c_double), ("sigma", C.c_double), ("tv", C.c_double), ("lambda_", C.c_double),
+    ]
+
+
+class NufftTvpdInfo(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("ntransforms", C.c_int32), ("dtype", C.c_int32), ("ndim", C.c_int32), ("max_iter", C.c_int32),
+        ("check_every", C.c_int32), ("iterations_enqueued", C.c_int32), ("reserved", C.c_int32),
+        ("tol", C.c_double), ("step", C.c_double), ("sigma", C.c_double), ("lambda_", C.c_double),
+        ("array_bytes", C.c_int64), ("workspace_bytes", C.c_int64),
+    ]
+
+
+TVPD_MAX_ITER, TVPD_CONVERGED, TVPD_BREAKDOWN = 0, 1, 2
+TVPD_STATUS_NAMES = {TVPD_MAX_ITER: "max_iter", TVPD_CONVERGED: "converged", TVPD_BREAKDOWN: "breakdown"}
+
+
 class NufftDcfParams(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int32), ("max_iter", C.c_int32), ("check_every", C.c_int32), ("normalize", C.c_int32),
@@ -347,6 +375,23 @@ SYMBOLS = {
     "nufft_sizeof_llr_info": (C.c_int64, []),
     "nufft_fista_create_llr": (C.c_int, [C.POINTER(_P), _P, C.POINTER(NufftFistaParams), C.POINTER(NufftLlrParams), C.c_double]),
     "nufft_fista_set_nuc": (C.c_int, [_P, C.c_double]),
+    "nufft_tv_create": (C.c_int, [C.POINTER(_P), _P]),
+    "nufft_tv_create_for_operator": (C.c_int, [C.POINTER(_P), _P]),
+    "nufft_tv_destroy": (C.c_int, [_P]),
+    "nufft_tv_get_info": (C.c_int, [_P, C.POINTER(NufftTvInfo)]),
+    "nufft_tv_gradient": (C.c_int, [_P, _PP, _PP, _P]),
+    "nufft_tv_adjoint": (C.c_int, [_P, _PP, _PP, _P]),
+    "nufft_tv_norm": (C.c_int, [_P, _PP, _P, _P]),
+    "nufft_sizeof_tv_info": (C.c_int64, []),
+    "nufft_tvpd_create": (C.c_int, [C.POINTER(_P), _P, C.POINTER(NufftTvpdParams)]),
+    "nufft_tvpd_destroy": (C.c_int, [_P]),
+    "nufft_tvpd_set_tv": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int64]),
+    "nufft_tvpd_solve": (C.c_int, [_P, _PP, _PP, C.c_int, _P]),
+    "nufft_tvpd_get_info": (C.c_int, [_P, C.POINTER(NufftTvpdInfo)]),
+    "nufft_tvpd_get_result": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int64, _P]),
+    "nufft_tvpd_history": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int64, _P]),
+    "nufft_sizeof_tvpd_params": (C.c_int64, []),
+    "nufft_sizeof_tvpd_info": (C.c_int64, []),
     "nufft_sizeof_params": (C.c_int64, []),
     "nufft_sizeof_info": (C.c_int64, []),
     "nufft_strerror": (C.c_char_p, [C.c_int]),
@@ -381,7 +426,8 @@ def _load():
                          ("nufft_sizeof_dcf_info", NufftDcfInfo), ("nufft_sizeof_wavelet_params", NufftWaveletParams),
                          ("nufft_sizeof_wavelet_info", NufftWaveletInfo), ("nufft_sizeof_fista_params", NufftFistaParams),
                          ("nufft_sizeof_fista_info", NufftFistaInfo), ("nufft_sizeof_llr_params", NufftLlrParams),
-                         ("nufft_sizeof_llr_info", NufftLlrInfo)):
+                         ("nufft_sizeof_llr_info", NufftLlrInfo), ("nufft_sizeof_tv_info", NufftTvInfo),
+                         ("nufft_sizeof_tvpd_params", NufftTvpdParams), ("nufft_sizeof_tvpd_info", NufftTvpdInfo)):
         if getattr(lib, name)() != C.sizeof(mirror):
             raise ImportError(f"{LIB_PATH}: {name}() = {getattr(lib, name)()} but the ctypes mirror has {C.sizeof(mirror)} bytes "
                               "(include/nufft_mi355x.h and _lib.py disagree)")

@@ -1,0 +1,277 @@
+"""Total variation on a :class:`ToeplitzOperator`: the periodic difference operator and the primal-dual solver, above the C ABI's
+``nufft_tv_*`` and ``nufft_tvpd_*`` entry points.
+
+    min_x  ½⟨x, (G + lam I) x⟩ − Re⟨b, x⟩ + Σ_c tv_c Σ_i |(∇x_c)_i|₂
+
+``(∇x)_d[i] = x[i + e_d] − x[i]`` with indices mod ``N_d`` on the array as stored, ``|(∇x)_i|₂`` one norm over the D complex differences of
+a cell (isotropic TV of a complex image).  The whole loop runs in the library: per iteration one apply of the operator, two stencil
+kernels and one decision kernel, every scalar on the device.  Plumbing only: argument checks, pointers, and reading the outcome back.
+
+    sol = ToeplitzTV(op, tv=1e-3, maxiter=200, tol=1e-4)
+    x = sol.solve(b)
+    sol.iterations, sol.status, sol.change, sol.history()
+
+    T = TotalVariation(op_or_plan)
+    y = T.gradient(x)                # a tuple of D tensors, dimension 1 first
+    x = T.adjoint(y)                 # ∇ᴴ y
+    T.norm(x)                        # Σ_i |(∇x)_i|₂ per component (float64, on the device)
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from . import _lib
+from ._lib import lib
+from .plan import DimensionMismatch, PlanNUFFT, _check, _ptr_table
+from .toeplitz import ToeplitzOperator
+
+
+def _weights(tv, n):
+    """One weight per component from a scalar (a Python or numpy number, a 0-d tensor) or from a sequence."""
+    if isinstance(tv, (list, tuple)) or getattr(tv, "ndim", 0) > 0:
+        return [float(v) for v in tv]
+    return [float(tv)] * n
+
+
+class TotalVariation:
+    """``TotalVariation(op_or_plan)``: element type, shape, ntransforms and device are those of a complex ``PlanNUFFT`` or of a
+    ``ToeplitzOperator`` (neither is kept).  Dimension 1 is the fastest one, the LAST axis of the tensors.  The operator is periodic
+    in the storage index and commutes with every cyclic shift: ``fftshift=True`` and ``False`` plans give the same prior after
+    reordering, whatever the sizes."""
+
+    def __init__(self, op_or_plan):
+        if not isinstance(op_or_plan, (PlanNUFFT, ToeplitzOperator)):
+            raise ValueError("TotalVariation takes a PlanNUFFT or a ToeplitzOperator")
+        src = op_or_plan
+        if isinstance(src, ToeplitzOperator):
+            src._require_open()
+            create, self.Z = lib.nufft_tv_create_for_operator, src.Z
+        else:
+            create, self.Z = lib.nufft_tv_create, src.eltype
+        self._handle = C.c_void_p()
+        _check(create(C.byref(self._handle), src._handle))
+        self.device, self.shape, self.ndim, self.ntransforms = src.device, src.shape, src.ndim, src.ntransforms
+
+    def close(self):
+        h = getattr(self, "_handle", None)
+        if h is not None and h.value:
+            lib.nufft_tv_destroy(h)
+            self._handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _require_open(self):
+        if not self._handle.value:
+            raise ValueError("this TotalVariation has been closed")
+
+    def info(self) -> _lib.NufftTvInfo:
+        self._require_open()
+        out = _lib.NufftTvInfo()
+        out.struct_size = C.sizeof(_lib.NufftTvInfo)
+        _check(lib.nufft_tv_get_info(self._handle, C.byref(out)))
+        return out
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _check_arrays(self, us, what, count):
+        if len(us) != count:
+            raise DimensionMismatch(f"wrong amount of {what} arrays (expected {count})")
+        for u in us:
+            if not isinstance(u, torch.Tensor) or u.device != self.device:
+                raise ValueError(f"{what} must be torch tensors on {self.device}")
+            if u.dtype != self.Z:
+                raise ValueError(f"{what} must have element type {self.Z} (got {u.dtype})")
+            if tuple(u.shape) != self.shape:
+                raise DimensionMismatch(f"wrong dimensions of {what} array (expected tensor shape {self.shape}, got {tuple(u.shape)})")
+            if not u.is_contiguous():
+                raise ValueError(f"{what} must be contiguous")
+
+    def _components(self, x):
+        """A tensor (one component) or a tuple of ntransforms tensors -> (single, tuple)."""
+        single = isinstance(x, torch.Tensor)
+        x_t = (x,) if single else tuple(x)
+        self._check_arrays(x_t, "input", self.ntransforms)
+        return single, x_t
+
+    def gradient(self, x):
+        """``∇x``: a tuple of D tensors, dimension 1 first (for a tuple of components: a tuple of such tuples)."""
+        self._require_open()
+        single, x_t = self._components(x)
+        y = tuple(tuple(torch.empty_like(v) for _ in range(self.ndim)) for v in x_t)
+        _check(lib.nufft_tv_gradient(self._handle, _ptr_table([u for comp in y for u in comp]), _ptr_table(x_t), self._stream()))
+        return y[0] if single else y
+
+    def adjoint(self, y):
+        """``∇ᴴy`` for ``y`` as ``gradient`` returns it."""
+        self._require_open()
+        single = len(y) > 0 and isinstance(y[0], torch.Tensor)
+        y_t = (tuple(y),) if single else tuple(tuple(comp) for comp in y)
+        if len(y_t) != self.ntransforms or (single and self.ntransforms != 1):
+            raise DimensionMismatch(f"wrong amount of components (expected {self.ntransforms})")
+        flat = [u for comp in y_t for u in comp]
+        for comp in y_t:
+            self._check_arrays(comp, "input", self.ndim)
+        out = tuple(torch.empty_like(comp[0]) for comp in y_t)
+        _check(lib.nufft_tv_adjoint(self._handle, _ptr_table(out), _ptr_table(flat), self._stream()))
+        return out[0] if single else out
+
+    def norm(self, x) -> torch.Tensor:
+        """``Σ_i |(∇x)_i|₂`` per component: a float64 device tensor of ntransforms values."""
+        self._require_open()
+        _, x_t = self._components(x)
+        sums = torch.empty(self.ntransforms, dtype=torch.float64, device=self.device)
+        _check(lib.nufft_tv_norm(self._handle, _ptr_table(x_t), C.c_void_p(sums.data_ptr()), self._stream()))
+        return sums
+
+    def __repr__(self):
+        i = self.info()
+        return (f"TotalVariation on {self.ndim}-dimensional {self.Z} arrays of shape {self.shape}, tile {tuple(i.tile[d] for d in range(self.ndim))}, "
+                f"{i.workspace_bytes / 1e3:.1f} kB")
+
+
+class ToeplitzTV:
+    """``ToeplitzTV(op, tv=0.0, step=None, sigma=None, lam=0.0, maxiter=100, tol=1e-4, check_every=0)``.
+
+    ``tv``: a scalar or one weight per component.  ``lam``: the Tikhonov weight (named as in :class:`ToeplitzCG`).  ``step``: the
+    primal step ``τ``; None computes ``1 / (1.05 · max(op.max_eigenvalue()) + lam)`` once, here (the operator then needs its spectrum
+    already).  ``sigma``: the dual step ``σ``; None is ``1 / (8 D τ)``, which keeps ``1/τ − σ‖∇‖² >= L/2`` for ``τ <= 1/L``.
+    ``check_every=0`` enqueues all ``maxiter`` iterations without synchronising (components whose relative change reached ``tol`` are
+    frozen on the device; legal inside ``torch.cuda.graph``); ``check_every=k`` lets the host stop early.  Both return the same bits.
+    The solver keeps ``op`` alive; ``op.set_points`` / ``set_spectrum`` between two solves is allowed.  On a coupled operator the
+    components are one system: one change and one stopping test, reported identically for every component.  The dual variable restarts
+    at zero in every ``solve``."""
+
+    def __init__(self, op: ToeplitzOperator, tv=0.0, step=None, sigma=None, lam: float = 0.0, maxiter: int = 100, tol: float = 1e-4,
+                 check_every: int = 0):
+        if not isinstance(op, ToeplitzOperator):
+            raise ValueError("ToeplitzTV takes a ToeplitzOperator")
+        for name, v in (("maxiter", maxiter), ("check_every", check_every)):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError(f"{name} must be an integer")
+        op._require_open()
+        tvs = _weights(tv, op.ntransforms)
+        if len(tvs) != op.ntransforms:
+            raise DimensionMismatch(f"wrong amount of tv weights (expected {op.ntransforms})")
+        if sigma is not None and not float(sigma) > 0.0:
+            raise ValueError("sigma must be positive (None: 1 / (8 D step))")
+        if step is None:
+            op._require_gpu()
+            step = 1.0 / (1.05 * max(op.max_eigenvalue()) + float(lam))
+        prm = _lib.NufftTvpdParams()
+        prm.struct_size = C.sizeof(_lib.NufftTvpdParams)
+        prm.max_iter, prm.check_every = maxiter, check_every
+        prm.tol, prm.step, prm.sigma, prm.tv, prm.lambda_ = float(tol), float(step), 0.0 if sigma is None else float(sigma), tvs[0], float(lam)
+        self._handle = C.c_void_p()
+        _check(lib.nufft_tvpd_create(C.byref(self._handle), op._handle, C.byref(prm)))
+        self.op = op
+        self.tv, self.step, self.lam = tuple(tvs), float(step), float(lam)
+        self.maxiter, self.tol, self.check_every = maxiter, float(tol), check_every
+        try:
+            _check(lib.nufft_tvpd_set_tv(self._handle, (C.c_double * len(tvs))(*tvs), len(tvs)))
+            self.sigma = self.info().sigma
+        except Exception:
+            self.close()
+            raise
+
+    def set_tv(self, tv):
+        """One weight per component (or a scalar) for the following solves."""
+        self._require_open()
+        n = self.op.ntransforms
+        tvs = _weights(tv, n)
+        _check(lib.nufft_tvpd_set_tv(self._handle, (C.c_double * len(tvs))(*tvs), len(tvs)))
+        self.tv = tuple(tvs)
+
+    def close(self):
+        h = getattr(self, "_handle", None)
+        if h is not None and h.value:
+            lib.nufft_tvpd_destroy(h)
+            self._handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _require_open(self):
+        """The library keeps a pointer to the operator: refuse to follow it once either object has been closed."""
+        if not self._handle.value:
+            raise ValueError("this ToeplitzTV has been closed")
+        if not self.op._handle.value:
+            raise ValueError("the ToeplitzOperator of this solver has been closed: the operator must outlive the solver")
+
+    def info(self) -> _lib.NufftTvpdInfo:
+        self._require_open()
+        out = _lib.NufftTvpdInfo()
+        out.struct_size = C.sizeof(_lib.NufftTvpdInfo)
+        _check(lib.nufft_tvpd_get_info(self._handle, C.byref(out)))
+        return out
+
+    def solve(self, b, x0=None, out=None):
+        """``b``: a tensor of ``plan.shape`` or a tuple of ntransforms such tensors (only read).  ``x0``: starting guess (None = zero);
+        ``out``: where the solution goes (may be ``x0``; None = new tensors; never ``b``).  Returns ``out``."""
+        self._require_open()
+        op = self.op
+        op._require_gpu()
+        single = isinstance(b, torch.Tensor)
+        b_t = (b,) if single else tuple(b)
+        op._check_uniform(b_t, "right-hand side")
+        if out is None:
+            out_t = tuple(torch.empty_like(v) for v in b_t)
+            out = out_t[0] if single else out_t
+        else:
+            out_t = (out,) if isinstance(out, torch.Tensor) else tuple(out)
+            op._check_uniform(out_t, "output")
+        if x0 is not None:
+            x0_t = (x0,) if isinstance(x0, torch.Tensor) else tuple(x0)
+            op._check_uniform(x0_t, "starting guess")
+            for o, g in zip(out_t, x0_t):
+                if o.data_ptr() != g.data_ptr():
+                    o.copy_(g)
+        _check(lib.nufft_tvpd_solve(self._handle, _ptr_table(out_t), _ptr_table(b_t), 0 if x0 is None else 1, op._stream()))
+        return out
+
+    def _result(self):
+        self._require_open()
+        n = self.op.ntransforms
+        it, st, ch = (C.c_int32 * n)(), (C.c_int32 * n)(), (C.c_double * n)()
+        _check(lib.nufft_tvpd_get_result(self._handle, it, st, ch, n, self.op._stream()))
+        return list(it), list(st), list(ch)
+
+    @property
+    def iterations(self):
+        """Per component: iterations that changed it (synchronises the current stream)."""
+        return tuple(self._result()[0])
+
+    @property
+    def status(self):
+        """Per component: ``"converged"``, ``"max_iter"`` or ``"breakdown"`` (a relative change that is not finite)."""
+        return tuple(_lib.TVPD_STATUS_NAMES[s] for s in self._result()[1])
+
+    @property
+    def change(self):
+        """Per component: ``‖x⁺ − x‖ / ‖x⁺‖`` of the last iteration that changed it."""
+        return tuple(self._result()[2])
+
+    def history(self) -> torch.Tensor:
+        """``[max(iterations), ntransforms, 2]`` (host, float64): relative change and ``Σ_i |(∇x)_i|₂`` after every iteration; NaN where
+        an iteration did not change the component."""
+        self._require_open()
+        n = self.op.ntransforms
+        buf = (C.c_double * (self.maxiter * n * 2))()
+        _check(lib.nufft_tvpd_history(self._handle, buf, len(buf), self.op._stream()))
+        rows = max(self.iterations)
+        return torch.tensor(list(buf), dtype=torch.float64).reshape(self.maxiter, n, 2)[:rows].clone()
+
+    def __repr__(self):
+        i = self.info()
+        return (f"ToeplitzTV on a {self.op.ndim}-dimensional {self.op.Z} operator, tv = {self.tv}, step = {self.step:g}, sigma = {self.sigma:g}, "
+                f"lam = {self.lam:g}, maxiter = {self.maxiter}, tol = {self.tol:g}, check_every = {self.check_every}, "
+                f"{i.workspace_bytes / 1e6:.1f} MB")
