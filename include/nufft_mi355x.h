@@ -1232,7 +1232,7 @@ typedef struct nufft_tvpd_info {
     int32_t iterations_enqueued; /* by the last nufft_tvpd_solve (check_every > 0 stops early); -1 before the first                */
     int32_t reserved;
     double tol, step, sigma, lambda;   /* sigma: the value in use                                                                  */
-    int64_t array_bytes;     /* q, y_1 ... y_ndim: 1 + ndim arrays per component                                                   */
+    int64_t array_bytes;     /* q, y_1 ... y_ndim: 1 + ndim arrays per component (nufft_tvpd_create_temporal: + z, − y if spatial = 0) */
     int64_t workspace_bytes; /* device bytes owned: array_bytes + partial sums + scalars + history                                 */
 } nufft_tvpd_info;
 
@@ -1257,6 +1257,94 @@ int nufft_tvpd_get_result(nufft_tvpd* s, int32_t* iterations, int32_t* status, d
 int nufft_tvpd_history(nufft_tvpd* s, double* host_out, int64_t capacity, void* stream);
 int64_t nufft_sizeof_tvpd_params(void);
 int64_t nufft_sizeof_tvpd_info(void);
+
+/* ---- Dynamic imaging: one Toeplitz multiplier per component ("frames") ----
+ * A FRAMED operator holds K = ntransforms real multipliers, one per component: out[c] = Toeplitz(T_c) in[c].  Every component runs
+ * exactly the launches of the plain apply with its own multiplier pointer, on the fused and on the dense path, so the result of frame c
+ * is bit-equal to that of a plain operator built from T_c; out[c] == in[c] stays allowed without coil maps, and with coil maps the same
+ * maps serve every frame.  nufft_toeplitz_num_coupled stays 0: the solvers (CG, FISTA, TV, nufft_toeplitz_max_eigenvalue) treat the
+ * frames as independent components.  There is no limit of 16 on K.
+ *
+ * Storage: K real grids of (2N)^D (each padded to 256 bytes), allocated by the first framed build, counted in workspace_bytes, kept
+ * across framed builds and freed by the next nufft_toeplitz_set_points / _set_spectrum, by a coupled build or by
+ * nufft_toeplitz_destroy; the operator is then bit for bit the plain (or coupled) operator again.  A framed build drops a coupled one
+ * and a coupled build drops a framed one.  nufft_precond_create, nufft_precond_create_block and nufft_precond_update on a framed
+ * operator return NUFFT_ERR_UNSUPPORTED (per-frame circulants are not built).
+ *
+ * Refusals of the two builds, in order: a null object or table NUFFT_ERR_INVALID_ARG; a host-only object NUFFT_ERR_NO_DEVICE; null
+ * entries (a spectrum; the coordinates of a frame with points) or a negative num_points[c] NUFFT_ERR_INVALID_ARG; a capturing stream
+ * NUFFT_ERR_INVALID_ARG.
+ *
+ * Added after the total-variation section under the same rule: detect by symbol (dlsym nufft_toeplitz_set_points_frames);
+ * NUFFT_MI355X_VERSION and nufft_toeplitz_info are unchanged. */
+/* K = ntransforms frames.  num_points[c] >= 0 (0: that frame's multiplier is zero); coords: K·D device vectors, frame c's
+ * dimension d at [c·D + d]; weights: NULL, or K entries each NULL (= ones) or real(T)[num_points[c]].  The internal 2N plan is created
+ * once, takes every frame's points in turn and is destroyed before the call returns: peak memory as nufft_toeplitz_set_points plus the
+ * K real grids. */
+int nufft_toeplitz_set_points_frames(nufft_toeplitz* tz, const nufft_params* build_params, const int64_t* num_points,
+                                     const void* const* coords, const void* const* weights, void* stream);
+/* T[c]: as nufft_toeplitz_set_spectrum, one per frame. */
+int nufft_toeplitz_set_spectra_frames(nufft_toeplitz* tz, const void* const* T, void* stream);
+/* K while a framed build is in force, else 0. */
+int32_t nufft_toeplitz_num_frames(const nufft_toeplitz* tz);
+/* The real multiplier of frame c (device, T[2N_1, 2N_2, 2N_3]); NUFFT_ERR_INVALID_ARG without a framed build or for c outside 0 ... K − 1. */
+int nufft_toeplitz_multiplier_frame_ptr(const nufft_toeplitz* tz, int32_t c, void** out_ptr, int64_t* out_bytes);
+
+/* ---- Total variation along the components (temporal TV) ----------- */
+/* Frames are the components c = 0 ... K − 1, K = ntransforms >= 2, the arrays those of nufft_toeplitz_apply:
+ *
+ *     (∇_t x)_c[i]  = x_{c+1}[i] − x_c[i]          c < K − 1;     c = K − 1:  x_0[i] − x_{K−1}[i] if periodic, else 0
+ *     (∇_tᴴ z)_c[i] = z_{c−1}[i] − z_c[i]          with z_{−1} = z_{K−1} if periodic, else z_{−1} = z_{K−1} = 0
+ *     ‖∇_t x‖₁      = Σ_c Σ_i |(∇_t x)_c[i]|       complex modulus
+ *
+ * The operator alone, on a nufft_tv object: host tables of ntransforms device pointers in and out, 16-byte aligned, no output
+ * overlapping an input or another output, `periodic` 0 or 1 (NUFFT_ERR_INVALID_ARG otherwise, and for ntransforms < 2).  One subtraction
+ * per value; no atomics; the calls do not synchronise.  nufft_tv_norm_t allocates the object's partial sums in its first call (never on
+ * a capturing stream); sums_out_device[c] = Σ_i |(∇_t x)_c[i]|, differences in T, modulus and sum in FP64 in one fixed order. */
+int nufft_tv_gradient_t(nufft_tv* tv, void* const* z_out, const void* const* x, int periodic, void* stream);
+int nufft_tv_adjoint_t(nufft_tv* tv, void* const* x_out, const void* const* z, int periodic, void* stream);
+int nufft_tv_norm_t(nufft_tv* tv, const void* const* x, int periodic, double* sums_out_device, void* stream);
+
+/* The primal-dual solver with a spatial and a temporal term (the usual form of golden-angle radial reconstruction),
+ *
+ *     ½ <x, (G + μ I) x> − Re<b, x> + Σ_c tv_c Σ_i |(∇x_c)_i|₂ + tv_t ‖∇_t x‖₁
+ *
+ * on whatever nufft_toeplitz_apply computes (plain, framed, with maps, coupled).  Condat–Vũ as above with one more dual array z_c per
+ * component:
+ *
+ *     q  = G x
+ *     x⁺ = x − τ (q + μ x − b + ∇ᴴy + ∇_tᴴz)         x <- x⁺,  q <- x̄ = x⁺ + (x⁺ − x);  partials of ‖x⁺ − x‖², ‖x⁺‖²
+ *     y  <- P_{tv_c}(y + σ ∇x̄)                        only when the spatial term is on
+ *     z  <- P_{tv_t}(z + σ ∇_t x̄)                     per cell: v · min(1, tv_t / |v|)
+ *     decide: always JOINT — one change, one flag, one stopping test, reported identically for every component
+ *
+ * History column 2 of component c is its share of the prior at x⁺: tv_c Σ_i |(∇x⁺_c)_i|₂ + tv_t Σ_i |(∇_t x⁺)_c[i]| (the first term
+ * absent when the spatial term is off); the rows sum to the prior.  Default σ = 1 / (8 n_d τ), n_d = ndim + 1 with the spatial term and
+ * 1 without: ‖[∇; ∇_t]‖² <= 4 ndim + 4 and ‖∇_t‖² <= 4 keep 1 / τ − σ ‖·‖² >= 1 / (2 τ) >= L / 2.
+ *
+ * `spatial` is decided at creation and never switched.  spatial = 0: the solver neither allocates nor touches y — it holds 2 arrays per
+ * component (q, z) instead of 2 + ndim, nufft_tvpd_params.tv is ignored and nufft_tvpd_set_tv with a non-zero weight is refused
+ * (NUFFT_ERR_INVALID_ARG).  nufft_tvpd_info.array_bytes reports what is held.  solve, get_result, history, get_info and destroy are the
+ * calls above; two runs, check_every = 0 and > 0, and a replayed hipGraph give the same bits.
+ *
+ * Refusals of nufft_tvpd_create_temporal: null arguments, ntransforms < 2, tv_t negative or not finite, spatial or periodic outside
+ * {0, 1} NUFFT_ERR_INVALID_ARG; otherwise whatever nufft_tvpd_create refuses, in its order.
+ *
+ * Added under the same rule: detect by symbol (dlsym nufft_tvpd_create_temporal) and compare nufft_sizeof_tvt_params() with your own;
+ * nufft_tvpd_params and nufft_tvpd_info keep their sizes. */
+typedef struct nufft_tvt_params {
+    int32_t struct_size;     /* sizeof(nufft_tvt_params) of the caller's header (0 = this layout)                                  */
+    int32_t periodic;        /* 0: the last frame has no successor (time is not a circle); 1: it is followed by frame 0 (cine)     */
+    int32_t spatial;         /* 1: the spatial term of nufft_tvpd_create is kept; 0: temporal term only                            */
+    int32_t reserved;        /* 0                                                                                                  */
+    double tv_t;             /* >= 0, finite: the weight of ‖∇_t x‖₁                                                               */
+} nufft_tvt_params;
+int nufft_tvpd_create_temporal(nufft_tvpd** out, nufft_toeplitz* tz, const nufft_tvpd_params* params, const nufft_tvt_params* temporal);
+/* The temporal weight of the following solves (finite, >= 0); NUFFT_ERR_INVALID_ARG on a solver made by nufft_tvpd_create. */
+int nufft_tvpd_set_tv_t(nufft_tvpd* s, double tv_t);
+/* periodic, spatial and tv_t in use; NUFFT_ERR_INVALID_ARG on a solver made by nufft_tvpd_create. */
+int nufft_tvpd_get_temporal(const nufft_tvpd* s, nufft_tvt_params* out);
+int64_t nufft_sizeof_tvt_params(void);
 
 /* ---- misc ----------------------------------------------------------------------------- */
 /* sizeof(nufft_params) / sizeof(nufft_info) of the library build: a binding that mirrors the structs by hand

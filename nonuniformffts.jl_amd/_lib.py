@@ -218,6 +218,10 @@ class NufftTvpdInfo(C.Structure):
     ]
 
 
+class NufftTvtParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("periodic", C.c_int32), ("spatial", C.c_int32), ("reserved", C.c_int32), ("tv_t", C.c_double)]
+
+
 TVPD_MAX_ITER, TVPD_CONVERGED, TVPD_BREAKDOWN = 0, 1, 2
 TVPD_STATUS_NAMES = {TVPD_MAX_ITER: "max_iter", TVPD_CONVERGED: "converged", TVPD_BREAKDOWN: "breakdown"}
 
@@ -392,6 +396,17 @@ SYMBOLS = {
     "nufft_tvpd_history": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int64, _P]),
     "nufft_sizeof_tvpd_params": (C.c_int64, []),
     "nufft_sizeof_tvpd_info": (C.c_int64, []),
+    "nufft_toeplitz_set_points_frames": (C.c_int, [_P, C.POINTER(NufftParams), C.POINTER(C.c_int64), _PP, _PP, _P]),
+    "nufft_toeplitz_set_spectra_frames": (C.c_int, [_P, _PP, _P]),
+    "nufft_toeplitz_num_frames": (C.c_int32, [_P]),
+    "nufft_toeplitz_multiplier_frame_ptr": (C.c_int, [_P, C.c_int32, C.POINTER(_P), C.POINTER(C.c_int64)]),
+    "nufft_tv_gradient_t": (C.c_int, [_P, _PP, _PP, C.c_int, _P]),
+    "nufft_tv_adjoint_t": (C.c_int, [_P, _PP, _PP, C.c_int, _P]),
+    "nufft_tv_norm_t": (C.c_int, [_P, _PP, C.c_int, _P, _P]),
+    "nufft_tvpd_create_temporal": (C.c_int, [C.POINTER(_P), _P, C.POINTER(NufftTvpdParams), C.POINTER(NufftTvtParams)]),
+    "nufft_tvpd_set_tv_t": (C.c_int, [_P, C.c_double]),
+    "nufft_tvpd_get_temporal": (C.c_int, [_P, C.POINTER(NufftTvtParams)]),
+    "nufft_sizeof_tvt_params": (C.c_int64, []),
     "nufft_sizeof_params": (C.c_int64, []),
     "nufft_sizeof_info": (C.c_int64, []),
     "nufft_strerror": (C.c_char_p, [C.c_int]),
@@ -427,7 +442,8 @@ def _load():
                          ("nufft_sizeof_wavelet_info", NufftWaveletInfo), ("nufft_sizeof_fista_params", NufftFistaParams),
                          ("nufft_sizeof_fista_info", NufftFistaInfo), ("nufft_sizeof_llr_params", NufftLlrParams),
                          ("nufft_sizeof_llr_info", NufftLlrInfo), ("nufft_sizeof_tv_info", NufftTvInfo),
-                         ("nufft_sizeof_tvpd_params", NufftTvpdParams), ("nufft_sizeof_tvpd_info", NufftTvpdInfo)):
+                         ("nufft_sizeof_tvpd_params", NufftTvpdParams), ("nufft_sizeof_tvpd_info", NufftTvpdInfo),
+                         ("nufft_sizeof_tvt_params", NufftTvtParams)):
         if getattr(lib, name)() != C.sizeof(mirror):
             raise ImportError(f"{LIB_PATH}: {name}() = {getattr(lib, name)()} but the ctypes mirror has {C.sizeof(mirror)} bytes "
                               "(include/nufft_mi355x.h and _lib.py disagree)")

@@ -184,6 +184,9 @@ struct BuildScratch {
 
 // The scalar object serves independent components, the block object the K coupled components it was created for.
 int check_coupling(const nufft_precond* p) {
+    if (nufft_toeplitz_num_frames(p->tz) > 0)
+        return fail(NUFFT_ERR_UNSUPPORTED, "the operator is framed (nufft_toeplitz_set_points_frames / _set_spectra_frames: one multiplier per component): "
+                                           "a preconditioner of per-frame circulants is not built");
     const int K = nufft_toeplitz_num_coupled(p->tz);
     if (p->K == 0 && K > 0)
         return fail(NUFFT_ERR_UNSUPPORTED, "the operator couples its components: nufft_precond_create builds the preconditioner of independent components; a "
@@ -429,6 +432,9 @@ int create(nufft_precond** out, nufft_toeplitz* tz, const nufft_precond_params* 
     ti.struct_size = (int32_t)sizeof(ti);
     if ((rc = nufft_toeplitz_get_info(tz, &ti))) return rc;
     if (ti.device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1): the preconditioner runs on the device");
+    if (nufft_toeplitz_num_frames(tz) > 0)
+        return fail(NUFFT_ERR_UNSUPPORTED, "the operator is framed (nufft_toeplitz_set_points_frames / _set_spectra_frames: one multiplier per component): "
+                                           "a preconditioner of per-frame circulants is not built");
 
     nufft_precond* p = new (std::nothrow) nufft_precond();
     if (!p) return fail(NUFFT_ERR_ALLOC, "out of host memory");

@@ -66,6 +66,10 @@ struct nufft_toeplitz {
     void* d_kd = nullptr;                              // T[C][2N_1, 2N_2, 2N_3]: the diagonal blocks K_aa
     void* d_kc = nullptr;                              // complex<T>[C (C − 1) / 2][2N_1, 2N_2, 2N_3]: K_ab, a < b, row-major
     void* d_grids = nullptr;                           // fused: C arrays like d_tmpB; dense: C arrays like d_work
+    // frames: one real multiplier per component, held from the first framed build to the next plain or
+    // coupled one
+    bool framed = false;
+    void* d_kf = nullptr;                              // C arrays like d_K, frame_stride bytes apart
 };
 
 namespace {
@@ -118,6 +122,17 @@ int acquire_coupled(nufft_toeplitz* t) {
     return NUFFT_OK;
 }
 
+// The multipliers of a framed build: C real grids, each padded on its own (the alignment of d_K for every frame).
+size_t frame_stride(const nufft_toeplitz* t) { return padded((size_t)grid_cells(t) * real_bytes(t->dtype)); }
+size_t frames_bytes(const nufft_toeplitz* t) { return (size_t)t->C * frame_stride(t); }
+void* frame_multiplier(const nufft_toeplitz* t, int c) { return static_cast<char*>(t->d_kf) + (size_t)c * frame_stride(t); }
+
+// Back to one shared multiplier (hipFree waits for the applies in flight).
+void drop_frames(nufft_toeplitz* t) {
+    t->framed = false;
+    free_buffer(t->own_bytes, t->d_kf, frames_bytes(t));
+}
+
 // Back to independent components (hipFree waits for the applies in flight).
 void drop_coupled(nufft_toeplitz* t) {
     t->coupled = false;
@@ -154,7 +169,7 @@ void release(nufft_toeplitz* t) {
             if (t->d_tw_fw[d]) (void)hipFree(t->d_tw_fw[d]);
             if (t->d_tw_bw[d]) (void)hipFree(t->d_tw_bw[d]);
         }
-        for (void* p : {t->d_ones, t->d_K, t->d_tmpA, t->d_tmpB, t->d_work, t->d_fft_work, t->d_coil, t->d_kd, t->d_kc, t->d_grids})
+        for (void* p : {t->d_ones, t->d_K, t->d_tmpA, t->d_tmpB, t->d_work, t->d_fft_work, t->d_coil, t->d_kd, t->d_kc, t->d_grids, t->d_kf})
             if (p) (void)hipFree(p);
         if (t->fft_bw) (void)rocfft_plan_destroy(t->fft_bw);
         if (t->fft_fw) (void)rocfft_plan_destroy(t->fft_fw);
@@ -225,14 +240,14 @@ int build_device(nufft_toeplitz* t) {
 }
 
 // K from the spectrum held in `grid` (complex<T>[2N...], overwritten): Nyquist planes zeroed, backward transform, scaled real part.
-// `src` may be `grid` itself.
-int multiplier_from(nufft_toeplitz* t, void* grid, const void* src, hipStream_t stream) {
+// `src` may be `grid` itself.  `K`: where the multiplier goes (d_K, or a frame's slot).
+int multiplier_from(nufft_toeplitz* t, void* K, void* grid, const void* src, hipStream_t stream) {
     const nufft::TzGrid g = grid_of(t);
     NUFFT_HIP(nufft::launch_tz_spectrum_load(g, grid, src, t->num_cus, stream));
     NUFFT_ROCFFT(rocfft_execution_info_set_stream(t->fft_info, stream));
     void* io[1] = {grid};
     NUFFT_ROCFFT(rocfft_execute(t->fft_bw, io, nullptr, t->fft_info));
-    NUFFT_HIP(nufft::launch_tz_real_part(g, t->d_K, grid, 1.0 / (double)grid_cells(t), t->num_cus, stream));
+    NUFFT_HIP(nufft::launch_tz_real_part(g, K, grid, 1.0 / (double)grid_cells(t), t->num_cus, stream));
     return NUFFT_OK;
 }
 
@@ -336,20 +351,21 @@ int fused_forward(nufft_toeplitz* t, void* out, const void* tmpB, hipStream_t st
     return strided_pass(t, 1, true, tmpB, out, stream, smap, accumulate);
 }
 
-int apply_fused(nufft_toeplitz* t, void* out, const void* in, hipStream_t stream, const void* smap = nullptr, bool accumulate = false) {
+// `K`: the multiplier of this component (d_K, or its frame's)
+int apply_fused(nufft_toeplitz* t, const void* K, void* out, const void* in, hipStream_t stream, const void* smap = nullptr, bool accumulate = false) {
     if (int rc = fused_backward(t, t->d_tmpB, in, stream, smap)) return rc;
-    NUFFT_HIP(nufft::launch_toeplitz_lines(t->dtype, t->N2[0], t->d_tmpB, t->d_K, t->N2[1] * t->N2[2], (int)t->N[0], t->d_map[0],
+    NUFFT_HIP(nufft::launch_toeplitz_lines(t->dtype, t->N2[0], t->d_tmpB, K, t->N2[1] * t->N2[2], (int)t->N[0], t->d_map[0],
                                         t->d_tw_fw[0], stream));
     return fused_forward(t, out, t->d_tmpB, stream, smap, accumulate);
 }
 
-int apply_dense(nufft_toeplitz* t, void* out, const void* in, hipStream_t stream, const void* smap = nullptr, bool accumulate = false) {
+int apply_dense(nufft_toeplitz* t, const void* K, void* out, const void* in, hipStream_t stream, const void* smap = nullptr, bool accumulate = false) {
     const nufft::TzGrid g = grid_of(t);
     void* io[1] = {t->d_work};
     if (smap) NUFFT_HIP(nufft::launch_tz_pad_map(g, t->d_work, in, smap, t->num_cus, stream));
     else NUFFT_HIP(nufft::launch_tz_pad(g, t->d_work, in, t->num_cus, stream));
     NUFFT_ROCFFT(rocfft_execute(t->fft_bw, io, nullptr, t->fft_info));
-    NUFFT_HIP(nufft::launch_tz_multiply(g, t->d_work, t->d_K, t->num_cus, stream));
+    NUFFT_HIP(nufft::launch_tz_multiply(g, t->d_work, K, t->num_cus, stream));
     NUFFT_ROCFFT(rocfft_execute(t->fft_fw, io, nullptr, t->fft_info));
     if (smap) NUFFT_HIP(nufft::launch_tz_crop_map(g, out, t->d_work, smap, accumulate, t->num_cus, stream));
     else NUFFT_HIP(nufft::launch_tz_crop(g, out, t->d_work, t->num_cus, stream));
@@ -358,14 +374,14 @@ int apply_dense(nufft_toeplitz* t, void* out, const void* in, hipStream_t stream
 
 // One coil of G_S: out (+)= conj(S) ⊙ G (S ⊙ in).  The streaming route of the fused path expands into d_coil, runs the plain apply
 // in place on it and combines into out.
-int apply_coil(nufft_toeplitz* t, void* out, const void* in, const void* smap, bool accumulate, hipStream_t stream) {
-    if (t->path == NUFFT_TOEPLITZ_PATH_DENSE) return apply_dense(t, out, in, stream, smap, accumulate);
-    if (t->maps_inpass) return apply_fused(t, out, in, stream, smap, accumulate);
+int apply_coil(nufft_toeplitz* t, const void* K, void* out, const void* in, const void* smap, bool accumulate, hipStream_t stream) {
+    if (t->path == NUFFT_TOEPLITZ_PATH_DENSE) return apply_dense(t, K, out, in, stream, smap, accumulate);
+    if (t->maps_inpass) return apply_fused(t, K, out, in, stream, smap, accumulate);
     void* outs[1] = {t->d_coil};
     const void* maps[1] = {smap};
     const void* ins[1] = {t->d_coil};
     NUFFT_HIP(nufft::launch_coil_expand(t->dtype, num_modes(t), 1, outs, maps, in, t->num_cus, stream));
-    if (int rc = apply_fused(t, t->d_coil, t->d_coil, stream)) return rc;
+    if (int rc = apply_fused(t, K, t->d_coil, t->d_coil, stream)) return rc;
     NUFFT_HIP(nufft::launch_coil_combine(t->dtype, num_modes(t), 1, out, maps, ins, accumulate, t->num_cus, stream));
     return NUFFT_OK;
 }
@@ -563,10 +579,11 @@ int nufft_toeplitz_set_spectrum(nufft_toeplitz* t, const void* T_modes, void* st
         return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_set_spectrum allocates and synchronises: not on a capturing stream");
     t->has_spectrum = false;
     drop_coupled(t);
+    drop_frames(t);
     Scratch s(t);
     int rc;
     if ((rc = s.acquire_grid()) || (rc = s.acquire_fft_work())) return rc;
-    if ((rc = multiplier_from(t, s.grid, T_modes, stream))) return rc;
+    if ((rc = multiplier_from(t, t->d_K, s.grid, T_modes, stream))) return rc;
     NUFFT_HIP(hipStreamSynchronize(stream));      // the temporaries are freed on return
     t->has_spectrum = true;
     return NUFFT_OK;
@@ -586,6 +603,7 @@ int nufft_toeplitz_set_points(nufft_toeplitz* t, const nufft_params* build, int6
         return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_set_points builds and destroys a plan: not on a capturing stream");
     t->has_spectrum = false;
     drop_coupled(t);
+    drop_frames(t);
 
     nufft_params prm;
     if (int prc = build_plan_params(t, build, prm)) return prc;
@@ -619,7 +637,7 @@ int nufft_toeplitz_set_points(nufft_toeplitz* t, const nufft_params* build, int6
     free_buffer(t->own_bytes, values, vbytes);
     if (rc) return fail(rc, "Toeplitz build (type 1 of the weights on the 2N grid): " + keep);
     if ((rc = s.acquire_fft_work())) return rc;
-    if ((rc = multiplier_from(t, s.grid, s.grid, stream))) return rc;
+    if ((rc = multiplier_from(t, t->d_K, s.grid, s.grid, stream))) return rc;
     NUFFT_HIP(hipStreamSynchronize(stream));
     t->has_spectrum = true;
     return NUFFT_OK;
@@ -640,6 +658,7 @@ int nufft_toeplitz_set_spectra_coupled(nufft_toeplitz* t, const void* const* T_p
         return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_set_spectra_coupled allocates and synchronises: not on a capturing stream");
     t->has_spectrum = false;
     t->coupled = false;
+    drop_frames(t);
     if ((rc = acquire_coupled(t))) return rc;
     Scratch s(t);
     if ((rc = s.acquire_grid()) || (rc = s.acquire_fft_work())) return rc;
@@ -671,6 +690,7 @@ int nufft_toeplitz_set_points_coupled(nufft_toeplitz* t, const nufft_params* bui
         return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_set_points_coupled builds and destroys a plan: not on a capturing stream");
     t->has_spectrum = false;
     t->coupled = false;
+    drop_frames(t);
     nufft_params prm;
     if ((rc = build_plan_params(t, build, prm))) return rc;
     if ((rc = acquire_coupled(t))) return rc;
@@ -710,6 +730,104 @@ int nufft_toeplitz_set_points_coupled(nufft_toeplitz* t, const nufft_params* bui
     if (rc) return fail(rc, (in_type1 ? "coupled Toeplitz build (type 1 of a pair's weights on the 2N grid): " : "coupled Toeplitz build: ") + keep);
     t->coupled = true;
     t->has_spectrum = true;
+    return NUFFT_OK;
+}
+
+int nufft_toeplitz_set_spectra_frames(nufft_toeplitz* t, const void* const* T, void* stream_) {
+    if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    if (!T) return fail(NUFFT_ERR_INVALID_ARG, "null table of spectra");
+    if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
+    for (int c = 0; c < t->C; ++c)
+        if (!T[c]) return fail(NUFFT_ERR_INVALID_ARG, "null spectrum");
+    DeviceGuard guard(t->device);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (capturing(stream))
+        return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_set_spectra_frames allocates and synchronises: not on a capturing stream");
+    t->has_spectrum = false;
+    t->framed = false;
+    drop_coupled(t);
+    int rc;
+    if (!t->d_kf && (rc = alloc(t, &t->d_kf, frames_bytes(t)))) return rc;
+    Scratch s(t);
+    if ((rc = s.acquire_grid()) || (rc = s.acquire_fft_work())) return rc;
+    for (int c = 0; c < t->C; ++c)
+        if ((rc = multiplier_from(t, frame_multiplier(t, c), s.grid, T[c], stream))) return rc;
+    NUFFT_HIP(hipStreamSynchronize(stream));      // the temporaries are freed on return
+    t->framed = true;
+    t->has_spectrum = true;
+    return NUFFT_OK;
+}
+
+int nufft_toeplitz_set_points_frames(nufft_toeplitz* t, const nufft_params* build, const int64_t* np, const void* const* coords,
+                                     const void* const* weights, void* stream_) {
+    if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    if (!np || !coords) return fail(NUFFT_ERR_INVALID_ARG, "null table of point counts or coordinates");
+    if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
+    int64_t most = 1;
+    for (int c = 0; c < t->C; ++c) {
+        if (np[c] < 0) return fail(NUFFT_ERR_INVALID_ARG, "negative number of points");
+        for (int d = 0; d < t->D; ++d)
+            if (np[c] > 0 && !coords[(size_t)c * t->D + d]) return fail(NUFFT_ERR_INVALID_ARG, "null coordinate vector");
+        most = std::max(most, np[c]);
+    }
+    DeviceGuard guard(t->device);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    if (capturing(stream))
+        return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_set_points_frames builds and destroys a plan: not on a capturing stream");
+    t->has_spectrum = false;
+    t->framed = false;
+    drop_coupled(t);
+    nufft_params prm;
+    int rc;
+    if ((rc = build_plan_params(t, build, prm))) return rc;
+    if (!t->d_kf && (rc = alloc(t, &t->d_kf, frames_bytes(t)))) return rc;
+
+    Scratch s(t);
+    // (the transform's own work buffer lives next to the plan here: every frame is transformed while the plan exists)
+    if ((rc = s.acquire_grid()) || (rc = s.acquire_fft_work())) return rc;
+    void* values = nullptr;
+    const size_t vbytes = (size_t)most * 2 * real_bytes(t->dtype);
+    if ((rc = alloc(t, &values, vbytes))) return rc;
+    nufft_plan* bp = nullptr;
+    rc = nufft_plan_create_ex(&bp, &prm);
+    bool in_type1 = true;
+    for (int c = 0; c < t->C && rc == NUFFT_OK; ++c) {
+        in_type1 = true;
+        t->build_bytes = bp->workspace_bytes;
+        rc = nufft_set_points(bp, np[c], coords + (size_t)c * t->D, stream);
+        t->build_bytes = bp->workspace_bytes;
+        if (rc == NUFFT_OK) {
+            hipError_t e = nufft::launch_tz_weights(t->dtype, values, weights ? weights[c] : nullptr, np[c], t->num_cus, stream);
+            if (e != hipSuccess) rc = fail(NUFFT_ERR_HIP, std::string("launch_tz_weights: ") + hipGetErrorString(e));
+        }
+        if (rc == NUFFT_OK) {
+            void* outs[1] = {s.grid};
+            const void* ins[1] = {values};
+            rc = nufft_exec_type1(bp, outs, ins, stream);
+        }
+        in_type1 = false;
+        if (rc == NUFFT_OK) rc = multiplier_from(t, frame_multiplier(t, c), s.grid, s.grid, stream);
+    }
+    if (rc == NUFFT_OK && hipStreamSynchronize(stream) != hipSuccess) rc = fail(NUFFT_ERR_HIP, "hipStreamSynchronize failed");
+    const std::string keep = rc ? nufft_last_error_message() : "";
+    if (bp) nufft_plan_destroy(bp);
+    t->build_bytes = 0;
+    free_buffer(t->own_bytes, values, vbytes);
+    if (rc) return fail(rc, (in_type1 ? "framed Toeplitz build (type 1 of a frame's weights on the 2N grid): " : "framed Toeplitz build: ") + keep);
+    t->framed = true;
+    t->has_spectrum = true;
+    return NUFFT_OK;
+}
+
+int32_t nufft_toeplitz_num_frames(const nufft_toeplitz* t) { return t && t->framed ? (int32_t)t->C : 0; }
+
+int nufft_toeplitz_multiplier_frame_ptr(const nufft_toeplitz* t, int32_t c, void** out_ptr, int64_t* out_bytes) {
+    if (!t || !out_ptr) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
+    if (!t->framed) return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_multiplier_frame_ptr: no framed build is in force");
+    if (c < 0 || c >= t->C) return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_multiplier_frame_ptr: the frame must satisfy 0 <= c < ntransforms");
+    *out_ptr = frame_multiplier(t, c);
+    if (out_bytes) *out_bytes = grid_cells(t) * (int64_t)real_bytes(t->dtype);
     return NUFFT_OK;
 }
 
@@ -756,8 +874,9 @@ int nufft_toeplitz_apply(nufft_toeplitz* t, void* const* out, const void* const*
     }
     for (int c = 0; c < t->C; ++c) {
         int rc = NUFFT_OK;
-        if (ncoils == 0) rc = t->path == NUFFT_TOEPLITZ_PATH_FUSED ? apply_fused(t, out[c], in[c], stream) : apply_dense(t, out[c], in[c], stream);
-        for (int s = 0; s < ncoils && !rc; ++s) rc = apply_coil(t, out[c], in[c], t->coil_maps[(size_t)s], s > 0, stream);
+        const void* K = t->framed ? frame_multiplier(t, c) : t->d_K;
+        if (ncoils == 0) rc = t->path == NUFFT_TOEPLITZ_PATH_FUSED ? apply_fused(t, K, out[c], in[c], stream) : apply_dense(t, K, out[c], in[c], stream);
+        for (int s = 0; s < ncoils && !rc; ++s) rc = apply_coil(t, K, out[c], in[c], t->coil_maps[(size_t)s], s > 0, stream);
         if (rc) return rc;
     }
     return NUFFT_OK;

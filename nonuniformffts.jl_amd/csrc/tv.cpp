@@ -22,12 +22,19 @@
 //
 // The host side only enqueues: per iteration one nufft_toeplitz_apply, the two stencil kernels and the decision kernel.  Every scalar
 // lives on the device; with check_every > 0 the host looks at the done flags now and then, and at nothing else.
+//
+// With the temporal term (nufft_tvpd_create_temporal) the objective gains tv_t ‖∇_t x‖₁, the difference along the
+// components, and the solver one more dual array z_c per component.  Without the spatial term the two kernels of tvt_kernels.hip are the
+// whole iteration (x⁺ = x − τ (q + μ x − b + ∇_tᴴz), then z <- P_{tv_t}(z + σ ∇_t x̄)) and y does not exist.  With it, one launch adds ∇_tᴴz
+// to q = G x, the spatial kernels run as they are (on q + ∇_tᴴz in place of q: the same x⁺), and the temporal dual kernel follows.  The
+// decision is always joint.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <string>
 #include <vector>
@@ -45,6 +52,10 @@ struct nufft_tv {
     int tile[3] = {1, 1, 1}, tiles[3] = {1, 1, 1};
     void* d_part = nullptr;               // double[C][G]
     int64_t own_bytes = 0;
+    // the difference along the components: flat over the n cells of a frame (tvt_kernels.hip)
+    int wide_t = 0;                       // two ComplexF32 per lane: n is even
+    int64_t Gt = 1;                       // workgroups per frame
+    void* d_part_t = nullptr;             // double[C][Gt], allocated by the first nufft_tv_norm_t
 };
 
 struct nufft_tvpd {
@@ -62,6 +73,12 @@ struct nufft_tvpd {
     void* d_hist = nullptr;               // double[max_iter][C][2]
     int64_t array_bytes = 0, own_bytes = 0;
     std::vector<void*> qtab;
+    // the temporal term (nufft_tvpd_create_temporal); without it nd = D and d_y holds [C][D] arrays as ever
+    bool temporal = false;
+    int periodic = 0, spatial = 1;
+    int nd = 1;                           // arrays per component in d_y: y_1 ... y_D (spatial term on), then z
+    double tv_t = 0.0;
+    void* d_part_t = nullptr;             // double[C][Gt] of the temporal dual kernel
 };
 
 namespace {
@@ -71,6 +88,7 @@ void release(nufft_tv* t) {
     if (t->device >= 0) {
         DeviceGuard g(t->device);
         if (t->d_part) (void)hipFree(t->d_part);
+        if (t->d_part_t) (void)hipFree(t->d_part_t);
     }
     delete t;
 }
@@ -80,7 +98,7 @@ void release(nufft_tvpd* s) {
     release(s->tv);
     if (s->device >= 0) {
         DeviceGuard g(s->device);
-        for (void* p : {s->d_q, s->d_y, s->d_part, s->d_hist})
+        for (void* p : {s->d_q, s->d_y, s->d_part, s->d_hist, s->d_part_t})
             if (p) (void)hipFree(p);
         s->scal.release();
     }
@@ -116,6 +134,8 @@ int create_geometry(nufft_tv** out, int dtype, int D, const int64_t* N, int C, i
         t->tiles[d] = (int)((t->N[d] + t->tile[d] - 1) / t->tile[d]);
         t->G *= t->tiles[d];
     }
+    t->wide_t = f32 && t->n % 2 == 0 ? 1 : 0;
+    t->Gt = (t->n / (t->wide_t ? 2 : 1) + (int64_t)stream::kThreads * kTvtPacks - 1) / ((int64_t)stream::kThreads * kTvtPacks);
     DeviceGuard guard(device);
     if (int rc = alloc_buffer(t->own_bytes, "total-variation", &t->d_part, (size_t)C * t->G * sizeof(double))) {
         const std::string keep = nufft_last_error_message();
@@ -187,6 +207,54 @@ int run_operator(nufft_tv* t, TvMode mode, void* const* x, void* const* y, hipSt
         hipError_t e = launch_tv(a, mode, stream);
         if (e != hipSuccess) return fail(NUFFT_ERR_HIP, std::string("launch of a total-variation kernel: ") + hipGetErrorString(e));
     }
+    return NUFFT_OK;
+}
+
+TvtLaunch launch_template_t(const nufft_tv* t) {
+    TvtLaunch a{};
+    a.dtype = t->dtype;
+    a.wide = t->wide_t;
+    a.C = t->C;
+    a.n = t->n;
+    a.G = t->Gt;
+    return a;
+}
+
+// Frame c of the axis: itself inside 0 ... C − 1, the other end on a periodic axis, −1 (no such frame) otherwise.
+int frame_of(int c, int C, int periodic) {
+    if (c >= 0 && c < C) return c;
+    if (!periodic) return -1;
+    return c < 0 ? C - 1 : 0;
+}
+
+// The slots of one batch (slot j: frame c0 + j − 1).  `zero_last`: the table is the z a ∇_tᴴ reads, whose last frame is zero by
+// definition on the non-periodic axis.
+template <typename Ptr>
+void fill_slots(Ptr* slots, int c0, int nc, int C, int periodic, bool zero_last, const std::function<Ptr(int)>& at) {
+    for (int j = 0; j < nc + 2; ++j) {
+        const int c = frame_of(c0 + j - 1, C, periodic);
+        slots[j] = c < 0 || (zero_last && !periodic && c == C - 1) ? nullptr : at(c);
+    }
+}
+
+// One temporal operator launch per batch of components
+int run_operator_t(nufft_tv* t, TvtMode mode, void* const* x, void* const* z, int periodic, hipStream_t stream) {
+    TvtLaunch a = launch_template_t(t);
+    a.part = static_cast<double*>(t->d_part_t);
+    for (int c0 = 0; c0 < t->C; c0 += kTvBatch) {
+        a.c0 = c0;
+        a.nc = std::min(kTvBatch, t->C - c0);
+        fill_slots<void*>(a.x, c0, a.nc, t->C, periodic, false, [&](int c) { return x[c]; });
+        if (z) fill_slots<void*>(a.z, c0, a.nc, t->C, periodic, mode == TVT_ADJOINT, [&](int c) { return z[c]; });
+        hipError_t e = launch_tvt(a, mode, stream);
+        if (e != hipSuccess) return fail(NUFFT_ERR_HIP, std::string("launch of a total-variation kernel: ") + hipGetErrorString(e));
+    }
+    return NUFFT_OK;
+}
+
+int check_temporal(const nufft_tv* t, int periodic) {
+    if (t->C < 2) return fail(NUFFT_ERR_INVALID_ARG, "the difference along the components needs ntransforms >= 2");
+    if (periodic != 0 && periodic != 1) return fail(NUFFT_ERR_INVALID_ARG, "periodic must be 0 or 1");
     return NUFFT_OK;
 }
 
@@ -288,12 +356,59 @@ int nufft_tv_norm(nufft_tv* t, const void* const* x, double* sums_out_device, vo
     return NUFFT_OK;
 }
 
-int nufft_tvpd_create(nufft_tvpd** out, nufft_toeplitz* tz, const nufft_tvpd_params* params) {
-    if (!out || !tz || !params) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
-    *out = nullptr;
+int nufft_tv_gradient_t(nufft_tv* t, void* const* z_out, const void* const* x, int periodic, void* stream) {
+    if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    int rc;
+    if ((rc = check_temporal(t, periodic)) || (rc = check_table(z_out, t->C)) || (rc = check_table(x, t->C)) || (rc = check_overlap(t, z_out, t->C, x, t->C)))
+        return rc;
+    DeviceGuard guard(t->device);
+    return run_operator_t(t, TVT_GRADIENT, const_cast<void* const*>(x), z_out, periodic, static_cast<hipStream_t>(stream));
+}
+
+int nufft_tv_adjoint_t(nufft_tv* t, void* const* x_out, const void* const* z, int periodic, void* stream) {
+    if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    int rc;
+    if ((rc = check_temporal(t, periodic)) || (rc = check_table(x_out, t->C)) || (rc = check_table(z, t->C)) || (rc = check_overlap(t, x_out, t->C, z, t->C)))
+        return rc;
+    DeviceGuard guard(t->device);
+    return run_operator_t(t, TVT_ADJOINT, x_out, const_cast<void* const*>(z), periodic, static_cast<hipStream_t>(stream));
+}
+
+int nufft_tv_norm_t(nufft_tv* t, const void* const* x, int periodic, double* sums_out_device, void* stream) {
+    if (!t || !sums_out_device) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    int rc;
+    if ((rc = check_temporal(t, periodic)) || (rc = check_table(x, t->C))) return rc;
+    DeviceGuard guard(t->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!t->d_part_t) {
+        if (capturing(s)) return fail(NUFFT_ERR_INVALID_ARG, "the first nufft_tv_norm_t allocates the partial sums: not on a capturing stream");
+        if ((rc = alloc_buffer(t->own_bytes, "total-variation", &t->d_part_t, (size_t)t->C * t->Gt * sizeof(double)))) return rc;
+    }
+    if ((rc = run_operator_t(t, TVT_NORM, const_cast<void* const*>(x), nullptr, periodic, s))) return rc;
+    hipError_t e = launch_tv_sum(static_cast<const double*>(t->d_part_t), t->Gt, t->C, sums_out_device, s);
+    if (e != hipSuccess) return fail(NUFFT_ERR_HIP, std::string("launch of a total-variation kernel: ") + hipGetErrorString(e));
+    return NUFFT_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// nufft_tvpd_create (tp = null) and nufft_tvpd_create_temporal
+int create_solver(nufft_tvpd** out, nufft_toeplitz* tz, const nufft_tvpd_params* params, const nufft_tvt_params* tparams) {
     nufft_toeplitz_info ti;
     int rc = toeplitz_info(tz, ti);
     if (rc) return rc;
+    nufft_tvt_params tp;
+    std::memset(&tp, 0, sizeof(tp));
+    tp.spatial = 1;
+    if (tparams) {
+        if ((rc = read_params(tp, tparams, "nufft_tvt_params"))) return rc;
+        if (ti.ntransforms < 2) return fail(NUFFT_ERR_INVALID_ARG, "the temporal term needs ntransforms >= 2 (the frames are the components)");
+        if (!weight_ok(tp.tv_t)) return fail(NUFFT_ERR_INVALID_ARG, "tv_t must be finite and not negative");
+        if ((tp.spatial != 0 && tp.spatial != 1) || (tp.periodic != 0 && tp.periodic != 1))
+            return fail(NUFFT_ERR_INVALID_ARG, "spatial and periodic must be 0 or 1");
+    }
     nufft_tvpd_params p;
     if ((rc = read_params(p, params, "nufft_tvpd_params"))) return rc;
     if (p.max_iter < 1) return fail(NUFFT_ERR_INVALID_ARG, "max_iter must be at least 1");
@@ -321,13 +436,23 @@ int nufft_tvpd_create(nufft_tvpd** out, nufft_toeplitz* tz, const nufft_tvpd_par
     s->check_every = p.check_every;
     s->tol = p.tol;
     s->step = p.step;
-    s->sigma = p.sigma > 0.0 ? p.sigma : 1.0 / (8.0 * s->D * p.step);
+    s->temporal = tparams != nullptr;
+    s->periodic = tp.periodic;
+    s->spatial = tp.spatial;
+    s->tv_t = tp.tv_t;
+    s->nd = s->temporal ? (s->spatial ? s->D : 0) + 1 : s->D;
+    const int differences = s->temporal ? s->nd : s->D;      // ‖[∇; ∇_t]‖² <= 4 (D + 1), ‖∇_t‖² <= 4, ‖∇‖² <= 4 D
+    s->sigma = p.sigma > 0.0 ? p.sigma : 1.0 / (8.0 * differences * p.step);
     s->lambda = p.lambda;
-    s->weight.assign(s->C, p.tv);
+    s->weight.assign(s->C, s->spatial ? p.tv : 0.0);
     s->n = s->tv->n;
     const size_t rb = real_bytes(s->dtype), comp = padded((size_t)s->n * 2 * rb);
     s->stride = (int64_t)(comp / rb);
-    s->array_bytes = (int64_t)(1 + s->D) * s->C * (int64_t)comp;
+    s->array_bytes = (int64_t)(1 + s->nd) * s->C * (int64_t)comp;
+    if (s->temporal && s->tv->Gt > (int64_t)INT_MAX / s->C) {
+        release(s);
+        return fail(NUFFT_ERR_UNSUPPORTED, std::to_string(s->tv->Gt) + " workgroups for each of " + std::to_string(s->C) + " frames: more than 2^31 - 1 rows of partial sums");
+    }
 
     DeviceGuard guard(s->device);
     int cus = 256;
@@ -337,8 +462,10 @@ int nufft_tvpd_create(nufft_tvpd** out, nufft_toeplitz* tz, const nufft_tvpd_par
     }
     s->G0 = stream::stream_workgroups((int64_t)(comp / 16), cus);
     auto alloc = [&](void** ptr, size_t bytes) { return alloc_buffer(s->own_bytes, "TV solver", ptr, bytes); };
-    if ((rc = alloc(&s->d_q, (size_t)s->C * comp)) || (rc = alloc(&s->d_y, (size_t)s->C * s->D * comp)) ||
-        (rc = alloc(&s->d_part, (size_t)s->C * s->tv->G * 2 * sizeof(double))) || (rc = alloc(&s->d_hist, hist_bytes(s))) ||
+    const int64_t primal_rows = s->temporal && !s->spatial ? s->tv->Gt : s->tv->G;      // of the kernel that forms x⁺
+    if ((rc = alloc(&s->d_q, (size_t)s->C * comp)) || (rc = alloc(&s->d_y, (size_t)s->C * s->nd * comp)) ||
+        (rc = alloc(&s->d_part, (size_t)s->C * primal_rows * 2 * sizeof(double))) || (rc = alloc(&s->d_hist, hist_bytes(s))) ||
+        (s->temporal && (rc = alloc(&s->d_part_t, (size_t)s->C * s->tv->Gt * sizeof(double)))) ||
         (rc = s->scal.create(s->own_bytes, "TV solver", scal_bytes(s), "hipHostMalloc of the solver's host mirror failed"))) {
         const std::string keep = nufft_last_error_message();
         release(s);
@@ -355,6 +482,44 @@ int nufft_tvpd_create(nufft_tvpd** out, nufft_toeplitz* tz, const nufft_tvpd_par
     return NUFFT_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+int64_t nufft_sizeof_tvt_params(void) { return (int64_t)sizeof(nufft_tvt_params); }
+
+int nufft_tvpd_create(nufft_tvpd** out, nufft_toeplitz* tz, const nufft_tvpd_params* params) {
+    if (!out || !tz || !params) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    return create_solver(out, tz, params, nullptr);
+}
+
+int nufft_tvpd_create_temporal(nufft_tvpd** out, nufft_toeplitz* tz, const nufft_tvpd_params* params, const nufft_tvt_params* temporal) {
+    if (!out || !tz || !params || !temporal) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    return create_solver(out, tz, params, temporal);
+}
+
+int nufft_tvpd_set_tv_t(nufft_tvpd* s, double tv_t) {
+    if (!s) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    if (!s->temporal) return fail(NUFFT_ERR_INVALID_ARG, "the solver has no temporal term (nufft_tvpd_create_temporal makes one)");
+    if (!weight_ok(tv_t)) return fail(NUFFT_ERR_INVALID_ARG, "tv_t must be finite and not negative");
+    s->tv_t = tv_t;
+    return NUFFT_OK;
+}
+
+int nufft_tvpd_get_temporal(const nufft_tvpd* s, nufft_tvt_params* o) {
+    if (!s || !o) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    if (!s->temporal) return fail(NUFFT_ERR_INVALID_ARG, "the solver has no temporal term (nufft_tvpd_create_temporal makes one)");
+    nufft_tvt_params i;
+    std::memset(&i, 0, sizeof(i));
+    i.periodic = s->periodic;
+    i.spatial = s->spatial;
+    i.tv_t = s->tv_t;
+    write_info(o, i);
+    return NUFFT_OK;
+}
+
 int nufft_tvpd_destroy(nufft_tvpd* s) {
     release(s);
     return NUFFT_OK;
@@ -365,6 +530,8 @@ int nufft_tvpd_set_tv(nufft_tvpd* s, const double* weights, int64_t count) {
     if (count != s->C) return fail(NUFFT_ERR_INVALID_ARG, "count must be ntransforms");
     for (int c = 0; c < s->C; ++c)
         if (!weight_ok(weights[c])) return fail(NUFFT_ERR_INVALID_ARG, "tv must be finite and not negative");
+    for (int c = 0; c < s->C && !s->spatial; ++c)
+        if (weights[c] != 0.0) return fail(NUFFT_ERR_INVALID_ARG, "the solver was created without the spatial term (spatial = 0): tv must be 0");
     s->weight.assign(weights, weights + s->C);
     return NUFFT_OK;
 }
@@ -418,7 +585,7 @@ int nufft_tvpd_solve(nufft_tvpd* s, void* const* x, const void* const* b, int us
     h.C = s->C;
     h.G = s->G0;
     h.n = s->n;
-    h.ystride = s->stride * s->D;
+    h.ystride = s->stride * s->nd;
     h.y = s->d_y;
     h.max_iter = s->max_iter;
     h.joint = nufft_toeplitz_num_coupled(s->tz) > 0 ? 1 : 0;
@@ -443,10 +610,55 @@ int nufft_tvpd_solve(nufft_tvpd* s, void* const* x, const void* const* b, int us
                 h.x[k] = a.x[k] = x[c];
                 a.b[k] = b[c];
                 a.q[k] = s->qtab[c];
-                for (int d = 0; d < s->D; ++d) a.y[k][d] = static_cast<char*>(s->d_y) + ((size_t)c * s->D + d) * comp;
+                for (int d = 0; d < s->D && s->spatial; ++d) a.y[k][d] = static_cast<char*>(s->d_y) + ((size_t)c * s->nd + d) * comp;
                 a.tv[k] = s->weight[c];
             }
             hipError_t e = launch();
+            if (e != hipSuccess) return fail(NUFFT_ERR_HIP, std::string("launch of a TV solver kernel: ") + hipGetErrorString(e));
+        }
+        return NUFFT_OK;
+    };
+
+    // the temporal term: z_c is the last of component c's arrays in d_y; one launch per batch of kTvBatch frames
+    TvtLaunch ta = launch_template_t(s->tv);
+    ta.tv_t = s->tv_t;
+    ta.step = s->step;
+    ta.sigma = s->sigma;
+    ta.lambda = s->lambda;
+    ta.flag = h.s.flag;
+    auto for_frames = [&](TvtMode mode) -> int {
+        const bool reads_z = mode != TVT_DUAL;      // ∇_tᴴz: the last frame's z is zero by definition on the non-periodic axis
+        for (int c0 = 0; c0 < s->C; c0 += kTvBatch) {
+            ta.c0 = c0;
+            ta.nc = std::min(kTvBatch, s->C - c0);
+            fill_slots<void*>(ta.x, c0, ta.nc, s->C, s->periodic, false, [&](int c) { return x[c]; });
+            fill_slots<void*>(ta.q, c0, ta.nc, s->C, s->periodic, false, [&](int c) { return s->qtab[c]; });
+            fill_slots<void*>(ta.z, c0, ta.nc, s->C, s->periodic, reads_z,
+                              [&](int c) { return static_cast<void*>(static_cast<char*>(s->d_y) + ((size_t)c * s->nd + s->nd - 1) * comp); });
+            for (int k = 0; k < ta.nc; ++k) ta.b[k] = b[c0 + k];
+            hipError_t e = launch_tvt(ta, mode, stream);
+            if (e != hipSuccess) return fail(NUFFT_ERR_HIP, std::string("launch of a TV solver kernel: ") + hipGetErrorString(e));
+        }
+        return NUFFT_OK;
+    };
+    TvtDecide td{};
+    td.C = s->C;
+    td.tol = s->tol;
+    td.tv_t = s->tv_t;
+    td.part_p = static_cast<const double*>(s->d_part);
+    td.part_s = s->spatial ? static_cast<const double*>(s->tv->d_part) : nullptr;
+    td.part_t = static_cast<const double*>(s->d_part_t);
+    td.Pp = s->spatial ? s->tv->G : s->tv->Gt;
+    td.Ps = s->tv->G;
+    td.Pt = s->tv->Gt;
+    td.s = h.s;
+    auto decide_frames = [&](int it) -> int {
+        td.it = it;
+        for (int c0 = 0; c0 < s->C; c0 += kTvBatch) {
+            td.c0 = c0;
+            td.nc = std::min(kTvBatch, s->C - c0);
+            for (int k = 0; k < td.nc; ++k) td.tv[k] = s->weight[c0 + k];
+            hipError_t e = launch_tvt_decide(td, stream);
             if (e != hipSuccess) return fail(NUFFT_ERR_HIP, std::string("launch of a TV solver kernel: ") + hipGetErrorString(e));
         }
         return NUFFT_OK;
@@ -459,11 +671,20 @@ int nufft_tvpd_solve(nufft_tvpd* s, void* const* x, const void* const* b, int us
     for (int it = 1; it <= s->max_iter; ++it) {
         h.it = it;
         if ((rc = nufft_toeplitz_apply(s->tz, s->qtab.data(), const_cast<const void* const*>(x), stream))) return rc;      // q = G x
-        a.part = static_cast<double*>(s->d_part);
-        if ((rc = for_batches([&]() { return launch_tv(a, TV_PRIMAL, stream); }))) return rc;
-        a.part = static_cast<double*>(s->tv->d_part);
-        if ((rc = for_batches([&]() { return launch_tv(a, TV_DUAL, stream); }))) return rc;
-        if ((rc = for_batches([&]() { return launch_tv_decide(h, stream); }))) return rc;
+        if (s->temporal && !s->spatial) {
+            ta.part = static_cast<double*>(s->d_part);
+            if ((rc = for_frames(TVT_PRIMAL))) return rc;
+        } else {
+            if (s->temporal && (rc = for_frames(TVT_ADD))) return rc;      // q <- q + ∇_tᴴz
+            a.part = static_cast<double*>(s->d_part);
+            if ((rc = for_batches([&]() { return launch_tv(a, TV_PRIMAL, stream); }))) return rc;
+            a.part = static_cast<double*>(s->tv->d_part);
+            if ((rc = for_batches([&]() { return launch_tv(a, TV_DUAL, stream); }))) return rc;
+        }
+        if (s->temporal) {
+            ta.part = static_cast<double*>(s->d_part_t);
+            if ((rc = for_frames(TVT_DUAL)) || (rc = decide_frames(it))) return rc;
+        } else if ((rc = for_batches([&]() { return launch_tv_decide(h, stream); }))) return rc;
         s->enqueued = it;
         if (s->check_every > 0 && it % s->check_every == 0 && it < s->max_iter) {
             if ((rc = s->scal.fetch(stream))) return rc;

@@ -22,41 +22,12 @@
 #include "nufft_mi355x.h"
 #include "stream_kernels.h"
 #include "tv.h"
+#include "tv_cells.h"
 
 namespace nufft {
 using namespace stream;
+using namespace tvcells;
 namespace {
-
-template <typename T>
-struct alignas(2 * sizeof(T)) Cx {
-    T re, im;
-};
-
-template <typename T, int V>
-struct alignas(V * 2 * sizeof(T)) Cells {
-    Cx<T> v[V];
-};
-
-template <typename T, int V>
-__device__ __forceinline__ Cells<T, V> load_cells(const Cx<T>* a, int64_t at) {
-    return *reinterpret_cast<const Cells<T, V>*>(a + at);
-}
-template <typename T, int V>
-__device__ __forceinline__ void store_cells(Cx<T>* a, int64_t at, const Cells<T, V>& c) {
-    *reinterpret_cast<Cells<T, V>*>(a + at) = c;
-}
-
-template <typename T>
-__device__ __forceinline__ Cx<T> sub(Cx<T> a, Cx<T> b) {
-    return Cx<T>{a.re - b.re, a.im - b.im};
-}
-template <typename T, int V>
-__device__ __forceinline__ Cells<T, V> sub(const Cells<T, V>& a, const Cells<T, V>& b) {
-    Cells<T, V> r;
-#pragma unroll
-    for (int w = 0; w < V; ++w) r.v[w] = sub(a.v[w], b.v[w]);
-    return r;
-}
 
 // Where a thread works: cell (i0 ... i0 + V − 1, i1, i2), the first of the `steps` cells it visits along the marching dimension
 // (D = 1: one cell, D = 2: dimension 2, D = 3: dimension 3), and whether it lies inside the box at all.

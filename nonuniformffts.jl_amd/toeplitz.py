@@ -163,17 +163,8 @@ class ToeplitzOperator:
             raise ValueError("basis must be contiguous")
         return _aligned(tuple(basis[a] for a in range(K)))
 
-    def set_points(self, points, weights: Optional[torch.Tensor] = None, *, basis: Optional[torch.Tensor] = None, m=None,
-                   sigma: Optional[float] = None, σ: Optional[float] = None, kernel=None, kernel_evalmode=None) -> "ToeplitzOperator":
-        """Builds the multiplier from ``points`` (what ``set_points`` of the plan accepts) and real ``weights`` (None = ones) with an
-        internal plan of 2N modes that is destroyed before the call returns (it is large while it lives: 17 GB at 256³, σ = 2,
-        ComplexF64).  ``m`` / ``sigma`` / ``kernel`` / ``kernel_evalmode`` override the parent plan's window for this build.
-
-        ``basis``: a contiguous complex tensor ``(ntransforms, Np)`` of the plan's element type (a ``(Np,)`` vector when
-        ``ntransforms == 1``): the components are then coupled, ``(G u)_a = Σ_b A^H diag(w conj(φ_a) φ_b) A u_b``."""
-        if basis is not None:
-            basis = self._basis_rows(basis)        # the component count needs no device
-        self._require_gpu()
+    def _check_points(self, points):
+        """One point set as ``set_points`` of the plan takes it -> (tuple of ndim contiguous vectors, their length)."""
         if isinstance(points, torch.Tensor):
             if points.dim() == 1:
                 points = (points,)
@@ -194,41 +185,112 @@ class ToeplitzOperator:
         n = points[0].numel()
         if any(x.numel() != n for x in points):
             raise DimensionMismatch("input points must have the same length along all dimensions")
-        wptr = None
-        if weights is not None:
-            if not isinstance(weights, torch.Tensor) or weights.device != self.device:
-                raise ValueError(f"weights must be a torch tensor on {self.device}")
-            if weights.dtype != self.T:
-                raise ValueError(f"weights must be real with the plan's accuracy ({self.T}); complex weights are not supported")
-            if weights.dim() != 1 or not weights.is_contiguous():
-                raise ValueError("weights must be a contiguous vector")
-            if weights.numel() != n:
-                raise DimensionMismatch(f"wrong length of the weights (expected {n}, got {weights.numel()})")
-            wptr = C.c_void_p(weights.data_ptr())
-        if σ is not None:
-            sigma = σ
-        build = None
-        if any(v is not None for v in (m, sigma, kernel, kernel_evalmode)):
-            kernel = self._kernel if kernel is None else (kernel() if isinstance(kernel, type) else kernel)
-            mode = self._evalmode if kernel_evalmode is None else (kernel_evalmode() if isinstance(kernel_evalmode, type) else kernel_evalmode)
-            if type(kernel) not in _KERNEL_IDS:
-                raise ValueError("kernel must be BackwardsKaiserBesselKernel, KaiserBesselKernel, GaussianKernel or BSplineKernel")
-            if not isinstance(mode, (Direct, FastApproximation)):
-                raise ValueError("kernel_evalmode must be Direct() or FastApproximation()")
-            prm = _lib.NufftParams()
-            prm.struct_size = C.sizeof(_lib.NufftParams)
-            prm.half_support = 0 if m is None else (m.M if isinstance(m, HalfSupport) else int(m))
-            prm.sigma = 0.0 if sigma is None else float(sigma)
-            prm.kernel = _KERNEL_IDS[type(kernel)]
-            kparam = getattr(kernel, "beta", None) if not isinstance(kernel, GaussianKernel) else kernel.ell
-            prm.kernel_param = 0.0 if kparam is None else float(kparam)
-            prm.evalmode = _lib.EVAL_DIRECT if isinstance(mode, Direct) else _lib.EVAL_FAST_APPROXIMATION
-            build = C.byref(prm)
+        return points, n
+
+    def _check_weights(self, weights, n):
+        """Real weights of ``n`` points -> their device pointer (None: ones)."""
+        if weights is None:
+            return None
+        if not isinstance(weights, torch.Tensor) or weights.device != self.device:
+            raise ValueError(f"weights must be a torch tensor on {self.device}")
+        if weights.dtype != self.T:
+            raise ValueError(f"weights must be real with the plan's accuracy ({self.T}); complex weights are not supported")
+        if weights.dim() != 1 or not weights.is_contiguous():
+            raise ValueError("weights must be a contiguous vector")
+        if weights.numel() != n:
+            raise DimensionMismatch(f"wrong length of the weights (expected {n}, got {weights.numel()})")
+        return C.c_void_p(weights.data_ptr())
+
+    def _build_params(self, m, sigma, kernel, kernel_evalmode):
+        """The window of a build that overrides the parent plan's: a ``byref`` for the C ABI, or None."""
+        if all(v is None for v in (m, sigma, kernel, kernel_evalmode)):
+            return None
+        kernel = self._kernel if kernel is None else (kernel() if isinstance(kernel, type) else kernel)
+        mode = self._evalmode if kernel_evalmode is None else (kernel_evalmode() if isinstance(kernel_evalmode, type) else kernel_evalmode)
+        if type(kernel) not in _KERNEL_IDS:
+            raise ValueError("kernel must be BackwardsKaiserBesselKernel, KaiserBesselKernel, GaussianKernel or BSplineKernel")
+        if not isinstance(mode, (Direct, FastApproximation)):
+            raise ValueError("kernel_evalmode must be Direct() or FastApproximation()")
+        prm = _lib.NufftParams()
+        prm.struct_size = C.sizeof(_lib.NufftParams)
+        prm.half_support = 0 if m is None else (m.M if isinstance(m, HalfSupport) else int(m))
+        prm.sigma = 0.0 if sigma is None else float(sigma)
+        prm.kernel = _KERNEL_IDS[type(kernel)]
+        kparam = getattr(kernel, "beta", None) if not isinstance(kernel, GaussianKernel) else kernel.ell
+        prm.kernel_param = 0.0 if kparam is None else float(kparam)
+        prm.evalmode = _lib.EVAL_DIRECT if isinstance(mode, Direct) else _lib.EVAL_FAST_APPROXIMATION
+        return C.byref(prm)
+
+    def set_points(self, points, weights: Optional[torch.Tensor] = None, *, basis: Optional[torch.Tensor] = None, m=None,
+                   sigma: Optional[float] = None, σ: Optional[float] = None, kernel=None, kernel_evalmode=None) -> "ToeplitzOperator":
+        """Builds the multiplier from ``points`` (what ``set_points`` of the plan accepts) and real ``weights`` (None = ones) with an
+        internal plan of 2N modes that is destroyed before the call returns (it is large while it lives: 17 GB at 256³, σ = 2,
+        ComplexF64).  ``m`` / ``sigma`` / ``kernel`` / ``kernel_evalmode`` override the parent plan's window for this build.
+
+        ``basis``: a contiguous complex tensor ``(ntransforms, Np)`` of the plan's element type (a ``(Np,)`` vector when
+        ``ntransforms == 1``): the components are then coupled, ``(G u)_a = Σ_b A^H diag(w conj(φ_a) φ_b) A u_b``."""
+        if basis is not None:
+            basis = self._basis_rows(basis)        # the component count needs no device
+        self._require_gpu()
+        points, n = self._check_points(points)
+        wptr = self._check_weights(weights, n)
+        build = self._build_params(m, σ if σ is not None else sigma, kernel, kernel_evalmode)
         if basis is not None:
             rows = self._check_basis(basis, n)
             _check(lib.nufft_toeplitz_set_points_coupled(self._handle, build, n, _ptr_table(points), wptr, _ptr_table(rows), self._stream()))
             return self
         _check(lib.nufft_toeplitz_set_points(self._handle, build, n, _ptr_table(points), wptr, self._stream()))
+        return self
+
+    @property
+    def framed(self) -> bool:
+        """True while a framed build (``set_points_frames`` / ``set_spectra_frames``) is in force: one multiplier per component."""
+        return bool(self._handle.value) and lib.nufft_toeplitz_num_frames(self._handle) > 0
+
+    def set_points_frames(self, points, weights=None, *, m=None, sigma: Optional[float] = None, σ: Optional[float] = None, kernel=None,
+                          kernel_evalmode=None) -> "ToeplitzOperator":
+        """Dynamic imaging: ``points`` is a sequence of ``ntransforms`` point sets, each as ``set_points`` takes one (a frame may have no
+        points: its multiplier is zero); ``weights``: None, or a sequence with None (= ones) or a real vector per frame.  From here on
+        ``apply`` computes ``out[c] = G_c u[c]`` with frame c's own multiplier; the solvers treat the frames as independent
+        components.  One internal 2N plan serves every frame and is destroyed before the call returns."""
+        self._require_gpu()
+        self._require_open()
+        K = self.ntransforms
+        points = tuple(points)
+        if len(points) != K:
+            raise DimensionMismatch(f"wrong amount of point sets (expected {K} frames, got {len(points)})")
+        weights = (None,) * K if weights is None else tuple(weights)
+        if len(weights) != K:
+            raise DimensionMismatch(f"wrong amount of weight vectors (expected {K} frames, got {len(weights)})")
+        sets, counts, wptrs = [], [], []
+        for pts, w in zip(points, weights):
+            pts, n = self._check_points(pts)
+            sets.extend(pts)
+            counts.append(n)
+            wptrs.append(self._check_weights(w, n))
+        build = self._build_params(m, σ if σ is not None else sigma, kernel, kernel_evalmode)
+        wtab = None if all(w is None for w in wptrs) else (C.c_void_p * K)(*wptrs)
+        _check(lib.nufft_toeplitz_set_points_frames(self._handle, build, (C.c_int64 * K)(*counts), _ptr_table(sets), wtab, self._stream()))
+        return self
+
+    def set_spectra_frames(self, T) -> "ToeplitzOperator":
+        """The framed counterpart of ``set_spectrum``: ``T`` of shape ``(ntransforms, *padded_shape)`` or a sequence of that many
+        ``padded_shape`` tensors, ``T[c]`` the spectrum of frame c.  Only read."""
+        K = self.ntransforms
+        if isinstance(T, torch.Tensor):
+            if T.dim() != self.ndim + 1 or T.shape[0] != K:
+                raise DimensionMismatch(f"wrong dimensions of the spectra (expected tensor shape ({K}, ...), got {tuple(T.shape)})")
+            if not T.is_contiguous():
+                raise ValueError("the spectra must be contiguous")
+            T = tuple(T[c] for c in range(K))
+        else:
+            T = tuple(T)
+            if len(T) != K:
+                raise DimensionMismatch(f"wrong amount of spectra (expected {K} frames, got {len(T)})")
+        self._require_gpu()
+        self._require_open()
+        _check_coil_arrays(T, self.device, self.Z, self.padded_shape, "the spectra")
+        _check(lib.nufft_toeplitz_set_spectra_frames(self._handle, _ptr_table(T), self._stream()))
         return self
 
     def set_maps(self, maps) -> "ToeplitzOperator":
@@ -334,17 +396,23 @@ class ToeplitzOperator:
         _check(lib.nufft_toeplitz_max_eigenvalue(self._handle, _ptr_table(v_t), iters, out, self._stream()))
         return tuple(out)
 
-    def multiplier(self, a: Optional[int] = None, b: Optional[int] = None) -> torch.Tensor:
+    def multiplier(self, a: Optional[int] = None, b: Optional[int] = None, *, frame: Optional[int] = None) -> torch.Tensor:
         """The real multiplier ``K`` (shape ``padded_shape``): a view of the device array the operator holds — valid while the
         operator lives, rewritten by the next ``set_points`` / ``set_spectrum``; ``.clone()`` it to keep it.
 
         On a coupled operator ``multiplier(a, b)`` is the block ``K_ab``: a real view for ``a == b``, a complex view for ``a < b``
-        (``K_ba = conj(K_ab)``: ``a > b`` raises), freed by the next uncoupled build."""
+        (``K_ba = conj(K_ab)``: ``a > b`` raises), freed by the next uncoupled build.  On a framed operator ``multiplier(frame=c)``
+        is the real multiplier of frame c, freed by the next plain or coupled build."""
         self._require_gpu()
         self._require_open()
         ptr, nbytes = C.c_void_p(), C.c_int64()
         if (a is None) != (b is None):
             raise ValueError("multiplier() takes no component or the pair (a, b)")
+        if frame is not None and a is not None:
+            raise ValueError("multiplier() takes the pair (a, b) of a coupled operator or the frame of a framed one, not both")
+        if (frame is not None) != self.framed:
+            raise ValueError("a framed operator has one multiplier per frame: ask for multiplier(frame=c)" if self.framed
+                             else "multiplier(frame=c) needs a framed build (set_points_frames or set_spectra_frames)")
         if a is None and self.coupled:
             raise ValueError("a coupled operator has a block of multipliers: ask for multiplier(a, b) with a <= b")
         if a is not None:
@@ -355,6 +423,10 @@ class ToeplitzOperator:
             if a > b:
                 raise ValueError("only the pairs a <= b are stored: multiplier(b, a) is the conjugate of multiplier(a, b)")
             _check(lib.nufft_toeplitz_multiplier_pair_ptr(self._handle, a, b, C.byref(ptr), C.byref(nbytes)))
+        elif frame is not None:
+            if isinstance(frame, bool) or not isinstance(frame, int) or not 0 <= frame < self.ntransforms:
+                raise ValueError(f"frame must lie in 0 ... {self.ntransforms - 1}")
+            _check(lib.nufft_toeplitz_multiplier_frame_ptr(self._handle, frame, C.byref(ptr), C.byref(nbytes)))
         else:
             _check(lib.nufft_toeplitz_multiplier_ptr(self._handle, C.byref(ptr), C.byref(nbytes)))
         shape = self.padded_shape
@@ -372,7 +444,7 @@ class ToeplitzOperator:
     def __repr__(self):
         i = self.info()
         return (f"ToeplitzOperator of a {self.ndim}-dimensional {self.Z} plan, N = {tuple(int(i.N[d]) for d in range(self.ndim))}, "
-                f"{self.path} path, {'coupled components, ' if self.coupled else ''}{f'{self.ncoils} coil maps, ' if self.ncoils else ''}{i.workspace_bytes / 1e6:.1f} MB")
+                f"{self.path} path, {'coupled components, ' if self.coupled else ''}{'one multiplier per frame, ' if self.framed else ''}{f'{self.ncoils} coil maps, ' if self.ncoils else ''}{i.workspace_bytes / 1e6:.1f} MB")
 
 
 def _check_coil_arrays(arrays, device, Z, shape, what):

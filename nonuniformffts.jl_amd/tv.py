@@ -15,6 +15,14 @@ kernels and one decision kernel, every scalar on the device.  Plumbing only: arg
     y = T.gradient(x)                # a tuple of D tensors, dimension 1 first
     x = T.adjoint(y)                 # ∇ᴴ y
     T.norm(x)                        # Σ_i |(∇x)_i|₂ per component (float64, on the device)
+
+Dynamic imaging: the components are frames, and ``tv_t`` adds ``tv_t ‖∇_t x‖₁``, the difference along the components,
+``(∇_t x)_c = x_{c+1} − x_c`` (the last one zero, or ``x_0 − x_{K−1}`` with ``periodic_t=True``); the frames are then one system.
+
+    op.set_points_frames(points_per_frame, weights_per_frame)
+    sol = ToeplitzTV(op, tv_t=1e-3, maxiter=200)           # temporal term only: two arrays per frame
+    sol = ToeplitzTV(op, tv=1e-4, tv_t=1e-3)               # spatial and temporal
+    T.gradient_t(x), T.adjoint_t(z), T.norm_t(x)           # tuples of ntransforms tensors
 """
 from __future__ import annotations
 
@@ -130,6 +138,39 @@ class TotalVariation:
         _check(lib.nufft_tv_norm(self._handle, _ptr_table(x_t), C.c_void_p(sums.data_ptr()), self._stream()))
         return sums
 
+    def _frames(self, x, periodic):
+        if self.ntransforms < 2:
+            raise ValueError("the difference along the components needs ntransforms >= 2")
+        if not isinstance(periodic, (bool, int)):
+            raise ValueError("periodic must be a bool")
+        x_t = tuple(x)
+        self._check_arrays(x_t, "input", self.ntransforms)
+        return x_t
+
+    def gradient_t(self, x, periodic: bool = False):
+        """``∇_t x``: a tuple of ntransforms tensors, ``x[c + 1] − x[c]``; the last one is zero, or ``x[0] − x[K − 1]`` if ``periodic``."""
+        self._require_open()
+        x_t = self._frames(x, periodic)
+        z = tuple(torch.empty_like(v) for v in x_t)
+        _check(lib.nufft_tv_gradient_t(self._handle, _ptr_table(z), _ptr_table(x_t), int(bool(periodic)), self._stream()))
+        return z
+
+    def adjoint_t(self, z, periodic: bool = False):
+        """``∇_tᴴ z``: ``z[c − 1] − z[c]`` with ``z[−1] = z[K − 1]`` if ``periodic``, else both taken as zero."""
+        self._require_open()
+        z_t = self._frames(z, periodic)
+        out = tuple(torch.empty_like(v) for v in z_t)
+        _check(lib.nufft_tv_adjoint_t(self._handle, _ptr_table(out), _ptr_table(z_t), int(bool(periodic)), self._stream()))
+        return out
+
+    def norm_t(self, x, periodic: bool = False) -> torch.Tensor:
+        """``Σ_i |(∇_t x)_c[i]|`` per component: a float64 device tensor of ntransforms values (their sum is ``‖∇_t x‖₁``)."""
+        self._require_open()
+        x_t = self._frames(x, periodic)
+        sums = torch.empty(self.ntransforms, dtype=torch.float64, device=self.device)
+        _check(lib.nufft_tv_norm_t(self._handle, _ptr_table(x_t), int(bool(periodic)), C.c_void_p(sums.data_ptr()), self._stream()))
+        return sums
+
     def __repr__(self):
         i = self.info()
         return (f"TotalVariation on {self.ndim}-dimensional {self.Z} arrays of shape {self.shape}, tile {tuple(i.tile[d] for d in range(self.ndim))}, "
@@ -137,7 +178,8 @@ class TotalVariation:
 
 
 class ToeplitzTV:
-    """``ToeplitzTV(op, tv=0.0, step=None, sigma=None, lam=0.0, maxiter=100, tol=1e-4, check_every=0)``.
+    """``ToeplitzTV(op, tv=0.0, step=None, sigma=None, lam=0.0, maxiter=100, tol=1e-4, check_every=0, tv_t=None, periodic_t=False,
+    spatial=None)``.
 
     ``tv``: a scalar or one weight per component.  ``lam``: the Tikhonov weight (named as in :class:`ToeplitzCG`).  ``step``: the
     primal step ``τ``; None computes ``1 / (1.05 · max(op.max_eigenvalue()) + lam)`` once, here (the operator then needs its spectrum
@@ -146,10 +188,17 @@ class ToeplitzTV:
     frozen on the device; legal inside ``torch.cuda.graph``); ``check_every=k`` lets the host stop early.  Both return the same bits.
     The solver keeps ``op`` alive; ``op.set_points`` / ``set_spectrum`` between two solves is allowed.  On a coupled operator the
     components are one system: one change and one stopping test, reported identically for every component.  The dual variable restarts
-    at zero in every ``solve``."""
+    at zero in every ``solve``.
+
+    ``tv_t`` (None: no temporal term, the solver above): the weight of ``‖∇_t x‖₁`` along the components, which needs
+    ``ntransforms >= 2`` and makes the frames one system on every operator (one change, one stopping test); history column 2 is then
+    each frame's share of the prior's value.  ``periodic_t``: the last frame is followed by the first (cine).  ``spatial``: keep the
+    spatial term (None: iff any ``tv > 0``), decided here and never switched; without it the solver holds two arrays per frame instead
+    of ``2 + D`` and ``set_tv`` with a non-zero weight is refused.  ``sigma=None`` is then ``1 / (8 n_d τ)`` with ``n_d = D + 1``
+    (spatial term on) or ``1``."""
 
     def __init__(self, op: ToeplitzOperator, tv=0.0, step=None, sigma=None, lam: float = 0.0, maxiter: int = 100, tol: float = 1e-4,
-                 check_every: int = 0):
+                 check_every: int = 0, tv_t=None, periodic_t: bool = False, spatial=None):
         if not isinstance(op, ToeplitzOperator):
             raise ValueError("ToeplitzTV takes a ToeplitzOperator")
         for name, v in (("maxiter", maxiter), ("check_every", check_every)):
@@ -169,7 +218,19 @@ class ToeplitzTV:
         prm.max_iter, prm.check_every = maxiter, check_every
         prm.tol, prm.step, prm.sigma, prm.tv, prm.lambda_ = float(tol), float(step), 0.0 if sigma is None else float(sigma), tvs[0], float(lam)
         self._handle = C.c_void_p()
-        _check(lib.nufft_tvpd_create(C.byref(self._handle), op._handle, C.byref(prm)))
+        self.temporal = tv_t is not None
+        if self.temporal:
+            if spatial is None:
+                spatial = any(v > 0.0 for v in tvs)
+            tprm = _lib.NufftTvtParams()
+            tprm.struct_size = C.sizeof(_lib.NufftTvtParams)
+            tprm.periodic, tprm.spatial, tprm.tv_t = int(bool(periodic_t)), int(bool(spatial)), float(tv_t)
+            _check(lib.nufft_tvpd_create_temporal(C.byref(self._handle), op._handle, C.byref(prm), C.byref(tprm)))
+        else:
+            if spatial is not None or periodic_t:
+                raise ValueError("spatial and periodic_t belong to the temporal term: give tv_t")
+            _check(lib.nufft_tvpd_create(C.byref(self._handle), op._handle, C.byref(prm)))
+        self.periodic_t, self.spatial = bool(periodic_t), True if not self.temporal else bool(spatial)
         self.op = op
         self.tv, self.step, self.lam = tuple(tvs), float(step), float(lam)
         self.maxiter, self.tol, self.check_every = maxiter, float(tol), check_every
@@ -187,6 +248,22 @@ class ToeplitzTV:
         tvs = _weights(tv, n)
         _check(lib.nufft_tvpd_set_tv(self._handle, (C.c_double * len(tvs))(*tvs), len(tvs)))
         self.tv = tuple(tvs)
+
+    @property
+    def tv_t(self):
+        """The temporal weight in use (None on a solver without the temporal term)."""
+        if not self.temporal:
+            return None
+        self._require_open()
+        out = _lib.NufftTvtParams()
+        out.struct_size = C.sizeof(_lib.NufftTvtParams)
+        _check(lib.nufft_tvpd_get_temporal(self._handle, C.byref(out)))
+        return out.tv_t
+
+    def set_tv_t(self, tv_t):
+        """The temporal weight of the following solves."""
+        self._require_open()
+        _check(lib.nufft_tvpd_set_tv_t(self._handle, float(tv_t)))
 
     def close(self):
         h = getattr(self, "_handle", None)
