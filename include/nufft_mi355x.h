@@ -1346,6 +1346,174 @@ int nufft_tvpd_set_tv_t(nufft_tvpd* s, double tv_t);
 int nufft_tvpd_get_temporal(const nufft_tvpd* s, nufft_tvt_params* out);
 int64_t nufft_sizeof_tvt_params(void);
 
+/* ---- Low-rank plus sparse reconstruction of a series of frames (L+S) ----
+ * The K = ntransforms components are frames x_c = L_c + S_c (Otazo, Candès & Sodickson, MRM 2015).  Three objects, each added after
+ * ABI 104 without changing NUFFT_MI355X_VERSION: detect by symbol (dlsym nufft_glr_create, nufft_tsparse_create, nufft_lps_create) and
+ * compare the nufft_sizeof_* functions below with your own.  1 <= K <= 32 for all three (more: NUFFT_ERR_UNSUPPORTED; the Jacobi team is
+ * one wave of at most 32 lanes, and the K x K matrices live in LDS).
+ *
+ * GLOBAL LOW RANK (nufft_glr_*).  C(x) is the n x K space-time (Casorati) matrix whose column c is frame c, n = Π N_d.  The map is
+ * singular-value soft-thresholding of that ONE matrix, by the route of the locally low-rank map above and with its constants:
+ *
+ *     H = C^H C  (K x K, FP64 for both element types)      H = V Λ V^H  (the same cyclic Jacobi, one team of 2^ceil(log2 K) lanes)
+ *     σ_i = sqrt(max(λ_i, 0))     f_i = σ_i > t ? 1 − t / σ_i : 0     P = V diag(f) V^H     C <- C P     nuc = Σ_i f_i σ_i
+ *
+ * in three launches: the Gram kernel (flat over the cells, one set of K (K + 1) / 2 FP64 partials per workgroup, every entry summed in
+ * cell order over fixed segments, the segments in segment order, the workgroup's tiles in tile order), the eigen kernel (one workgroup:
+ * adds the partial sets in workgroup order, diagonalises, writes P, nuc and the sweep count to device memory) and the apply kernel
+ * (Σ_i C_vi P_ij in FP64, one store).  No atomics: two runs and a replayed hipGraph give the same bits.  The Gram route resolves a
+ * direction with σ_i << σ_max only to about (σ_max / σ_i)² ε of FP64 relative to σ_i, as the locally low-rank map does. */
+typedef struct nufft_glr nufft_glr; /* opaque */
+
+typedef struct nufft_glr_info {
+    int32_t struct_size;     /* sizeof(nufft_glr_info) of the caller's header, set before the call (0 = this layout)               */
+    int32_t ndim, dtype, ntransforms, device;
+    int32_t tile_cells;      /* cells of one LDS tile (times ntransforms frames)                                                   */
+    int32_t jacobi_sweeps_max;
+    int32_t reserved;
+    int64_t N[3];            /* 1 beyond ndim                                                                                      */
+    int64_t cells;           /* n = Π N_d                                                                                          */
+    int64_t workgroups;      /* of the Gram and apply kernels = sets of partial sums                                               */
+    int64_t workspace_bytes; /* device bytes owned: Gram partials, P, the nuclear norm and the sweep count                         */
+} nufft_glr_info;
+
+/* Takes element type, shape, ntransforms and device from the plan; the plan is not kept.  Refusals, in order: null arguments
+ * NUFFT_ERR_INVALID_ARG; a real-data plan NUFFT_ERR_UNSUPPORTED; more than 32 transforms NUFFT_ERR_UNSUPPORTED; a host-only plan
+ * NUFFT_ERR_NO_DEVICE. */
+int nufft_glr_create(nufft_glr** out, const nufft_plan* plan);
+/* The same from a Toeplitz operator (the operator is not kept). */
+int nufft_glr_create_for_operator(nufft_glr** out, const nufft_toeplitz* tz);
+int nufft_glr_destroy(nufft_glr* g);
+/* Static facts and sizes; does not synchronise. */
+int nufft_glr_get_info(const nufft_glr* g, nufft_glr_info* out);
+/* out = prox_{t ‖C(·)‖_*}(in).  Host tables of ntransforms device pointers, 16-byte aligned.  out[c] may be exactly in[c] (a tile is
+ * owned by one workgroup, which stores after it has loaded); any other overlap is refused.  nuc_out_device (device, double[1], may be
+ * NULL): ‖C(out)‖_* = Σ_i max(σ_i − t, 0).  Allocates nothing, does not synchronise, hipGraph-capture safe; one call at a time per
+ * object.  Refusals, before anything is enqueued: a null table or vector, a pointer that is not 16-byte aligned, a partial overlap,
+ * t < 0 or not finite NUFFT_ERR_INVALID_ARG. */
+int nufft_glr_apply(nufft_glr* g, void* const* out, const void* const* in, double t, double* nuc_out_device, void* stream);
+/* The Jacobi sweeps of the last apply (the last one rotates nothing; 0 for K = 1).  Synchronises `stream` (never a capturing one). */
+int nufft_glr_last_sweeps(nufft_glr* g, int32_t* sweeps_out, void* stream);
+int64_t nufft_sizeof_glr_info(void);
+
+/* TEMPORAL SPARSITY (nufft_tsparse_*).  A unitary transform T along the frames, per cell:
+ *
+ *     NUFFT_TSPARSE_DFT:       (T x)_k[i] = K^-1/2 Σ_c x_c[i] exp(−2πi k c / K)      (Tᴴ y)_c[i] = K^-1/2 Σ_k y_k[i] exp(+2πi k c / K)
+ *     NUFFT_TSPARSE_IDENTITY:  T = I
+ *
+ * The DFT is the direct sum of K terms for any K in 1 ... 32, accumulated in the element type, with a table of K twiddles (K^-1/2 folded
+ * in) computed in FP64 on the host, rounded once to the element type and indexed (k · c) mod K.  A workgroup stages a tile [frame][cell]
+ * in LDS.  The shrink is the complex soft threshold c · max(1 − t / |c|, 0), applied where the coefficient is produced; nothing is
+ * divided where |c| <= t.  A temporal difference is not offered (it is not unitary: nufft_tvpd_create_temporal covers it). */
+typedef struct nufft_tsparse nufft_tsparse; /* opaque */
+
+enum { NUFFT_TSPARSE_IDENTITY = 0, NUFFT_TSPARSE_DFT = 1 };
+
+typedef struct nufft_tsparse_info {
+    int32_t struct_size;     /* sizeof(nufft_tsparse_info) of the caller's header, set before the call (0 = this layout)           */
+    int32_t ndim, dtype, ntransforms, device;
+    int32_t transform;       /* NUFFT_TSPARSE_*                                                                                    */
+    int32_t tile_cells;      /* cells of one LDS tile (times ntransforms frames)                                                   */
+    int32_t reserved;
+    int64_t N[3];            /* 1 beyond ndim                                                                                      */
+    int64_t cells;           /* n = Π N_d                                                                                          */
+    int64_t workgroups;      /* per launch = rows of partial sums                                                                  */
+    int64_t workspace_bytes; /* device bytes owned: the partial sums                                                               */
+} nufft_tsparse_info;
+
+/* Refusals, in order: null arguments, an unknown transform NUFFT_ERR_INVALID_ARG; a real-data plan NUFFT_ERR_UNSUPPORTED; more than 32
+ * transforms NUFFT_ERR_UNSUPPORTED; a host-only plan NUFFT_ERR_NO_DEVICE. */
+int nufft_tsparse_create(nufft_tsparse** out, const nufft_plan* plan, int32_t transform);
+int nufft_tsparse_create_for_operator(nufft_tsparse** out, const nufft_toeplitz* tz, int32_t transform);
+int nufft_tsparse_destroy(nufft_tsparse* ts);
+int nufft_tsparse_get_info(const nufft_tsparse* ts, nufft_tsparse_info* out);
+/* out = T in and out = Tᴴ in.  Tables and overlap rules as for nufft_glr_apply (out[c] may be exactly in[c]).  No allocation, no
+ * synchronisation, hipGraph-capture safe. */
+int nufft_tsparse_forward(nufft_tsparse* ts, void* const* out, const void* const* in, void* stream);
+int nufft_tsparse_inverse(nufft_tsparse* ts, void* const* out, const void* const* in, void* stream);
+/* coeff_out = soft_t(T in): the coefficients after thresholding, so that nufft_tsparse_inverse of them is prox_{t ‖T·‖₁}(in).
+ * l1_out_device (device, double[1], may be NULL): ‖coeff_out‖₁, FP64, one fixed order.  t >= 0 and finite. */
+int nufft_tsparse_shrink(nufft_tsparse* ts, void* const* coeff_out, const void* const* in, double t, double* l1_out_device, void* stream);
+int64_t nufft_sizeof_tsparse_info(void);
+
+/* THE SOLVER (nufft_lps_*).  Minimises over the pair (L, S)
+ *
+ *     ½ <L + S, (G + μ I)(L + S)> − Re<b, L + S> + nuc · ‖C(L)‖_* + l1 · ‖T S‖₁
+ *
+ * G what the nufft_toeplitz object applies (framed, plain, with coil maps, coupled).  Proximal gradient on the pair, with FISTA momentum
+ * (β of iteration `it` as in nufft_fista_create; momentum = 0: β = 0, the scheme of Otazo et al.):
+ *
+ *     start:  L = x0 (or 0),  S = 0,  zL = L,  zS = 0,  u = zL + zS
+ *     for it = 1 ... max_iter:
+ *         q  = G u                                                  nufft_toeplitz_apply
+ *         g  = τ (q + μ u − b);  H = C(zL − g)^H C(zL − g)           Gram kernel: stores g over q
+ *         P, ‖C(L⁺)‖_*                                              eigen kernel, t = τ · nuc
+ *         L⁺ = (zL − g) P;  zL = L⁺ + β (L⁺ − L);  L = L⁺             apply kernel: partials of ‖L⁺ − L‖², ‖L⁺‖²
+ *         S⁺ = Tᴴ soft_{τ·l1}(T (zS − g));  zS likewise;  S = S⁺;  u = zL + zS      temporal kernel: partials of ‖S⁺ − S‖², ‖S⁺‖², ‖T S⁺‖₁
+ *         change = sqrt((‖L⁺ − L‖² + ‖S⁺ − S‖²) / (‖L⁺‖² + ‖S⁺‖²)) (0 when both are 0);  history row (change, ‖C(L⁺)‖_*, ‖T S⁺‖₁)
+ *         done <- change <= tol, or change not finite (NUFFT_LPS_BREAKDOWN)
+ *     x = L + S
+ *
+ * The smooth term ½ <L + S, (G + μ)(L + S)> has, as a function of the PAIR, the Hessian [[A, A], [A, A]] (A = G + μ I), whose largest
+ * eigenvalue is 2 λ_max(A): τ <= 1 / (2 (λ_max(G) + μ)).  The frames are ONE system: one change, one flag, one status, reported
+ * identically for every component.  u lives in the caller's x between the iterations.  The solver owns five arrays per frame (L, S,
+ * zL, zS, q).  Sums and scalars are FP64, formed without atomics in one fixed order; a done system is frozen (every kernel reads the
+ * flag before its first load); check_every as for nufft_fista_create: 0 enqueues everything without synchronising or allocating
+ * (hipGraph-capture safe), k > 0 stops early and is refused on a capturing stream; both give the same bits. */
+typedef struct nufft_lps nufft_lps; /* opaque */
+
+enum { NUFFT_LPS_MAX_ITER = 0,   /* max_iter iterations ran without reaching tol */
+       NUFFT_LPS_CONVERGED = 1,  /* change <= tol                                */
+       NUFFT_LPS_BREAKDOWN = 2   /* change not finite: the system was frozen     */ };
+
+typedef struct nufft_lps_params {
+    int32_t struct_size;     /* sizeof(nufft_lps_params) of the caller's header (0 = this layout)                                  */
+    int32_t max_iter;        /* 1 ... 2^24                                                                                         */
+    int32_t check_every;     /* 0, or the number of iterations between two looks at the done flag                                  */
+    int32_t transform;       /* NUFFT_TSPARSE_*                                                                                    */
+    int32_t momentum;        /* 1: FISTA's β;  0: β = 0                                                                            */
+    int32_t reserved;        /* 0                                                                                                  */
+    double tol;              /* >= 0, finite                                                                                       */
+    double step;             /* τ > 0, finite: 1 / (2 (λ_max + lambda)), nufft_toeplitz_max_eigenvalue                             */
+    double lambda;           /* the Tikhonov μ: >= 0, finite                                                                       */
+    double nuc;              /* >= 0, finite                                                                                       */
+    double l1;               /* >= 0, finite                                                                                       */
+} nufft_lps_params;
+
+typedef struct nufft_lps_info {
+    int32_t struct_size;     /* sizeof(nufft_lps_info) of the caller's header, set before the call (0 = this layout)               */
+    int32_t ntransforms, dtype, max_iter, check_every, transform, momentum;
+    int32_t iterations_enqueued; /* by the last nufft_lps_solve (check_every > 0 stops early); -1 before the first                 */
+    double tol, step, lambda, nuc, l1;
+    int64_t array_bytes;     /* L, S, zL, zS, q: five arrays per frame                                                             */
+    int64_t workspace_bytes; /* device bytes owned: array_bytes + partial sums + scalars + history + the two prior objects'        */
+} nufft_lps_info;
+
+/* The solver keeps the POINTER `tz`: the operator must outlive it; a new build of the operator between two solves is allowed.
+ * Refusals: null arguments, max_iter < 1 or > 2^24, check_every < 0, an unknown transform, momentum outside {0, 1}, tol < 0, lambda < 0,
+ * nuc < 0, l1 < 0, step <= 0 or non-finite values NUFFT_ERR_INVALID_ARG; more than 32 transforms NUFFT_ERR_UNSUPPORTED; a host-only
+ * operator NUFFT_ERR_NO_DEVICE (after the argument checks). */
+int nufft_lps_create(nufft_lps** out, nufft_toeplitz* tz, const nufft_lps_params* params);
+int nufft_lps_destroy(nufft_lps* s);
+/* The two weights of the following solves (each finite and >= 0). */
+int nufft_lps_set_weights(nufft_lps* s, double nuc, double l1);
+/* x_inout[c], b[c] as in nufft_fista_solve, with the same refusals.  use_x0 = 0: start from zero.  On return (in stream order)
+ * x = L + S. */
+int nufft_lps_solve(nufft_lps* s, void* const* x_inout, const void* const* b, int use_x0, void* stream);
+/* Copies the two parts of the last solve into the caller's arrays (tables of ntransforms device pointers; either table may be NULL).
+ * Enqueues device-to-device copies; does not synchronise.  Refusals: a null entry, two destinations (of either table) that overlap, a
+ * destination that overlaps the solver's own arrays NUFFT_ERR_INVALID_ARG. */
+int nufft_lps_get_parts(nufft_lps* s, void* const* L_out, void* const* S_out, void* stream);
+int nufft_lps_get_info(const nufft_lps* s, nufft_lps_info* out);
+/* The outcome of the last solve, the same for every component: iterations that changed the system, NUFFT_LPS_* status, the last
+ * change.  Each output may be NULL; `capacity` entries each, at least ntransforms.  Synchronises `stream` (never a capturing one). */
+int nufft_lps_get_result(nufft_lps* s, int32_t* iterations, int32_t* status, double* change, int64_t capacity, void* stream);
+/* host_out[max_iter][3]: row it − 1 holds the change, ‖C(L⁺)‖_* and ‖T S⁺‖₁ after iteration it; NaN where the iteration did not run.
+ * Synchronises `stream`. */
+int nufft_lps_history(nufft_lps* s, double* host_out, int64_t capacity, void* stream);
+int64_t nufft_sizeof_lps_params(void);
+int64_t nufft_sizeof_lps_info(void);
+
 /* ---- misc ----------------------------------------------------------------------------- */
 /* sizeof(nufft_params) / sizeof(nufft_info) of the library build: a binding that mirrors the structs by hand
  * (ctypes, Julia) compares them with its own layout before the first call. */

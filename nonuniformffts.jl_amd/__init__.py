@@ -24,6 +24,7 @@ from .wavelet import WaveletTransform  # noqa: F401
 from .llr import LocallyLowRank  # noqa: F401
 from .fista import ToeplitzFISTA  # noqa: F401
 from .tv import ToeplitzTV, TotalVariation  # noqa: F401
+from .lps import GlobalLowRank, TemporalSparsity, ToeplitzLPS  # noqa: F401
 from .dcf import DensityCompensation, density_weights  # noqa: F401
 from . import autograd  # noqa: F401
 
@@ -36,5 +37,6 @@ __all__ = [
     "exec_type2_grad", "interpolate_grad", "autograd",
     "ToeplitzOperator", "ToeplitzCG", "ToeplitzPreconditioner", "coil_expand", "coil_combine",
     "WaveletTransform", "LocallyLowRank", "ToeplitzFISTA", "TotalVariation", "ToeplitzTV",
+    "GlobalLowRank", "TemporalSparsity", "ToeplitzLPS",
     "DensityCompensation", "density_weights",
 ]

@@ -226,6 +226,47 @@ TVPD_MAX_ITER, TVPD_CONVERGED, TVPD_BREAKDOWN = 0, 1, 2
 TVPD_STATUS_NAMES = {TVPD_MAX_ITER: "max_iter", TVPD_CONVERGED: "converged", TVPD_BREAKDOWN: "breakdown"}
 
 
+class NufftGlrInfo(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("ndim", C.c_int32), ("dtype", C.c_int32), ("ntransforms", C.c_int32), ("device", C.c_int32),
+        ("tile_cells", C.c_int32), ("jacobi_sweeps_max", C.c_int32), ("reserved", C.c_int32),
+        ("N", C.c_int64 * 3), ("cells", C.c_int64), ("workgroups", C.c_int64), ("workspace_bytes", C.c_int64),
+    ]
+
+
+class NufftTsparseInfo(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("ndim", C.c_int32), ("dtype", C.c_int32), ("ntransforms", C.c_int32), ("device", C.c_int32),
+        ("transform", C.c_int32), ("tile_cells", C.c_int32), ("reserved", C.c_int32),
+        ("N", C.c_int64 * 3), ("cells", C.c_int64), ("workgroups", C.c_int64), ("workspace_bytes", C.c_int64),
+    ]
+
+
+TSPARSE_IDENTITY, TSPARSE_DFT = 0, 1
+TSPARSE_IDS = {"identity": TSPARSE_IDENTITY, "dft": TSPARSE_DFT}
+
+
+class NufftLpsParams(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("max_iter", C.c_int32), ("check_every", C.c_int32), ("transform", C.c_int32),
+        ("momentum", C.c_int32), ("reserved", C.c_int32),
+        ("tol", C.c_double), ("step", C.c_double), ("lambda_", C.c_double), ("nuc", C.c_double), ("l1", C.c_double),
+    ]
+
+
+class NufftLpsInfo(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("ntransforms", C.c_int32), ("dtype", C.c_int32), ("max_iter", C.c_int32),
+        ("check_every", C.c_int32), ("transform", C.c_int32), ("momentum", C.c_int32), ("iterations_enqueued", C.c_int32),
+        ("tol", C.c_double), ("step", C.c_double), ("lambda_", C.c_double), ("nuc", C.c_double), ("l1", C.c_double),
+        ("array_bytes", C.c_int64), ("workspace_bytes", C.c_int64),
+    ]
+
+
+LPS_MAX_ITER, LPS_CONVERGED, LPS_BREAKDOWN = 0, 1, 2
+LPS_STATUS_NAMES = {LPS_MAX_ITER: "max_iter", LPS_CONVERGED: "converged", LPS_BREAKDOWN: "breakdown"}
+
+
 class NufftDcfParams(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int32), ("max_iter", C.c_int32), ("check_every", C.c_int32), ("normalize", C.c_int32),
@@ -407,6 +448,31 @@ SYMBOLS = {
     "nufft_tvpd_set_tv_t": (C.c_int, [_P, C.c_double]),
     "nufft_tvpd_get_temporal": (C.c_int, [_P, C.POINTER(NufftTvtParams)]),
     "nufft_sizeof_tvt_params": (C.c_int64, []),
+    "nufft_glr_create": (C.c_int, [C.POINTER(_P), _P]),
+    "nufft_glr_create_for_operator": (C.c_int, [C.POINTER(_P), _P]),
+    "nufft_glr_destroy": (C.c_int, [_P]),
+    "nufft_glr_get_info": (C.c_int, [_P, C.POINTER(NufftGlrInfo)]),
+    "nufft_glr_apply": (C.c_int, [_P, _PP, _PP, C.c_double, _P, _P]),
+    "nufft_glr_last_sweeps": (C.c_int, [_P, C.POINTER(C.c_int32), _P]),
+    "nufft_sizeof_glr_info": (C.c_int64, []),
+    "nufft_tsparse_create": (C.c_int, [C.POINTER(_P), _P, C.c_int32]),
+    "nufft_tsparse_create_for_operator": (C.c_int, [C.POINTER(_P), _P, C.c_int32]),
+    "nufft_tsparse_destroy": (C.c_int, [_P]),
+    "nufft_tsparse_get_info": (C.c_int, [_P, C.POINTER(NufftTsparseInfo)]),
+    "nufft_tsparse_forward": (C.c_int, [_P, _PP, _PP, _P]),
+    "nufft_tsparse_inverse": (C.c_int, [_P, _PP, _PP, _P]),
+    "nufft_tsparse_shrink": (C.c_int, [_P, _PP, _PP, C.c_double, _P, _P]),
+    "nufft_sizeof_tsparse_info": (C.c_int64, []),
+    "nufft_lps_create": (C.c_int, [C.POINTER(_P), _P, C.POINTER(NufftLpsParams)]),
+    "nufft_lps_destroy": (C.c_int, [_P]),
+    "nufft_lps_set_weights": (C.c_int, [_P, C.c_double, C.c_double]),
+    "nufft_lps_solve": (C.c_int, [_P, _PP, _PP, C.c_int, _P]),
+    "nufft_lps_get_parts": (C.c_int, [_P, _PP, _PP, _P]),
+    "nufft_lps_get_info": (C.c_int, [_P, C.POINTER(NufftLpsInfo)]),
+    "nufft_lps_get_result": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int64, _P]),
+    "nufft_lps_history": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int64, _P]),
+    "nufft_sizeof_lps_params": (C.c_int64, []),
+    "nufft_sizeof_lps_info": (C.c_int64, []),
     "nufft_sizeof_params": (C.c_int64, []),
     "nufft_sizeof_info": (C.c_int64, []),
     "nufft_strerror": (C.c_char_p, [C.c_int]),
@@ -443,7 +509,9 @@ def _load():
                          ("nufft_sizeof_fista_info", NufftFistaInfo), ("nufft_sizeof_llr_params", NufftLlrParams),
                          ("nufft_sizeof_llr_info", NufftLlrInfo), ("nufft_sizeof_tv_info", NufftTvInfo),
                          ("nufft_sizeof_tvpd_params", NufftTvpdParams), ("nufft_sizeof_tvpd_info", NufftTvpdInfo),
-                         ("nufft_sizeof_tvt_params", NufftTvtParams)):
+                         ("nufft_sizeof_tvt_params", NufftTvtParams), ("nufft_sizeof_glr_info", NufftGlrInfo),
+                         ("nufft_sizeof_tsparse_info", NufftTsparseInfo), ("nufft_sizeof_lps_params", NufftLpsParams),
+                         ("nufft_sizeof_lps_info", NufftLpsInfo)):
         if getattr(lib, name)() != C.sizeof(mirror):
             raise ImportError(f"{LIB_PATH}: {name}() = {getattr(lib, name)()} but the ctypes mirror has {C.sizeof(mirror)} bytes "
                               "(include/nufft_mi355x.h and _lib.py disagree)")

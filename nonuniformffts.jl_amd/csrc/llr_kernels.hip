@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "jacobi.h"
 #include "llr.h"
 #include "stream_kernels.h"
 
@@ -25,95 +26,11 @@ namespace nufft {
 using namespace stream;
 
 static_assert(kLlrThreads == kThreads, "the reductions of stream_kernels.h");
+static_assert(kLlrSweepsMax == jacobi_team::kSweepsMax, "nufft_llr_info.jacobi_sweeps_max reports the cap of jacobi.h");
 
 namespace {
 
-template <typename T>
-struct Cx {
-    T re, im;
-};
-using Cd = Cx<double>;
-
-constexpr double kSkipRel = 0x1p-106;      // a rotation is skipped when |h_pq|² <= 2^-106 h_pp h_qq ...
-constexpr double kSkipAbs = 0x1p-60;       // ... or |h_pq| <= 2^-60 trace(H)
-
-__device__ __forceinline__ void team_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// (x, y) <- (c x − conj(sp) y, sp x + c y): a pair of one row of A J, J = [[c, sp], [−conj(sp), c]]
-__device__ __forceinline__ void rotate_columns(Cd& x, Cd& y, double c, double sr, double si) {
-    const Cd nx{c * x.re - (y.re * sr + y.im * si), c * x.im - (y.im * sr - y.re * si)};
-    const Cd ny{(x.re * sr - x.im * si) + c * y.re, (x.re * si + x.im * sr) + c * y.im};
-    x = nx;
-    y = ny;
-}
-
-// (x, y) <- (c x − sp y, conj(sp) x + c y): a pair of one column of J^H A
-__device__ __forceinline__ void rotate_rows(Cd& x, Cd& y, double c, double sr, double si) {
-    const Cd nx{c * x.re - (sr * y.re - si * y.im), c * x.im - (sr * y.im + si * y.re)};
-    const Cd ny{(sr * x.re + si * x.im) + c * y.re, (sr * x.im - si * x.re) + c * y.im};
-    x = nx;
-    y = ny;
-}
-
-// Cyclic-by-rows Jacobi on the Hermitian K x K matrix H (row-major), V <- V J for every rotation; lane r < TW of the team.  Stops after
-// the first sweep that rotates nothing, or after kLlrSweepsMax sweeps.  tests/llr_reference.py (jacobi_eigh) restates it.
-__device__ void jacobi(Cd* H, Cd* V, int K, int r) {
-    double tr = 0.0;
-    for (int i = 0; i < K; ++i) tr += H[i * K + i].re;
-    const double floor2 = (kSkipAbs * tr) * (kSkipAbs * tr);
-    const bool mine = r < K;
-    for (int sweep = 0; sweep < kLlrSweepsMax; ++sweep) {
-        bool rotated = false;
-        for (int p = 0; p < K - 1; ++p)
-            for (int q = p + 1; q < K; ++q) {
-                team_sync();
-                const double app = H[p * K + p].re, aqq = H[q * K + q].re;
-                const Cd g = H[p * K + q];
-                // |h_pq|² underflows to 0 for |h_pq| below about 1e-162, that is for data below about 1e-81 (both element types:
-                // H is FP64): such a block is treated as diagonal.  Data above about 1e+150 overflow H.
-                const double g2 = g.re * g.re + g.im * g.im;
-                if (g2 <= fmax(kSkipRel * fabs(app * aqq), floor2)) continue;
-                rotated = true;
-                const double ag = sqrt(g2);
-                const double tau = (aqq - app) / (2.0 * ag);
-                const double tt = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-                const double c = 1.0 / sqrt(1.0 + tt * tt), s = tt * c;
-                const double sr = s * (g.re / ag), si = s * (g.im / ag);
-                team_sync();                                       // every lane has read h_pp, h_qq, h_pq
-                if (mine) {
-                    Cd x = H[r * K + p], y = H[r * K + q];
-                    rotate_columns(x, y, c, sr, si);
-                    H[r * K + p] = x;
-                    H[r * K + q] = y;
-                    x = V[r * K + p];
-                    y = V[r * K + q];
-                    rotate_columns(x, y, c, sr, si);
-                    V[r * K + p] = x;
-                    V[r * K + q] = y;
-                }
-                team_sync();
-                if (mine) {
-                    Cd x = H[p * K + r], y = H[q * K + r];
-                    rotate_rows(x, y, c, sr, si);
-                    H[p * K + r] = x;
-                    H[q * K + r] = y;
-                }
-                team_sync();
-                if (r == 0) {
-                    H[p * K + q] = Cd{0.0, 0.0};
-                    H[q * K + p] = Cd{0.0, 0.0};
-                    H[p * K + p].im = 0.0;
-                    H[q * K + q].im = 0.0;
-                }
-            }
-        if (!rotated) break;
-    }
-    team_sync();
-}
+using namespace jacobi_team;
 
 template <typename T, int MODE>
 __global__ __launch_bounds__(kLlrThreads) void llr_kernel(LlrLaunch a, LlrLayout L) {

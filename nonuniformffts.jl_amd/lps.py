@@ -1,0 +1,339 @@
+"""Low-rank plus sparse (L+S) reconstruction of a series of frames on a :class:`ToeplitzOperator`, above the C ABI's ``nufft_glr_*``,
+``nufft_tsparse_*`` and ``nufft_lps_*`` entry points.
+
+    min over (L, S)   ½⟨L + S, (G + lam I)(L + S)⟩ − Re⟨b, L + S⟩ + nuc ‖C(L)‖_* + l1 ‖T S‖₁
+
+The K = ntransforms components are frames.  ``C(L)`` is the n × K space-time matrix whose column c is frame c; ``T`` is a unitary
+transform along the frames, applied per cell: ``"dft"`` (length-K DFT scaled by 1/√K) or ``"identity"``.  The whole loop runs in the
+library: per iteration one apply of the operator, four kernels and one decision kernel, every scalar on the device.  Plumbing only.
+
+    op.set_points_frames(points_per_frame, weights_per_frame)
+    sol = ToeplitzLPS(op, nuc=…, l1=…, transform="dft", maxiter=200, tol=1e-4)
+    x = sol.solve(b)                 # a tuple of K tensors, x = L + S
+    sol.low_rank, sol.sparse         # tuples of K tensors (copies)
+    sol.iterations, sol.status, sol.change, sol.history()
+
+    G = GlobalLowRank(op_or_plan);   y, nuc = G.apply(x, t)          # singular-value soft-thresholding of C(x)
+    T = TemporalSparsity(op_or_plan, "dft");  T.forward(x), T.inverse(c), T.shrink(x, t)
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from . import _lib
+from ._lib import lib
+from .plan import DimensionMismatch, PlanNUFFT, _check, _ptr_table
+from .toeplitz import ToeplitzOperator
+
+
+def _transform_id(transform) -> int:
+    if transform not in _lib.TSPARSE_IDS:
+        raise ValueError(f"transform must be one of {sorted(_lib.TSPARSE_IDS)} (got {transform!r})")
+    return _lib.TSPARSE_IDS[transform]
+
+
+class _FrameObject:
+    """What the two operator objects share: the source's geometry, the handle and the argument checks."""
+
+    _destroy = None
+    _name = ""
+
+    def _adopt(self, src):
+        self.device, self.shape, self.ndim, self.ntransforms = src.device, src.shape, src.ndim, src.ntransforms
+
+    def close(self):
+        h = getattr(self, "_handle", None)
+        if h is not None and h.value:
+            type(self)._destroy(h)
+            self._handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _require_open(self):
+        if not self._handle.value:
+            raise ValueError(f"this {self._name} has been closed")
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _check_arrays(self, us, what):
+        if len(us) != self.ntransforms:
+            raise DimensionMismatch(f"wrong amount of {what} arrays (expected a tuple of {self.ntransforms} arrays)")
+        for u in us:
+            if not isinstance(u, torch.Tensor) or u.device != self.device:
+                raise ValueError(f"{what} must be torch tensors on {self.device}")
+            if u.dtype != self.Z:
+                raise ValueError(f"{what} must have element type {self.Z} (got {u.dtype})")
+            if tuple(u.shape) != self.shape:
+                raise DimensionMismatch(f"wrong dimensions of {what} array (expected tensor shape {self.shape}, got {tuple(u.shape)})")
+            if not u.is_contiguous():
+                raise ValueError(f"{what} must be contiguous")
+
+    def _in_out(self, x, out):
+        """(inputs, outputs, what to return) for a tensor or a tuple of ntransforms tensors; ``out`` may be ``x``."""
+        single = isinstance(x, torch.Tensor)
+        x_t = (x,) if single else tuple(x)
+        self._check_arrays(x_t, "input")
+        if out is None:
+            out_t = tuple(torch.empty_like(v) for v in x_t)
+            out = out_t[0] if single else out_t
+        else:
+            out_t = (out,) if isinstance(out, torch.Tensor) else tuple(out)
+            self._check_arrays(out_t, "output")
+        return x_t, out_t, out
+
+
+class GlobalLowRank(_FrameObject):
+    """``GlobalLowRank(op_or_plan)``: element type, shape, ntransforms (1 … 32) and device are those of a complex ``PlanNUFFT`` or of a
+    ``ToeplitzOperator`` (neither is kept).  ``apply`` shrinks the singular values of the n × K matrix whose columns are the K arrays,
+    through its K × K Gram matrix in FP64: a direction with ``σ_i ≪ σ_max`` is resolved to about ``(σ_max/σ_i)² ε``."""
+
+    _destroy = lib.nufft_glr_destroy
+    _name = "GlobalLowRank"
+
+    def __init__(self, op_or_plan):
+        if not isinstance(op_or_plan, (PlanNUFFT, ToeplitzOperator)):
+            raise ValueError("GlobalLowRank takes a PlanNUFFT or a ToeplitzOperator")
+        src = op_or_plan
+        if isinstance(src, ToeplitzOperator):
+            src._require_open()
+            create, self.Z = lib.nufft_glr_create_for_operator, src.Z
+        else:
+            create, self.Z = lib.nufft_glr_create, src.eltype
+        self._handle = C.c_void_p()
+        _check(create(C.byref(self._handle), src._handle))
+        self._adopt(src)
+
+    def info(self) -> _lib.NufftGlrInfo:
+        self._require_open()
+        out = _lib.NufftGlrInfo()
+        out.struct_size = C.sizeof(_lib.NufftGlrInfo)
+        _check(lib.nufft_glr_get_info(self._handle, C.byref(out)))
+        return out
+
+    def apply(self, x, t, out=None):
+        """``out = prox_{t ‖C(·)‖_*}(x)``; ``out`` may be ``x`` itself.  Returns ``(out, nuc)`` with ``nuc`` a float64 device tensor of
+        one element, the nuclear norm of the result."""
+        self._require_open()
+        x_t, out_t, out = self._in_out(x, out)
+        nuc = torch.empty(1, dtype=torch.float64, device=self.device)
+        _check(lib.nufft_glr_apply(self._handle, _ptr_table(out_t), _ptr_table(x_t), float(t), C.c_void_p(nuc.data_ptr()), self._stream()))
+        return out, nuc
+
+    def last_sweeps(self) -> int:
+        """Jacobi sweeps of the last ``apply`` (synchronises the current stream)."""
+        self._require_open()
+        n = C.c_int32()
+        _check(lib.nufft_glr_last_sweeps(self._handle, C.byref(n), self._stream()))
+        return n.value
+
+    def __repr__(self):
+        i = self.info()
+        return (f"GlobalLowRank on {self.ndim}-dimensional {self.Z} arrays of shape {self.shape} x {self.ntransforms} frames, "
+                f"tiles of {i.tile_cells} cells, {i.workgroups} workgroups")
+
+
+class TemporalSparsity(_FrameObject):
+    """``TemporalSparsity(op_or_plan, transform="dft" | "identity")``: the unitary transform along the ntransforms (1 … 32) frames,
+    per cell.  ``forward`` / ``inverse`` apply ``T`` / ``Tᴴ``; ``shrink(x, t)`` returns the coefficients after the complex soft
+    threshold, so that ``inverse`` of them is ``prox_{t ‖T·‖₁}(x)``."""
+
+    _destroy = lib.nufft_tsparse_destroy
+    _name = "TemporalSparsity"
+
+    def __init__(self, op_or_plan, transform="dft"):
+        if not isinstance(op_or_plan, (PlanNUFFT, ToeplitzOperator)):
+            raise ValueError("TemporalSparsity takes a PlanNUFFT or a ToeplitzOperator")
+        tid = _transform_id(transform)
+        src = op_or_plan
+        if isinstance(src, ToeplitzOperator):
+            src._require_open()
+            create, self.Z = lib.nufft_tsparse_create_for_operator, src.Z
+        else:
+            create, self.Z = lib.nufft_tsparse_create, src.eltype
+        self._handle = C.c_void_p()
+        _check(create(C.byref(self._handle), src._handle, tid))
+        self._adopt(src)
+        self.transform = transform
+
+    def info(self) -> _lib.NufftTsparseInfo:
+        self._require_open()
+        out = _lib.NufftTsparseInfo()
+        out.struct_size = C.sizeof(_lib.NufftTsparseInfo)
+        _check(lib.nufft_tsparse_get_info(self._handle, C.byref(out)))
+        return out
+
+    def forward(self, x, out=None):
+        self._require_open()
+        x_t, out_t, out = self._in_out(x, out)
+        _check(lib.nufft_tsparse_forward(self._handle, _ptr_table(out_t), _ptr_table(x_t), self._stream()))
+        return out
+
+    def inverse(self, c, out=None):
+        self._require_open()
+        c_t, out_t, out = self._in_out(c, out)
+        _check(lib.nufft_tsparse_inverse(self._handle, _ptr_table(out_t), _ptr_table(c_t), self._stream()))
+        return out
+
+    def shrink(self, x, t, out=None):
+        """Returns ``(coefficients, l1)``: ``soft_t(T x)`` and its 1-norm (a float64 device tensor of one element)."""
+        self._require_open()
+        x_t, out_t, out = self._in_out(x, out)
+        l1 = torch.empty(1, dtype=torch.float64, device=self.device)
+        _check(lib.nufft_tsparse_shrink(self._handle, _ptr_table(out_t), _ptr_table(x_t), float(t), C.c_void_p(l1.data_ptr()), self._stream()))
+        return out, l1
+
+    def __repr__(self):
+        return f"TemporalSparsity({self.transform!r}) on {self.ndim}-dimensional {self.Z} arrays of shape {self.shape} x {self.ntransforms} frames"
+
+
+class ToeplitzLPS:
+    """``ToeplitzLPS(op, nuc, l1, transform="dft", momentum=True, step=None, lam=0.0, maxiter=100, tol=1e-4, check_every=0)``.
+
+    ``nuc``, ``l1``: the weights of ``‖C(L)‖_*`` and ``‖T S‖₁``.  ``momentum=False`` is the scheme of Otazo, Candès & Sodickson.
+    ``step``: None computes ``1 / (2 · (1.05 · max(op.max_eigenvalue()) + lam))`` once, here (the operator then needs its spectrum
+    already); the 2 is there because the smooth term, as a function of the pair ``(L, S)``, has the Hessian ``[[A, A], [A, A]]`` with
+    largest eigenvalue ``2 λ_max(A)``.  ``check_every`` as for :class:`ToeplitzFISTA`.  The frames are one system: one change, one
+    status, reported identically for every component.  The solver keeps ``op`` alive; a new build of it between two solves is allowed."""
+
+    def __init__(self, op: ToeplitzOperator, nuc, l1, transform="dft", momentum: bool = True, step=None, lam: float = 0.0,
+                 maxiter: int = 100, tol: float = 1e-4, check_every: int = 0):
+        if not isinstance(op, ToeplitzOperator):
+            raise ValueError("ToeplitzLPS takes a ToeplitzOperator")
+        for name, v in (("maxiter", maxiter), ("check_every", check_every)):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError(f"{name} must be an integer")
+        tid = _transform_id(transform)
+        op._require_open()
+        if step is None:
+            op._require_gpu()
+            step = 1.0 / (2.0 * (1.05 * max(op.max_eigenvalue()) + float(lam)))
+        prm = _lib.NufftLpsParams()
+        prm.struct_size = C.sizeof(_lib.NufftLpsParams)
+        prm.max_iter, prm.check_every, prm.transform, prm.momentum = maxiter, check_every, tid, int(bool(momentum))
+        prm.tol, prm.step, prm.lambda_, prm.nuc, prm.l1 = float(tol), float(step), float(lam), float(nuc), float(l1)
+        self._handle = C.c_void_p()
+        _check(lib.nufft_lps_create(C.byref(self._handle), op._handle, C.byref(prm)))
+        self.op = op
+        self.nuc, self.l1, self.transform, self.momentum = float(nuc), float(l1), transform, bool(momentum)
+        self.step, self.lam, self.maxiter, self.tol, self.check_every = float(step), float(lam), maxiter, float(tol), check_every
+
+    def set_weights(self, nuc, l1):
+        """The two weights of the following solves."""
+        self._require_open()
+        _check(lib.nufft_lps_set_weights(self._handle, float(nuc), float(l1)))
+        self.nuc, self.l1 = float(nuc), float(l1)
+
+    def close(self):
+        h = getattr(self, "_handle", None)
+        if h is not None and h.value:
+            lib.nufft_lps_destroy(h)
+            self._handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _require_open(self):
+        """The library keeps a pointer to the operator: refuse to follow it once either object has been closed."""
+        if not self._handle.value:
+            raise ValueError("this ToeplitzLPS has been closed")
+        if not self.op._handle.value:
+            raise ValueError("the ToeplitzOperator of this solver has been closed: the operator must outlive the solver")
+
+    def info(self) -> _lib.NufftLpsInfo:
+        self._require_open()
+        out = _lib.NufftLpsInfo()
+        out.struct_size = C.sizeof(_lib.NufftLpsInfo)
+        _check(lib.nufft_lps_get_info(self._handle, C.byref(out)))
+        return out
+
+    def solve(self, b, x0=None, out=None):
+        """``b``: a tensor of ``plan.shape`` or a tuple of ntransforms such tensors (only read).  ``x0``: starting guess for ``L``
+        (None = zero; ``S`` always starts at zero); ``out``: where ``x = L + S`` goes (may be ``x0``; None = new tensors; never ``b``).
+        Returns ``out``."""
+        self._require_open()
+        op = self.op
+        op._require_gpu()
+        single = isinstance(b, torch.Tensor)
+        b_t = (b,) if single else tuple(b)
+        op._check_uniform(b_t, "right-hand side")
+        if out is None:
+            out_t = tuple(torch.empty_like(v) for v in b_t)
+            out = out_t[0] if single else out_t
+        else:
+            out_t = (out,) if isinstance(out, torch.Tensor) else tuple(out)
+            op._check_uniform(out_t, "output")
+        if x0 is not None:
+            x0_t = (x0,) if isinstance(x0, torch.Tensor) else tuple(x0)
+            op._check_uniform(x0_t, "starting guess")
+            for o, g in zip(out_t, x0_t):
+                if o.data_ptr() != g.data_ptr():
+                    o.copy_(g)
+        _check(lib.nufft_lps_solve(self._handle, _ptr_table(out_t), _ptr_table(b_t), 0 if x0 is None else 1, op._stream()))
+        self._like = b_t
+        return out
+
+    def _parts(self, which):
+        self._require_open()
+        like = getattr(self, "_like", None)
+        if like is None:
+            raise ValueError("no solve yet")
+        out = tuple(torch.empty_like(v) for v in like)
+        tab = _ptr_table(out)
+        _check(lib.nufft_lps_get_parts(self._handle, tab if which == 0 else None, tab if which == 1 else None, self.op._stream()))
+        return out
+
+    @property
+    def low_rank(self):
+        """``L`` of the last solve: a tuple of ntransforms new tensors."""
+        return self._parts(0)
+
+    @property
+    def sparse(self):
+        """``S`` of the last solve: a tuple of ntransforms new tensors."""
+        return self._parts(1)
+
+    def _result(self):
+        self._require_open()
+        n = self.op.ntransforms
+        it, st, ch = (C.c_int32 * n)(), (C.c_int32 * n)(), (C.c_double * n)()
+        _check(lib.nufft_lps_get_result(self._handle, it, st, ch, n, self.op._stream()))
+        return list(it), list(st), list(ch)
+
+    @property
+    def iterations(self):
+        """Per component (all equal): iterations that changed the system (synchronises the current stream)."""
+        return tuple(self._result()[0])
+
+    @property
+    def status(self):
+        """Per component (all equal): ``"converged"``, ``"max_iter"`` or ``"breakdown"``."""
+        return tuple(_lib.LPS_STATUS_NAMES[s] for s in self._result()[1])
+
+    @property
+    def change(self):
+        """Per component (all equal): ``sqrt((‖L⁺−L‖² + ‖S⁺−S‖²) / (‖L⁺‖² + ‖S⁺‖²))`` of the last iteration that ran."""
+        return tuple(self._result()[2])
+
+    def history(self) -> torch.Tensor:
+        """``[iterations, 3]`` (host, float64): the change, ``‖C(L)‖_*`` and ``‖T S‖₁`` after every iteration."""
+        self._require_open()
+        buf = (C.c_double * (self.maxiter * 3))()
+        _check(lib.nufft_lps_history(self._handle, buf, len(buf), self.op._stream()))
+        rows = max(self.iterations)
+        return torch.tensor(list(buf), dtype=torch.float64).reshape(self.maxiter, 3)[:rows].clone()
+
+    def __repr__(self):
+        i = self.info()
+        return (f"ToeplitzLPS on a {self.op.ndim}-dimensional {self.op.Z} operator x {self.op.ntransforms} frames, nuc = {self.nuc:g}, l1 = {self.l1:g}, "
+                f"transform = {self.transform!r}, momentum = {self.momentum}, step = {self.step:g}, lam = {self.lam:g}, maxiter = {self.maxiter}, "
+                f"tol = {self.tol:g}, check_every = {self.check_every}, {i.workspace_bytes / 1e6:.1f} MB")
