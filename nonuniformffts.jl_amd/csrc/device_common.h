@@ -10,7 +10,10 @@
 namespace nufft {
 
 constexpr int kWave = 64;
-constexpr int kMaxCompPerLaunch = 8;    // components (ntransforms) handled by one launch
+// components (ntransforms) handled by one launch.  Plans with more run host loops `for (c0 = 0; c0 < C; c0 += kMaxCompPerLaunch)`
+// that derive every per-component pointer from c0 + c (tile_launch.hip, deconv.hip, interp_grad_inst.h, type3.cpp): every such loop
+// is exercised with c0 > 0 (C = 9, 16, 17) by tests/test_gpu_many_transforms.py, so a new one belongs in tests/many_transforms_cases.py
+constexpr int kMaxCompPerLaunch = 8;
 
 template <typename T> struct TwoPi;
 template <> struct TwoPi<float>  { static constexpr float  value = 6.28318530717958647692f; };
