@@ -1514,6 +1514,90 @@ int nufft_lps_history(nufft_lps* s, double* host_out, int64_t capacity, void* st
 int64_t nufft_sizeof_lps_params(void);
 int64_t nufft_sizeof_lps_info(void);
 
+/* ---- Coil sensitivity maps from coil images ----
+ * The adaptive estimate of Walsh, Gmitro & Marcellin (MRM 2000): at every cell the dominant eigenvector of the covariance of the coil
+ * values over a box around the cell.  Added after ABI 104 without changing NUFFT_MI355X_VERSION: detect by symbol (dlsym
+ * nufft_coilmaps_create) and compare nufft_sizeof_coilmaps_params() / nufft_sizeof_coilmaps_info() with your own.
+ *
+ * Input: C = ncoils complex arrays a_c of the given shape (the low-resolution coil images), 1 <= C <= 32.  Box sides b_d odd,
+ * 1 <= b_d <= min(9, N_d).  For every cell x:
+ *
+ *     R(x)[c, c'] = Σ_{x' ∈ box(x)} a_c(x') conj(a_c'(x'))     the box centred at x and periodic on the array as stored; FP64 for both
+ *                                                              element types; summed with k_3 outermost and k_1 innermost
+ *     R = V Λ V^H                                              the cyclic Jacobi of the locally low-rank map, with its constants
+ *     λ1 = the largest final diagonal entry (the first index on a tie), λ2 = the second largest (0 for C = 1), v = the column of λ1,
+ *                                                              scaled back to unit length (the rotations cost it a few ε)
+ *     s = Σ_c conj(p_c) v_c;   v <- v conj(s) / |s| if |s| > 0     p = phase_ref (default e_0: coil 0 becomes real and non-negative)
+ *     S_c(x) = v_c, rounded once to the element type;  S(x) = 0 exactly where λ1(x) = 0
+ *     crop > 0:  S(x) = 0 exactly where λ1(x) < crop² max_x λ1(x)     (formed on the device; both sides are λ1 as stored, that is
+ *                                                              rounded to the real element type)
+ *
+ * so Σ_c |S_c|² = 1 at every cell that is not zeroed.  No atomics, every sum in one fixed order: two runs and a replayed hipGraph give
+ * the same bits. */
+typedef struct nufft_coilmaps nufft_coilmaps; /* opaque */
+
+typedef struct nufft_coilmaps_params {
+    int32_t struct_size;     /* sizeof(nufft_coilmaps_params) of the caller's header (0 = this layout)                             */
+    int32_t box[3];          /* box sides, odd; 1 (or 0) beyond ndim                                                               */
+    double crop;             /* >= 0, finite; 0: nothing is cropped                                                                */
+    int64_t reserved[2];     /* 0                                                                                                  */
+} nufft_coilmaps_params;
+
+typedef struct nufft_coilmaps_info {
+    int32_t struct_size;     /* sizeof(nufft_coilmaps_info) of the caller's header, set before the call (0 = this layout)          */
+    int32_t ndim, dtype, ncoils, device;
+    int32_t box[3];
+    int32_t tile[3];         /* output cells of one workgroup per dimension                                                        */
+    int32_t tile_cells;
+    int32_t team_lanes;      /* lanes that diagonalise one cell: the next power of two >= ncoils                                   */
+    int32_t teams;           /* teams per workgroup                                                                                */
+    int32_t staged;          /* 1: tile plus halo are staged in LDS;  0: the neighbours are read from global memory                */
+    int32_t lds_bytes;       /* of one workgroup                                                                                   */
+    int32_t jacobi_sweeps_max;
+    int32_t reserved;
+    double crop;
+    int64_t N[3];            /* 1 beyond ndim                                                                                      */
+    int64_t cells;           /* n = Π N_d                                                                                          */
+    int64_t workgroups;      /* of the main kernel = max partials                                                                  */
+    int64_t workspace_bytes; /* device bytes owned: the partials, two words and, with crop > 0, n reals for λ1                     */
+} nufft_coilmaps_info;
+
+/* dtype: NUFFT_F32 / NUFFT_F64, the real type of the complex arrays (the arrays are always complex: a binding that starts from a plan
+ * refuses a real-data plan itself).  N: ndim sizes, N[0] the fastest.  Refusals, in order: a null argument, a struct_size below the
+ * published layout, an unknown dtype, ndim outside 1 ... 3, N_d < 1, ncoils < 1, an even or non-positive box side, a negative or
+ * non-finite crop NUFFT_ERR_INVALID_ARG; ncoils > 32, b_d > 9 or b_d > N_d NUFFT_ERR_UNSUPPORTED; device < 0 NUFFT_ERR_NO_DEVICE. */
+int nufft_coilmaps_create(nufft_coilmaps** out, int dtype, int ndim, const int64_t* N, int32_t ncoils, int device, const nufft_coilmaps_params* params);
+/* Element type, shape and device of a Toeplitz operator (the operator is not kept; its ntransforms plays no part). */
+int nufft_coilmaps_create_for_operator(nufft_coilmaps** out, const nufft_toeplitz* tz, int32_t ncoils, const nufft_coilmaps_params* params);
+int nufft_coilmaps_destroy(nufft_coilmaps* h);
+/* What nufft_coilmaps_create would lay out for these arguments, without a device: the same checks in the same order (the device
+ * aside), the same tile, teams and LDS bytes; device = -1 and workspace_bytes = what the object would allocate. */
+int nufft_coilmaps_layout(int dtype, int ndim, const int64_t* N, int32_t ncoils, const nufft_coilmaps_params* params, nufft_coilmaps_info* out);
+/* Static facts and sizes; does not synchronise. */
+int nufft_coilmaps_get_info(const nufft_coilmaps* h, nufft_coilmaps_info* out);
+/* maps_out, images_in: host tables of ncoils device pointers, 16-byte aligned.  phase_ref: ncoils complex doubles (re, im) on the HOST,
+ * or NULL for e_0; it travels by value in the kernel arguments.  lambda1, lambda2: device arrays of n reals of the element type, or
+ * NULL.  λ is about box cells x |a|²: in Float32 it overflows to infinity for |a| above about 1e18 and underflows to 0 for |a| below
+ * about 1e-23; the maps do not (R is FP64), but the crop compares the stored values: with an infinite maximum every finite cell is
+ * cropped, and a cell whose stored λ1 is 0 is cropped whenever the threshold is positive.  Scale such images first.  With crop > 0 and
+ * lambda1 = NULL the object uses an array of its own, allocated at create time.  Allocates nothing, does not
+ * synchronise, hipGraph-capture safe; one call at a time per object.  Refusals, before anything is enqueued: a null object or table, a
+ * non-finite phase_ref, a null or not 16-byte aligned entry, two outputs (maps and eigenvalue arrays) that overlap, an output that
+ * overlaps any input NUFFT_ERR_INVALID_ARG. */
+int nufft_coilmaps_estimate(nufft_coilmaps* h, void* const* maps_out, const void* const* images_in, const double* phase_ref, void* lambda1, void* lambda2,
+                            void* stream);
+/* The crop pass on its own, with another level: maps_inout[c][x] = 0 where lambda1[x] < crop² max λ1, the maximum being that of the LAST
+ * nufft_coilmaps_estimate of this object (on the device; nothing is read back).  lambda1: what that call wrote, or NULL for the object's
+ * own array (an object created with crop > 0).  Reads lambda1, writes only the cells it zeroes; crop = 0 does nothing.  Capturable.
+ * Refusals: a null object or table, a negative or non-finite crop, no lambda1 at all, a null or misaligned entry, maps that overlap each
+ * other or lambda1 NUFFT_ERR_INVALID_ARG. */
+int nufft_coilmaps_apply_crop(nufft_coilmaps* h, void* const* maps_inout, const void* lambda1, double crop, void* stream);
+/* The largest Jacobi sweep count over the cells of the last estimate (the last sweep rotates nothing; 0 for ncoils = 1).
+ * Synchronises `stream` (never a capturing one). */
+int nufft_coilmaps_last_sweeps(nufft_coilmaps* h, int32_t* sweeps_out, void* stream);
+int64_t nufft_sizeof_coilmaps_params(void);
+int64_t nufft_sizeof_coilmaps_info(void);
+
 /* ---- misc ----------------------------------------------------------------------------- */
 /* sizeof(nufft_params) / sizeof(nufft_info) of the library build: a binding that mirrors the structs by hand
  * (ctypes, Julia) compares them with its own layout before the first call. */

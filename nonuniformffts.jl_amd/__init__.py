@@ -26,6 +26,7 @@ from .fista import ToeplitzFISTA  # noqa: F401
 from .tv import ToeplitzTV, TotalVariation  # noqa: F401
 from .lps import GlobalLowRank, TemporalSparsity, ToeplitzLPS  # noqa: F401
 from .dcf import DensityCompensation, density_weights  # noqa: F401
+from .coilmaps import CoilMapEstimator, calibration_weights, estimate_maps  # noqa: F401
 from . import autograd  # noqa: F401
 
 __all__ = [
@@ -39,4 +40,5 @@ __all__ = [
     "WaveletTransform", "LocallyLowRank", "ToeplitzFISTA", "TotalVariation", "ToeplitzTV",
     "GlobalLowRank", "TemporalSparsity", "ToeplitzLPS",
     "DensityCompensation", "density_weights",
+    "CoilMapEstimator", "estimate_maps", "calibration_weights",
 ]

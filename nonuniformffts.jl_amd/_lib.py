@@ -267,6 +267,19 @@ LPS_MAX_ITER, LPS_CONVERGED, LPS_BREAKDOWN = 0, 1, 2
 LPS_STATUS_NAMES = {LPS_MAX_ITER: "max_iter", LPS_CONVERGED: "converged", LPS_BREAKDOWN: "breakdown"}
 
 
+class NufftCoilmapsParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("box", C.c_int32 * 3), ("crop", C.c_double), ("reserved", C.c_int64 * 2)]
+
+
+class NufftCoilmapsInfo(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("ndim", C.c_int32), ("dtype", C.c_int32), ("ncoils", C.c_int32), ("device", C.c_int32),
+        ("box", C.c_int32 * 3), ("tile", C.c_int32 * 3), ("tile_cells", C.c_int32), ("team_lanes", C.c_int32), ("teams", C.c_int32),
+        ("staged", C.c_int32), ("lds_bytes", C.c_int32), ("jacobi_sweeps_max", C.c_int32), ("reserved", C.c_int32),
+        ("crop", C.c_double), ("N", C.c_int64 * 3), ("cells", C.c_int64), ("workgroups", C.c_int64), ("workspace_bytes", C.c_int64),
+    ]
+
+
 class NufftDcfParams(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int32), ("max_iter", C.c_int32), ("check_every", C.c_int32), ("normalize", C.c_int32),
@@ -473,6 +486,16 @@ SYMBOLS = {
     "nufft_lps_history": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int64, _P]),
     "nufft_sizeof_lps_params": (C.c_int64, []),
     "nufft_sizeof_lps_info": (C.c_int64, []),
+    "nufft_coilmaps_create": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int32, C.c_int, C.POINTER(NufftCoilmapsParams)]),
+    "nufft_coilmaps_create_for_operator": (C.c_int, [C.POINTER(_P), _P, C.c_int32, C.POINTER(NufftCoilmapsParams)]),
+    "nufft_coilmaps_destroy": (C.c_int, [_P]),
+    "nufft_coilmaps_get_info": (C.c_int, [_P, C.POINTER(NufftCoilmapsInfo)]),
+    "nufft_coilmaps_estimate": (C.c_int, [_P, _PP, _PP, C.POINTER(C.c_double), _P, _P, _P]),
+    "nufft_coilmaps_layout": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int32, C.POINTER(NufftCoilmapsParams), C.POINTER(NufftCoilmapsInfo)]),
+    "nufft_coilmaps_apply_crop": (C.c_int, [_P, _PP, _P, C.c_double, _P]),
+    "nufft_coilmaps_last_sweeps": (C.c_int, [_P, C.POINTER(C.c_int32), _P]),
+    "nufft_sizeof_coilmaps_params": (C.c_int64, []),
+    "nufft_sizeof_coilmaps_info": (C.c_int64, []),
     "nufft_sizeof_params": (C.c_int64, []),
     "nufft_sizeof_info": (C.c_int64, []),
     "nufft_strerror": (C.c_char_p, [C.c_int]),
@@ -511,7 +534,8 @@ def _load():
                          ("nufft_sizeof_tvpd_params", NufftTvpdParams), ("nufft_sizeof_tvpd_info", NufftTvpdInfo),
                          ("nufft_sizeof_tvt_params", NufftTvtParams), ("nufft_sizeof_glr_info", NufftGlrInfo),
                          ("nufft_sizeof_tsparse_info", NufftTsparseInfo), ("nufft_sizeof_lps_params", NufftLpsParams),
-                         ("nufft_sizeof_lps_info", NufftLpsInfo)):
+                         ("nufft_sizeof_lps_info", NufftLpsInfo), ("nufft_sizeof_coilmaps_params", NufftCoilmapsParams),
+                         ("nufft_sizeof_coilmaps_info", NufftCoilmapsInfo)):
         if getattr(lib, name)() != C.sizeof(mirror):
             raise ImportError(f"{LIB_PATH}: {name}() = {getattr(lib, name)()} but the ctypes mirror has {C.sizeof(mirror)} bytes "
                               "(include/nufft_mi355x.h and _lib.py disagree)")
