@@ -20,11 +20,12 @@ import torch
 
 from . import _lib
 from ._lib import lib
-from .plan import _check, _ptr_table
+from ._solver import _ToeplitzSolver, _doc
+from .plan import _check
 from .toeplitz import ToeplitzOperator
 
 
-class ToeplitzCG:
+class ToeplitzCG(_ToeplitzSolver):
     """``ToeplitzCG(op, maxiter=50, rtol=1e-6, lam=0.0, check_every=0)``: allocates three arrays per component next to the operator.
 
     ``check_every=0`` enqueues all ``maxiter`` iterations without synchronising (components that reached ``rtol`` are frozen on the
@@ -37,12 +38,13 @@ class ToeplitzCG:
     ``precond``: a :class:`ToeplitzPreconditioner` built for ``op`` (kept alive by the solver) or None; ``set_preconditioner`` changes it
     between two solves.  Without one the solver enqueues exactly what it always did."""
 
+    _prefix, _info, _status_names = "cg", _lib.NufftCgInfo, _lib.CG_STATUS_NAMES
+    _start_row, _columns = 1, staticmethod(lambda n: (n,))
+
     def __init__(self, op: ToeplitzOperator, maxiter: int = 50, rtol: float = 1e-6, lam: float = 0.0, check_every: int = 0, precond=None):
         if not isinstance(op, ToeplitzOperator):
             raise ValueError("ToeplitzCG takes a ToeplitzOperator")
-        for name, v in (("maxiter", maxiter), ("check_every", check_every)):
-            if isinstance(v, bool) or not isinstance(v, int):
-                raise ValueError(f"{name} must be an integer")
+        self._check_ints(maxiter=maxiter, check_every=check_every)
         prm = _lib.NufftCgParams()
         prm.struct_size = C.sizeof(_lib.NufftCgParams)
         prm.max_iter, prm.check_every = maxiter, check_every
@@ -74,89 +76,24 @@ class ToeplitzCG:
         self.precond = precond
         return self
 
-    def close(self):
-        h = getattr(self, "_handle", None)
-        if h is not None and h.value:
-            lib.nufft_cg_destroy(h)
-            self._handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def _require_open(self, check_precond=True):
-        """The library keeps a pointer to the operator: refuse to follow it once either object has been closed."""
-        if not self._handle.value:
-            raise ValueError("this ToeplitzCG has been closed")
-        if not self.op._handle.value:
-            raise ValueError("the ToeplitzOperator of this solver has been closed: the operator must outlive the solver")
+        super()._require_open()
         if check_precond and self.precond is not None and not self.precond._handle.value:
             raise ValueError("the ToeplitzPreconditioner of this solver has been closed: clear it with set_preconditioner(None) first")
 
-    def info(self) -> _lib.NufftCgInfo:
-        self._require_open()
-        out = _lib.NufftCgInfo()
-        out.struct_size = C.sizeof(_lib.NufftCgInfo)
-        _check(lib.nufft_cg_get_info(self._handle, C.byref(out)))
-        return out
-
-    def solve(self, b, x0=None, out=None):
-        """``b``: a tensor of ``plan.shape`` or a tuple of ntransforms such tensors (only read).  ``x0``: starting guess (None = zero);
-        ``out``: where the solution goes (may be ``x0``: it is then refined in place; None = new tensors).  Returns ``out``."""
-        self._require_open()
-        op = self.op
-        op._require_gpu()
-        single = isinstance(b, torch.Tensor)
-        b_t = (b,) if single else tuple(b)
-        op._check_uniform(b_t, "right-hand side")
-        if out is None:
-            out_t = tuple(torch.empty_like(v) for v in b_t)
-            out = out_t[0] if single else out_t
-        else:
-            out_t = (out,) if isinstance(out, torch.Tensor) else tuple(out)
-            op._check_uniform(out_t, "output")
-        if x0 is not None:
-            x0_t = (x0,) if isinstance(x0, torch.Tensor) else tuple(x0)
-            op._check_uniform(x0_t, "starting guess")
-            for o, g in zip(out_t, x0_t):
-                if o.data_ptr() != g.data_ptr():
-                    o.copy_(g)
-        _check(lib.nufft_cg_solve(self._handle, _ptr_table(out_t), _ptr_table(b_t), 0 if x0 is None else 1, op._stream()))
-        return out
-
-    def _result(self):
-        self._require_open()
-        n = self.op.ntransforms
-        it, st, res = (C.c_int32 * n)(), (C.c_int32 * n)(), (C.c_double * n)()
-        _check(lib.nufft_cg_get_result(self._handle, it, st, res, n, self.op._stream()))
-        return list(it), list(st), list(res)
-
-    @property
-    def iterations(self):
-        """Per component: iterations that changed it (synchronises the current stream)."""
-        return tuple(self._result()[0])
-
-    @property
-    def status(self):
-        """Per component: ``"converged"``, ``"max_iter"`` or ``"breakdown"``."""
-        return tuple(_lib.CG_STATUS_NAMES[s] for s in self._result()[1])
+    solve = _doc(_ToeplitzSolver.solve,
+                 """``b``: a tensor of ``plan.shape`` or a tuple of ntransforms such tensors (only read).  ``x0``: starting guess (None = zero);
+        ``out``: where the solution goes (may be ``x0``: it is then refined in place; None = new tensors).  Returns ``out``.""")
+    status = _doc(_ToeplitzSolver.status, """Per component: ``"converged"``, ``"max_iter"`` or ``"breakdown"``.""")
 
     @property
     def residual(self):
         """Per component: the recursive relative residual ``‖r‖ / ‖b‖`` the stopping rule saw last."""
         return tuple(self._result()[2])
 
-    def history(self) -> torch.Tensor:
-        """``[max(iterations) + 1, ntransforms]`` (host, float64): relative residual after every iteration, row 0 the start; NaN
-        where an iteration did not change the component."""
-        self._require_open()
-        n = self.op.ntransforms
-        buf = (C.c_double * ((self.maxiter + 1) * n))()
-        _check(lib.nufft_cg_history(self._handle, buf, len(buf), self.op._stream()))
-        rows = max(self.iterations) + 1
-        return torch.tensor(list(buf), dtype=torch.float64).reshape(self.maxiter + 1, n)[:rows].clone()
+    history = _doc(_ToeplitzSolver.history,
+                   """``[max(iterations) + 1, ntransforms]`` (host, float64): relative residual after every iteration, row 0 the start; NaN
+        where an iteration did not change the component.""")
 
     def __repr__(self):
         i = self.info()

@@ -15,8 +15,8 @@
 #include <vector>
 
 #include "cg.h"
-#include "host_common.h"
 #include "precond.h"
+#include "solver_common.h"
 
 using namespace nufft;
 
@@ -78,12 +78,6 @@ CgScalars scalars_at(const nufft_cg* s, void* base) {
     return k;
 }
 
-bool overlap(const void* a, const void* b, size_t bytes) {
-    const char* x = static_cast<const char*>(a);
-    const char* y = static_cast<const char*>(b);
-    return x < y + bytes && y < x + bytes;
-}
-
 // One kernel over all components, kCgBatch at a time.
 template <typename F>
 int for_batches(const nufft_cg* s, CgLaunch& a, void* const* x, const void* const* b, F&& launch) {
@@ -111,9 +105,7 @@ int nufft_cg_create(nufft_cg** out, nufft_toeplitz* tz, const nufft_cg_params* p
     if (!out || !tz || !params) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
     *out = nullptr;
     nufft_toeplitz_info ti;
-    std::memset(&ti, 0, sizeof(ti));
-    ti.struct_size = (int32_t)sizeof(ti);
-    int rc = nufft_toeplitz_get_info(tz, &ti);
+    int rc = toeplitz_info(tz, ti);
     if (rc) return rc;
     if (ti.device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1): the solver runs on the device");
     nufft_cg_params p;
@@ -140,23 +132,14 @@ int nufft_cg_create(nufft_cg** out, nufft_toeplitz* tz, const nufft_cg_params* p
     s->array_bytes = 3 * (int64_t)s->C * (int64_t)comp;
 
     DeviceGuard guard(s->device);
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device) == hipSuccess && cus > 0) s->num_cus = cus;
-    else (void)hipGetLastError();
+    s->num_cus = device_cus(s->device);
     s->G = cg_workgroups(s->dtype, s->n, s->num_cus);
     if ((rc = alloc(s, &s->d_r, (size_t)s->C * comp)) || (rc = alloc(s, &s->d_p, (size_t)s->C * comp)) ||
         (rc = alloc(s, &s->d_q, (size_t)s->C * comp)) || (rc = alloc(s, &s->d_part, part_bytes(s))) ||
-        (rc = alloc(s, &s->d_hist, hist_bytes(s))) ||
-        (rc = s->scal.create(s->own_bytes, "CG", scal_bytes(s), "hipHostMalloc of the solver's host mirror failed"))) {
+        (rc = create_outcome(s->own_bytes, "CG", s->scal, &s->d_hist, scal_bytes(s), hist_bytes(s)))) {
         const std::string keep = nufft_last_error_message();
         release(s);
         return fail(rc, keep);
-    }
-    // a defined answer from nufft_cg_get_result / nufft_cg_history before the first solve
-    if (s->scal.zero() != hipSuccess || hipMemset(s->d_hist, 0xFF, hist_bytes(s)) != hipSuccess) {
-        (void)hipGetLastError();
-        release(s);
-        return fail(NUFFT_ERR_HIP, "hipMemset of the solver's scalars failed");
     }
     for (int c = 0; c < s->C; ++c) {
         s->ptab.push_back(static_cast<char*>(s->d_p) + (size_t)c * comp);
@@ -211,28 +194,10 @@ int nufft_cg_get_info(const nufft_cg* s, nufft_cg_info* o) {
 
 int nufft_cg_solve(nufft_cg* s, void* const* x, const void* const* b, int use_x0, void* stream_) {
     if (!s) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
-    nufft_toeplitz_info ti;
-    std::memset(&ti, 0, sizeof(ti));
-    ti.struct_size = (int32_t)sizeof(ti);
-    int rc = nufft_toeplitz_get_info(s->tz, &ti);
-    if (rc) return rc;
-    if (!ti.has_spectrum)
-        return fail(NUFFT_ERR_NO_POINTS, "nufft_toeplitz_set_spectrum or nufft_toeplitz_set_points must be called before nufft_cg_solve");
-    if (!x || !b) return fail(NUFFT_ERR_INVALID_ARG, "null table");
-    const size_t bytes = (size_t)s->n * 2 * real_bytes(s->dtype);
-    for (int c = 0; c < s->C; ++c) {
-        if (!x[c] || !b[c]) return fail(NUFFT_ERR_INVALID_ARG, "null data vector");
-        if (((uintptr_t)x[c] | (uintptr_t)b[c]) & 15) return fail(NUFFT_ERR_INVALID_ARG, "x and b must be 16-byte aligned");
-    }
-    for (int c = 0; c < s->C; ++c)
-        for (int k = 0; k < s->C; ++k) {
-            if (overlap(x[c], b[k], bytes)) return fail(NUFFT_ERR_INVALID_ARG, "x overlaps b: the right-hand side is read while x is written");
-            if (k != c && overlap(x[c], x[k], bytes)) return fail(NUFFT_ERR_INVALID_ARG, "two components of x overlap");
-        }
     DeviceGuard guard(s->device);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (s->check_every > 0 && capturing(stream))
-        return fail(NUFFT_ERR_INVALID_ARG, "check_every > 0 synchronises the stream: not on a capturing stream (use check_every = 0)");
+    int rc = check_solve_args(s->tz, "nufft_cg_solve", s->C, s->n, s->dtype, x, b, s->check_every, stream);
+    if (rc) return rc;
 
     CgLaunch a{};
     a.dtype = s->dtype;
@@ -291,9 +256,8 @@ int nufft_cg_solve(nufft_cg* s, void* const* x, const void* const* b, int use_x0
         }
         s->enqueued = it;
         if (s->check_every > 0 && it % s->check_every == 0 && it < s->max_iter) {
-            if ((rc = s->scal.fetch(stream))) return rc;
-            bool all = true;
-            for (int c = 0; c < s->C; ++c) all = all && host.flag[((it + 1) & 1) * s->C + c] != 0;
+            bool all;
+            if ((rc = all_done(s->scal, stream, host.flag + ((it + 1) & 1) * s->C, s->C, &all))) return rc;
             if (all) break;
         }
     }
@@ -305,9 +269,8 @@ int nufft_cg_get_result(nufft_cg* s, int32_t* iterations, int32_t* status, doubl
     if (capacity < s->C) return fail(NUFFT_ERR_INVALID_ARG, "capacity is smaller than ntransforms");
     DeviceGuard guard(s->device);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (capturing(stream)) return fail(NUFFT_ERR_INVALID_ARG, "nufft_cg_get_result synchronises: not on a capturing stream");
-    int rc = s->scal.fetch(stream);
-    if (rc) return rc;
+    int rc;
+    if ((rc = refuse_capture("nufft_cg_get_result", stream)) || (rc = s->scal.fetch(stream))) return rc;
     const CgScalars host = scalars_at(s, s->scal.host);
     for (int c = 0; c < s->C; ++c) {
         if (iterations) iterations[c] = host.iters[c];
@@ -321,11 +284,7 @@ int nufft_cg_history(nufft_cg* s, double* host_out, int64_t capacity, void* stre
     if (!s || !host_out) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
     if (capacity < (int64_t)(s->max_iter + 1) * s->C) return fail(NUFFT_ERR_INVALID_ARG, "capacity is smaller than (max_iter + 1) * ntransforms");
     DeviceGuard guard(s->device);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (capturing(stream)) return fail(NUFFT_ERR_INVALID_ARG, "nufft_cg_history synchronises: not on a capturing stream");
-    NUFFT_HIP(hipMemcpyAsync(host_out, s->d_hist, hist_bytes(s), hipMemcpyDeviceToHost, stream));
-    NUFFT_HIP(hipStreamSynchronize(stream));
-    return NUFFT_OK;
+    return fetch_history("nufft_cg_history", host_out, s->d_hist, hist_bytes(s), static_cast<hipStream_t>(stream_));
 }
 
 }  // extern "C"

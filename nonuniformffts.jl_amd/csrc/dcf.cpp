@@ -13,7 +13,7 @@
 #include <string>
 
 #include "dcf.h"
-#include "host_common.h"
+#include "solver_common.h"
 
 using namespace nufft;
 
@@ -221,8 +221,7 @@ int nufft_dcf_compute(nufft_dcf* s, void* w, int use_w0, void* stream_) {
     if ((uintptr_t)w & 15) return fail(NUFFT_ERR_INVALID_ARG, "the weight vector must be 16-byte aligned");
     DeviceGuard guard(s->device);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (s->check_every > 0 && capturing(stream))
-        return fail(NUFFT_ERR_INVALID_ARG, "check_every > 0 synchronises the stream: not on a capturing stream (use check_every = 0)");
+    if (int prc = refuse_polling_capture(s->check_every, stream)) return prc;
 
     DcfLaunch a{};
     a.dtype = s->dtype;
@@ -258,8 +257,9 @@ int nufft_dcf_compute(nufft_dcf* s, void* w, int use_w0, void* stream_) {
         if ((rc = launched(launch_dcf_update(a, stream)))) return rc;
         s->enqueued = k + 1;
         if (s->check_every > 0 && (k + 1) % s->check_every == 0 && k + 1 < s->max_iter) {
-            if ((rc = s->scal.fetch(stream))) return rc;
-            if (host.flag[(k + 1) & 1]) break;
+            bool done;
+            if ((rc = all_done(s->scal, stream, host.flag + ((k + 1) & 1), 1, &done))) return rc;
+            if (done) break;
         }
     }
     if (s->normalize == NUFFT_DCF_NORMALIZE_SUM) {
@@ -276,9 +276,8 @@ int nufft_dcf_get_result(nufft_dcf* s, int32_t* iterations, int32_t* status, dou
     if (s->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only density-compensation object (device = -1)");
     DeviceGuard guard(s->device);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (capturing(stream)) return fail(NUFFT_ERR_INVALID_ARG, "nufft_dcf_get_result synchronises: not on a capturing stream");
-    int rc = s->scal.fetch(stream);
-    if (rc) return rc;
+    int rc;
+    if ((rc = refuse_capture("nufft_dcf_get_result", stream)) || (rc = s->scal.fetch(stream))) return rc;
     const DcfScalars host = scalars_at(s, s->scal.host);
     if (iterations) *iterations = host.iters[0];
     if (status) *status = host.status[0];
@@ -291,11 +290,7 @@ int nufft_dcf_history(nufft_dcf* s, double* host_out, int64_t capacity, void* st
     if (s->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only density-compensation object (device = -1)");
     if (capacity < (int64_t)s->max_iter) return fail(NUFFT_ERR_INVALID_ARG, "capacity is smaller than max_iter");
     DeviceGuard guard(s->device);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (capturing(stream)) return fail(NUFFT_ERR_INVALID_ARG, "nufft_dcf_history synchronises: not on a capturing stream");
-    NUFFT_HIP(hipMemcpyAsync(host_out, s->d_hist, hist_bytes(s), hipMemcpyDeviceToHost, stream));
-    NUFFT_HIP(hipStreamSynchronize(stream));
-    return NUFFT_OK;
+    return fetch_history("nufft_dcf_history", host_out, s->d_hist, hist_bytes(s), static_cast<hipStream_t>(stream_));
 }
 
 }  // extern "C"

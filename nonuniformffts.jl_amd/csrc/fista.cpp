@@ -17,8 +17,8 @@
 #include <vector>
 
 #include "fista.h"
-#include "host_common.h"
 #include "llr.h"
+#include "solver_common.h"
 #include "wavelet.h"
 
 using namespace nufft;
@@ -45,7 +45,6 @@ struct nufft_fista {
 
 namespace {
 
-size_t scal_bytes(const nufft_fista* s) { return (size_t)s->C * (sizeof(double) + 3 * sizeof(int32_t)); }
 size_t hist_bytes(const nufft_fista* s) { return (size_t)s->max_iter * s->C * 2 * sizeof(double); }
 
 void release(nufft_fista* s) {
@@ -59,24 +58,6 @@ void release(nufft_fista* s) {
         s->scal.release();
     }
     delete s;
-}
-
-FistaScalars scalars_at(const nufft_fista* s, void* base) {
-    FistaScalars k{};
-    double* d = static_cast<double*>(base);
-    k.change = d;
-    int32_t* i = reinterpret_cast<int32_t*>(d + s->C);
-    k.flag = i;
-    k.iters = i + s->C;
-    k.status = i + 2 * s->C;
-    k.history = static_cast<double*>(s->d_hist);
-    return k;
-}
-
-bool overlap(const void* a, const void* b, size_t bytes) {
-    const char* x = static_cast<const char*>(a);
-    const char* y = static_cast<const char*>(b);
-    return x < y + bytes && y < x + bytes;
 }
 
 template <typename F>
@@ -94,14 +75,10 @@ int for_batches(const nufft_fista* s, FistaLaunch& a, void* const* x, const void
     return NUFFT_OK;
 }
 
-bool weight_ok(double v) { return std::isfinite(v) && v >= 0.0; }
-
 // nufft_fista_create (lp null) and nufft_fista_create_llr
 int create(nufft_fista** out, nufft_toeplitz* tz, const nufft_fista_params* params, const nufft_llr_params* lp, double nuc) {
     nufft_toeplitz_info ti;
-    std::memset(&ti, 0, sizeof(ti));
-    ti.struct_size = (int32_t)sizeof(ti);
-    int rc = nufft_toeplitz_get_info(tz, &ti);
+    int rc = toeplitz_info(tz, ti);
     if (rc) return rc;
     nufft_fista_params p;
     if ((rc = read_params(p, params, "nufft_fista_params"))) return rc;
@@ -150,24 +127,16 @@ int create(nufft_fista** out, nufft_toeplitz* tz, const nufft_fista_params* para
     s->array_bytes = (lp ? 2 : 3) * (int64_t)s->C * (int64_t)comp;      // the locally low-rank kernel needs no coefficient array
 
     DeviceGuard guard(s->device);
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device) == hipSuccess && cus > 0) s->num_cus = cus;
-    else (void)hipGetLastError();
+    s->num_cus = device_cus(s->device);
     s->G = fista_workgroups(s->dtype, s->n, s->num_cus);
     s->G0 = lp ? 1 : wavelet_level0_workgroups(s->wav);
     auto alloc = [&](void** ptr, size_t bytes) { return alloc_buffer(s->own_bytes, "FISTA", ptr, bytes); };
     if ((rc = alloc(&s->d_z, (size_t)s->C * comp)) || (rc = alloc(&s->d_q, (size_t)s->C * comp)) ||
-        (!lp && ((rc = alloc(&s->d_c, (size_t)s->C * comp)) || (rc = alloc(&s->d_mom, (size_t)s->C * s->G0 * 2 * sizeof(double))))) || (rc = alloc(&s->d_hist, hist_bytes(s))) ||
-        (rc = s->scal.create(s->own_bytes, "FISTA", scal_bytes(s), "hipHostMalloc of the solver's host mirror failed"))) {
+        (!lp && ((rc = alloc(&s->d_c, (size_t)s->C * comp)) || (rc = alloc(&s->d_mom, (size_t)s->C * s->G0 * 2 * sizeof(double))))) ||
+        (rc = create_outcome(s->own_bytes, "FISTA", s->scal, &s->d_hist, prox_scal_bytes(s->C), hist_bytes(s)))) {
         const std::string keep = nufft_last_error_message();
         release(s);
         return fail(rc, keep);
-    }
-    // a defined answer from nufft_fista_get_result / nufft_fista_history before the first solve
-    if (s->scal.zero() != hipSuccess || hipMemset(s->d_hist, 0xFF, hist_bytes(s)) != hipSuccess) {
-        (void)hipGetLastError();
-        release(s);
-        return fail(NUFFT_ERR_HIP, "hipMemset of the solver's scalars failed");
     }
     for (int c = 0; c < s->C; ++c) {
         s->ztab.push_back(static_cast<char*>(s->d_z) + (size_t)c * comp);
@@ -195,7 +164,7 @@ int solve_llr(nufft_fista* s, FistaLaunch& a, void* const* x, const void* const*
         l.out[c] = x[c];
     }
     const int64_t G = llr_workgroups(l);
-    const FistaScalars host = scalars_at(s, s->scal.host);
+    const ProxScalars host = prox_scalars_at(s->scal.host, s->C, nullptr);
     uint64_t state = llr_seed(s->llr);
     double t = 1.0;
     for (int it = 1; it <= s->max_iter; ++it) {
@@ -214,8 +183,9 @@ int solve_llr(nufft_fista* s, FistaLaunch& a, void* const* x, const void* const*
         if (e != hipSuccess) return fail(NUFFT_ERR_HIP, std::string("launch of a FISTA kernel: ") + hipGetErrorString(e));
         s->enqueued = it;
         if (s->check_every > 0 && it % s->check_every == 0 && it < s->max_iter) {
-            if ((rc = s->scal.fetch(stream))) return rc;
-            if (host.flag[0] != 0) break;
+            bool done;
+            if ((rc = all_done(s->scal, stream, host.flag, 1, &done))) return rc;
+            if (done) break;
         }
     }
     return NUFFT_OK;
@@ -299,28 +269,10 @@ int nufft_fista_get_info(const nufft_fista* s, nufft_fista_info* o) {
 
 int nufft_fista_solve(nufft_fista* s, void* const* x, const void* const* b, int use_x0, void* stream_) {
     if (!s) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
-    nufft_toeplitz_info ti;
-    std::memset(&ti, 0, sizeof(ti));
-    ti.struct_size = (int32_t)sizeof(ti);
-    int rc = nufft_toeplitz_get_info(s->tz, &ti);
-    if (rc) return rc;
-    if (!ti.has_spectrum)
-        return fail(NUFFT_ERR_NO_POINTS, "nufft_toeplitz_set_spectrum or nufft_toeplitz_set_points must be called before nufft_fista_solve");
-    if (!x || !b) return fail(NUFFT_ERR_INVALID_ARG, "null table");
-    const size_t bytes = (size_t)s->n * 2 * real_bytes(s->dtype);
-    for (int c = 0; c < s->C; ++c) {
-        if (!x[c] || !b[c]) return fail(NUFFT_ERR_INVALID_ARG, "null data vector");
-        if (((uintptr_t)x[c] | (uintptr_t)b[c]) & 15) return fail(NUFFT_ERR_INVALID_ARG, "x and b must be 16-byte aligned");
-    }
-    for (int c = 0; c < s->C; ++c)
-        for (int k = 0; k < s->C; ++k) {
-            if (overlap(x[c], b[k], bytes)) return fail(NUFFT_ERR_INVALID_ARG, "x overlaps b: the right-hand side is read while x is written");
-            if (k != c && overlap(x[c], x[k], bytes)) return fail(NUFFT_ERR_INVALID_ARG, "two components of x overlap");
-        }
     DeviceGuard guard(s->device);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (s->check_every > 0 && capturing(stream))
-        return fail(NUFFT_ERR_INVALID_ARG, "check_every > 0 synchronises the stream: not on a capturing stream (use check_every = 0)");
+    int rc = check_solve_args(s->tz, "nufft_fista_solve", s->C, s->n, s->dtype, x, b, s->check_every, stream);
+    if (rc) return rc;
 
     FistaLaunch a{};
     a.dtype = s->dtype;
@@ -338,14 +290,14 @@ int nufft_fista_solve(nufft_fista* s, void* const* x, const void* const* b, int 
     a.mom_part = static_cast<const double*>(s->d_mom);
     a.G0 = s->G0;
     if (s->wav) a.l1_part = wavelet_partials(s->wav, &a.P);
-    a.s = scalars_at(s, s->scal.dev);
+    a.s = prox_scalars_at(s->scal.dev, s->C, s->d_hist);
     for (int c = 0; c < s->C; ++c) s->thr[c] = s->step * s->l1[c];
 
     s->enqueued = 0;
     const bool warm = use_x0 != 0;
     if ((rc = for_batches(s, a, x, b, [&](const FistaLaunch& l) { return launch_fista_start(l, warm, stream); }))) return rc;
     if (s->llr) return solve_llr(s, a, x, b, stream);
-    const FistaScalars host = scalars_at(s, s->scal.host);
+    const ProxScalars host = prox_scalars_at(s->scal.host, s->C, nullptr);
     double t = 1.0;
     for (int it = 1; it <= s->max_iter; ++it) {
         a.it = it;
@@ -363,9 +315,8 @@ int nufft_fista_solve(nufft_fista* s, void* const* x, const void* const* b, int 
         if ((rc = for_batches(s, a, x, b, [&](const FistaLaunch& l) { return launch_fista_decide(l, stream); }))) return rc;
         s->enqueued = it;
         if (s->check_every > 0 && it % s->check_every == 0 && it < s->max_iter) {
-            if ((rc = s->scal.fetch(stream))) return rc;
-            bool all = true;
-            for (int c = 0; c < s->C; ++c) all = all && host.flag[c] != 0;
+            bool all;
+            if ((rc = all_done(s->scal, stream, host.flag, s->C, &all))) return rc;
             if (all) break;
         }
     }
@@ -376,28 +327,14 @@ int nufft_fista_get_result(nufft_fista* s, int32_t* iterations, int32_t* status,
     if (!s) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
     if (capacity < s->C) return fail(NUFFT_ERR_INVALID_ARG, "capacity is smaller than ntransforms");
     DeviceGuard guard(s->device);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (capturing(stream)) return fail(NUFFT_ERR_INVALID_ARG, "nufft_fista_get_result synchronises: not on a capturing stream");
-    int rc = s->scal.fetch(stream);
-    if (rc) return rc;
-    const FistaScalars host = scalars_at(s, s->scal.host);
-    for (int c = 0; c < s->C; ++c) {
-        if (iterations) iterations[c] = host.iters[c];
-        if (status) status[c] = host.status[c];
-        if (change) change[c] = host.change[c];
-    }
-    return NUFFT_OK;
+    return copy_result("nufft_fista_get_result", s->scal, s->C, s->C, 1, iterations, status, change, static_cast<hipStream_t>(stream_));
 }
 
 int nufft_fista_history(nufft_fista* s, double* host_out, int64_t capacity, void* stream_) {
     if (!s || !host_out) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
     if (capacity < (int64_t)s->max_iter * s->C * 2) return fail(NUFFT_ERR_INVALID_ARG, "capacity is smaller than max_iter * ntransforms * 2");
     DeviceGuard guard(s->device);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (capturing(stream)) return fail(NUFFT_ERR_INVALID_ARG, "nufft_fista_history synchronises: not on a capturing stream");
-    NUFFT_HIP(hipMemcpyAsync(host_out, s->d_hist, hist_bytes(s), hipMemcpyDeviceToHost, stream));
-    NUFFT_HIP(hipStreamSynchronize(stream));
-    return NUFFT_OK;
+    return fetch_history("nufft_fista_history", host_out, s->d_hist, hist_bytes(s), static_cast<hipStream_t>(stream_));
 }
 
 // Power iteration on what nufft_toeplitz_apply computes (header: largest eigenvalue).  Lives here, above the operator's public entry
@@ -406,9 +343,7 @@ int nufft_toeplitz_max_eigenvalue(nufft_toeplitz* tz, const void* const* v0, int
     if (!tz || !v0 || !out_host) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
     if (iters < 1) return fail(NUFFT_ERR_INVALID_ARG, "iters must be at least 1");
     nufft_toeplitz_info ti;
-    std::memset(&ti, 0, sizeof(ti));
-    ti.struct_size = (int32_t)sizeof(ti);
-    int rc = nufft_toeplitz_get_info(tz, &ti);
+    int rc = toeplitz_info(tz, ti);
     if (rc) return rc;
     if (ti.device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
     if (!ti.has_spectrum)
@@ -429,12 +364,7 @@ int nufft_toeplitz_max_eigenvalue(nufft_toeplitz* tz, const void* const* v0, int
     a.n = ti.N[0] * ti.N[1] * ti.N[2];
     const size_t rb = real_bytes(a.dtype), bytes = (size_t)a.n * 2 * rb, comp = padded(bytes);
     a.stride = (int64_t)(comp / rb);
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ti.device) != hipSuccess || cus <= 0) {
-        (void)hipGetLastError();
-        cus = 256;
-    }
-    a.G = fista_workgroups(a.dtype, a.n, cus);
+    a.G = fista_workgroups(a.dtype, a.n, device_cus(ti.device));
     int64_t own = 0;
     void* d_part = nullptr;
     void* d_rho = nullptr;

@@ -5,19 +5,11 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "solver_decide.h"
+
 namespace nufft {
 
 constexpr int kFistaBatch = 8;       // components per launch (gridDim.y): the callers' pointers travel as kernel arguments
-
-// Scalars of the solver on the device, per component, FP64.  The decision kernel is the only writer after the start, and it is a launch
-// of its own: every other kernel of an iteration only reads the flags.
-struct FistaScalars {
-    double* change;     // [C]   ‖x⁺ − x‖ / ‖x⁺‖ after the last iteration that changed the component
-    int32_t* flag;      // [C]   done (frozen)
-    int32_t* iters;     // [C]
-    int32_t* status;    // [C]   NUFFT_FISTA_*
-    double* history;    // [max_iter][C][2]   change, ‖D W x‖₁
-};
 
 struct FistaLaunch {
     int dtype;
@@ -37,7 +29,7 @@ struct FistaLaunch {
     int G0;
     const double* l1_part;   // [C][P]      Σ|stored detail| per workgroup of the analysis levels
     int P;
-    FistaScalars s;
+    ProxScalars s;           // one slot per component; history [max_iter][C][2]: change, ‖D W x‖₁
 };
 
 // z = x (warm) or x = z = 0;  scalars reset, NaN into the history

@@ -9,10 +9,17 @@
 
 #include "fista.h"
 #include "nufft_mi355x.h"
+#include "solver_decide.h"
 #include "stream_kernels.h"
 
 namespace nufft {
 using namespace stream;
+
+// one decision step for the three solvers (solver_decide.h)
+static_assert(NUFFT_FISTA_MAX_ITER == kProxMaxIter && NUFFT_FISTA_CONVERGED == kProxConverged && NUFFT_FISTA_BREAKDOWN == kProxBreakdown, "status values");
+static_assert(NUFFT_TVPD_MAX_ITER == kProxMaxIter && NUFFT_TVPD_CONVERGED == kProxConverged && NUFFT_TVPD_BREAKDOWN == kProxBreakdown, "status values");
+static_assert(NUFFT_LPS_MAX_ITER == kProxMaxIter && NUFFT_LPS_CONVERGED == kProxConverged && NUFFT_LPS_BREAKDOWN == kProxBreakdown, "status values");
+
 namespace {
 
 // z = x (WARM) or x = z = 0;  the first workgroup of a component resets its scalars and fills its history with NaN
@@ -39,20 +46,12 @@ __global__ __launch_bounds__(kThreads) void fista_start_kernel(FistaLaunch a) {
         }
     }
     if (blockIdx.x == 0) {
-        for (int it = threadIdx.x; it < a.max_iter; it += kThreads) {
-            a.s.history[((int64_t)it * a.C + c) * 2] = NAN;
-            a.s.history[((int64_t)it * a.C + c) * 2 + 1] = NAN;
-        }
-        if (threadIdx.x == 0) {
+        if (threadIdx.x == 0)
             for (int64_t e = npacks__ * W; e < nreal; ++e) {
                 if (!WARM) x[e] = T(0);
                 z[e] = WARM ? x[e] : T(0);
             }
-            a.s.change[c] = NAN;
-            a.s.flag[c] = 0;
-            a.s.iters[c] = 0;
-            a.s.status[c] = NUFFT_FISTA_MAX_ITER;
-        }
+        reset_outcome<2>(a.s, c, a.C, a.max_iter);
     }
 }
 
@@ -98,15 +97,9 @@ __global__ __launch_bounds__(kThreads) void fista_decide_kernel(FistaLaunch a) {
     const double xx = row_reduce<Sum>(mp + 1, rows * a.G0, 2, lds);
     const double l1 = row_reduce<Sum>(a.l1_part + (int64_t)sc * a.P, rows * a.P, 1, lds);
     if (threadIdx.x == 0) {
-        const double change = (dd == 0.0 && xx == 0.0) ? 0.0 : sqrt(dd / xx);
-        const bool bad = !isfinite(change);
-        const bool done = !bad && change <= a.tol;
-        a.s.change[c] = change;
-        a.s.history[((int64_t)(a.it - 1) * a.C + c) * 2] = change;
-        a.s.history[((int64_t)(a.it - 1) * a.C + c) * 2 + 1] = l1;
-        a.s.iters[c] = a.it;
-        a.s.status[c] = bad ? NUFFT_FISTA_BREAKDOWN : (done ? NUFFT_FISTA_CONVERGED : NUFFT_FISTA_MAX_ITER);
-        a.s.flag[c] = bad || done ? 1 : 0;
+        const int64_t row = ((int64_t)(a.it - 1) * a.C + c) * 2;
+        store_decision(a.s, c, row, dd, xx, a.tol, a.it);
+        a.s.history[row + 1] = l1;
     }
 }
 
@@ -124,19 +117,12 @@ __global__ __launch_bounds__(kThreads) void fista_decide_llr_kernel(FistaLaunch 
     dd = block_reduce<Sum>(dd, lds);
     xx = block_reduce<Sum>(xx, lds);
     nuc = block_reduce<Sum>(nuc, lds);
-    if (threadIdx.x == 0) {
-        const double change = (dd == 0.0 && xx == 0.0) ? 0.0 : sqrt(dd / xx);
-        const bool bad = !isfinite(change);
-        const bool done = !bad && change <= a.tol;
+    if (threadIdx.x == 0)
         for (int c = 0; c < a.C; ++c) {
-            a.s.change[c] = change;
-            a.s.history[((int64_t)(a.it - 1) * a.C + c) * 2] = change;
-            a.s.history[((int64_t)(a.it - 1) * a.C + c) * 2 + 1] = nuc;
-            a.s.iters[c] = a.it;
-            a.s.status[c] = bad ? NUFFT_FISTA_BREAKDOWN : (done ? NUFFT_FISTA_CONVERGED : NUFFT_FISTA_MAX_ITER);
-            a.s.flag[c] = bad || done ? 1 : 0;
+            const int64_t row = ((int64_t)(a.it - 1) * a.C + c) * 2;
+            store_decision(a.s, c, row, dd, xx, a.tol, a.it);
+            a.s.history[row + 1] = nuc;
         }
-    }
 }
 
 // partial sums of Re<v, g>, <v, v>, <g, g>

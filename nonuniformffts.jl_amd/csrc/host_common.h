@@ -1,6 +1,7 @@
-// Host helpers shared by the objects of the C ABI (plan.cpp, type3.cpp, toeplitz.cpp, cg.cpp, dcf.cpp): error reporting, the device
-// guard, device buffers counted into an object's own_bytes, the struct_size rule of the parameter and info structs, and the pinned
-// mirror of a block of device scalars.
+// Host helpers shared by the objects of the C ABI (plan.cpp, type3.cpp, toeplitz.cpp, coilmaps.cpp, wavelet.cpp, llr.cpp and, through
+// solver_common.h, the solvers): error reporting, the device guard, device buffers counted into an object's own_bytes, the
+// struct_size rule of the parameter and info structs, and the pinned mirror of a block of device scalars.  What only the iterative
+// solvers need (cg.cpp, fista.cpp, tv.cpp, lps.cpp, dcf.cpp, precond.cpp) is in solver_common.h, which includes this file.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -15,9 +15,9 @@
 #include <string>
 #include <vector>
 
-#include "host_common.h"
 #include "jacobi.h"
 #include "lps.h"
+#include "solver_common.h"
 #include "stream_kernels.h"
 
 using namespace nufft;
@@ -174,21 +174,9 @@ int tsparse_geometry(nufft_tsparse** out, int dtype, int D, const int64_t* N, in
     return NUFFT_OK;
 }
 
-int toeplitz_info(const nufft_toeplitz* tz, nufft_toeplitz_info& ti) {
-    std::memset(&ti, 0, sizeof(ti));
-    ti.struct_size = (int32_t)sizeof(ti);
-    return nufft_toeplitz_get_info(tz, &ti);
-}
-
 int real_plan() {
     return fail(NUFFT_ERR_UNSUPPORTED, "the low-rank plus sparse objects need a complex plan: their arrays are those of the Toeplitz normal operator, "
                                        "which a real-data plan cannot have");
-}
-
-bool overlap(const void* a, const void* b, size_t bytes) {
-    const char* x = static_cast<const char*>(a);
-    const char* y = static_cast<const char*>(b);
-    return x < y + bytes && y < x + bytes;
 }
 
 // C outputs and C inputs, 16-byte aligned; out[c] may be exactly in[c], nothing else may overlap
@@ -207,8 +195,6 @@ int check_tables(int C, int64_t n, int dtype, void* const* out, const void* cons
         }
     return NUFFT_OK;
 }
-
-bool weight_ok(double v) { return std::isfinite(v) && v >= 0.0; }
 
 GlrLaunch glr_template(const nufft_glr* g) {
     GlrLaunch a{};
@@ -260,17 +246,6 @@ int run_transform(nufft_tsparse* t, int mode, void* const* out, const void* cons
 }
 
 size_t hist_bytes(const nufft_lps* s) { return (size_t)s->max_iter * 3 * sizeof(double); }
-
-LpsScalars scalars_at(const nufft_lps* s, void* base) {
-    LpsScalars k{};
-    k.change = static_cast<double*>(base);
-    int32_t* i = reinterpret_cast<int32_t*>(k.change + 1);
-    k.flag = i;
-    k.iters = i + 1;
-    k.status = i + 2;
-    k.history = static_cast<double*>(s->d_hist);
-    return k;
-}
 
 }  // namespace
 
@@ -452,22 +427,15 @@ int nufft_lps_create(nufft_lps** out, nufft_toeplitz* tz, const nufft_lps_params
     s->array_bytes = 5 * (int64_t)s->C * (int64_t)comp;
 
     DeviceGuard guard(s->device);
-    int cus = 256;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device) != hipSuccess || cus <= 0) {
-        (void)hipGetLastError();
-        cus = 256;
-    }
-    s->G0 = (int)stream::grid_for(s->n, cus);
+    s->G0 = (int)stream::grid_for(s->n, device_cus(s->device));
     if ((rc = alloc_buffer(s->own_bytes, "L+S solver", &s->d_arrays, (size_t)5 * s->C * comp)) ||
-        (rc = alloc_buffer(s->own_bytes, "L+S solver", &s->d_hist, hist_bytes(s))) ||
-        (rc = s->scal.create(s->own_bytes, "L+S solver", sizeof(double) + 4 * sizeof(int32_t), "hipHostMalloc of the solver's host mirror failed"))) {
+        (rc = create_outcome(s->own_bytes, "L+S solver", s->scal, &s->d_hist, prox_scal_bytes(1), hist_bytes(s)))) {
         const std::string keep = nufft_last_error_message();
         release(s);
         return fail(rc, keep);
     }
-    // a defined answer from nufft_lps_get_result / nufft_lps_history / nufft_lps_get_parts before the first solve
-    if (s->scal.zero() != hipSuccess || hipMemset(s->d_hist, 0xFF, hist_bytes(s)) != hipSuccess ||
-        hipMemset(s->d_arrays, 0, (size_t)5 * s->C * comp) != hipSuccess) {
+    // a defined answer from nufft_lps_get_parts before the first solve
+    if (hipMemset(s->d_arrays, 0, (size_t)5 * s->C * comp) != hipSuccess) {
         (void)hipGetLastError();
         release(s);
         return fail(NUFFT_ERR_HIP, "hipMemset of the solver's arrays failed");
@@ -517,26 +485,10 @@ int nufft_lps_get_info(const nufft_lps* s, nufft_lps_info* o) {
 
 int nufft_lps_solve(nufft_lps* s, void* const* x, const void* const* b, int use_x0, void* stream_) {
     if (!s) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
-    nufft_toeplitz_info ti;
-    int rc = toeplitz_info(s->tz, ti);
-    if (rc) return rc;
-    if (!ti.has_spectrum)
-        return fail(NUFFT_ERR_NO_POINTS, "nufft_toeplitz_set_spectrum or nufft_toeplitz_set_points must be called before nufft_lps_solve");
-    if (!x || !b) return fail(NUFFT_ERR_INVALID_ARG, "null table");
-    const size_t bytes = (size_t)s->n * 2 * real_bytes(s->dtype);
-    for (int c = 0; c < s->C; ++c) {
-        if (!x[c] || !b[c]) return fail(NUFFT_ERR_INVALID_ARG, "null data vector");
-        if (((uintptr_t)x[c] | (uintptr_t)b[c]) & 15) return fail(NUFFT_ERR_INVALID_ARG, "x and b must be 16-byte aligned");
-    }
-    for (int c = 0; c < s->C; ++c)
-        for (int k = 0; k < s->C; ++k) {
-            if (overlap(x[c], b[k], bytes)) return fail(NUFFT_ERR_INVALID_ARG, "x overlaps b: the right-hand side is read while x is written");
-            if (k != c && overlap(x[c], x[k], bytes)) return fail(NUFFT_ERR_INVALID_ARG, "two components of x overlap");
-        }
     DeviceGuard guard(s->device);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (s->check_every > 0 && capturing(stream))
-        return fail(NUFFT_ERR_INVALID_ARG, "check_every > 0 synchronises the stream: not on a capturing stream (use check_every = 0)");
+    int rc = check_solve_args(s->tz, "nufft_lps_solve", s->C, s->n, s->dtype, x, b, s->check_every, stream);
+    if (rc) return rc;
 
     const int C = s->C;
     LpsSolve h{};
@@ -551,7 +503,7 @@ int nufft_lps_solve(nufft_lps* s, void* const* x, const void* const* b, int use_
     h.Gl = s->glr->tla.G;
     h.Gs = s->ts->tl.G;
     h.nuc = static_cast<const double*>(s->glr->d_words);
-    h.s = scalars_at(s, s->scal.dev);
+    h.s = prox_scalars_at(s->scal.dev, 1, s->d_hist);
     fill(h.x, x, C);
     fill(h.L, s->Ltab.data(), C);
     fill(h.S, s->Stab.data(), C);
@@ -586,7 +538,7 @@ int nufft_lps_solve(nufft_lps* s, void* const* x, const void* const* b, int use_
     s->enqueued = 0;
     hipError_t e = launch_lps_start(h, use_x0 != 0, stream);
     if (e != hipSuccess) return fail(NUFFT_ERR_HIP, std::string("launch of an L+S solver kernel: ") + hipGetErrorString(e));
-    const LpsScalars host = scalars_at(s, s->scal.host);
+    const ProxScalars host = prox_scalars_at(s->scal.host, 1, nullptr);
     double t = 1.0;
     for (int it = 1; it <= s->max_iter; ++it) {
         h.it = it;
@@ -602,8 +554,9 @@ int nufft_lps_solve(nufft_lps* s, void* const* x, const void* const* b, int use_
         if (e != hipSuccess) return fail(NUFFT_ERR_HIP, std::string("launch of an L+S solver kernel: ") + hipGetErrorString(e));
         s->enqueued = it;
         if (s->check_every > 0 && it % s->check_every == 0 && it < s->max_iter) {
-            if ((rc = s->scal.fetch(stream))) return rc;
-            if (host.flag[0] != 0) break;
+            bool done;
+            if ((rc = all_done(s->scal, stream, host.flag, 1, &done))) return rc;
+            if (done) break;
         }
     }
     e = launch_lps_sum(h, stream);                                                                                           // x = L + S
@@ -641,28 +594,14 @@ int nufft_lps_get_result(nufft_lps* s, int32_t* iterations, int32_t* status, dou
     if (!s) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
     if (capacity < s->C) return fail(NUFFT_ERR_INVALID_ARG, "capacity is smaller than ntransforms");
     DeviceGuard guard(s->device);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (capturing(stream)) return fail(NUFFT_ERR_INVALID_ARG, "nufft_lps_get_result synchronises: not on a capturing stream");
-    int rc = s->scal.fetch(stream);
-    if (rc) return rc;
-    const LpsScalars host = scalars_at(s, s->scal.host);
-    for (int c = 0; c < s->C; ++c) {
-        if (iterations) iterations[c] = host.iters[0];
-        if (status) status[c] = host.status[0];
-        if (change) change[c] = host.change[0];
-    }
-    return NUFFT_OK;
+    return copy_result("nufft_lps_get_result", s->scal, 1, s->C, 0, iterations, status, change, static_cast<hipStream_t>(stream_));
 }
 
 int nufft_lps_history(nufft_lps* s, double* host_out, int64_t capacity, void* stream_) {
     if (!s || !host_out) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
     if (capacity < (int64_t)s->max_iter * 3) return fail(NUFFT_ERR_INVALID_ARG, "capacity is smaller than max_iter * 3");
     DeviceGuard guard(s->device);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (capturing(stream)) return fail(NUFFT_ERR_INVALID_ARG, "nufft_lps_history synchronises: not on a capturing stream");
-    NUFFT_HIP(hipMemcpyAsync(host_out, s->d_hist, hist_bytes(s), hipMemcpyDeviceToHost, stream));
-    NUFFT_HIP(hipStreamSynchronize(stream));
-    return NUFFT_OK;
+    return fetch_history("nufft_lps_history", host_out, s->d_hist, hist_bytes(s), static_cast<hipStream_t>(stream_));
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "nufft_mi355x.h"
+#include "solver_decide.h"
 
 namespace nufft {
 
@@ -76,15 +77,6 @@ hipError_t launch_tsparse(const TsLaunch& a, hipStream_t stream);
 // out[0] = Σ_g part[g * 3 + 2], one workgroup, fixed order
 hipError_t launch_tsparse_sum(const double* part, int G, double* out, hipStream_t stream);
 
-// The solver's scalars: one system
-struct LpsScalars {
-    double* change;      // [1]
-    int32_t* flag;       // [1]
-    int32_t* iters;      // [1]
-    int32_t* status;     // [1]
-    double* history;     // [max_iter][3]
-};
-
 struct LpsSolve {
     int dtype, K, G;
     int64_t n;
@@ -94,7 +86,7 @@ struct LpsSolve {
     const double* part_s;        // [Gs][3] of the temporal kernel
     int Gl, Gs;
     const double* nuc;           // the eigen kernel's word
-    LpsScalars s;
+    ProxScalars s;               // one slot: the frames are one system; history [max_iter][3]: change, ‖C(L)‖_*, ‖T S‖₁
     LpsFrames x, L, S, zL, zS;
 };
 

@@ -23,9 +23,9 @@
 #include <string>
 #include <vector>
 
-#include "host_common.h"
 #include "kernels.h"
 #include "precond.h"
+#include "solver_common.h"
 #include "toeplitz.h"
 
 using namespace nufft;
@@ -470,9 +470,7 @@ int create(nufft_precond** out, nufft_toeplitz* tz, const nufft_precond_params* 
     p->path = fused ? NUFFT_PRECOND_PATH_FUSED : NUFFT_PRECOND_PATH_DENSE;
 
     DeviceGuard guard(p->device);
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device) == hipSuccess && cus > 0) p->num_cus = cus;
-    else (void)hipGetLastError();
+    p->num_cus = device_cus(p->device);
     if ((rc = build_device(p)) || (rc = build(p, nullptr))) {
         const std::string keep = nufft_last_error_message();
         release(p);

@@ -169,15 +169,7 @@ __global__ __launch_bounds__(kThreads) void lps_start_kernel(LpsSolve a) {
         S[i] = Cx<T>{T(0), T(0)};
         zS[i] = Cx<T>{T(0), T(0)};
     }
-    if (blockIdx.x == 0 && c == 0) {
-        for (int e = threadIdx.x; e < a.max_iter * 3; e += kThreads) a.s.history[e] = NAN;
-        if (threadIdx.x == 0) {
-            a.s.change[0] = NAN;
-            a.s.flag[0] = 0;
-            a.s.iters[0] = 0;
-            a.s.status[0] = NUFFT_LPS_MAX_ITER;
-        }
-    }
+    if (blockIdx.x == 0 && c == 0) reset_outcome<3>(a.s, 0, 1, a.max_iter);
 }
 
 // One workgroup: the change, the history row and the done flag of iteration a.it
@@ -190,18 +182,10 @@ __global__ __launch_bounds__(kThreads) void lps_decide_kernel(LpsSolve a) {
     const double xs = row_reduce<Sum>(a.part_s + 1, a.Gs, 3, lds);
     const double l1 = row_reduce<Sum>(a.part_s + 2, a.Gs, 3, lds);
     if (threadIdx.x == 0) {
-        const double dd = dl + ds, xx = xl + xs;
-        const double change = (dd == 0.0 && xx == 0.0) ? 0.0 : sqrt(dd / xx);
-        const bool bad = !isfinite(change);
-        const bool done = !bad && change <= a.tol;
-        a.s.change[0] = change;
-        double* row = a.s.history + (int64_t)(a.it - 1) * 3;
-        row[0] = change;
-        row[1] = a.nuc[0];
-        row[2] = l1;
-        a.s.iters[0] = a.it;
-        a.s.status[0] = bad ? NUFFT_LPS_BREAKDOWN : (done ? NUFFT_LPS_CONVERGED : NUFFT_LPS_MAX_ITER);
-        a.s.flag[0] = bad || done ? 1 : 0;
+        const int64_t row = (int64_t)(a.it - 1) * 3;
+        store_decision(a.s, 0, row, dl + ds, xl + xs, a.tol, a.it);
+        a.s.history[row + 1] = a.nuc[0];
+        a.s.history[row + 2] = l1;
     }
 }
 

@@ -39,7 +39,7 @@
 #include <string>
 #include <vector>
 
-#include "host_common.h"
+#include "solver_common.h"
 #include "stream_kernels.h"
 #include "tv.h"
 
@@ -164,12 +164,6 @@ TvLaunch launch_template(const nufft_tv* t) {
 // components per launch: the callers' pointers travel as kernel arguments, and gridDim.z = tiles[2] · components stays below 2^16
 int batch_of(const nufft_tv* t) { return std::max(1, std::min(kTvBatch, 65535 / t->tiles[2])); }
 
-bool overlap(const void* a, const void* b, size_t bytes) {
-    const char* x = static_cast<const char*>(a);
-    const char* y = static_cast<const char*>(b);
-    return x < y + bytes && y < x + bytes;
-}
-
 // `count` device pointers, 16-byte aligned
 int check_table(const void* const* tab, int count) {
     if (!tab) return fail(NUFFT_ERR_INVALID_ARG, "null table");
@@ -258,28 +252,7 @@ int check_temporal(const nufft_tv* t, int periodic) {
     return NUFFT_OK;
 }
 
-size_t scal_bytes(const nufft_tvpd* s) { return (size_t)s->C * (sizeof(double) + 3 * sizeof(int32_t)); }
 size_t hist_bytes(const nufft_tvpd* s) { return (size_t)s->max_iter * s->C * 2 * sizeof(double); }
-
-TvScalars scalars_at(const nufft_tvpd* s, void* base) {
-    TvScalars k{};
-    double* d = static_cast<double*>(base);
-    k.change = d;
-    int32_t* i = reinterpret_cast<int32_t*>(d + s->C);
-    k.flag = i;
-    k.iters = i + s->C;
-    k.status = i + 2 * s->C;
-    k.history = static_cast<double*>(s->d_hist);
-    return k;
-}
-
-bool weight_ok(double v) { return std::isfinite(v) && v >= 0.0; }
-
-int toeplitz_info(const nufft_toeplitz* tz, nufft_toeplitz_info& ti) {
-    std::memset(&ti, 0, sizeof(ti));
-    ti.struct_size = (int32_t)sizeof(ti);
-    return nufft_toeplitz_get_info(tz, &ti);
-}
 
 }  // namespace
 
@@ -455,27 +428,16 @@ int create_solver(nufft_tvpd** out, nufft_toeplitz* tz, const nufft_tvpd_params*
     }
 
     DeviceGuard guard(s->device);
-    int cus = 256;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device) != hipSuccess || cus <= 0) {
-        (void)hipGetLastError();
-        cus = 256;
-    }
-    s->G0 = stream::stream_workgroups((int64_t)(comp / 16), cus);
+    s->G0 = stream::stream_workgroups((int64_t)(comp / 16), device_cus(s->device));
     auto alloc = [&](void** ptr, size_t bytes) { return alloc_buffer(s->own_bytes, "TV solver", ptr, bytes); };
     const int64_t primal_rows = s->temporal && !s->spatial ? s->tv->Gt : s->tv->G;      // of the kernel that forms x⁺
     if ((rc = alloc(&s->d_q, (size_t)s->C * comp)) || (rc = alloc(&s->d_y, (size_t)s->C * s->nd * comp)) ||
-        (rc = alloc(&s->d_part, (size_t)s->C * primal_rows * 2 * sizeof(double))) || (rc = alloc(&s->d_hist, hist_bytes(s))) ||
+        (rc = alloc(&s->d_part, (size_t)s->C * primal_rows * 2 * sizeof(double))) ||
         (s->temporal && (rc = alloc(&s->d_part_t, (size_t)s->C * s->tv->Gt * sizeof(double)))) ||
-        (rc = s->scal.create(s->own_bytes, "TV solver", scal_bytes(s), "hipHostMalloc of the solver's host mirror failed"))) {
+        (rc = create_outcome(s->own_bytes, "TV solver", s->scal, &s->d_hist, prox_scal_bytes(s->C), hist_bytes(s)))) {
         const std::string keep = nufft_last_error_message();
         release(s);
         return fail(rc, keep);
-    }
-    // a defined answer from nufft_tvpd_get_result / nufft_tvpd_history before the first solve
-    if (s->scal.zero() != hipSuccess || hipMemset(s->d_hist, 0xFF, hist_bytes(s)) != hipSuccess) {
-        (void)hipGetLastError();
-        release(s);
-        return fail(NUFFT_ERR_HIP, "hipMemset of the solver's scalars failed");
     }
     for (int c = 0; c < s->C; ++c) s->qtab.push_back(static_cast<char*>(s->d_q) + (size_t)c * comp);
     *out = s;
@@ -558,26 +520,10 @@ int nufft_tvpd_get_info(const nufft_tvpd* s, nufft_tvpd_info* o) {
 
 int nufft_tvpd_solve(nufft_tvpd* s, void* const* x, const void* const* b, int use_x0, void* stream_) {
     if (!s) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
-    nufft_toeplitz_info ti;
-    int rc = toeplitz_info(s->tz, ti);
-    if (rc) return rc;
-    if (!ti.has_spectrum)
-        return fail(NUFFT_ERR_NO_POINTS, "nufft_toeplitz_set_spectrum or nufft_toeplitz_set_points must be called before nufft_tvpd_solve");
-    if (!x || !b) return fail(NUFFT_ERR_INVALID_ARG, "null table");
-    const size_t bytes = (size_t)s->n * 2 * real_bytes(s->dtype);
-    for (int c = 0; c < s->C; ++c) {
-        if (!x[c] || !b[c]) return fail(NUFFT_ERR_INVALID_ARG, "null data vector");
-        if (((uintptr_t)x[c] | (uintptr_t)b[c]) & 15) return fail(NUFFT_ERR_INVALID_ARG, "x and b must be 16-byte aligned");
-    }
-    for (int c = 0; c < s->C; ++c)
-        for (int k = 0; k < s->C; ++k) {
-            if (overlap(x[c], b[k], bytes)) return fail(NUFFT_ERR_INVALID_ARG, "x overlaps b: the right-hand side is read while x is written");
-            if (k != c && overlap(x[c], x[k], bytes)) return fail(NUFFT_ERR_INVALID_ARG, "two components of x overlap");
-        }
     DeviceGuard guard(s->device);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (s->check_every > 0 && capturing(stream))
-        return fail(NUFFT_ERR_INVALID_ARG, "check_every > 0 synchronises the stream: not on a capturing stream (use check_every = 0)");
+    int rc = check_solve_args(s->tz, "nufft_tvpd_solve", s->C, s->n, s->dtype, x, b, s->check_every, stream);
+    if (rc) return rc;
 
     const size_t rb = real_bytes(s->dtype), comp = (size_t)s->stride * rb;
     TvSolve h{};
@@ -593,7 +539,7 @@ int nufft_tvpd_solve(nufft_tvpd* s, void* const* x, const void* const* b, int us
     h.part_p = static_cast<const double*>(s->d_part);
     h.part_d = static_cast<const double*>(s->tv->d_part);
     h.P = s->tv->G;
-    h.s = scalars_at(s, s->scal.dev);
+    h.s = prox_scalars_at(s->scal.dev, s->C, s->d_hist);
     TvLaunch a = launch_template(s->tv);
     a.step = s->step;
     a.sigma = s->sigma;
@@ -667,7 +613,7 @@ int nufft_tvpd_solve(nufft_tvpd* s, void* const* x, const void* const* b, int us
     s->enqueued = 0;
     const bool warm = use_x0 != 0;
     if ((rc = for_batches([&]() { return launch_tv_start(h, warm, stream); }))) return rc;
-    const TvScalars host = scalars_at(s, s->scal.host);
+    const ProxScalars host = prox_scalars_at(s->scal.host, s->C, nullptr);
     for (int it = 1; it <= s->max_iter; ++it) {
         h.it = it;
         if ((rc = nufft_toeplitz_apply(s->tz, s->qtab.data(), const_cast<const void* const*>(x), stream))) return rc;      // q = G x
@@ -687,9 +633,8 @@ int nufft_tvpd_solve(nufft_tvpd* s, void* const* x, const void* const* b, int us
         } else if ((rc = for_batches([&]() { return launch_tv_decide(h, stream); }))) return rc;
         s->enqueued = it;
         if (s->check_every > 0 && it % s->check_every == 0 && it < s->max_iter) {
-            if ((rc = s->scal.fetch(stream))) return rc;
-            bool all = true;
-            for (int c = 0; c < s->C; ++c) all = all && host.flag[c] != 0;
+            bool all;
+            if ((rc = all_done(s->scal, stream, host.flag, s->C, &all))) return rc;
             if (all) break;
         }
     }
@@ -700,28 +645,14 @@ int nufft_tvpd_get_result(nufft_tvpd* s, int32_t* iterations, int32_t* status, d
     if (!s) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
     if (capacity < s->C) return fail(NUFFT_ERR_INVALID_ARG, "capacity is smaller than ntransforms");
     DeviceGuard guard(s->device);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (capturing(stream)) return fail(NUFFT_ERR_INVALID_ARG, "nufft_tvpd_get_result synchronises: not on a capturing stream");
-    int rc = s->scal.fetch(stream);
-    if (rc) return rc;
-    const TvScalars host = scalars_at(s, s->scal.host);
-    for (int c = 0; c < s->C; ++c) {
-        if (iterations) iterations[c] = host.iters[c];
-        if (status) status[c] = host.status[c];
-        if (change) change[c] = host.change[c];
-    }
-    return NUFFT_OK;
+    return copy_result("nufft_tvpd_get_result", s->scal, s->C, s->C, 1, iterations, status, change, static_cast<hipStream_t>(stream_));
 }
 
 int nufft_tvpd_history(nufft_tvpd* s, double* host_out, int64_t capacity, void* stream_) {
     if (!s || !host_out) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
     if (capacity < (int64_t)s->max_iter * s->C * 2) return fail(NUFFT_ERR_INVALID_ARG, "capacity is smaller than max_iter * ntransforms * 2");
     DeviceGuard guard(s->device);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (capturing(stream)) return fail(NUFFT_ERR_INVALID_ARG, "nufft_tvpd_history synchronises: not on a capturing stream");
-    NUFFT_HIP(hipMemcpyAsync(host_out, s->d_hist, hist_bytes(s), hipMemcpyDeviceToHost, stream));
-    NUFFT_HIP(hipStreamSynchronize(stream));
-    return NUFFT_OK;
+    return fetch_history("nufft_tvpd_history", host_out, s->d_hist, hist_bytes(s), static_cast<hipStream_t>(stream_));
 }
 
 }  // extern "C"

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "solver_decide.h"
+
 namespace nufft {
 
 constexpr int kTvBatch = 8;       // components per launch (gridDim.z / tiles of dimension 3): the pointers travel as kernel arguments
@@ -19,16 +21,6 @@ constexpr int tv_tile(bool f32, bool wide, int D, int d) {
     if (d == 1) return D == 2 ? 4 * kTvMarch : (D == 3 ? 4 : 1);
     return D == 3 ? kTvMarch : 1;
 }
-
-// Scalars of the solver on the device, per component, FP64 (the layout of the FISTA solver's).  tv_decide_kernel is the only writer
-// after the start, and it is a launch of its own.
-struct TvScalars {
-    double* change;     // [C]
-    int32_t* flag;      // [C]   done (frozen)
-    int32_t* iters;     // [C]
-    int32_t* status;    // [C]   NUFFT_TVPD_*
-    double* history;    // [max_iter][C][2]   change, Σ_i |(∇x⁺)_i|₂
-};
 
 enum TvMode { TV_PRIMAL = 0, TV_ADJOINT = 1, TV_DUAL = 2, TV_GRADIENT = 3, TV_NORM = 4 };
 
@@ -60,7 +52,7 @@ struct TvSolve {
     const double* part_p;         // [C][P][2]
     const double* part_d;         // [C][P]
     int64_t P;
-    TvScalars s;
+    ProxScalars s;                // one slot per component; history [max_iter][C][2]: change, Σ_i |(∇x⁺)_i|₂
 };
 
 // x = 0 unless warm;  y = 0;  scalars reset, NaN into the history
@@ -107,7 +99,7 @@ struct TvtDecide {
     const double* part_s;         // [C][Ps], null when the spatial term is off
     const double* part_t;         // [C][Pt]
     int64_t Pp, Ps, Pt;
-    TvScalars s;
+    ProxScalars s;
 };
 hipError_t launch_tvt_decide(const TvtDecide& a, hipStream_t stream);
 

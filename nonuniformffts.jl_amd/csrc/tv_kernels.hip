@@ -278,18 +278,7 @@ __global__ __launch_bounds__(kThreads) void tv_start_kernel(TvSolve a) {
         if (blockIdx.x == 0 && threadIdx.x == 0)
             for (int64_t e = npacks__ * W; e < nreal; ++e) x[e] = T(0);
     }
-    if (blockIdx.x == 0) {
-        for (int it = threadIdx.x; it < a.max_iter; it += kThreads) {
-            a.s.history[((int64_t)it * a.C + c) * 2] = NAN;
-            a.s.history[((int64_t)it * a.C + c) * 2 + 1] = NAN;
-        }
-        if (threadIdx.x == 0) {
-            a.s.change[c] = NAN;
-            a.s.flag[c] = 0;
-            a.s.iters[c] = 0;
-            a.s.status[c] = NUFFT_TVPD_MAX_ITER;
-        }
-    }
+    if (blockIdx.x == 0) reset_outcome<2>(a.s, c, a.C, a.max_iter);
 }
 
 // One workgroup per component: change, Σ_i |(∇x⁺)_i|₂, the history row and the done flag of iteration a.it.  Coupled components are one
@@ -305,15 +294,9 @@ __global__ __launch_bounds__(kThreads) void tv_decide_kernel(TvSolve a) {
     const double xx = row_reduce<Sum>(pp + 1, rows, 2, lds);
     const double tv = row_reduce<Sum>(a.part_d + (int64_t)sc * a.P, rows, 1, lds);
     if (threadIdx.x == 0) {
-        const double change = (dd == 0.0 && xx == 0.0) ? 0.0 : sqrt(dd / xx);
-        const bool bad = !isfinite(change);
-        const bool done = !bad && change <= a.tol;
-        a.s.change[c] = change;
-        a.s.history[((int64_t)(a.it - 1) * a.C + c) * 2] = change;
-        a.s.history[((int64_t)(a.it - 1) * a.C + c) * 2 + 1] = tv;
-        a.s.iters[c] = a.it;
-        a.s.status[c] = bad ? NUFFT_TVPD_BREAKDOWN : (done ? NUFFT_TVPD_CONVERGED : NUFFT_TVPD_MAX_ITER);
-        a.s.flag[c] = bad || done ? 1 : 0;
+        const int64_t row = ((int64_t)(a.it - 1) * a.C + c) * 2;
+        store_decision(a.s, c, row, dd, xx, a.tol, a.it);
+        a.s.history[row + 1] = tv;
     }
 }
 

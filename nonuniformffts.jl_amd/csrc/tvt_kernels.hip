@@ -145,15 +145,9 @@ __global__ __launch_bounds__(kThreads) void tvt_decide_kernel(TvtDecide a) {
     double ts = 0.0;
     if (a.part_s) ts = row_reduce<Sum>(a.part_s + (int64_t)c * a.Ps, (int)a.Ps, 1, lds);
     if (threadIdx.x == 0) {
-        const double change = (dd == 0.0 && xx == 0.0) ? 0.0 : sqrt(dd / xx);
-        const bool bad = !isfinite(change);
-        const bool done = !bad && change <= a.tol;
-        a.s.change[c] = change;
-        a.s.history[((int64_t)(a.it - 1) * a.C + c) * 2] = change;
-        a.s.history[((int64_t)(a.it - 1) * a.C + c) * 2 + 1] = a.part_s ? a.tv[k] * ts + a.tv_t * tt : a.tv_t * tt;
-        a.s.iters[c] = a.it;
-        a.s.status[c] = bad ? NUFFT_TVPD_BREAKDOWN : (done ? NUFFT_TVPD_CONVERGED : NUFFT_TVPD_MAX_ITER);
-        a.s.flag[c] = bad || done ? 1 : 0;
+        const int64_t row = ((int64_t)(a.it - 1) * a.C + c) * 2;
+        store_decision(a.s, c, row, dd, xx, a.tol, a.it);
+        a.s.history[row + 1] = a.part_s ? a.tv[k] * ts + a.tv_t * tt : a.tv_t * tt;
     }
 }
 

@@ -25,13 +25,14 @@ import torch
 
 from . import _lib
 from ._lib import lib
-from .plan import DimensionMismatch, _check, _ptr_table
+from ._solver import _ToeplitzSolver, _change, _doc
+from .plan import DimensionMismatch, _check
 from .toeplitz import ToeplitzOperator
 from .llr import _llr_params
 from .wavelet import _wavelet_id
 
 
-class ToeplitzFISTA:
+class ToeplitzFISTA(_ToeplitzSolver):
     """``ToeplitzFISTA(op, wavelet="db2", levels=3, l1=0.0, step=None, lam=0.0, maxiter=100, tol=1e-4, check_every=0)``.
 
     ``l1``: a scalar or one weight per component.  ``lam``: the Tikhonov weight (named as in :class:`ToeplitzCG`).  ``step``: the step
@@ -48,6 +49,9 @@ class ToeplitzFISTA:
     the objective then changes every iteration and the relative change does not fall to a small ``tol``: use ``tol=0`` and a fixed
     ``maxiter``.  ``wavelet``, ``levels`` and ``l1`` belong to ``prior="wavelet"`` (the default), ``block``, ``nuc``, ``shifts`` and
     ``seed`` to ``prior="llr"``; passing the other prior's arguments raises ``ValueError``."""
+
+    _prefix, _info, _status_names = "fista", _lib.NufftFistaInfo, _lib.FISTA_STATUS_NAMES
+    _columns = staticmethod(lambda n: (n, 2))
 
     def __init__(self, op: ToeplitzOperator, wavelet=None, levels=None, l1=None, step=None, lam: float = 0.0,
                  maxiter: int = 100, tol: float = 1e-4, check_every: int = 0, prior: str = "wavelet", block=None, nuc=None, shifts=None,
@@ -66,16 +70,13 @@ class ToeplitzFISTA:
                            maxiter, tol, check_every)
             return
         wavelet, levels, l1 = "db2" if wavelet is None else wavelet, 3 if levels is None else levels, 0.0 if l1 is None else l1
-        for name, v in (("maxiter", maxiter), ("check_every", check_every), ("levels", levels)):
-            if isinstance(v, bool) or not isinstance(v, int):
-                raise ValueError(f"{name} must be an integer")
+        self._check_ints(maxiter=maxiter, check_every=check_every, levels=levels)
         l1s = [float(l1)] * op.ntransforms if isinstance(l1, (int, float)) else [float(v) for v in l1]
         if len(l1s) != op.ntransforms:
             raise DimensionMismatch(f"wrong amount of l1 weights (expected {op.ntransforms})")
         wid = _wavelet_id(wavelet)
         if step is None:
-            op._require_gpu()
-            step = 1.0 / (1.05 * max(op.max_eigenvalue()) + float(lam))
+            step = self._default_step(op, lam)
         prm = _lib.NufftFistaParams()
         prm.struct_size = C.sizeof(_lib.NufftFistaParams)
         prm.max_iter, prm.check_every, prm.wavelet, prm.levels = maxiter, check_every, wid, levels
@@ -92,14 +93,11 @@ class ToeplitzFISTA:
             raise
 
     def _init_llr(self, op, block, nuc, shifts, seed, step, lam, maxiter, tol, check_every):
-        for name, v in (("maxiter", maxiter), ("check_every", check_every)):
-            if isinstance(v, bool) or not isinstance(v, int):
-                raise ValueError(f"{name} must be an integer")
+        self._check_ints(maxiter=maxiter, check_every=check_every)
         op._require_open()
         lp = _llr_params(op.ndim, block, shifts, seed)
         if step is None:
-            op._require_gpu()
-            step = 1.0 / (1.05 * max(op.max_eigenvalue()) + float(lam))
+            step = self._default_step(op, lam)
         prm = _lib.NufftFistaParams()
         prm.struct_size = C.sizeof(_lib.NufftFistaParams)
         prm.max_iter, prm.check_every = maxiter, check_every
@@ -124,87 +122,10 @@ class ToeplitzFISTA:
         _check(lib.nufft_fista_set_l1(self._handle, (C.c_double * len(l1s))(*l1s), len(l1s)))
         self.l1 = tuple(l1s)
 
-    def close(self):
-        h = getattr(self, "_handle", None)
-        if h is not None and h.value:
-            lib.nufft_fista_destroy(h)
-            self._handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _require_open(self):
-        """The library keeps a pointer to the operator: refuse to follow it once either object has been closed."""
-        if not self._handle.value:
-            raise ValueError("this ToeplitzFISTA has been closed")
-        if not self.op._handle.value:
-            raise ValueError("the ToeplitzOperator of this solver has been closed: the operator must outlive the solver")
-
-    def info(self) -> _lib.NufftFistaInfo:
-        self._require_open()
-        out = _lib.NufftFistaInfo()
-        out.struct_size = C.sizeof(_lib.NufftFistaInfo)
-        _check(lib.nufft_fista_get_info(self._handle, C.byref(out)))
-        return out
-
-    def solve(self, b, x0=None, out=None):
-        """``b``: a tensor of ``plan.shape`` or a tuple of ntransforms such tensors (only read).  ``x0``: starting guess (None = zero);
-        ``out``: where the solution goes (may be ``x0``; None = new tensors; never ``b``).  Returns ``out``."""
-        self._require_open()
-        op = self.op
-        op._require_gpu()
-        single = isinstance(b, torch.Tensor)
-        b_t = (b,) if single else tuple(b)
-        op._check_uniform(b_t, "right-hand side")
-        if out is None:
-            out_t = tuple(torch.empty_like(v) for v in b_t)
-            out = out_t[0] if single else out_t
-        else:
-            out_t = (out,) if isinstance(out, torch.Tensor) else tuple(out)
-            op._check_uniform(out_t, "output")
-        if x0 is not None:
-            x0_t = (x0,) if isinstance(x0, torch.Tensor) else tuple(x0)
-            op._check_uniform(x0_t, "starting guess")
-            for o, g in zip(out_t, x0_t):
-                if o.data_ptr() != g.data_ptr():
-                    o.copy_(g)
-        _check(lib.nufft_fista_solve(self._handle, _ptr_table(out_t), _ptr_table(b_t), 0 if x0 is None else 1, op._stream()))
-        return out
-
-    def _result(self):
-        self._require_open()
-        n = self.op.ntransforms
-        it, st, ch = (C.c_int32 * n)(), (C.c_int32 * n)(), (C.c_double * n)()
-        _check(lib.nufft_fista_get_result(self._handle, it, st, ch, n, self.op._stream()))
-        return list(it), list(st), list(ch)
-
-    @property
-    def iterations(self):
-        """Per component: iterations that changed it (synchronises the current stream)."""
-        return tuple(self._result()[0])
-
-    @property
-    def status(self):
-        """Per component: ``"converged"``, ``"max_iter"`` or ``"breakdown"`` (a relative change that is not finite)."""
-        return tuple(_lib.FISTA_STATUS_NAMES[s] for s in self._result()[1])
-
-    @property
-    def change(self):
-        """Per component: ``‖x⁺ − x‖ / ‖x⁺‖`` of the last iteration that changed it."""
-        return tuple(self._result()[2])
-
-    def history(self) -> torch.Tensor:
-        """``[max(iterations), ntransforms, 2]`` (host, float64): relative change and ``‖D W x‖₁`` (``prior="llr"``: the sum of the
-        blocks' nuclear norms) after every iteration; NaN where an iteration did not change the component."""
-        self._require_open()
-        n = self.op.ntransforms
-        buf = (C.c_double * (self.maxiter * n * 2))()
-        _check(lib.nufft_fista_history(self._handle, buf, len(buf), self.op._stream()))
-        rows = max(self.iterations)
-        return torch.tensor(list(buf), dtype=torch.float64).reshape(self.maxiter, n, 2)[:rows].clone()
+    change = _change
+    history = _doc(_ToeplitzSolver.history,
+                   """``[max(iterations), ntransforms, 2]`` (host, float64): relative change and ``‖D W x‖₁`` (``prior="llr"``: the sum of the
+        blocks' nuclear norms) after every iteration; NaN where an iteration did not change the component.""")
 
     def __repr__(self):
         i = self.info()

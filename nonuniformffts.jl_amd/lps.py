@@ -24,6 +24,7 @@ import torch
 
 from . import _lib
 from ._lib import lib
+from ._solver import _ToeplitzSolver, _change, _doc
 from .plan import DimensionMismatch, PlanNUFFT, _check, _ptr_table
 from .toeplitz import ToeplitzOperator
 
@@ -193,7 +194,7 @@ class TemporalSparsity(_FrameObject):
         return f"TemporalSparsity({self.transform!r}) on {self.ndim}-dimensional {self.Z} arrays of shape {self.shape} x {self.ntransforms} frames"
 
 
-class ToeplitzLPS:
+class ToeplitzLPS(_ToeplitzSolver):
     """``ToeplitzLPS(op, nuc, l1, transform="dft", momentum=True, step=None, lam=0.0, maxiter=100, tol=1e-4, check_every=0)``.
 
     ``nuc``, ``l1``: the weights of ``‖C(L)‖_*`` and ``‖T S‖₁``.  ``momentum=False`` is the scheme of Otazo, Candès & Sodickson.
@@ -202,18 +203,18 @@ class ToeplitzLPS:
     largest eigenvalue ``2 λ_max(A)``.  ``check_every`` as for :class:`ToeplitzFISTA`.  The frames are one system: one change, one
     status, reported identically for every component.  The solver keeps ``op`` alive; a new build of it between two solves is allowed."""
 
+    _prefix, _info, _status_names = "lps", _lib.NufftLpsInfo, _lib.LPS_STATUS_NAMES
+    _columns = staticmethod(lambda n: (3,))
+
     def __init__(self, op: ToeplitzOperator, nuc, l1, transform="dft", momentum: bool = True, step=None, lam: float = 0.0,
                  maxiter: int = 100, tol: float = 1e-4, check_every: int = 0):
         if not isinstance(op, ToeplitzOperator):
             raise ValueError("ToeplitzLPS takes a ToeplitzOperator")
-        for name, v in (("maxiter", maxiter), ("check_every", check_every)):
-            if isinstance(v, bool) or not isinstance(v, int):
-                raise ValueError(f"{name} must be an integer")
+        self._check_ints(maxiter=maxiter, check_every=check_every)
         tid = _transform_id(transform)
         op._require_open()
         if step is None:
-            op._require_gpu()
-            step = 1.0 / (2.0 * (1.05 * max(op.max_eigenvalue()) + float(lam)))
+            step = self._default_step(op, lam, factor=2.0)
         prm = _lib.NufftLpsParams()
         prm.struct_size = C.sizeof(_lib.NufftLpsParams)
         prm.max_iter, prm.check_every, prm.transform, prm.momentum = maxiter, check_every, tid, int(bool(momentum))
@@ -230,57 +231,13 @@ class ToeplitzLPS:
         _check(lib.nufft_lps_set_weights(self._handle, float(nuc), float(l1)))
         self.nuc, self.l1 = float(nuc), float(l1)
 
-    def close(self):
-        h = getattr(self, "_handle", None)
-        if h is not None and h.value:
-            lib.nufft_lps_destroy(h)
-            self._handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _require_open(self):
-        """The library keeps a pointer to the operator: refuse to follow it once either object has been closed."""
-        if not self._handle.value:
-            raise ValueError("this ToeplitzLPS has been closed")
-        if not self.op._handle.value:
-            raise ValueError("the ToeplitzOperator of this solver has been closed: the operator must outlive the solver")
-
-    def info(self) -> _lib.NufftLpsInfo:
-        self._require_open()
-        out = _lib.NufftLpsInfo()
-        out.struct_size = C.sizeof(_lib.NufftLpsInfo)
-        _check(lib.nufft_lps_get_info(self._handle, C.byref(out)))
-        return out
-
-    def solve(self, b, x0=None, out=None):
-        """``b``: a tensor of ``plan.shape`` or a tuple of ntransforms such tensors (only read).  ``x0``: starting guess for ``L``
+    solve = _doc(_ToeplitzSolver.solve,
+                 """``b``: a tensor of ``plan.shape`` or a tuple of ntransforms such tensors (only read).  ``x0``: starting guess for ``L``
         (None = zero; ``S`` always starts at zero); ``out``: where ``x = L + S`` goes (may be ``x0``; None = new tensors; never ``b``).
-        Returns ``out``."""
-        self._require_open()
-        op = self.op
-        op._require_gpu()
-        single = isinstance(b, torch.Tensor)
-        b_t = (b,) if single else tuple(b)
-        op._check_uniform(b_t, "right-hand side")
-        if out is None:
-            out_t = tuple(torch.empty_like(v) for v in b_t)
-            out = out_t[0] if single else out_t
-        else:
-            out_t = (out,) if isinstance(out, torch.Tensor) else tuple(out)
-            op._check_uniform(out_t, "output")
-        if x0 is not None:
-            x0_t = (x0,) if isinstance(x0, torch.Tensor) else tuple(x0)
-            op._check_uniform(x0_t, "starting guess")
-            for o, g in zip(out_t, x0_t):
-                if o.data_ptr() != g.data_ptr():
-                    o.copy_(g)
-        _check(lib.nufft_lps_solve(self._handle, _ptr_table(out_t), _ptr_table(b_t), 0 if x0 is None else 1, op._stream()))
+        Returns ``out``.""")
+
+    def _solved(self, b_t):
         self._like = b_t
-        return out
 
     def _parts(self, which):
         self._require_open()
@@ -302,35 +259,10 @@ class ToeplitzLPS:
         """``S`` of the last solve: a tuple of ntransforms new tensors."""
         return self._parts(1)
 
-    def _result(self):
-        self._require_open()
-        n = self.op.ntransforms
-        it, st, ch = (C.c_int32 * n)(), (C.c_int32 * n)(), (C.c_double * n)()
-        _check(lib.nufft_lps_get_result(self._handle, it, st, ch, n, self.op._stream()))
-        return list(it), list(st), list(ch)
-
-    @property
-    def iterations(self):
-        """Per component (all equal): iterations that changed the system (synchronises the current stream)."""
-        return tuple(self._result()[0])
-
-    @property
-    def status(self):
-        """Per component (all equal): ``"converged"``, ``"max_iter"`` or ``"breakdown"``."""
-        return tuple(_lib.LPS_STATUS_NAMES[s] for s in self._result()[1])
-
-    @property
-    def change(self):
-        """Per component (all equal): ``sqrt((‖L⁺−L‖² + ‖S⁺−S‖²) / (‖L⁺‖² + ‖S⁺‖²))`` of the last iteration that ran."""
-        return tuple(self._result()[2])
-
-    def history(self) -> torch.Tensor:
-        """``[iterations, 3]`` (host, float64): the change, ``‖C(L)‖_*`` and ``‖T S‖₁`` after every iteration."""
-        self._require_open()
-        buf = (C.c_double * (self.maxiter * 3))()
-        _check(lib.nufft_lps_history(self._handle, buf, len(buf), self.op._stream()))
-        rows = max(self.iterations)
-        return torch.tensor(list(buf), dtype=torch.float64).reshape(self.maxiter, 3)[:rows].clone()
+    iterations = _doc(_ToeplitzSolver.iterations, """Per component (all equal): iterations that changed the system (synchronises the current stream).""")
+    status = _doc(_ToeplitzSolver.status, """Per component (all equal): ``"converged"``, ``"max_iter"`` or ``"breakdown"``.""")
+    change = _doc(_change, """Per component (all equal): ``sqrt((‖L⁺−L‖² + ‖S⁺−S‖²) / (‖L⁺‖² + ‖S⁺‖²))`` of the last iteration that ran.""")
+    history = _doc(_ToeplitzSolver.history, """``[iterations, 3]`` (host, float64): the change, ``‖C(L)‖_*`` and ``‖T S‖₁`` after every iteration.""")
 
     def __repr__(self):
         i = self.info()

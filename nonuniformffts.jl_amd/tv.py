@@ -32,6 +32,7 @@ import torch
 
 from . import _lib
 from ._lib import lib
+from ._solver import _ToeplitzSolver, _change, _doc
 from .plan import DimensionMismatch, PlanNUFFT, _check, _ptr_table
 from .toeplitz import ToeplitzOperator
 
@@ -177,7 +178,7 @@ class TotalVariation:
                 f"{i.workspace_bytes / 1e3:.1f} kB")
 
 
-class ToeplitzTV:
+class ToeplitzTV(_ToeplitzSolver):
     """``ToeplitzTV(op, tv=0.0, step=None, sigma=None, lam=0.0, maxiter=100, tol=1e-4, check_every=0, tv_t=None, periodic_t=False,
     spatial=None)``.
 
@@ -197,13 +198,14 @@ class ToeplitzTV:
     of ``2 + D`` and ``set_tv`` with a non-zero weight is refused.  ``sigma=None`` is then ``1 / (8 n_d τ)`` with ``n_d = D + 1``
     (spatial term on) or ``1``."""
 
+    _prefix, _info, _status_names = "tvpd", _lib.NufftTvpdInfo, _lib.TVPD_STATUS_NAMES
+    _columns = staticmethod(lambda n: (n, 2))
+
     def __init__(self, op: ToeplitzOperator, tv=0.0, step=None, sigma=None, lam: float = 0.0, maxiter: int = 100, tol: float = 1e-4,
                  check_every: int = 0, tv_t=None, periodic_t: bool = False, spatial=None):
         if not isinstance(op, ToeplitzOperator):
             raise ValueError("ToeplitzTV takes a ToeplitzOperator")
-        for name, v in (("maxiter", maxiter), ("check_every", check_every)):
-            if isinstance(v, bool) or not isinstance(v, int):
-                raise ValueError(f"{name} must be an integer")
+        self._check_ints(maxiter=maxiter, check_every=check_every)
         op._require_open()
         tvs = _weights(tv, op.ntransforms)
         if len(tvs) != op.ntransforms:
@@ -211,8 +213,7 @@ class ToeplitzTV:
         if sigma is not None and not float(sigma) > 0.0:
             raise ValueError("sigma must be positive (None: 1 / (8 D step))")
         if step is None:
-            op._require_gpu()
-            step = 1.0 / (1.05 * max(op.max_eigenvalue()) + float(lam))
+            step = self._default_step(op, lam)
         prm = _lib.NufftTvpdParams()
         prm.struct_size = C.sizeof(_lib.NufftTvpdParams)
         prm.max_iter, prm.check_every = maxiter, check_every
@@ -265,87 +266,10 @@ class ToeplitzTV:
         self._require_open()
         _check(lib.nufft_tvpd_set_tv_t(self._handle, float(tv_t)))
 
-    def close(self):
-        h = getattr(self, "_handle", None)
-        if h is not None and h.value:
-            lib.nufft_tvpd_destroy(h)
-            self._handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _require_open(self):
-        """The library keeps a pointer to the operator: refuse to follow it once either object has been closed."""
-        if not self._handle.value:
-            raise ValueError("this ToeplitzTV has been closed")
-        if not self.op._handle.value:
-            raise ValueError("the ToeplitzOperator of this solver has been closed: the operator must outlive the solver")
-
-    def info(self) -> _lib.NufftTvpdInfo:
-        self._require_open()
-        out = _lib.NufftTvpdInfo()
-        out.struct_size = C.sizeof(_lib.NufftTvpdInfo)
-        _check(lib.nufft_tvpd_get_info(self._handle, C.byref(out)))
-        return out
-
-    def solve(self, b, x0=None, out=None):
-        """``b``: a tensor of ``plan.shape`` or a tuple of ntransforms such tensors (only read).  ``x0``: starting guess (None = zero);
-        ``out``: where the solution goes (may be ``x0``; None = new tensors; never ``b``).  Returns ``out``."""
-        self._require_open()
-        op = self.op
-        op._require_gpu()
-        single = isinstance(b, torch.Tensor)
-        b_t = (b,) if single else tuple(b)
-        op._check_uniform(b_t, "right-hand side")
-        if out is None:
-            out_t = tuple(torch.empty_like(v) for v in b_t)
-            out = out_t[0] if single else out_t
-        else:
-            out_t = (out,) if isinstance(out, torch.Tensor) else tuple(out)
-            op._check_uniform(out_t, "output")
-        if x0 is not None:
-            x0_t = (x0,) if isinstance(x0, torch.Tensor) else tuple(x0)
-            op._check_uniform(x0_t, "starting guess")
-            for o, g in zip(out_t, x0_t):
-                if o.data_ptr() != g.data_ptr():
-                    o.copy_(g)
-        _check(lib.nufft_tvpd_solve(self._handle, _ptr_table(out_t), _ptr_table(b_t), 0 if x0 is None else 1, op._stream()))
-        return out
-
-    def _result(self):
-        self._require_open()
-        n = self.op.ntransforms
-        it, st, ch = (C.c_int32 * n)(), (C.c_int32 * n)(), (C.c_double * n)()
-        _check(lib.nufft_tvpd_get_result(self._handle, it, st, ch, n, self.op._stream()))
-        return list(it), list(st), list(ch)
-
-    @property
-    def iterations(self):
-        """Per component: iterations that changed it (synchronises the current stream)."""
-        return tuple(self._result()[0])
-
-    @property
-    def status(self):
-        """Per component: ``"converged"``, ``"max_iter"`` or ``"breakdown"`` (a relative change that is not finite)."""
-        return tuple(_lib.TVPD_STATUS_NAMES[s] for s in self._result()[1])
-
-    @property
-    def change(self):
-        """Per component: ``‖x⁺ − x‖ / ‖x⁺‖`` of the last iteration that changed it."""
-        return tuple(self._result()[2])
-
-    def history(self) -> torch.Tensor:
-        """``[max(iterations), ntransforms, 2]`` (host, float64): relative change and ``Σ_i |(∇x)_i|₂`` after every iteration; NaN where
-        an iteration did not change the component."""
-        self._require_open()
-        n = self.op.ntransforms
-        buf = (C.c_double * (self.maxiter * n * 2))()
-        _check(lib.nufft_tvpd_history(self._handle, buf, len(buf), self.op._stream()))
-        rows = max(self.iterations)
-        return torch.tensor(list(buf), dtype=torch.float64).reshape(self.maxiter, n, 2)[:rows].clone()
+    change = _change
+    history = _doc(_ToeplitzSolver.history,
+                   """``[max(iterations), ntransforms, 2]`` (host, float64): relative change and ``Σ_i |(∇x)_i|₂`` after every iteration; NaN where
+        an iteration did not change the component.""")
 
     def __repr__(self):
         i = self.info()

@@ -307,3 +307,41 @@ def test_lifetime_and_arguments():
     sol.close()
     with pytest.raises(ValueError, match="closed"):
         sol.info()
+
+
+@pytest.mark.parametrize("Z", TYPES)
+def test_breakdown_freezes_one_component(Z):
+    """A NaN in one cell of b[1]: the reference's rule (fista_reference.fista: a change that is not finite is BREAKDOWN, and the iteration
+    that found it is the last) for that component alone; component 0 runs as if b[1] were finite.  Then the same solver on finite data:
+    the start kernel's reset leaves nothing behind."""
+    from nufft_pkg import nufft
+    L, lib = nufft._lib, nufft.lib
+    _, Zc, bar, _ = FC.dt(Z)
+    Ns = (16, 12)
+    s = FC.Analytic(Ns, seed=4 * sum(Ns))
+    plan = nufft.PlanNUFFT(Zc, Ns, backend=nufft.ROCBackend(0), ntransforms=2)
+    op = nufft.ToeplitzOperator(plan)
+    op.set_spectrum(_dev(s.spec.astype(Zc)))
+    plan.close()
+    good = [s.bs[0].astype(Zc), (0.4 * s.bs[1]).astype(Zc)]
+    bad = [good[0], good[1].copy()]
+    bad[1][5, 7] = np.nan
+    l1 = 0.3 * float(np.abs(W.forward(s.bs[0], "haar", 2)).max())
+    kw = dict(wavelet="haar", levels=2, l1=l1, step=FC.step(s), maxiter=4, tol=0.0)
+    fresh = nufft.ToeplitzFISTA(op, **kw)
+    xg, ig, sg, hg = _solve(fresh, good)
+    assert ig == (4, 4) and sg == ("max_iter", "max_iter") and np.isfinite(hg).all()
+    sol = nufft.ToeplitzFISTA(op, **kw)
+    xb, ib, sb, hb = _solve(sol, bad)
+    print(f"breakdown {Z}: iterations {ib}, status {sb}, history of component 1 {hb[:, 1, 0]}")
+    assert sb[1] == "breakdown" and ib[1] == 1 and np.isnan(hb[0, 1, 0]) and np.isnan(sol.change[1])
+    assert sb[0] == sg[0] and ib[0] == ig[0] and _same(hb[:, 0], hg[:, 0])
+    assert R.rel(xb[0], xg[0]) <= 10 * bar
+    full = (C.c_double * (4 * 2 * 2))()
+    assert lib.nufft_fista_history(sol._handle, full, len(full), op._stream()) == L.OK
+    assert np.isnan(np.array(full).reshape(4, 2, 2)[1:, 1]).all()                  # the frozen component writes no later row
+    x2, i2, s2, h2 = _solve(sol, good)                                             # a second solve on the solver that broke down
+    assert i2 == ig and s2 == sg and _same(h2, hg) and all(np.array_equal(u, v) for u, v in zip(x2, xg))
+    sol.close()
+    fresh.close()
+    op.close()

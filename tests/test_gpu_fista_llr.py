@@ -16,6 +16,8 @@ Bars:
     reference at test time (1.0e-7 ... 1.9e-7); iterations <= 1.1 × the reference's + 2 (the reference: 321 / 325 at (48, 40) K = 2,
     640 / 673 at K = 4, 368 / 387 at (16, 16, 8) K = 3, ComplexF64 / ComplexF32; the GPU takes the same counts except 674 for 673).
 """
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -312,3 +314,37 @@ def test_arguments_and_lifetime():
     sol.close()
     with pytest.raises(ValueError, match="closed"):
         sol.info()
+
+
+@pytest.mark.parametrize("Z", TYPES)
+def test_breakdown_freezes_the_system(Z):
+    """A NaN in one cell of b[1]: the frames are one system, so the reference's rule (llr_reference.fista_llr: a change that is not finite is
+    BREAKDOWN, and the iteration that found it is the last) holds for every frame.  Then the same solver on finite data: the start kernel's
+    reset leaves nothing behind."""
+    from nufft_pkg import nufft
+    Ns, K, block = (16, 12), 3, (4, 4)
+    s = FC.Analytic(Ns, seed=4 * sum(Ns))
+    Zc = LC.CTYPE[Z]
+    plan = nufft.PlanNUFFT(Zc, Ns, backend=nufft.ROCBackend(0), ntransforms=K)
+    op = nufft.ToeplitzOperator(plan)
+    op.set_spectrum(_dev(s.spec.astype(Zc)))
+    plan.close()
+    good = np.stack([s.apply(v) for v in LC.low_rank_input(Ns, K)]).astype(Zc)
+    kw = dict(prior="llr", block=block, nuc=0.2 * float(L.block_singular_values(good, block).max()), step=FC.step(s), maxiter=4, tol=0.0)
+    bad = good.copy()
+    bad[1, 5, 7] = np.nan
+    fresh = nufft.ToeplitzFISTA(op, **kw)
+    xg, ig, sg, hg = _solve(fresh, good)
+    assert ig == (4,) * 3 and sg == ("max_iter",) * 3 and np.isfinite(hg).all()
+    sol = nufft.ToeplitzFISTA(op, **kw)
+    _, ib, sb, hb = _solve(sol, bad)
+    print(f"breakdown {Z}: iterations {ib}, status {sb}, history {hb.tolist()}")
+    assert sb == ("breakdown",) * 3 and ib == (1,) * 3 and np.isnan(sol.change).all() and np.isnan(hb[0, :, 0]).all()
+    full = (C.c_double * (4 * 3 * 2))()
+    assert nufft.lib.nufft_fista_history(sol._handle, full, len(full), op._stream()) == nufft._lib.OK
+    assert np.isnan(np.array(full).reshape(4, -1)[1:]).all()                       # the frozen system writes no later row
+    x2, i2, s2, h2 = _solve(sol, good)                                      # a second solve on the solver that broke down
+    assert i2 == ig and s2 == sg and _same(h2, hg) and np.array_equal(x2, xg)
+    sol.close()
+    fresh.close()
+    op.close()

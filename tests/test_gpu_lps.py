@@ -10,6 +10,8 @@ Bars:
     363 with momentum and 488 without), the float64 fixed-point residual of the GPU's (L, S) <= 3 × the reference's own, taken from the
     reference at test time.
 """
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -280,3 +282,35 @@ def test_arguments_and_lifetime():
     sol.close()
     with pytest.raises(ValueError, match="closed"):
         sol.info()
+
+
+@pytest.mark.parametrize("Z", TYPES)
+def test_breakdown_freezes_the_system(Z):
+    """A NaN in one cell of b[1]: the frames are one system, so the reference's rule (lps_reference.lps: a change that is not finite is
+    BREAKDOWN, and the iteration that found it is the last) holds for every frame.  Then the same solver on finite data: the start kernel's
+    reset leaves nothing behind."""
+    from nufft_pkg import nufft
+    Ns, K = (16, 12), 3
+    c = LC.Case(Ns, K)
+    op = c.s.operator(nufft, Z)
+    good = c.b.astype(LC.dt(Z)[1])
+    nuc, l1 = c.weights("dft")
+    make = lambda: nufft.ToeplitzLPS(op, nuc, l1, step=c.step(), maxiter=4, tol=0.0)      # noqa: E731
+    run = lambda sol, b: (lambda g: (g, g["iterations"], g["status"], g["history"]))(_solve(sol, b))      # noqa: E731
+    bad = good.copy()
+    bad[1, 5, 7] = np.nan
+    fresh = make()
+    gg, ig, sg, hg = run(fresh, good)
+    assert ig == (4,) * 3 and sg == ("max_iter",) * 3 and np.isfinite(hg).all()
+    sol = make()
+    _, ib, sb, hb = run(sol, bad)
+    print(f"breakdown {Z}: iterations {ib}, status {sb}, history {hb.tolist()}")
+    assert sb == ("breakdown",) * 3 and ib == (1,) * 3 and np.isnan(sol.change).all() and np.isnan(hb[0, 0]).all()
+    full = (C.c_double * (4 * 3))()
+    assert nufft.lib.nufft_lps_history(sol._handle, full, len(full), op._stream()) == nufft._lib.OK
+    assert np.isnan(np.array(full).reshape(4, -1)[1:]).all()                       # the frozen system writes no later row
+    g2, i2, s2, h2 = run(sol, good)                                                # a second solve on the solver that broke down
+    assert i2 == ig and s2 == sg and _same(h2, hg) and all(np.array_equal(g2[k], gg[k]) for k in ("x", "L", "S"))
+    sol.close()
+    fresh.close()
+    op.close()

@@ -11,6 +11,8 @@ Bars:
     with the reference's z as the certificate (the library keeps its own to itself).  ComplexF32 with tol = 1e-4 stops within one
     iteration of its reference (40; 1.078e-4 / 0.911e-4).
 """
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -340,3 +342,34 @@ def test_arguments_and_the_spatial_switch():
             call(u)
     tvop.close()
     one.close()
+
+
+@pytest.mark.parametrize("Z", TYPES)
+def test_breakdown_freezes_the_system(Z):
+    """A NaN in one cell of b[1]: the frames are one system, so the reference's rule (tvt_reference.tvpd_t: a change that is not finite is
+    BREAKDOWN, and the iteration that found it is the last) holds for every frame.  Then the same solver on finite data: the start kernel's
+    reset leaves nothing behind."""
+    from nufft_pkg import nufft
+    Ns, K = (16, 12), 3
+    s = TC.Frames(Ns, K)
+    op = s.operator(nufft, Z)
+    good = s.b.astype(TC.dt(Z)[1])
+    top = float(np.abs(s.b).max())
+    kw = dict(tv=0.1 * top, tv_t=0.1 * top, step=s.step(), maxiter=4, tol=0.0)
+    bad = good.copy()
+    bad[1, 5, 7] = np.nan
+    fresh = nufft.ToeplitzTV(op, **kw)
+    xg, ig, sg, hg = _solve(fresh, good)
+    assert ig == (4,) * 3 and sg == ("max_iter",) * 3 and np.isfinite(hg).all()
+    sol = nufft.ToeplitzTV(op, **kw)
+    _, ib, sb, hb = _solve(sol, bad)
+    print(f"breakdown {Z}: iterations {ib}, status {sb}, history {hb.tolist()}")
+    assert sb == ("breakdown",) * 3 and ib == (1,) * 3 and np.isnan(sol.change).all() and np.isnan(hb[0, :, 0]).all()
+    full = (C.c_double * (4 * 3 * 2))()
+    assert nufft.lib.nufft_tvpd_history(sol._handle, full, len(full), op._stream()) == nufft._lib.OK
+    assert np.isnan(np.array(full).reshape(4, -1)[1:]).all()                       # the frozen system writes no later row
+    x2, i2, s2, h2 = _solve(sol, good)                                      # a second solve on the solver that broke down
+    assert i2 == ig and s2 == sg and _same(h2, hg) and np.array_equal(x2, xg)
+    sol.close()
+    fresh.close()
+    op.close()
