@@ -1598,6 +1598,104 @@ int nufft_coilmaps_last_sweeps(nufft_coilmaps* h, int32_t* sweeps_out, void* str
 int64_t nufft_sizeof_coilmaps_params(void);
 int64_t nufft_sizeof_coilmaps_info(void);
 
+/* ---- Coil compression and noise pre-whitening ----
+ * The principal components of the coil covariance (Huang et al., MRI 2008; Buehrer et al., MRM 2007): C = ncoils physical coils become
+ * V <= C virtual coils, the first stage of a parallel-imaging reconstruction.  Added after ABI 104 without changing
+ * NUFFT_MI355X_VERSION: detect by symbol (dlsym nufft_coilcomp_create) and compare nufft_sizeof_coilcomp_info() with your own.
+ *
+ * The object knows the element type (complex of NUFFT_F32 / NUFFT_F64), 1 <= C <= 64 and the device.  It needs no plan: every call takes
+ * tables of C device vectors of n >= 1 complex elements, each vector 16-byte aligned, and n may differ from call to call (sample
+ * vectors, coil images and maps all pass through the same entries).
+ *
+ *     R[c, c'] = Σ_j h_j y_c[j] conj(y_c'[j])        h: optional real weights (NULL = ones).  Every product and sum is FP64 for both
+ *                                                    element types, in one fixed order: within a tile of samples, then the tiles of a
+ *                                                    workgroup, then the workgroups; no atomics.  Accumulated over every
+ *                                                    nufft_coilcomp_accumulate since the last reset, each call added to R in stream order
+ *                                                    (two sets accumulated one after the other give the same bits in every run, not
+ *                                                    necessarily those of the concatenated vector)
+ *     Ψ = L L^H,  W = L^-1                           on the host, FP64 (nufft_coilcomp_set_noise_covariance; W = I without)
+ *     R~ = W R W^H                                   skipped bit-exactly when no noise covariance is set
+ *     R~ = U Λ U^H                                   the cyclic Jacobi of the low-rank maps, with its constants; eigenvalues sorted
+ *                                                    descending (ties: the lower original index first); every eigenvector scaled back
+ *                                                    to unit length, its entry of largest modulus (lowest index on a tie) real and
+ *                                                    positive
+ *     A = U^H W                                      all C rows; row v is virtual coil v.  A zero Gram matrix gives A = W, λ = 0
+ *     out_v[j] = Σ_c A[v, c] in_c[j]                 FP64 in coil order, rounded once to the element type
+ *
+ * R, A (complex double, row-major), λ (double[C]), the sweep count and a status word stay on the device.  reset, accumulate, finish and
+ * apply allocate nothing, never synchronise and are hipGraph-capture safe; two runs and a replayed graph give the same bits.  One call at
+ * a time per object. */
+typedef struct nufft_coilcomp nufft_coilcomp; /* opaque */
+
+#define NUFFT_COILCOMP_OK 0          /* status of the last finish                                                                   */
+#define NUFFT_COILCOMP_SWEEPS 1      /* the Jacobi ran into its sweep cap                                                           */
+#define NUFFT_COILCOMP_NONFINITE 2   /* an eigenvalue is not finite (the data were not): A holds U^H W in the Jacobi's own order    */
+
+typedef struct nufft_coilcomp_info {
+    int32_t struct_size;     /* sizeof(nufft_coilcomp_info) of the caller's header, set before the call (0 = this layout)          */
+    int32_t dtype, ncoils, device;
+    int32_t threads;         /* of a workgroup of the Gram kernel                                                                  */
+    int32_t tile_samples;    /* samples of one tile in LDS                                                                         */
+    int32_t segments;        /* parts of a tile that are summed side by side                                                       */
+    int32_t pairs;           /* C (C + 1) / 2 entries of the upper triangle                                                        */
+    int32_t pairs_per_thread; /* entries one thread owns, at most 9                                                                */
+    int32_t max_workgroups;  /* cap of the Gram kernel's grid = partial sets the object holds                                      */
+    int32_t apply_chunk;     /* virtual coils per apply launch; the inputs are read once per chunk                                 */
+    int32_t jacobi_team_lanes;
+    int32_t jacobi_sweeps_max;
+    int32_t lds_bytes_gram, lds_bytes_eigen;   /* of one workgroup                                                                 */
+    int32_t matrix_rows;     /* rows of the matrix apply uses: 0 before the first finish / set_matrix                              */
+    int32_t has_noise;
+    int32_t reserved;
+    int64_t n;               /* the vector length these numbers are for                                                            */
+    int64_t tiles;           /* ceil(n / tile_samples)                                                                             */
+    int64_t tiles_per_workgroup;
+    int64_t workgroups;      /* of the Gram kernel for this n                                                                      */
+    int64_t workspace_bytes; /* device bytes owned: max_workgroups sets of partials, R, W, W R W^H, U^H and A with 16 spare rows  */
+} nufft_coilcomp_info;
+
+/* dtype: the real type of the complex vectors.  Refusals, in order: a null argument, an unknown dtype, ncoils < 1
+ * NUFFT_ERR_INVALID_ARG; ncoils > 64 NUFFT_ERR_UNSUPPORTED; device < 0 NUFFT_ERR_NO_DEVICE. */
+int nufft_coilcomp_create(nufft_coilcomp** out, int dtype, int32_t ncoils, int device);
+int nufft_coilcomp_destroy(nufft_coilcomp* h);
+/* What an object of these arguments would do with vectors of n elements, without a device: the same checks in the same order (n < 1
+ * NUFFT_ERR_INVALID_ARG before the limit on ncoils), the same tiling and LDS bytes; device = -1. */
+int nufft_coilcomp_layout(int dtype, int32_t ncoils, int64_t n, nufft_coilcomp_info* out);
+/* Static facts, and the tiling of an accumulate of n elements; does not synchronise. */
+int nufft_coilcomp_get_info(const nufft_coilcomp* h, int64_t n, nufft_coilcomp_info* out);
+/* w_out = L^-1 of psi = L L^H, both ncoils x ncoils complex doubles (re, im), row-major, on the HOST; no device is touched.  Refusals,
+ * in order: a null argument, ncoils < 1 NUFFT_ERR_INVALID_ARG; ncoils > 64 NUFFT_ERR_UNSUPPORTED; an entry that is not finite, a
+ * matrix that is not Hermitian to 1e-12 max |psi|, a pivot that is not positive NUFFT_ERR_INVALID_ARG. */
+int nufft_coilcomp_whitening_matrix(int32_t ncoils, const double* psi, double* w_out);
+/* psi as above, or NULL to return to W = I.  Factors on the host (the refusals of nufft_coilcomp_whitening_matrix, before the device
+ * is touched) and uploads W: set-up, synchronises `stream` (never a capturing one).  Takes effect at the next finish. */
+int nufft_coilcomp_set_noise_covariance(nufft_coilcomp* h, const double* psi, void* stream);
+/* R = 0 (a memset node). */
+int nufft_coilcomp_reset(nufft_coilcomp* h, void* stream);
+/* R += the weighted Gram matrix of y[0 .. ncoils): a host table of device pointers.  weights: n reals of the element type on the
+ * device, or NULL.  The weights are NOT checked on the device: a negative weight is subtracted, a non-finite one spoils R.  A weight
+ * of exactly zero contributes exactly nothing.  Refusals: a null object or table, n < 1, a null or not 16-byte aligned vector,
+ * misaligned weights NUFFT_ERR_INVALID_ARG. */
+int nufft_coilcomp_accumulate(nufft_coilcomp* h, const void* const* y, const void* weights, int64_t n, void* stream);
+/* Whitening (when set), eigen-decomposition, A = U^H W: one launch of one workgroup without a noise covariance, three with. */
+int nufft_coilcomp_finish(nufft_coilcomp* h, void* stream);
+/* Installs rows x ncoils complex doubles from the HOST as the matrix of apply (for example one fitted on another scan), 1 <= rows <=
+ * ncoils; λ, the sweep count and the status keep what the last finish left.  Synchronises `stream` (never a capturing one).
+ * Refusals: a null argument, rows out of range, an entry that is not finite NUFFT_ERR_INVALID_ARG. */
+int nufft_coilcomp_set_matrix(nufft_coilcomp* h, const double* A_host, int32_t rows, void* stream);
+/* out[0 .. nvirtual), in[0 .. ncoils): host tables of device pointers to vectors of n elements, 1 <= nvirtual <= the rows of the
+ * matrix.  The inputs are only read, once per 16 virtual coils.  Refusals, before anything is enqueued: a null object or table, no
+ * finish or set_matrix yet, nvirtual out of range, n < 1, a null or not 16-byte aligned vector, an output that overlaps an input or
+ * another output NUFFT_ERR_INVALID_ARG. */
+int nufft_coilcomp_apply(nufft_coilcomp* h, void* const* out, int32_t nvirtual, const void* const* in, int64_t n, void* stream);
+/* Copies to the host: R and A as ncoils x ncoils complex doubles (rows of A behind those of a set_matrix are zero); λ as ncoils doubles
+ * with the sweep count and the NUFFT_COILCOMP_* status of the last finish (each output may be NULL).  They synchronise `stream` (never
+ * a capturing one); get_matrix is refused before the first finish / set_matrix. */
+int nufft_coilcomp_get_gram(nufft_coilcomp* h, double* host_out, void* stream);
+int nufft_coilcomp_get_matrix(nufft_coilcomp* h, double* host_out, void* stream);
+int nufft_coilcomp_get_spectrum(nufft_coilcomp* h, double* lambda_out, int32_t* sweeps_out, int32_t* status_out, void* stream);
+int64_t nufft_sizeof_coilcomp_info(void);
+
 /* ---- misc ----------------------------------------------------------------------------- */
 /* sizeof(nufft_params) / sizeof(nufft_info) of the library build: a binding that mirrors the structs by hand
  * (ctypes, Julia) compares them with its own layout before the first call. */

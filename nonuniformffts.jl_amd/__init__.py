@@ -27,6 +27,7 @@ from .tv import ToeplitzTV, TotalVariation  # noqa: F401
 from .lps import GlobalLowRank, TemporalSparsity, ToeplitzLPS  # noqa: F401
 from .dcf import DensityCompensation, density_weights  # noqa: F401
 from .coilmaps import CoilMapEstimator, calibration_weights, estimate_maps  # noqa: F401
+from .coilcomp import CoilCompressor, compress_coils  # noqa: F401
 from . import autograd  # noqa: F401
 
 __all__ = [
@@ -41,4 +42,5 @@ __all__ = [
     "GlobalLowRank", "TemporalSparsity", "ToeplitzLPS",
     "DensityCompensation", "density_weights",
     "CoilMapEstimator", "estimate_maps", "calibration_weights",
+    "CoilCompressor", "compress_coils",
 ]

@@ -280,6 +280,20 @@ class NufftCoilmapsInfo(C.Structure):
     ]
 
 
+class NufftCoilcompInfo(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("dtype", C.c_int32), ("ncoils", C.c_int32), ("device", C.c_int32), ("threads", C.c_int32),
+        ("tile_samples", C.c_int32), ("segments", C.c_int32), ("pairs", C.c_int32), ("pairs_per_thread", C.c_int32),
+        ("max_workgroups", C.c_int32), ("apply_chunk", C.c_int32), ("jacobi_team_lanes", C.c_int32), ("jacobi_sweeps_max", C.c_int32),
+        ("lds_bytes_gram", C.c_int32), ("lds_bytes_eigen", C.c_int32), ("matrix_rows", C.c_int32), ("has_noise", C.c_int32),
+        ("reserved", C.c_int32),
+        ("n", C.c_int64), ("tiles", C.c_int64), ("tiles_per_workgroup", C.c_int64), ("workgroups", C.c_int64), ("workspace_bytes", C.c_int64),
+    ]
+
+
+COILCOMP_OK, COILCOMP_SWEEPS, COILCOMP_NONFINITE = 0, 1, 2
+
+
 class NufftDcfParams(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int32), ("max_iter", C.c_int32), ("check_every", C.c_int32), ("normalize", C.c_int32),
@@ -496,6 +510,21 @@ SYMBOLS = {
     "nufft_coilmaps_last_sweeps": (C.c_int, [_P, C.POINTER(C.c_int32), _P]),
     "nufft_sizeof_coilmaps_params": (C.c_int64, []),
     "nufft_sizeof_coilmaps_info": (C.c_int64, []),
+    "nufft_coilcomp_create": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int32, C.c_int]),
+    "nufft_coilcomp_destroy": (C.c_int, [_P]),
+    "nufft_coilcomp_layout": (C.c_int, [C.c_int, C.c_int32, C.c_int64, C.POINTER(NufftCoilcompInfo)]),
+    "nufft_coilcomp_get_info": (C.c_int, [_P, C.c_int64, C.POINTER(NufftCoilcompInfo)]),
+    "nufft_coilcomp_whitening_matrix": (C.c_int, [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "nufft_coilcomp_set_noise_covariance": (C.c_int, [_P, C.POINTER(C.c_double), _P]),
+    "nufft_coilcomp_reset": (C.c_int, [_P, _P]),
+    "nufft_coilcomp_accumulate": (C.c_int, [_P, _PP, _P, C.c_int64, _P]),
+    "nufft_coilcomp_finish": (C.c_int, [_P, _P]),
+    "nufft_coilcomp_set_matrix": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int32, _P]),
+    "nufft_coilcomp_apply": (C.c_int, [_P, _PP, C.c_int32, _PP, C.c_int64, _P]),
+    "nufft_coilcomp_get_gram": (C.c_int, [_P, C.POINTER(C.c_double), _P]),
+    "nufft_coilcomp_get_matrix": (C.c_int, [_P, C.POINTER(C.c_double), _P]),
+    "nufft_coilcomp_get_spectrum": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
+    "nufft_sizeof_coilcomp_info": (C.c_int64, []),
     "nufft_sizeof_params": (C.c_int64, []),
     "nufft_sizeof_info": (C.c_int64, []),
     "nufft_strerror": (C.c_char_p, [C.c_int]),
@@ -535,7 +564,7 @@ def _load():
                          ("nufft_sizeof_tvt_params", NufftTvtParams), ("nufft_sizeof_glr_info", NufftGlrInfo),
                          ("nufft_sizeof_tsparse_info", NufftTsparseInfo), ("nufft_sizeof_lps_params", NufftLpsParams),
                          ("nufft_sizeof_lps_info", NufftLpsInfo), ("nufft_sizeof_coilmaps_params", NufftCoilmapsParams),
-                         ("nufft_sizeof_coilmaps_info", NufftCoilmapsInfo)):
+                         ("nufft_sizeof_coilmaps_info", NufftCoilmapsInfo), ("nufft_sizeof_coilcomp_info", NufftCoilcompInfo)):
         if getattr(lib, name)() != C.sizeof(mirror):
             raise ImportError(f"{LIB_PATH}: {name}() = {getattr(lib, name)()} but the ctypes mirror has {C.sizeof(mirror)} bytes "
                               "(include/nufft_mi355x.h and _lib.py disagree)")
