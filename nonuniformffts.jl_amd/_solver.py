@@ -1,5 +1,5 @@
 """What the solver classes on a :class:`ToeplitzOperator` share (:class:`ToeplitzCG`, :class:`ToeplitzFISTA`, :class:`ToeplitzTV`,
-:class:`ToeplitzLPS`): the life of the handle, ``solve`` and reading the outcome back.  The C ABI's solvers are shaped alike
+:class:`ToeplitzLPS`) on top of the handle of ``_handle.py``: ``solve`` and reading the outcome back.  The C ABI's solvers are shaped alike
 (``nufft_<prefix>_destroy / _get_info / _solve / _get_result / _history``), so a class states its prefix and the shape of its history."""
 from __future__ import annotations
 
@@ -9,7 +9,7 @@ import math
 
 import torch
 
-from ._lib import lib
+from ._handle import _HandleObject
 from .plan import _check, _ptr_table
 
 
@@ -25,15 +25,10 @@ def _doc(member, doc):
     return method
 
 
-class _ToeplitzSolver:
-    _prefix = None            # "cg": the entry points are lib.nufft_cg_*
-    _info = None              # the info struct of _lib
+class _ToeplitzSolver(_HandleObject):
     _status_names = None      # of _lib
     _start_row = 0            # 1: row 0 of the history is the start
     _columns = None           # n -> the shape of one history row
-
-    def _entry(self, name):
-        return getattr(lib, f"nufft_{self._prefix}_{name}")
 
     @staticmethod
     def _check_ints(**values):
@@ -47,31 +42,11 @@ class _ToeplitzSolver:
         op._require_gpu()
         return 1.0 / (factor * (1.05 * max(op.max_eigenvalue()) + float(lam)))
 
-    def close(self):
-        h = getattr(self, "_handle", None)
-        if h is not None and h.value:
-            self._entry("destroy")(h)
-            self._handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def _require_open(self):
         """The library keeps a pointer to the operator: refuse to follow it once either object has been closed."""
-        if not self._handle.value:
-            raise ValueError(f"this {type(self).__name__} has been closed")
+        super()._require_open()
         if not self.op._handle.value:
             raise ValueError("the ToeplitzOperator of this solver has been closed: the operator must outlive the solver")
-
-    def info(self):
-        self._require_open()
-        out = self._info()
-        out.struct_size = C.sizeof(self._info)
-        _check(self._entry("get_info")(self._handle, C.byref(out)))
-        return out
 
     def solve(self, b, x0=None, out=None):
         """``b``: a tensor of ``plan.shape`` or a tuple of ntransforms such tensors (only read).  ``x0``: starting guess (None = zero);

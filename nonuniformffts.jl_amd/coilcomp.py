@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._handle import _HandleObject
 from ._lib import lib
 from .plan import DimensionMismatch, PlanNUFFT, _check, _ptr_table
 from .toeplitz import ToeplitzOperator
@@ -37,11 +38,13 @@ def _dptr(m):
     return m.ctypes.data_as(C.POINTER(C.c_double))
 
 
-class CoilCompressor:
+class CoilCompressor(_HandleObject):
     """``CoilCompressor(Z, ncoils, device=None)`` with ``Z`` ``torch.complex64`` or ``torch.complex128`` (the current device when
     ``device`` is None), or ``CoilCompressor(plan_or_op, ncoils)``: element type and device of a complex ``PlanNUFFT`` or of a
     ``ToeplitzOperator`` (neither is kept).  ``1 <= ncoils <= 64``.  The object needs no shape: every call takes tensors of any shape,
     which are read as flat vectors."""
+
+    _prefix = "coilcomp"
 
     def __init__(self, Z_or_plan, ncoils: int, device=None):
         if isinstance(ncoils, bool) or not isinstance(ncoils, int):
@@ -71,25 +74,6 @@ class CoilCompressor:
         self._handle = C.c_void_p()
         _check(lib.nufft_coilcomp_create(C.byref(self._handle), _lib.F32 if Z == torch.complex64 else _lib.F64, ncoils, index))
         self.Z, self.T, self.device, self.ncoils = Z, _COMPLEX[Z], device, ncoils
-
-    def close(self):
-        h = getattr(self, "_handle", None)
-        if h is not None and h.value:
-            lib.nufft_coilcomp_destroy(h)
-            self._handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _require_open(self):
-        if not self._handle.value:
-            raise ValueError("this CoilCompressor has been closed")
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def info(self, n: int = 1) -> _lib.NufftCoilcompInfo:
         """Static facts, and the tiling of an ``accumulate`` of vectors of ``n`` elements."""

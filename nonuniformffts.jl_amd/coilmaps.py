@@ -19,6 +19,7 @@ import math
 import torch
 
 from . import _lib
+from ._handle import _HandleObject
 from ._lib import lib
 from .plan import DimensionMismatch, PlanNUFFT, _check, _ptr_table
 from .toeplitz import ToeplitzOperator
@@ -41,10 +42,12 @@ def _params(ndim: int, box, crop) -> _lib.NufftCoilmapsParams:
     return prm
 
 
-class CoilMapEstimator:
+class CoilMapEstimator(_HandleObject):
     """``CoilMapEstimator(plan_or_op, ncoils, box=5 | (b1, …, bD), crop=0.0)``: element type, shape and device are those of a complex
     ``PlanNUFFT`` or of a ``ToeplitzOperator`` (neither is kept; their ntransforms plays no part).  ``1 <= ncoils <= 32``; box sides are
     odd, ``1 <= b_d <= min(9, N_d)``.  With ``crop > 0`` the maps are set to exact zeros where ``λ1 < crop² · max λ1``."""
+
+    _prefix, _info = "coilmaps", _lib.NufftCoilmapsInfo
 
     def __init__(self, plan_or_op, ncoils: int, box=5, crop: float = 0.0):
         if not isinstance(plan_or_op, (PlanNUFFT, ToeplitzOperator)):
@@ -72,45 +75,6 @@ class CoilMapEstimator:
         # allocated here, so that estimate() itself allocates nothing but (without ``out``) the maps
         self.lambda1 = torch.empty(self.shape, dtype=self.T, device=self.device)
         self.lambda2 = torch.empty(self.shape, dtype=self.T, device=self.device)
-
-    def close(self):
-        h = getattr(self, "_handle", None)
-        if h is not None and h.value:
-            lib.nufft_coilmaps_destroy(h)
-            self._handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _require_open(self):
-        if not self._handle.value:
-            raise ValueError("this CoilMapEstimator has been closed")
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def info(self) -> _lib.NufftCoilmapsInfo:
-        self._require_open()
-        out = _lib.NufftCoilmapsInfo()
-        out.struct_size = C.sizeof(_lib.NufftCoilmapsInfo)
-        _check(lib.nufft_coilmaps_get_info(self._handle, C.byref(out)))
-        return out
-
-    def _check_arrays(self, us, what):
-        if len(us) != self.ncoils:
-            raise DimensionMismatch(f"wrong amount of {what} arrays (expected a tuple of {self.ncoils} arrays)")
-        for u in us:
-            if not isinstance(u, torch.Tensor) or u.device != self.device:
-                raise ValueError(f"{what} must be torch tensors on {self.device}")
-            if u.dtype != self.Z:
-                raise ValueError(f"{what} must have element type {self.Z} (got {u.dtype})")
-            if tuple(u.shape) != self.shape:
-                raise DimensionMismatch(f"wrong dimensions of {what} array (expected tensor shape {self.shape}, got {tuple(u.shape)})")
-            if not u.is_contiguous():
-                raise ValueError(f"{what} must be contiguous")
 
     def _phase(self, phase, images):
         """The reference vector as ncoils (re, im) pairs of doubles, or None for the library's default e_0."""
@@ -156,13 +120,13 @@ class CoilMapEstimator:
             images = tuple(images[c] for c in range(images.shape[0]))
         else:
             images = tuple(images)
-        self._check_arrays(images, "coil image")
+        self._check_arrays(images, "coil image", self.ncoils)
         images = tuple(a if a.data_ptr() % 16 == 0 else a.clone() for a in images)
         if out is None:
             out = tuple(torch.empty(self.shape, dtype=self.Z, device=self.device) for _ in range(self.ncoils))
         else:
             out = tuple(out)
-            self._check_arrays(out, "output")
+            self._check_arrays(out, "output", self.ncoils)
         p = self._phase(phase, images)
         _check(lib.nufft_coilmaps_estimate(self._handle, _ptr_table(out), _ptr_table(images), p, C.c_void_p(self.lambda1.data_ptr()),
                                            C.c_void_p(self.lambda2.data_ptr()), self._stream()))
@@ -173,7 +137,7 @@ class CoilMapEstimator:
         object (``maps``: its result).  Returns ``maps``.  Does not synchronise."""
         self._require_open()
         maps = tuple(maps)
-        self._check_arrays(maps, "map")
+        self._check_arrays(maps, "map", self.ncoils)
         _check(lib.nufft_coilmaps_apply_crop(self._handle, _ptr_table(maps), C.c_void_p(self.lambda1.data_ptr()), float(crop), self._stream()))
         return maps
 

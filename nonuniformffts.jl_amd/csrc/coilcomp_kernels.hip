@@ -4,8 +4,8 @@
 //     R[c, c'] = Σ_j h_j y_c[j] conj(y_c'[j])  (FP64)      R~ = W R W^H      R~ = U Λ U^H  (jacobi.h, FP64)      A = U^H W
 //     out_v[j] = Σ_c A[v, c] in_c[j]           (FP64, rounded once)
 //
-//   gram      flat over the n samples, the tile structure of glr_gram_kernel: a workgroup takes `tpw` consecutive tiles of TC samples x C
-//             coils into LDS, every entry i <= j of a tile is summed in sample order over S fixed segments, the segments are added in
+//   gram      flat over the n samples (FlatTiles and the Gram steps of hermitian.h): a workgroup takes `tpw` consecutive tiles of TC samples
+//             x C coils into LDS, every entry i <= j of a tile is summed in sample order over S fixed segments, the segments are added in
 //             segment order into the thread that owns the entry, tile after tile; a workgroup leaves C (C + 1) / 2 complex partials
 //             with plain stores.  The weight is multiplied into y_i where the product is formed.
 //   fold      one workgroup adds the partial sets in workgroup order and adds the sum to R.
@@ -21,7 +21,7 @@
 #include <cmath>
 
 #include "coilcomp.h"
-#include "jacobi.h"
+#include "hermitian.h"
 #include "stream_kernels.h"
 
 namespace nufft {
@@ -34,24 +34,12 @@ namespace {
 
 using namespace jacobi_team;
 
-size_t up16(size_t v) { return (v + 15) / 16 * 16; }
-
-// entry pr of the upper triangle, rows first: (0,0) (0,1) ... (0,C-1) (1,1) ...
-__device__ __forceinline__ void pair_of(int pr, int C, int& i, int& j) {
-    i = 0;
-    while (pr >= C - i) {
-        pr -= C - i;
-        ++i;
-    }
-    j = i + pr;
-}
-
 template <typename T>
 __global__ __launch_bounds__(kCcThreads) void cc_gram_kernel(CcGramLaunch a) {
     extern __shared__ __align__(16) unsigned char smem[];
-    const int C = a.C, TC = a.tl.TC, TCP = TC + 1, S = a.tl.S, np = C * (C + 1) / 2, tid = threadIdx.x;
-    int tcs = 0;
-    while ((1 << tcs) < TC) ++tcs;
+    const int C = a.C, S = a.tl.S, np = C * (C + 1) / 2, tid = threadIdx.x;
+    const FlatTiles ft(a.tl);
+    const int TC = ft.TC, TCP = ft.TCP;
     Cx<T>* data = reinterpret_cast<Cx<T>*>(smem);
     double* wl = reinterpret_cast<double*>(smem + a.tl.off_w);
     Cd* gp = reinterpret_cast<Cd*>(smem + a.tl.off_gp);                           // [segment][entry]
@@ -66,33 +54,17 @@ __global__ __launch_bounds__(kCcThreads) void cc_gram_kernel(CcGramLaunch a) {
     for (int m = 0; m < kCcPairsPerThread; ++m) acc[m] = Cd{0.0, 0.0};
     const T* h = static_cast<const T*>(a.weights);
     const int seg_len = TC / S;
-    const int64_t tile0 = (int64_t)blockIdx.x * a.tl.tpw, tile1 = min(tile0 + a.tl.tpw, a.tl.tiles);
-    for (int64_t tile = tile0; tile < tile1; ++tile) {
-        const int64_t s0 = tile << tcs;
-        const int ns = (int)min((int64_t)TC, a.n - s0);
-        for (int u = tid; u < (C << tcs); u += kCcThreads) {
-            const int c = u >> tcs, v = u & (TC - 1);
-            // samples beyond n add exact zeros: the load is clamped to the last sample and its value replaced (a conditional 16-byte
-            // load went through scratch memory)
-            const Cx<T> got = static_cast<const Cx<T>*>(a.y.p[c])[s0 + min(v, ns - 1)];
-            data[c * TCP + v] = Cx<T>{v < ns ? got.re : T(0), v < ns ? got.im : T(0)};
-        }
+    for (int64_t tile = ft.tile0; tile < ft.tile1; ++tile) {
+        const int64_t s0 = ft.first_cell(tile);
+        const int ns = ft.cells(tile, a.n);
+        stage_padded<kCcThreads>(data, ft, C, s0, ns, [&](int c, int64_t at, bool) { return static_cast<const Cx<T>*>(a.y.p[c])[at]; });
         for (int v = tid; v < TC; v += kCcThreads) wl[v] = v < ns ? (h ? (double)h[s0 + v] : 1.0) : 0.0;
         __syncthreads();
         for (int u = tid; u < S * np; u += kCcThreads) {
             const int pr = u % np, seg = u / np;
             const int i = ij[pr] >> 8, j = ij[pr] & 255;
-            const Cx<T>* yi = data + i * TCP + seg * seg_len;
-            const Cx<T>* yj = data + j * TCP + seg * seg_len;
-            const double* ws = wl + seg * seg_len;
-            double hr = 0.0, hi = 0.0;
-            for (int v = 0; v < seg_len; ++v) {
-                const double w = ws[v];
-                const double ar = w * (double)yi[v].re, ai = w * (double)yi[v].im, br = (double)yj[v].re, bi = (double)yj[v].im;
-                hr += ar * br + ai * bi;
-                hi += ai * br - ar * bi;
-            }
-            gp[u] = Cd{hr, hi};
+            // Σ h y_i conj(y_j): the conjugate is on the other factor than in M^H M
+            gp[u] = gram_segment<true>(data + j * TCP + seg * seg_len, data + i * TCP + seg * seg_len, seg_len, wl + seg * seg_len);
         }
         __syncthreads();
 #pragma unroll
@@ -124,22 +96,8 @@ __global__ __launch_bounds__(kCcThreads) void cc_fold_kernel(const double* part_
     for (int pr = threadIdx.x; pr < np; pr += kCcThreads) {
         int i, j;
         pair_of(pr, C, i, j);
-        double hr = 0.0, hi = 0.0;
-#pragma unroll 8
-        for (int g = 0; g < G; ++g) {
-            const Cd v = part[(int64_t)g * np + pr];
-            hr += v.re;
-            hi += v.im;
-        }
-        const Cd old = R[i * C + j];
-        hr += old.re;
-        hi += old.im;
-        if (i == j) {
-            R[i * C + i] = Cd{hr, 0.0};
-        } else {
-            R[i * C + j] = Cd{hr, hi};
-            R[j * C + i] = Cd{hr, -hi};
-        }
+        const Cd sum = fold(part + pr, G, np), old = R[i * C + j];
+        store_hermitian(R, C, i, j, Cd{sum.re + old.re, sum.im + old.im});
     }
 }
 
@@ -193,13 +151,11 @@ __global__ __launch_bounds__(kCcThreads) void cc_eigen_kernel(CcFinishLaunch a) 
     const Cd* src = reinterpret_cast<const Cd*>(a.whiten ? a.T : a.R);
     for (int e = tid; e < C * C; e += kCcThreads) {
         H[e] = src[e];
-        V[e] = Cd{e / C == e % C ? 1.0 : 0.0, 0.0};
+        V[e] = identity_entry(e / C, e % C);
     }
     __syncthreads();
-    int TW = 1;
-    while (TW < C) TW *= 2;
     int sweeps = 0;
-    if (C > 1 && tid < TW) sweeps = jacobi(H, V, C, tid);
+    if (C > 1 && tid < team_width(C)) sweeps = jacobi(H, V, C, tid);
     __syncthreads();
     // rank of every eigenvalue: the number of entries that come before it
     if (tid < C) {
@@ -347,14 +303,13 @@ hipError_t launch_apply_t(const CcApplyLaunch& a, unsigned grid, hipStream_t str
 CcTiling coilcomp_tiling(bool f32, int C, int64_t n) {
     CcTiling tl{};
     const size_t eb = f32 ? 8 : 16;
-    tl.TC = 32;
-    while (tl.TC < 1024 && (size_t)C * (2 * tl.TC + 1) * eb <= (size_t)kCcTileBytes) tl.TC *= 2;
+    const FlatTiling ft = flat_tiling(C, n, kCcTileBytes / (int)eb, kCcThreads, kCcMaxGroups);
     const int np = C * (C + 1) / 2;
-    tl.S = 1;
-    while (tl.S < std::min(tl.TC / 4, 64) && np * tl.S < 2 * kCcThreads) tl.S *= 2;
-    tl.tiles = (n + tl.TC - 1) / tl.TC;
-    tl.tpw = (tl.tiles + kCcMaxGroups - 1) / kCcMaxGroups;
-    tl.G = (int)((tl.tiles + tl.tpw - 1) / tl.tpw);
+    tl.TC = ft.TC;
+    tl.S = ft.S;
+    tl.tiles = ft.tiles;
+    tl.tpw = ft.tpw;
+    tl.G = ft.G;
     tl.off_w = up16((size_t)C * (tl.TC + 1) * eb);
     tl.off_gp = tl.off_w + (size_t)tl.TC * 8;
     tl.off_ij = tl.off_gp + (size_t)tl.S * np * 16;
@@ -366,10 +321,8 @@ size_t coilcomp_eigen_lds(int C) { return (size_t)C * C * 32 + (size_t)C * 8 + u
 
 // Workgroups above 64 KiB of dynamic LDS must be allowed per kernel (and device): called when an object is created.
 hipError_t coilcomp_allow_lds() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cc_eigen_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cc_gram_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cc_gram_kernel<double>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
-    return e;
+    return allow_large_lds({reinterpret_cast<const void*>(&cc_eigen_kernel), reinterpret_cast<const void*>(&cc_gram_kernel<float>),
+                            reinterpret_cast<const void*>(&cc_gram_kernel<double>)});
 }
 
 hipError_t launch_coilcomp_gram(const CcGramLaunch& a, hipStream_t stream) {

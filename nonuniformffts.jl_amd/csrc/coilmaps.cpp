@@ -44,12 +44,6 @@ void release(nufft_coilmaps* h) {
     delete h;
 }
 
-bool overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const char* x = static_cast<const char*>(a);
-    const char* y = static_cast<const char*>(b);
-    return x < y + nb && y < x + na;
-}
-
 // The argument checks of a create call, in the documented order, and the geometry they lead to; no device is touched.
 int describe(nufft_coilmaps& g, int dtype, int D, const int64_t* N, int C, const nufft_coilmaps_params* params) {
     nufft_coilmaps_params p;

@@ -19,7 +19,7 @@
 #include <cmath>
 
 #include "coilmaps.h"
-#include "jacobi.h"
+#include "hermitian.h"
 #include "stream_kernels.h"
 
 namespace nufft {
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(kCmMaxThreads) void coilmaps_kernel(CoilmapsLaunch 
                     }
                 }
             }
-            for (int c = 0; c < C; ++c) V[r * C + c] = Cd{c == r ? 1.0 : 0.0, 0.0};
+            for (int c = 0; c < C; ++c) V[r * C + c] = identity_entry(r, c);
         }
         team_sync();
         int sweeps = 0;
@@ -247,8 +247,6 @@ __global__ __launch_bounds__(kThreads) void coilmaps_crop_kernel(CropTable tab, 
         for (int c = 0; c < C; ++c) reinterpret_cast<Cx<T>*>(tab.out[c])[n - 1] = Cx<T>{T(0), T(0)};
 }
 
-size_t up16(size_t v) { return (v + 15) / 16 * 16; }
-
 template <typename T, int CT>
 hipError_t launch_one(const CoilmapsLaunch& a, const CoilmapsLayout& L, hipStream_t stream) {
     hipLaunchKernelGGL((coilmaps_kernel<T, CT>), dim3((unsigned)L.G), dim3(L.threads), L.bytes, stream, a, L);
@@ -264,8 +262,8 @@ hipError_t launch_typed(const CoilmapsLaunch& a, const CoilmapsLayout& L, hipStr
 }
 
 template <typename T, int CT>
-hipError_t allow_one() {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&coilmaps_kernel<T, CT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10);
+const void* kernel_of() {
+    return reinterpret_cast<const void*>(&coilmaps_kernel<T, CT>);
 }
 
 }  // namespace
@@ -274,8 +272,7 @@ CoilmapsLayout coilmaps_layout(bool f32, int C, int D, const int* box, const int
     CoilmapsLayout L{};
     const size_t eb = f32 ? 8 : 16;
     const bool wide = C > 16;
-    L.TW = 1;
-    while (L.TW < C) L.TW *= 2;
+    L.TW = team_width(C);
     L.teams = kCmMaxThreads / L.TW;
     while (L.teams > 1 && (size_t)L.teams * C * C * 32 > (size_t)(wide ? kCmMatrixBytesWide : kCmMatrixBytes)) L.teams /= 2;
     while (L.teams * L.TW < 64) L.teams *= 2;                          // whole waves (C = 1 ... : more teams cost C * C * 32 bytes each)
@@ -334,15 +331,8 @@ CoilmapsLayout coilmaps_layout(bool f32, int C, int D, const int* box, const int
 }
 
 hipError_t coilmaps_allow_lds() {
-    hipError_t e = allow_one<float, 4>();
-    if (e == hipSuccess) e = allow_one<float, 8>();
-    if (e == hipSuccess) e = allow_one<float, 16>();
-    if (e == hipSuccess) e = allow_one<float, 32>();
-    if (e == hipSuccess) e = allow_one<double, 4>();
-    if (e == hipSuccess) e = allow_one<double, 8>();
-    if (e == hipSuccess) e = allow_one<double, 16>();
-    if (e == hipSuccess) e = allow_one<double, 32>();
-    return e;
+    return allow_large_lds({kernel_of<float, 4>(), kernel_of<float, 8>(), kernel_of<float, 16>(), kernel_of<float, 32>(),
+                            kernel_of<double, 4>(), kernel_of<double, 8>(), kernel_of<double, 16>(), kernel_of<double, 32>()});
 }
 
 hipError_t launch_coilmaps(const CoilmapsLaunch& a, const CoilmapsLayout& L, hipStream_t stream) {

@@ -5,7 +5,7 @@
 //     P = V diag(f) V^H      M <- M P                           nuc = Σ_i f_i σ_i
 //
 // Three launches.  The Gram and apply kernels are flat over the n cells: a workgroup takes `tpw` consecutive tiles of TC cells x K frames
-// into LDS, laid out [frame][cell] with the cell fastest (one padding cell per frame keeps the frames of one cell on different banks).
+// into LDS (FlatTiles of hermitian.h, which also holds the Gram, fold, shrink, projector and apply steps named below).
 //
 //   gram   every entry i <= j of a tile is summed in FP64 in cell order over S fixed segments, the segments are added in segment order
 //          into the thread that owns the entry, tile after tile; a workgroup leaves K (K + 1) / 2 complex partials with plain stores.
@@ -21,7 +21,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "jacobi.h"
+#include "hermitian.h"
 #include "lps.h"
 #include "stream_kernels.h"
 
@@ -34,8 +34,6 @@ static_assert(kLpsMaxK * (kLpsMaxK + 1) / 2 <= kGlrPairsPerThread * kLpsThreads,
 namespace {
 
 using namespace jacobi_team;
-
-size_t up16(size_t v) { return (v + 15) / 16 * 16; }
 
 // g = τ (q + μ u − b), every operation rounded on its own: the apply and temporal kernels subtract the STORED g, and the Gram kernel
 // must see the same zL − g
@@ -54,23 +52,12 @@ __device__ __forceinline__ Cx<T>* frame_w(const LpsFrames& f, int k) {
     return static_cast<Cx<T>*>(f.p[k]);
 }
 
-// entry pr of the upper triangle, rows first: (0,0) (0,1) ... (0,K-1) (1,1) ...
-__device__ __forceinline__ void pair_of(int pr, int K, int& i, int& j) {
-    i = 0;
-    while (pr >= K - i) {
-        pr -= K - i;
-        ++i;
-    }
-    j = i + pr;
-}
-
 template <typename T, int MODE>
 __global__ __launch_bounds__(kLpsThreads) void glr_gram_kernel(GlrLaunch a, int off_gp, int off_ij) {
     extern __shared__ __align__(16) unsigned char smem[];
     if (a.flag && a.flag[0]) return;
-    const int K = a.K, TC = a.tl.TC, TCP = TC + 1, S = a.tl.S, np = K * (K + 1) / 2, tid = threadIdx.x;
-    int tcs = 0;
-    while ((1 << tcs) < TC) ++tcs;
+    const int K = a.K, S = a.tl.S, np = K * (K + 1) / 2, tid = threadIdx.x;
+    const FlatTiles ft(a.tl);
     Cx<T>* data = reinterpret_cast<Cx<T>*>(smem);
     Cd* gp = reinterpret_cast<Cd*>(smem + off_gp);                                // [segment][entry]
     unsigned short* ij = reinterpret_cast<unsigned short*>(smem + off_ij);      // [entry]: i << 8 | j
@@ -83,39 +70,23 @@ __global__ __launch_bounds__(kLpsThreads) void glr_gram_kernel(GlrLaunch a, int 
 #pragma unroll
     for (int m = 0; m < kGlrPairsPerThread; ++m) acc[m] = Cd{0.0, 0.0};
     const T tau = (T)a.step, mu = (T)a.lambda;
-    const int seg_len = TC / S;
-    const int64_t tile0 = (int64_t)blockIdx.x * a.tl.tpw, tile1 = min(tile0 + a.tl.tpw, a.tl.tiles);
-    for (int64_t tile = tile0; tile < tile1; ++tile) {
-        const int64_t cell0 = tile << tcs;
-        const int nc = (int)min((int64_t)TC, a.n - cell0);
-        for (int u = tid; u < (K << tcs); u += kLpsThreads) {
-            const int k = u >> tcs, v = u & (TC - 1);
-            Cx<T> val{T(0), T(0)};                                              // cells beyond n add exact zeros
-            if (v < nc) {
-                const int64_t at = cell0 + v;
-                val = frame<T>(a.f0, k)[at];
-                if (MODE == GLR_SOLVER) {
-                    const Cx<T> zs = frame<T>(a.f1, k)[at];
-                    const Cx<T> g = gradient<T>(frame<T>(a.f2, k)[at], Cx<T>{val.re + zs.re, val.im + zs.im}, frame<T>(a.f3, k)[at], tau, mu);
-                    frame_w<T>(a.f2, k)[at] = g;
-                    val = Cx<T>{val.re - g.re, val.im - g.im};
-                }
+    const int seg_len = ft.TC / S;
+    for (int64_t tile = ft.tile0; tile < ft.tile1; ++tile) {
+        stage_padded<kLpsThreads>(data, ft, K, ft.first_cell(tile), ft.cells(tile, a.n), [&](int k, int64_t at, bool live) {
+            Cx<T> val = frame<T>(a.f0, k)[at];
+            if (MODE == GLR_SOLVER && live) {
+                const Cx<T> zs = frame<T>(a.f1, k)[at];
+                const Cx<T> g = gradient<T>(frame<T>(a.f2, k)[at], Cx<T>{val.re + zs.re, val.im + zs.im}, frame<T>(a.f3, k)[at], tau, mu);
+                frame_w<T>(a.f2, k)[at] = g;
+                val = Cx<T>{val.re - g.re, val.im - g.im};
             }
-            data[k * TCP + v] = val;
-        }
+            return val;
+        });
         __syncthreads();
         for (int u = tid; u < S * np; u += kLpsThreads) {
             const int pr = u % np, seg = u / np;
             const int i = ij[pr] >> 8, j = ij[pr] & 255;
-            const Cx<T>* mi = data + i * TCP + seg * seg_len;
-            const Cx<T>* mj = data + j * TCP + seg * seg_len;
-            double hr = 0.0, hi = 0.0;
-            for (int v = 0; v < seg_len; ++v) {
-                const double ar = (double)mi[v].re, ai = (double)mi[v].im, br = (double)mj[v].re, bi = (double)mj[v].im;
-                hr += ar * br + ai * bi;
-                hi += ar * bi - ai * br;
-            }
-            gp[u] = Cd{hr, hi};
+            gp[u] = gram_segment<false>(data + i * ft.TCP + seg * seg_len, data + j * ft.TCP + seg * seg_len, seg_len);
         }
         __syncthreads();
 #pragma unroll
@@ -151,52 +122,23 @@ __global__ __launch_bounds__(kLpsThreads) void glr_eigen_kernel(GlrLaunch a) {
     for (int pr = tid; pr < np; pr += kLpsThreads) {
         int i, j;
         pair_of(pr, K, i, j);
-        double hr = 0.0, hi = 0.0;
-#pragma unroll 8
-        for (int g = 0; g < G; ++g) {
-            const Cd v = gram[(int64_t)g * np + pr];
-            hr += v.re;
-            hi += v.im;
-        }
-        if (i == j) {
-            H[i * K + i] = Cd{hr, 0.0};
-        } else {
-            H[i * K + j] = Cd{hr, hi};
-            H[j * K + i] = Cd{hr, -hi};
-        }
+        store_hermitian(H, K, i, j, fold(gram + pr, G, np));
     }
-    for (int e = tid; e < K * K; e += kLpsThreads) V[e] = Cd{e / K == e % K ? 1.0 : 0.0, 0.0};
+    for (int e = tid; e < K * K; e += kLpsThreads) V[e] = identity_entry(e / K, e % K);
     __syncthreads();
-    int TW = 1;
-    while (TW < K) TW *= 2;
     int sweeps = 0;
-    if (K > 1 && tid < TW) sweeps = jacobi(H, V, K, tid);
+    if (K > 1 && tid < team_width(K)) sweeps = jacobi(H, V, K, tid);
     __syncthreads();
     if (tid == 0) {
         double nuc = 0.0;
-        for (int i = 0; i < K; ++i) {
-            const double sigma = sqrt(fmax(H[i * K + i].re, 0.0));
-            const double f = sigma > a.t ? 1.0 - a.t / sigma : 0.0;
-            fs[i] = f;
-            nuc += f * sigma;
-        }
+        for (int i = 0; i < K; ++i) fs[i] = shrink_factor(H[i * K + i].re, a.t, nuc);
         a.nuc[0] = nuc;
         if (a.nuc_out) a.nuc_out[0] = nuc;
         a.sweeps[0] = sweeps;
     }
     __syncthreads();
     Cd* P = reinterpret_cast<Cd*>(a.P);
-    for (int e = tid; e < K * K; e += kLpsThreads) {
-        const int i = e / K, j = e % K;
-        double pr = 0.0, pi = 0.0;
-        for (int k = 0; k < K; ++k) {
-            const Cd x = V[i * K + k], y = V[j * K + k];
-            const double f = fs[k];
-            pr += f * (x.re * y.re + x.im * y.im);
-            pi += f * (x.im * y.re - x.re * y.im);
-        }
-        P[e] = Cd{pr, pi};
-    }
+    for (int e = tid; e < K * K; e += kLpsThreads) P[e] = projector_entry(V, fs, K, e / K, e % K);
 }
 
 template <typename T, int MODE>
@@ -204,54 +146,39 @@ __global__ __launch_bounds__(kLpsThreads) void glr_apply_kernel(GlrLaunch a, int
     extern __shared__ __align__(16) unsigned char smem[];
     __shared__ double red[kWaves];
     if (a.flag && a.flag[0]) return;
-    const int K = a.K, TC = a.tl.TC, TCP = TC + 1, tid = threadIdx.x;
-    int tcs = 0;
-    while ((1 << tcs) < TC) ++tcs;
+    const int K = a.K, tid = threadIdx.x;
+    const FlatTiles ft(a.tl);
     Cx<T>* data = reinterpret_cast<Cx<T>*>(smem);
     Cd* P = reinterpret_cast<Cd*>(smem + off_P);
     for (int e = tid; e < K * K; e += kLpsThreads) P[e] = reinterpret_cast<const Cd*>(a.P)[e];
     const T beta = (T)a.beta;
     double sdd = 0.0, sxx = 0.0;
-    const int64_t tile0 = (int64_t)blockIdx.x * a.tl.tpw, tile1 = min(tile0 + a.tl.tpw, a.tl.tiles);
-    for (int64_t tile = tile0; tile < tile1; ++tile) {
-        const int64_t cell0 = tile << tcs;
-        const int nc = (int)min((int64_t)TC, a.n - cell0);
-        for (int u = tid; u < (K << tcs); u += kLpsThreads) {
-            const int k = u >> tcs, v = u & (TC - 1);
-            if (v >= nc) continue;
+    for (int64_t tile = ft.tile0; tile < ft.tile1; ++tile) {
+        const int64_t cell0 = ft.first_cell(tile);
+        const int nc = ft.cells(tile, a.n);
+        for_tile<kLpsThreads>(ft, K, nc, [&](int k, int v) {
             const int64_t at = cell0 + v;
             Cx<T> val = frame<T>(a.f0, k)[at];
             if (MODE == GLR_SOLVER) {
                 const Cx<T> g = frame<T>(a.f2, k)[at];
                 val = Cx<T>{val.re - g.re, val.im - g.im};
             }
-            data[k * TCP + v] = val;
-        }
+            data[k * ft.TCP + v] = val;
+        });
         __syncthreads();                                                        // also: P is in LDS
-        for (int u = tid; u < (K << tcs); u += kLpsThreads) {
-            const int j = u >> tcs, v = u & (TC - 1);
-            if (v >= nc) continue;
+        for_tile<kLpsThreads>(ft, K, nc, [&](int j, int v) {
             const int64_t at = cell0 + v;
             double rr = 0.0, ri = 0.0;
             for (int i = 0; i < K; ++i) {
-                const double mr = (double)data[i * TCP + v].re, mi = (double)data[i * TCP + v].im;
+                const double mr = (double)data[i * ft.TCP + v].re, mi = (double)data[i * ft.TCP + v].im;
                 const Cd p = P[i * K + j];
                 rr += mr * p.re - mi * p.im;
                 ri += mr * p.im + mi * p.re;
             }
             const Cx<T> res{(T)rr, (T)ri};
-            Cx<T>* x = frame_w<T>(a.f1, j);
-            if (MODE == GLR_SOLVER) {
-                const Cx<T> old = x[at];
-                const T dr = res.re - old.re, di = res.im - old.im;
-                sdd += (double)dr * (double)dr + (double)di * (double)di;
-                sxx += (double)res.re * (double)res.re + (double)res.im * (double)res.im;
-                x[at] = res;
-                frame_w<T>(a.f0, j)[at] = Cx<T>{res.re + beta * dr, res.im + beta * di};
-            } else {
-                x[at] = res;
-            }
-        }
+            if (MODE == GLR_SOLVER) solver_epilogue(frame_w<T>(a.f1, j), frame_w<T>(a.f0, j), at, res, beta, sdd, sxx);
+            else frame_w<T>(a.f1, j)[at] = res;
+        });
         __syncthreads();
     }
     if (MODE == GLR_SOLVER) {
@@ -264,7 +191,7 @@ __global__ __launch_bounds__(kLpsThreads) void glr_apply_kernel(GlrLaunch a, int
     }
 }
 
-size_t tile_bytes(bool f32, int K, const LpsTiling& tl) { return up16((size_t)K * (tl.TC + 1) * (f32 ? 8 : 16)); }
+size_t tile_bytes(bool f32, int K, const FlatTiling& tl) { return up16((size_t)K * (tl.TC + 1) * (f32 ? 8 : 16)); }
 
 template <typename T, int MODE>
 hipError_t launch_gram(const GlrLaunch& a, hipStream_t stream) {
@@ -282,19 +209,6 @@ hipError_t launch_apply(const GlrLaunch& a, hipStream_t stream) {
 }
 
 }  // namespace
-
-LpsTiling lps_tiling(int K, int64_t n, int tile_elems, int max_groups) {
-    LpsTiling tl{};
-    tl.TC = 32;
-    while (tl.TC < 1024 && 2 * tl.TC * K <= tile_elems) tl.TC *= 2;
-    const int np = K * (K + 1) / 2;
-    tl.S = 1;
-    while (tl.S < std::min(tl.TC / 4, 64) && np * tl.S < 2 * kLpsThreads) tl.S *= 2;
-    tl.tiles = (n + tl.TC - 1) / tl.TC;
-    tl.tpw = (int)((tl.tiles + max_groups - 1) / max_groups);
-    tl.G = (int)((tl.tiles + tl.tpw - 1) / tl.tpw);
-    return tl;
-}
 
 hipError_t launch_glr_gram(const GlrLaunch& a, hipStream_t stream) {
     const bool f32 = a.dtype == NUFFT_F32;

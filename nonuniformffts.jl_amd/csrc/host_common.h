@@ -1,6 +1,6 @@
 // Host helpers shared by the objects of the C ABI (plan.cpp, type3.cpp, toeplitz.cpp, coilmaps.cpp, wavelet.cpp, llr.cpp and, through
 // solver_common.h, the solvers): error reporting, the device guard, device buffers counted into an object's own_bytes, the
-// struct_size rule of the parameter and info structs, and the pinned mirror of a block of device scalars.  What only the iterative
+// struct_size rule of the parameter and info structs, the checks of the callers' pointer tables, and the pinned mirror of a block of device scalars.  What only the iterative
 // solvers need (cg.cpp, fista.cpp, tv.cpp, lps.cpp, dcf.cpp, precond.cpp) is in solver_common.h, which includes this file.
 #pragma once
 
@@ -76,6 +76,40 @@ void free_buffer(int64_t& own_bytes, P*& ptr, size_t bytes) {
     (void)hipFree(ptr);
     own_bytes -= (int64_t)padded(bytes);
     ptr = nullptr;
+}
+
+// Whether the na bytes at a and the nb bytes at b (or `bytes` at both) share a byte
+inline bool overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const char* x = static_cast<const char*>(a);
+    const char* y = static_cast<const char*>(b);
+    return x < y + nb && y < x + na;
+}
+inline bool overlap(const void* a, const void* b, size_t bytes) { return overlap(a, bytes, b, bytes); }
+
+// A table of `count` device pointers, 16-byte aligned
+inline int check_table(const void* const* tab, int count) {
+    if (!tab) return fail(NUFFT_ERR_INVALID_ARG, "null table");
+    for (int k = 0; k < count; ++k) {
+        if (!tab[k]) return fail(NUFFT_ERR_INVALID_ARG, "null data vector");
+        if ((uintptr_t)tab[k] & 15) return fail(NUFFT_ERR_INVALID_ARG, "the arrays must be 16-byte aligned");
+    }
+    return NUFFT_OK;
+}
+
+// C outputs and C inputs of `bytes` bytes each, 16-byte aligned.  No output overlaps another output; none overlaps an input either (the
+// caller's `refusal` says why), except that out[c] may be exactly in[c] where `in_place` allows it.
+inline int check_tables(int C, size_t bytes, void* const* out, const void* const* in, bool in_place, const char* refusal) {
+    if (!out || !in) return fail(NUFFT_ERR_INVALID_ARG, "null table");
+    for (int c = 0; c < C; ++c) {
+        if (!out[c] || !in[c]) return fail(NUFFT_ERR_INVALID_ARG, "null data vector");
+        if (((uintptr_t)out[c] | (uintptr_t)in[c]) & 15) return fail(NUFFT_ERR_INVALID_ARG, "the arrays must be 16-byte aligned");
+    }
+    for (int c = 0; c < C; ++c)
+        for (int k = 0; k < C; ++k) {
+            if (!(in_place && k == c && out[c] == in[k]) && overlap(out[c], in[k], bytes)) return fail(NUFFT_ERR_INVALID_ARG, refusal);
+            if (k != c && overlap(out[c], out[k], bytes)) return fail(NUFFT_ERR_INVALID_ARG, "two components of the output overlap");
+        }
+    return NUFFT_OK;
 }
 
 // The struct_size rule.  A caller states how much of a struct its header knows (0: this library's layout).  Parameters: a struct

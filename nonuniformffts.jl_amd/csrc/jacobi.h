@@ -1,6 +1,8 @@
 // The cyclic complex Jacobi of a Hermitian K x K matrix by a team of lanes of one wave: device code shared by the locally low-rank
-// kernel (llr_kernels.hip) and the global low-rank eigen kernel (glr_kernels.hip; section 27).  Both get the
-// same rotation order and the same skip constants; tests/llr_reference.py (jacobi_eigh) restates them.
+// kernel (llr_kernels.hip), the global low-rank eigen kernel (glr_kernels.hip; section 27), the coil-map kernel
+// (coilmaps_kernels.hip; section 28) and the eigen kernel of coil compression (coilcomp_kernels.hip; section 29).  All get the same
+// rotation order and the same skip constants; tests/llr_reference.py (jacobi_eigh) restates them.  hermitian.h holds what these kernels
+// do around the Jacobi.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -39,22 +39,8 @@ void release(nufft_llr* l) {
 }
 
 int check_tables(const nufft_llr* l, void* const* out, const void* const* in) {
-    if (!out || !in) return fail(NUFFT_ERR_INVALID_ARG, "null table");
-    const size_t bytes = (size_t)l->n * 2 * real_bytes(l->dtype);
-    for (int c = 0; c < l->C; ++c) {
-        if (!out[c] || !in[c]) return fail(NUFFT_ERR_INVALID_ARG, "null data vector");
-        if (((uintptr_t)out[c] | (uintptr_t)in[c]) & 15) return fail(NUFFT_ERR_INVALID_ARG, "the arrays must be 16-byte aligned");
-    }
-    for (int c = 0; c < l->C; ++c)
-        for (int k = 0; k < l->C; ++k) {
-            const char* a = static_cast<const char*>(out[c]);
-            const char* b = static_cast<const char*>(in[k]);
-            if (!(k == c && a == b) && a < b + bytes && b < a + bytes)
-                return fail(NUFFT_ERR_INVALID_ARG, "the output overlaps the input: out[c] may be exactly in[c], nothing else");
-            const char* o = static_cast<const char*>(out[k]);
-            if (k != c && a < o + bytes && o < a + bytes) return fail(NUFFT_ERR_INVALID_ARG, "two components of the output overlap");
-        }
-    return NUFFT_OK;
+    return nufft::check_tables(l->C, (size_t)l->n * 2 * real_bytes(l->dtype), out, in, true,
+                               "the output overlaps the input: out[c] may be exactly in[c], nothing else");
 }
 
 }  // namespace

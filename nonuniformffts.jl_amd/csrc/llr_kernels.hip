@@ -1,15 +1,14 @@
 // The locally low-rank proximal map: singular-value soft-thresholding of the B x K Casorati matrix M of every spatial block, through
 // the K x K Gram matrix (llr.h, llr.cpp, fista.cpp).
 //
-//     H = M^H M  (FP64)      H = V Λ V^H  (cyclic complex Jacobi, FP64)      σ_i = sqrt(max(λ_i, 0))      f_i = σ_i > t ? 1 − t / σ_i : 0
+//     H = M^H M  (FP64)      H = V Λ V^H  (jacobi.h, FP64)                    σ_i = sqrt(max(λ_i, 0))      f_i = σ_i > t ? 1 − t / σ_i : 0
 //     P = V diag(f) V^H      M <- M P                                        nuclear-norm partial += Σ_i f_i σ_i
 //
 // A workgroup owns nb whole blocks.  Their values are read from global memory once, into LDS ([blk][k][voxel], in the element type), stay
 // there through the Gram pass and the multiply by P, and are written once.  H, V and P are FP64 in LDS.  A block is diagonalised by a
-// team of TW = 2^ceil(log2 K) lanes of one wave: the rotations run one after the other in the cyclic-by-rows order, lane r of the team
-// updates row r of H J and of V J, then column r of J^H (H J); the lanes of a team take every branch together and the LDS serves a wave's
-// accesses in order, so the team needs no workgroup barrier.  Every sum has one fixed order (Gram entries: voxel order inside a
-// segment, then segment order; partial sums: stream_kernels.h), and there are no atomics: two runs give the same bits.
+// team of TW = team_width(K) lanes of one wave (jacobi.h).  The Gram sum, the Hermitian store, the shrink factors and the projector are
+// those of hermitian.h.  Every sum has one fixed order (Gram entries: voxel order inside a segment, then segment order; partial sums:
+// stream_kernels.h), and there are no atomics: two runs give the same bits.
 //
 // LLR_FISTA forms v = z − τ (q + μ z − b) while it loads and x⁺ = result, z = x⁺ + β (x⁺ − x), x = x⁺ while it stores, with the partial
 // sums of |x⁺ − x|², |x⁺|² next to the nuclear norm's: with the decision kernel that is a whole iteration outside the apply.
@@ -18,7 +17,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "jacobi.h"
+#include "hermitian.h"
 #include "llr.h"
 #include "stream_kernels.h"
 
@@ -101,50 +100,28 @@ __global__ __launch_bounds__(kLlrThreads) void llr_kernel(LlrLaunch a, LlrLayout
     // Gram entries (i <= j) of every block, S voxel segments each
     const int seg_len = B / S;
     for (int u = tid; u < nbl * S * np; u += kLlrThreads) {
-        int pr = u % np, i = 0;
         const int seg = (u / np) % S, blk = u / (np * S);
-        while (pr >= K - i) {
-            pr -= K - i;
-            ++i;
-        }
-        const int j = i + pr;
-        const Cx<T>* mi = data + ((blk * K + i) << bsB) + seg * seg_len;
-        const Cx<T>* mj = data + ((blk * K + j) << bsB) + seg * seg_len;
-        double hr = 0.0, hi = 0.0;
-        for (int v = 0; v < seg_len; ++v) {
-            const double ar = (double)mi[v].re, ai = (double)mi[v].im, br = (double)mj[v].re, bi = (double)mj[v].im;
-            hr += ar * br + ai * bi;
-            hi += ar * bi - ai * br;
-        }
-        gp[u] = Cd{hr, hi};
+        int i, j;
+        pair_of(u % np, K, i, j);
+        gp[u] = gram_segment<false>(data + ((blk * K + i) << bsB) + seg * seg_len, data + ((blk * K + j) << bsB) + seg * seg_len, seg_len);
     }
     __syncthreads();
     for (int u = tid; u < nbl * np; u += kLlrThreads) {
-        int pr = u % np, i = 0;
         const int blk = u / np;
-        while (pr >= K - i) {
-            pr -= K - i;
-            ++i;
-        }
-        const int j = i + pr;
-        double hr = 0.0, hi = 0.0;
+        int i, j;
+        pair_of(u % np, K, i, j);
+        Cd h{0.0, 0.0};                                         // the segments in order (fold of hermitian.h unrolls for long global sums)
         for (int seg = 0; seg < S; ++seg) {
             const Cd g = gp[(blk * S + seg) * np + (u % np)];
-            hr += g.re;
-            hi += g.im;
+            h.re += g.re;
+            h.im += g.im;
         }
-        Cd* H = Hs + blk * K * K;
-        if (i == j) {
-            H[i * K + i] = Cd{hr, 0.0};
-        } else {
-            H[i * K + j] = Cd{hr, hi};
-            H[j * K + i] = Cd{hr, -hi};
-        }
+        store_hermitian(Hs + blk * K * K, K, i, j, h);
     }
     __syncthreads();
     for (int u = tid; u < nbl * K * K; u += kLlrThreads) {
         const int e = u % (K * K);
-        Vs[u] = Cd{e / K == e % K ? 1.0 : 0.0, 0.0};
+        Vs[u] = identity_entry(e / K, e % K);
     }
     __syncthreads();
 
@@ -157,24 +134,12 @@ __global__ __launch_bounds__(kLlrThreads) void llr_kernel(LlrLaunch a, LlrLayout
     double nuc = 0.0;
     for (int u = tid; u < nbl * K; u += kLlrThreads) {
         const int blk = u / K, i = u % K;
-        const double lam = Hs[blk * K * K + i * K + i].re;
-        const double sigma = sqrt(fmax(lam, 0.0));
-        const double f = sigma > a.t ? 1.0 - a.t / sigma : 0.0;
-        fs[u] = f;
-        nuc += f * sigma;
+        fs[u] = shrink_factor(Hs[blk * K * K + i * K + i].re, a.t, nuc);
     }
     __syncthreads();
     for (int u = tid; u < nbl * K * K; u += kLlrThreads) {      // P over H
-        const int blk = u / (K * K), e = u % (K * K), i = e / K, j = e % K;
-        const Cd* V = Vs + blk * K * K;
-        double pr = 0.0, pi = 0.0;
-        for (int k = 0; k < K; ++k) {
-            const Cd x = V[i * K + k], y = V[j * K + k];
-            const double f = fs[blk * K + k];
-            pr += f * (x.re * y.re + x.im * y.im);
-            pi += f * (x.im * y.re - x.re * y.im);
-        }
-        Hs[u] = Cd{pr, pi};
+        const int blk = u / (K * K), e = u % (K * K);
+        Hs[u] = projector_entry(Vs + blk * K * K, fs + blk * K, K, e / K, e % K);
     }
     __syncthreads();
 
@@ -196,10 +161,12 @@ __global__ __launch_bounds__(kLlrThreads) void llr_kernel(LlrLaunch a, LlrLayout
         const Cx<T> res{(T)rr, (T)ri};
         Cx<T>* x = static_cast<Cx<T>*>(a.out[j]);
         if (MODE == LLR_FISTA) {
+            // solver_epilogue of hermitian.h with both sums of squares as explicit fused multiply-adds: which product the compiler fuses
+            // on its own changes with the code around it, and with it the last bit of the ComplexF64 partials
             const Cx<T> old = x[at];
             const T dr = res.re - old.re, di = res.im - old.im;
-            sdd += (double)dr * (double)dr + (double)di * (double)di;
-            sxx += (double)res.re * (double)res.re + (double)res.im * (double)res.im;
+            sdd += fma((double)dr, (double)dr, (double)di * (double)di);
+            sxx += fma((double)res.re, (double)res.re, (double)res.im * (double)res.im);
             x[at] = res;
             reinterpret_cast<Cx<T>*>(static_cast<T*>(a.z) + j * a.stride)[at] = Cx<T>{res.re + beta * dr, res.im + beta * di};
         } else {
@@ -227,8 +194,6 @@ __global__ __launch_bounds__(kThreads) void llr_sum_kernel(const double* part, i
     if (threadIdx.x == 0) out[0] = v;
 }
 
-size_t up16(size_t v) { return (v + 15) / 16 * 16; }
-
 template <typename T, int MODE>
 hipError_t launch_one(const LlrLaunch& a, const LlrLayout& L, hipStream_t stream) {
     hipLaunchKernelGGL((llr_kernel<T, MODE>), dim3((unsigned)llr_workgroups(a)), dim3(kLlrThreads), L.bytes, stream, a, L);
@@ -241,8 +206,7 @@ LlrLayout llr_layout(bool f32, int K, int B) {
     LlrLayout L{};
     const int E = B * K, np = K * (K + 1) / 2;
     const size_t eb = f32 ? 8 : 16;
-    L.TW = 1;
-    while (L.TW < K) L.TW *= 2;
+    L.TW = team_width(K);
     int nb = 1;
     while (nb < 256 && 2 * nb * E <= kLlrTileElems) nb *= 2;
     for (;; nb /= 2) {
@@ -268,12 +232,8 @@ int64_t llr_workgroups(const LlrLaunch& a) {
 
 // Workgroups above 64 KiB of dynamic LDS must be allowed per kernel (and device): called when an object is created.
 hipError_t llr_allow_lds() {
-    const int most = 160 << 10;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&llr_kernel<float, LLR_PLAIN>), hipFuncAttributeMaxDynamicSharedMemorySize, most);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&llr_kernel<float, LLR_FISTA>), hipFuncAttributeMaxDynamicSharedMemorySize, most);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&llr_kernel<double, LLR_PLAIN>), hipFuncAttributeMaxDynamicSharedMemorySize, most);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&llr_kernel<double, LLR_FISTA>), hipFuncAttributeMaxDynamicSharedMemorySize, most);
-    return e;
+    return allow_large_lds({reinterpret_cast<const void*>(&llr_kernel<float, LLR_PLAIN>), reinterpret_cast<const void*>(&llr_kernel<float, LLR_FISTA>),
+                            reinterpret_cast<const void*>(&llr_kernel<double, LLR_PLAIN>), reinterpret_cast<const void*>(&llr_kernel<double, LLR_FISTA>)});
 }
 
 hipError_t launch_llr(const LlrLaunch& a, hipStream_t stream) {

@@ -15,7 +15,6 @@
 #include <string>
 #include <vector>
 
-#include "jacobi.h"
 #include "lps.h"
 #include "solver_common.h"
 #include "stream_kernels.h"
@@ -26,7 +25,7 @@ struct nufft_glr {
     int dtype = NUFFT_F64, D = 1, C = 1, device = -1;
     int64_t N[3] = {1, 1, 1};
     int64_t n = 1;
-    LpsTiling tl{}, tla{};       // of the Gram kernel, of the apply kernel (the same tiles, more workgroups)
+    FlatTiling tl{}, tla{};       // of the Gram kernel, of the apply kernel (the same tiles, more workgroups)
     void* d_gram = nullptr;      // complex double [G][K (K + 1) / 2]
     void* d_P = nullptr;         // complex double [K][K]
     void* d_words = nullptr;     // double nuc; int32 sweeps
@@ -38,7 +37,7 @@ struct nufft_tsparse {
     int dtype = NUFFT_F64, D = 1, C = 1, device = -1, transform = NUFFT_TSPARSE_DFT;
     int64_t N[3] = {1, 1, 1};
     int64_t n = 1;
-    LpsTiling tl{};
+    FlatTiling tl{};
     double tw[2 * kLpsMaxK] = {};
     void* d_part = nullptr;      // double[G][3]
     int64_t own_bytes = 0;
@@ -181,19 +180,7 @@ int real_plan() {
 
 // C outputs and C inputs, 16-byte aligned; out[c] may be exactly in[c], nothing else may overlap
 int check_tables(int C, int64_t n, int dtype, void* const* out, const void* const* in) {
-    if (!out || !in) return fail(NUFFT_ERR_INVALID_ARG, "null table");
-    const size_t bytes = (size_t)n * 2 * real_bytes(dtype);
-    for (int c = 0; c < C; ++c) {
-        if (!out[c] || !in[c]) return fail(NUFFT_ERR_INVALID_ARG, "null data vector");
-        if (((uintptr_t)out[c] | (uintptr_t)in[c]) & 15) return fail(NUFFT_ERR_INVALID_ARG, "the arrays must be 16-byte aligned");
-    }
-    for (int c = 0; c < C; ++c)
-        for (int k = 0; k < C; ++k) {
-            if (!(k == c && out[c] == in[k]) && overlap(out[c], in[k], bytes))
-                return fail(NUFFT_ERR_INVALID_ARG, "the output overlaps the input: out[c] may be exactly in[c], nothing else");
-            if (k != c && overlap(out[c], out[k], bytes)) return fail(NUFFT_ERR_INVALID_ARG, "two components of the output overlap");
-        }
-    return NUFFT_OK;
+    return nufft::check_tables(C, (size_t)n * 2 * real_bytes(dtype), out, in, true, "the output overlaps the input: out[c] may be exactly in[c], nothing else");
 }
 
 GlrLaunch glr_template(const nufft_glr* g) {

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "hermitian.h"
 #include "nufft_mi355x.h"
 #include "solver_decide.h"
 
@@ -18,13 +19,8 @@ constexpr int kGlrGramGroups = 1024;    // workgroups of the Gram kernel: the ei
 constexpr int kLpsStreamGroups = 4096;  // workgroups of the apply and temporal kernels, which leave two or three partial sums each
 constexpr int kGlrPairsPerThread = 3;    // ceil(32 * 33 / 2 / 256) Gram entries a thread accumulates
 
-// How the n cells are cut: tiles of TC cells (a power of two, K * TC <= tile_elems, 32 ... 1024), `tpw` consecutive tiles per workgroup,
-// G <= max_groups workgroups.  S: segments of a tile's cells per Gram entry (a power of two).  Host and device use the same numbers.
-struct LpsTiling {
-    int TC, S, tpw, G;
-    int64_t tiles;
-};
-LpsTiling lps_tiling(int K, int64_t n, int tile_elems, int max_groups);
+// How the n cells are cut (FlatTiling of hermitian.h): K * TC <= tile_elems, stated as the budget that counts the padding cell of every frame
+inline FlatTiling lps_tiling(int K, int64_t n, int tile_elems, int max_groups) { return flat_tiling(K, n, tile_elems + K, kLpsThreads, max_groups); }
 
 // One array of K frames: the pointers travel as kernel arguments, the host writes no device table.
 struct LpsFrames {
@@ -39,7 +35,7 @@ enum { GLR_PLAIN = 0, GLR_SOLVER = 1 };
 //             zL <- L⁺ + beta (L⁺ − L) and the partials of ‖L⁺ − L‖², ‖L⁺‖².
 struct GlrLaunch {
     int dtype, K, mode;
-    LpsTiling tl;                // of the launch: the Gram kernel's (the eigen kernel adds tl.G sets) or the apply kernel's
+    FlatTiling tl;               // of the launch: the Gram kernel's (the eigen kernel adds tl.G sets) or the apply kernel's
     int64_t n;
     double t;                    // the threshold on the singular values
     double step, lambda, beta;
@@ -64,7 +60,7 @@ enum { TS_FORWARD = 0, TS_INVERSE = 1, TS_SHRINK = 2, TS_SOLVER = 3 };
 //            the partials of ‖S⁺ − S‖², ‖S⁺‖², ‖T S⁺‖₁.
 struct TsLaunch {
     int dtype, K, mode, transform;
-    LpsTiling tl;
+    FlatTiling tl;
     int64_t n;
     double t, beta;
     double tw[2 * kLpsMaxK];     // K^-1/2 exp(−2πi m / K), m < K, FP64: rounded once to the element type by the kernel

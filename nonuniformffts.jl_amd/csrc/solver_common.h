@@ -11,12 +11,6 @@
 
 namespace nufft {
 
-static inline bool overlap(const void* a, const void* b, size_t bytes) {
-    const char* x = static_cast<const char*>(a);
-    const char* y = static_cast<const char*>(b);
-    return x < y + bytes && y < x + bytes;
-}
-
 static inline bool weight_ok(double v) { return std::isfinite(v) && v >= 0.0; }
 
 static inline int toeplitz_info(const nufft_toeplitz* tz, nufft_toeplitz_info& ti) {

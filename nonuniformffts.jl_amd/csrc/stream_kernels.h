@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <climits>
 #include <cstdint>
+#include <initializer_list>
 
 #include "nufft_mi355x.h"
 
@@ -96,6 +97,16 @@ inline unsigned grid_for(int64_t chunks, int num_cus) {
     const int64_t cap = (int64_t)num_cus * 8;      // 8 workgroups of 4 waves per CU: enough bytes in flight for HBM
     const int64_t need = (chunks + kThreads - 1) / kThreads;
     return (unsigned)std::max<int64_t>(1, std::min(need, cap));
+}
+
+// Byte counts and offsets of the LDS layouts are whole 16-byte packs.
+inline size_t up16(size_t v) { return (v + 15) / 16 * 16; }
+
+// Workgroups above 64 KiB of dynamic LDS must be allowed per kernel (and device): called when an object is created.
+inline hipError_t allow_large_lds(std::initializer_list<const void*> kernels) {
+    for (const void* k : kernels)
+        if (hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 << 10); e != hipSuccess) return e;
+    return hipSuccess;
 }
 
 // Launches the Float32 or the Float64 instantiation of a kernel; every argument is converted to the parameter type of the kernel that

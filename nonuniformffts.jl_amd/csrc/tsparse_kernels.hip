@@ -4,7 +4,7 @@
 //     NUFFT_TSPARSE_DFT:       (T x)_k[i] = K^-1/2 Σ_c x_c[i] w^(k c mod K),  w = exp(−2πi / K);   Tᴴ with conj(w)
 //     NUFFT_TSPARSE_IDENTITY:  T = I
 //
-// One kernel, flat over the n cells.  A workgroup stages a tile [frame][cell] (the cell fastest) in LDS; one thread per (frequency, cell)
+// One kernel, flat over the n cells.  A workgroup stages a tile [frame][cell] in LDS (FlatTiles of hermitian.h); one thread per (frequency, cell)
 // forms the direct sum of K terms in the element type (any K in 1 ... 32), with the K twiddles (K^-1/2 folded in, FP64 on the host,
 // rounded once) in LDS.  The thread soft-thresholds the coefficient where it is produced: c · (1 − t / |c|) for |c| > t, else 0, nothing
 // divided.  TS_SOLVER writes the coefficients to a second LDS tile and runs the inverse from there: S⁺ = Tᴴ soft_t(T (zS − g)),
@@ -16,7 +16,7 @@
 
 #include <cmath>
 
-#include "jacobi.h"
+#include "hermitian.h"
 #include "lps.h"
 #include "stream_kernels.h"
 
@@ -27,7 +27,7 @@ static_assert(kLpsThreads == kThreads, "the reductions of stream_kernels.h");
 
 namespace {
 
-using jacobi_team::Cx;
+using namespace jacobi_team;
 
 template <typename T>
 __device__ __forceinline__ const Cx<T>* frame(const LpsFrames& f, int k) {
@@ -71,22 +71,19 @@ __global__ __launch_bounds__(kLpsThreads) void tsparse_kernel(TsLaunch a, int of
     extern __shared__ __align__(16) unsigned char smem[];
     __shared__ double red[kWaves];
     if (a.flag && a.flag[0]) return;
-    const int K = a.K, TC = a.tl.TC, TCP = TC + 1, tid = threadIdx.x;
-    int tcs = 0;
-    while ((1 << tcs) < TC) ++tcs;
+    const int K = a.K, tid = threadIdx.x;
+    const FlatTiles ft(a.tl);
+    const int TCP = ft.TCP;
     Cx<T>* A = reinterpret_cast<Cx<T>*>(smem);
     Cx<T>* B = reinterpret_cast<Cx<T>*>(smem + off_B);
     Cx<T>* tw = reinterpret_cast<Cx<T>*>(smem + off_tw);
     if (DFT && tid < K) tw[tid] = Cx<T>{(T)a.tw[2 * tid], (T)a.tw[2 * tid + 1]};
     const T t = (T)a.t, beta = (T)a.beta;
     double sdd = 0.0, sxx = 0.0, l1 = 0.0;
-    const int64_t tile0 = (int64_t)blockIdx.x * a.tl.tpw, tile1 = min(tile0 + a.tl.tpw, a.tl.tiles);
-    for (int64_t tile = tile0; tile < tile1; ++tile) {
-        const int64_t cell0 = tile << tcs;
-        const int nc = (int)min((int64_t)TC, a.n - cell0);
-        for (int u = tid; u < (K << tcs); u += kLpsThreads) {
-            const int c = u >> tcs, v = u & (TC - 1);
-            if (v >= nc) continue;
+    for (int64_t tile = ft.tile0; tile < ft.tile1; ++tile) {
+        const int64_t cell0 = ft.first_cell(tile);
+        const int nc = ft.cells(tile, a.n);
+        for_tile<kLpsThreads>(ft, K, nc, [&](int c, int v) {
             const int64_t at = cell0 + v;
             Cx<T> val = frame<T>(a.f0, c)[at];
             if (MODE == TS_SOLVER) {
@@ -94,41 +91,30 @@ __global__ __launch_bounds__(kLpsThreads) void tsparse_kernel(TsLaunch a, int of
                 val = Cx<T>{val.re - g.re, val.im - g.im};
             }
             A[c * TCP + v] = val;
-        }
+        });
         __syncthreads();                                                        // also: the twiddles are in LDS
         if (MODE != TS_INVERSE) {
-            for (int u = tid; u < (K << tcs); u += kLpsThreads) {
-                const int k = u >> tcs, v = u & (TC - 1);
-                if (v >= nc) continue;
+            for_tile<kLpsThreads>(ft, K, nc, [&](int k, int v) {
                 Cx<T> cf = DFT ? dft_sum<T, false>(A, TCP, v, tw, K, k) : A[k * TCP + v];
                 if (MODE != TS_FORWARD) cf = soft<T>(cf, t, l1);
                 if (MODE == TS_SOLVER) B[k * TCP + v] = cf;
                 else frame_w<T>(a.f1, k)[cell0 + v] = cf;
-            }
+            });
         }
         if (MODE == TS_SOLVER) __syncthreads();
         if (MODE == TS_INVERSE || MODE == TS_SOLVER) {
             const Cx<T>* src = MODE == TS_INVERSE ? A : B;
-            for (int u = tid; u < (K << tcs); u += kLpsThreads) {
-                const int c = u >> tcs, v = u & (TC - 1);
-                if (v >= nc) continue;
+            for_tile<kLpsThreads>(ft, K, nc, [&](int c, int v) {
                 const int64_t at = cell0 + v;
                 const Cx<T> res = DFT ? dft_sum<T, true>(src, TCP, v, tw, K, c) : src[c * TCP + v];
                 if (MODE == TS_INVERSE) {
                     frame_w<T>(a.f1, c)[at] = res;
                 } else {
-                    Cx<T>* s = frame_w<T>(a.f2, c);
-                    const Cx<T> old = s[at];
-                    const T dr = res.re - old.re, di = res.im - old.im;
-                    sdd += (double)dr * (double)dr + (double)di * (double)di;
-                    sxx += (double)res.re * (double)res.re + (double)res.im * (double)res.im;
-                    s[at] = res;
-                    const Cx<T> zs{res.re + beta * dr, res.im + beta * di};
-                    frame_w<T>(a.f0, c)[at] = zs;
+                    const Cx<T> zs = solver_epilogue(frame_w<T>(a.f2, c), frame_w<T>(a.f0, c), at, res, beta, sdd, sxx);
                     const Cx<T> zl = frame<T>(a.f3, c)[at];
                     frame_w<T>(a.f4, c)[at] = Cx<T>{zl.re + zs.re, zl.im + zs.im};
                 }
-            }
+            });
         }
         __syncthreads();
     }
@@ -201,7 +187,7 @@ __global__ __launch_bounds__(kThreads) void lps_sum_kernel(LpsSolve a) {
 
 template <typename T, int MODE>
 hipError_t launch_ts(const TsLaunch& a, hipStream_t stream) {
-    const size_t tile = ((size_t)a.K * (a.tl.TC + 1) * sizeof(T) * 2 + 15) / 16 * 16;
+    const size_t tile = up16((size_t)a.K * (a.tl.TC + 1) * sizeof(T) * 2);
     const size_t off_B = tile, off_tw = MODE == TS_SOLVER ? 2 * tile : tile;
     const size_t bytes = off_tw + (size_t)a.K * sizeof(T) * 2;
     const dim3 gr((unsigned)a.tl.G), bl(kLpsThreads);

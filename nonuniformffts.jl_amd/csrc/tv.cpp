@@ -164,16 +164,6 @@ TvLaunch launch_template(const nufft_tv* t) {
 // components per launch: the callers' pointers travel as kernel arguments, and gridDim.z = tiles[2] · components stays below 2^16
 int batch_of(const nufft_tv* t) { return std::max(1, std::min(kTvBatch, 65535 / t->tiles[2])); }
 
-// `count` device pointers, 16-byte aligned
-int check_table(const void* const* tab, int count) {
-    if (!tab) return fail(NUFFT_ERR_INVALID_ARG, "null table");
-    for (int k = 0; k < count; ++k) {
-        if (!tab[k]) return fail(NUFFT_ERR_INVALID_ARG, "null data vector");
-        if ((uintptr_t)tab[k] & 15) return fail(NUFFT_ERR_INVALID_ARG, "the arrays must be 16-byte aligned");
-    }
-    return NUFFT_OK;
-}
-
 // no output may overlap an input or another output
 int check_overlap(const nufft_tv* t, void* const* out, int nout, const void* const* in, int nin) {
     const size_t bytes = (size_t)t->n * 2 * real_bytes(t->dtype);

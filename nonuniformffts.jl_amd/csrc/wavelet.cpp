@@ -69,22 +69,8 @@ WaveletLevel geometry(const nufft_wavelet* w, int l) {
 int64_t workgroups(const WaveletLevel& g) { return (int64_t)g.tiles[0] * g.tiles[1] * g.tiles[2]; }
 
 int check_tables(const nufft_wavelet* w, void* const* out, const void* const* in) {
-    if (!out || !in) return fail(NUFFT_ERR_INVALID_ARG, "null table");
-    const size_t bytes = (size_t)w->n * elem_bytes(w);
-    for (int c = 0; c < w->C; ++c) {
-        if (!out[c] || !in[c]) return fail(NUFFT_ERR_INVALID_ARG, "null data vector");
-        if (((uintptr_t)out[c] | (uintptr_t)in[c]) & 15) return fail(NUFFT_ERR_INVALID_ARG, "the arrays must be 16-byte aligned");
-    }
-    for (int c = 0; c < w->C; ++c)
-        for (int k = 0; k < w->C; ++k) {
-            const char* a = static_cast<const char*>(out[c]);
-            const char* b = static_cast<const char*>(in[k]);
-            if (a < b + bytes && b < a + bytes)
-                return fail(NUFFT_ERR_INVALID_ARG, "the output overlaps the input: a level reads its sub-box while other tiles store into it");
-            const char* o = static_cast<const char*>(out[k]);
-            if (k != c && a < o + bytes && o < a + bytes) return fail(NUFFT_ERR_INVALID_ARG, "two components of the output overlap");
-        }
-    return NUFFT_OK;
+    return nufft::check_tables(w->C, (size_t)w->n * elem_bytes(w), out, in, false,
+                               "the output overlaps the input: a level reads its sub-box while other tiles store into it");
 }
 
 char* at(void* base, size_t stride, int c) { return static_cast<char*>(base) + stride * (size_t)c; }

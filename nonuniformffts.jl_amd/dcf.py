@@ -21,11 +21,12 @@ from typing import Optional
 import torch
 
 from . import _lib
+from ._handle import _HandleObject
 from ._lib import lib
 from .plan import _check, _ptr_table, DimensionMismatch, PlanNUFFT
 
 
-class DensityCompensation:
+class DensityCompensation(_HandleObject):
     """``DensityCompensation(plan, maxiter=20, tol=0.0, check_every=0, normalize="sum")``: owns a real-data plan with the geometry and
     window of ``plan`` (which is not kept and may be closed afterwards), kept across point sets.
 
@@ -33,6 +34,8 @@ class DensityCompensation:
     fixed count is the default).  ``check_every=0`` enqueues everything without synchronising (a finished state is frozen on the device;
     legal inside ``torch.cuda.graph``); ``check_every=k`` lets the host look at the done flag every ``k`` iterations and stop early.
     ``normalize="sum"`` returns ``Σ w = 1``, ``"none"`` the raw fixed-point iterate."""
+
+    _prefix, _info = "dcf", _lib.NufftDcfInfo
 
     def __init__(self, plan: PlanNUFFT, maxiter: int = 20, tol: float = 0.0, check_every: int = 0, normalize: str = "sum"):
         if not isinstance(plan, PlanNUFFT):
@@ -54,36 +57,10 @@ class DensityCompensation:
         self.maxiter, self.tol, self.check_every, self.normalize = maxiter, float(tol), check_every, normalize
         self.num_points = None
 
-    def close(self):
-        h = getattr(self, "_handle", None)
-        if h is not None and h.value:
-            lib.nufft_dcf_destroy(h)
-            self._handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _require_open(self):
-        if not self._handle.value:
-            raise ValueError("this DensityCompensation has been closed")
-
     def _require_gpu(self):
         self._require_open()
         if self.device is None:
             raise ValueError("host-only density compensation (plan with backend=None) has no device path")
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def info(self) -> _lib.NufftDcfInfo:
-        self._require_open()
-        out = _lib.NufftDcfInfo()
-        out.struct_size = C.sizeof(_lib.NufftDcfInfo)
-        _check(lib.nufft_dcf_get_info(self._handle, C.byref(out)))
-        return out
 
     @property
     def oversampled_dims(self):

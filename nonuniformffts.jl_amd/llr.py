@@ -13,6 +13,7 @@ import ctypes as C
 import torch
 
 from . import _lib
+from ._handle import _HandleObject
 from ._lib import lib
 from .plan import DimensionMismatch, PlanNUFFT, _check, _ptr_table
 from .toeplitz import ToeplitzOperator
@@ -37,12 +38,14 @@ def _llr_params(ndim: int, block, shifts, seed) -> _lib.NufftLlrParams:
     return prm
 
 
-class LocallyLowRank:
+class LocallyLowRank(_HandleObject):
     """``LocallyLowRank(op_or_plan, block=8 | (b1, …, bD), shifts=False, seed=0)``: element type, shape, ntransforms and device are
     those of a complex ``PlanNUFFT`` or of a ``ToeplitzOperator`` (neither is kept).  Block sides are powers of two, 1 … 16, each
     dividing its ``N_d``, with ``Π b_d · ntransforms <= 8192``.  ``shifts`` and ``seed`` only matter to :class:`ToeplitzFISTA`, which
     draws a new cyclic shift every iteration; ``apply`` takes its shift as an argument.  The map acts on the arrays as stored, periodic
     in the storage index."""
+
+    _prefix, _info = "llr", _lib.NufftLlrInfo
 
     def __init__(self, op_or_plan, block=8, shifts: bool = False, seed: int = 0):
         if not isinstance(op_or_plan, (PlanNUFFT, ToeplitzOperator)):
@@ -58,42 +61,6 @@ class LocallyLowRank:
         _check(create(C.byref(self._handle), src._handle, C.byref(prm)))
         self.device, self.shape, self.ndim, self.ntransforms = src.device, src.shape, src.ndim, src.ntransforms
         self.block, self.shifts, self.seed = tuple(prm.block[d] for d in range(self.ndim)), bool(shifts), seed
-
-    def close(self):
-        h = getattr(self, "_handle", None)
-        if h is not None and h.value:
-            lib.nufft_llr_destroy(h)
-            self._handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _require_open(self):
-        if not self._handle.value:
-            raise ValueError("this LocallyLowRank has been closed")
-
-    def info(self) -> _lib.NufftLlrInfo:
-        self._require_open()
-        out = _lib.NufftLlrInfo()
-        out.struct_size = C.sizeof(_lib.NufftLlrInfo)
-        _check(lib.nufft_llr_get_info(self._handle, C.byref(out)))
-        return out
-
-    def _check_arrays(self, us, what):
-        if len(us) != self.ntransforms:
-            raise DimensionMismatch(f"wrong amount of {what} arrays (expected a tuple of {self.ntransforms} arrays)")
-        for u in us:
-            if not isinstance(u, torch.Tensor) or u.device != self.device:
-                raise ValueError(f"{what} must be torch tensors on {self.device}")
-            if u.dtype != self.Z:
-                raise ValueError(f"{what} must have element type {self.Z} (got {u.dtype})")
-            if tuple(u.shape) != self.shape:
-                raise DimensionMismatch(f"wrong dimensions of {what} array (expected tensor shape {self.shape}, got {tuple(u.shape)})")
-            if not u.is_contiguous():
-                raise ValueError(f"{what} must be contiguous")
 
     def apply(self, x, t, out=None, shift=None):
         """``out = prox_{t ‖·‖_LLR}(x)``: a tensor of the plan's shape or a tuple of ntransforms such tensors.  ``out`` may be ``x``

@@ -23,9 +23,10 @@ import ctypes as C
 import torch
 
 from . import _lib
+from ._handle import _HandleObject
 from ._lib import lib
 from ._solver import _ToeplitzSolver, _change, _doc
-from .plan import DimensionMismatch, PlanNUFFT, _check, _ptr_table
+from .plan import PlanNUFFT, _check, _ptr_table
 from .toeplitz import ToeplitzOperator
 
 
@@ -35,46 +36,11 @@ def _transform_id(transform) -> int:
     return _lib.TSPARSE_IDS[transform]
 
 
-class _FrameObject:
-    """What the two operator objects share: the source's geometry, the handle and the argument checks."""
-
-    _destroy = None
-    _name = ""
+class _FrameObject(_HandleObject):
+    """What the two operator objects share: the source's geometry and the argument checks."""
 
     def _adopt(self, src):
         self.device, self.shape, self.ndim, self.ntransforms = src.device, src.shape, src.ndim, src.ntransforms
-
-    def close(self):
-        h = getattr(self, "_handle", None)
-        if h is not None and h.value:
-            type(self)._destroy(h)
-            self._handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _require_open(self):
-        if not self._handle.value:
-            raise ValueError(f"this {self._name} has been closed")
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _check_arrays(self, us, what):
-        if len(us) != self.ntransforms:
-            raise DimensionMismatch(f"wrong amount of {what} arrays (expected a tuple of {self.ntransforms} arrays)")
-        for u in us:
-            if not isinstance(u, torch.Tensor) or u.device != self.device:
-                raise ValueError(f"{what} must be torch tensors on {self.device}")
-            if u.dtype != self.Z:
-                raise ValueError(f"{what} must have element type {self.Z} (got {u.dtype})")
-            if tuple(u.shape) != self.shape:
-                raise DimensionMismatch(f"wrong dimensions of {what} array (expected tensor shape {self.shape}, got {tuple(u.shape)})")
-            if not u.is_contiguous():
-                raise ValueError(f"{what} must be contiguous")
 
     def _in_out(self, x, out):
         """(inputs, outputs, what to return) for a tensor or a tuple of ntransforms tensors; ``out`` may be ``x``."""
@@ -95,8 +61,7 @@ class GlobalLowRank(_FrameObject):
     ``ToeplitzOperator`` (neither is kept).  ``apply`` shrinks the singular values of the n × K matrix whose columns are the K arrays,
     through its K × K Gram matrix in FP64: a direction with ``σ_i ≪ σ_max`` is resolved to about ``(σ_max/σ_i)² ε``."""
 
-    _destroy = lib.nufft_glr_destroy
-    _name = "GlobalLowRank"
+    _prefix, _info = "glr", _lib.NufftGlrInfo
 
     def __init__(self, op_or_plan):
         if not isinstance(op_or_plan, (PlanNUFFT, ToeplitzOperator)):
@@ -110,13 +75,6 @@ class GlobalLowRank(_FrameObject):
         self._handle = C.c_void_p()
         _check(create(C.byref(self._handle), src._handle))
         self._adopt(src)
-
-    def info(self) -> _lib.NufftGlrInfo:
-        self._require_open()
-        out = _lib.NufftGlrInfo()
-        out.struct_size = C.sizeof(_lib.NufftGlrInfo)
-        _check(lib.nufft_glr_get_info(self._handle, C.byref(out)))
-        return out
 
     def apply(self, x, t, out=None):
         """``out = prox_{t ‖C(·)‖_*}(x)``; ``out`` may be ``x`` itself.  Returns ``(out, nuc)`` with ``nuc`` a float64 device tensor of
@@ -145,8 +103,7 @@ class TemporalSparsity(_FrameObject):
     per cell.  ``forward`` / ``inverse`` apply ``T`` / ``Tᴴ``; ``shrink(x, t)`` returns the coefficients after the complex soft
     threshold, so that ``inverse`` of them is ``prox_{t ‖T·‖₁}(x)``."""
 
-    _destroy = lib.nufft_tsparse_destroy
-    _name = "TemporalSparsity"
+    _prefix, _info = "tsparse", _lib.NufftTsparseInfo
 
     def __init__(self, op_or_plan, transform="dft"):
         if not isinstance(op_or_plan, (PlanNUFFT, ToeplitzOperator)):
@@ -162,13 +119,6 @@ class TemporalSparsity(_FrameObject):
         _check(create(C.byref(self._handle), src._handle, tid))
         self._adopt(src)
         self.transform = transform
-
-    def info(self) -> _lib.NufftTsparseInfo:
-        self._require_open()
-        out = _lib.NufftTsparseInfo()
-        out.struct_size = C.sizeof(_lib.NufftTsparseInfo)
-        _check(lib.nufft_tsparse_get_info(self._handle, C.byref(out)))
-        return out
 
     def forward(self, x, out=None):
         self._require_open()

@@ -23,6 +23,7 @@ from typing import Optional
 import torch
 
 from . import _lib
+from ._handle import _HandleObject
 from ._lib import lib
 from .plan import _check, _ptr_table, DimensionMismatch
 from .toeplitz import ToeplitzOperator
@@ -30,7 +31,7 @@ from .toeplitz import ToeplitzOperator
 _PATHS = {_lib.PRECOND_PATH_DENSE: "dense", _lib.PRECOND_PATH_FUSED: "fused"}
 
 
-class ToeplitzPreconditioner:
+class ToeplitzPreconditioner(_HandleObject):
     """``ToeplitzPreconditioner(op, lam=0.0, floor=1e-6)``: built from the multiplier ``op`` holds now (``op.set_points`` /
     ``set_spectrum`` first); ``update()`` rebuilds it after the operator's spectrum or coil maps changed.  ``lam`` is the λ of the system
     ``(G + λ I)`` it preconditions.  With coil maps set on ``op`` the scaling ``d = (Σ_c |S_c|²)^(-1/2)`` is computed and owned here and
@@ -43,6 +44,8 @@ class ToeplitzPreconditioner:
     (rocFFT); it does not depend on the operator's own path — a 48 × 40 operator is fused while its preconditioner is dense.  Building
     allocates temporaries and synchronises (not inside ``torch.cuda.graph``); ``apply`` allocates nothing and is capturable.  The object
     keeps ``op`` alive."""
+
+    _prefix, _info = "precond", _lib.NufftPrecondInfo
 
     def __init__(self, op: ToeplitzOperator, lam: float = 0.0, floor: float = 1e-6, block: bool = False):
         if not isinstance(op, ToeplitzOperator):
@@ -61,30 +64,13 @@ class ToeplitzPreconditioner:
         self.lam, self.floor = float(lam), float(floor)
 
     def close(self):
-        h = getattr(self, "_handle", None)
-        if h is not None and h.value:
-            lib.nufft_precond_destroy(h)
-            self._handle = C.c_void_p()
+        super().close()
         self._d = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def _require_open(self):
-        if not self._handle.value:
-            raise ValueError("this ToeplitzPreconditioner has been closed")
+        super()._require_open()
         if not self.op._handle.value:
             raise ValueError("the ToeplitzOperator of this preconditioner has been closed: the operator must outlive it")
-
-    def info(self) -> _lib.NufftPrecondInfo:
-        self._require_open()
-        out = _lib.NufftPrecondInfo()
-        out.struct_size = C.sizeof(_lib.NufftPrecondInfo)
-        _check(lib.nufft_precond_get_info(self._handle, C.byref(out)))
-        return out
 
     @property
     def path(self) -> str:

@@ -31,6 +31,7 @@ import ctypes as C
 import torch
 
 from . import _lib
+from ._handle import _HandleObject
 from ._lib import lib
 from ._solver import _ToeplitzSolver, _change, _doc
 from .plan import DimensionMismatch, PlanNUFFT, _check, _ptr_table
@@ -44,11 +45,13 @@ def _weights(tv, n):
     return [float(tv)] * n
 
 
-class TotalVariation:
+class TotalVariation(_HandleObject):
     """``TotalVariation(op_or_plan)``: element type, shape, ntransforms and device are those of a complex ``PlanNUFFT`` or of a
     ``ToeplitzOperator`` (neither is kept).  Dimension 1 is the fastest one, the LAST axis of the tensors.  The operator is periodic
     in the storage index and commutes with every cyclic shift: ``fftshift=True`` and ``False`` plans give the same prior after
     reordering, whatever the sizes."""
+
+    _prefix, _info = "tv", _lib.NufftTvInfo
 
     def __init__(self, op_or_plan):
         if not isinstance(op_or_plan, (PlanNUFFT, ToeplitzOperator)):
@@ -63,44 +66,10 @@ class TotalVariation:
         _check(create(C.byref(self._handle), src._handle))
         self.device, self.shape, self.ndim, self.ntransforms = src.device, src.shape, src.ndim, src.ntransforms
 
-    def close(self):
-        h = getattr(self, "_handle", None)
-        if h is not None and h.value:
-            lib.nufft_tv_destroy(h)
-            self._handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _require_open(self):
-        if not self._handle.value:
-            raise ValueError("this TotalVariation has been closed")
-
-    def info(self) -> _lib.NufftTvInfo:
-        self._require_open()
-        out = _lib.NufftTvInfo()
-        out.struct_size = C.sizeof(_lib.NufftTvInfo)
-        _check(lib.nufft_tv_get_info(self._handle, C.byref(out)))
-        return out
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _check_arrays(self, us, what, count):
         if len(us) != count:
             raise DimensionMismatch(f"wrong amount of {what} arrays (expected {count})")
-        for u in us:
-            if not isinstance(u, torch.Tensor) or u.device != self.device:
-                raise ValueError(f"{what} must be torch tensors on {self.device}")
-            if u.dtype != self.Z:
-                raise ValueError(f"{what} must have element type {self.Z} (got {u.dtype})")
-            if tuple(u.shape) != self.shape:
-                raise DimensionMismatch(f"wrong dimensions of {what} array (expected tensor shape {self.shape}, got {tuple(u.shape)})")
-            if not u.is_contiguous():
-                raise ValueError(f"{what} must be contiguous")
+        super()._check_arrays(us, what, count)
 
     def _components(self, x):
         """A tensor (one component) or a tuple of ntransforms tensors -> (single, tuple)."""

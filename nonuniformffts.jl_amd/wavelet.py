@@ -15,6 +15,7 @@ import ctypes as C
 import torch
 
 from . import _lib
+from ._handle import _HandleObject
 from ._lib import lib
 from .plan import DimensionMismatch, PlanNUFFT, _check, _ptr_table
 from .toeplitz import ToeplitzOperator
@@ -26,12 +27,14 @@ def _wavelet_id(wavelet) -> int:
     return _lib.WAVELET_IDS[wavelet]
 
 
-class WaveletTransform:
+class WaveletTransform(_HandleObject):
     """``WaveletTransform(op_or_plan, wavelet="haar" | "db2", levels=L)``: element type, shape, ntransforms and device are those of a
     complex ``PlanNUFFT`` or of a ``ToeplitzOperator`` (neither is kept).  Every ``N_d`` must be a multiple of ``2^L``, and for
     ``"db2"`` ``N_d / 2^L >= 2``.  The transform acts on the array as stored, periodic in the storage index; it commutes with cyclic
     shifts by multiples of ``2^L``, so ``fftshift=True`` and ``False`` plans give the same prox whenever ``2^(L+1)`` divides every
     ``N_d``."""
+
+    _prefix, _info = "wavelet", _lib.NufftWaveletInfo
 
     def __init__(self, op_or_plan, wavelet: str = "haar", levels: int = 1):
         if not isinstance(op_or_plan, (PlanNUFFT, ToeplitzOperator)):
@@ -51,45 +54,6 @@ class WaveletTransform:
         _check(create(C.byref(self._handle), src._handle, C.byref(prm)))
         self.device, self.shape, self.ndim, self.ntransforms = src.device, src.shape, src.ndim, src.ntransforms
         self.wavelet, self.levels = wavelet, levels
-
-    def close(self):
-        h = getattr(self, "_handle", None)
-        if h is not None and h.value:
-            lib.nufft_wavelet_destroy(h)
-            self._handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _require_open(self):
-        if not self._handle.value:
-            raise ValueError("this WaveletTransform has been closed")
-
-    def info(self) -> _lib.NufftWaveletInfo:
-        self._require_open()
-        out = _lib.NufftWaveletInfo()
-        out.struct_size = C.sizeof(_lib.NufftWaveletInfo)
-        _check(lib.nufft_wavelet_get_info(self._handle, C.byref(out)))
-        return out
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _check_arrays(self, us, what):
-        if len(us) != self.ntransforms:
-            raise DimensionMismatch(f"wrong amount of {what} arrays (expected a tuple of {self.ntransforms} arrays)")
-        for u in us:
-            if not isinstance(u, torch.Tensor) or u.device != self.device:
-                raise ValueError(f"{what} must be torch tensors on {self.device}")
-            if u.dtype != self.Z:
-                raise ValueError(f"{what} must have element type {self.Z} (got {u.dtype})")
-            if tuple(u.shape) != self.shape:
-                raise DimensionMismatch(f"wrong dimensions of {what} array (expected tensor shape {self.shape}, got {tuple(u.shape)})")
-            if not u.is_contiguous():
-                raise ValueError(f"{what} must be contiguous")
 
     def _io(self, x, out):
         self._require_open()

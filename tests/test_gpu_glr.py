@@ -73,6 +73,43 @@ def test_map_against_the_svd(Ns, K, Z):
     glr.close()
 
 
+@pytest.mark.parametrize("Z", TYPES)
+def test_more_than_one_tile_per_workgroup(Z):
+    """A workgroup of the Gram kernel takes more than one tile, and both the last tile and the last workgroup are partial (asserted through
+    get_info).  K = 32 frames of 300 x 219 = 65 700 cells: plain seeded data, every singular value present (a random mixing matrix with
+    singular values from 1 down to 1/4), no operator."""
+    from nufft_pkg import nufft
+    _, Zc, _, eps = LC.dt(Z)
+    Ns, K = (300, 219), 32
+    plan = _plan(nufft, Z, Ns, K)
+    glr = nufft.GlobalLowRank(plan)
+    plan.close()
+    info = glr.info()
+    tiles = -(-info.cells // info.tile_cells)
+    per_group = -(-tiles // info.workgroups)
+    print(f"{Z}: {info.cells} cells, {tiles} tiles of {info.tile_cells}, {per_group} per workgroup, {info.workgroups} workgroups")
+    assert info.cells == 65700 and info.workgroups < tiles and per_group > 1
+    assert info.cells % info.tile_cells != 0                                              # the last tile is partial
+    assert (info.workgroups - 1) * per_group < tiles < info.workgroups * per_group      # and so is the last workgroup
+    rng = np.random.default_rng(65700)
+    n = info.cells
+    q, _ = np.linalg.qr(rng.standard_normal((K, K)) + 1j * rng.standard_normal((K, K)))
+    mix = q * np.geomspace(1.0, 0.25, K)[None, :]
+    x = (mix @ (rng.standard_normal((K, n)) + 1j * rng.standard_normal((K, n)))).reshape((K,) + Ns[::-1]).astype(Zc)
+    t = float(np.median(P.singular_values(x)))
+    want, nuc, zeroed = P.svt(x, t)
+    xd = tuple(_dev(v) for v in x)
+    y, nd = glr.apply(xd, t)
+    got = _host(y)
+    err, en = LC.rel(got, want), abs(float(nd.cpu()[0]) - nuc) / nuc
+    print(f"map {Z} N={Ns} K={K}: {err / eps:.1f} ε, nuclear norm {en / eps:.1f} ε (bar 256 ε), {glr.last_sweeps()} sweeps, {zeroed}/{K} zeroed")
+    assert err <= 256 * eps and en <= 256 * eps
+    assert 0 < zeroed < K
+    y2, n2 = glr.apply(xd, t)
+    assert np.array_equal(_host(y2), got) and np.array_equal(n2.cpu().numpy(), nd.cpu().numpy())
+    glr.close()
+
+
 @pytest.mark.parametrize("Ns,K", [((32, 40), 8), ((12, 10), 17)])
 def test_large_values_in_single_precision(Ns, K):
     from nufft_pkg import nufft
