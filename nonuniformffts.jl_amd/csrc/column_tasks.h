@@ -40,6 +40,17 @@ struct SMarchPlan {
     double visits, efficiency;  // model: point visits per point, and the share of the chip the launch keeps busy
 };
 
+// Decomposition of a grid for the spreading on MFMA patches (patch_kernels.h), chosen at plan creation (patch_plan)
+struct PatchPlan {
+    bool eligible;
+    int npx, npy, nseg, segl, ntasks;   // patch columns, segments of cube layers along dimension 3, wave tasks
+    int lds_bytes;                      // dynamic LDS per workgroup
+    int pby;                            // rows of cube columns per patch
+    int occ;                            // waves per SIMD the kernel is compiled for
+    int f32acc;                         // ComplexF32 on the FP32 matrix pipe with Float32 accumulators (patch32_kernels.h)
+    int planar;                         // real plans with ntransforms = 2 / 3: that many components spread together (0: one at a time)
+};
+
 // Side buffer of the halo variant: one record of reals per (plane z, column ty, tx) —
 //   [n2 strips of SW reals: the x reach of the column's own rows, XLO cells below then XHI above]
 //   [YLO + YHI rows of RW reals: the y reach (rows below, then above), each the full width of the window]

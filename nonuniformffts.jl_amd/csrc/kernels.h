@@ -127,18 +127,9 @@ hipError_t prepare_interp(int dtype, int is_complex, int D, int M, int lds_bytes
 bool needs_other_eval(int kernel, int evalmode);
 
 // ---- spreading on MFMA patches (patch_kernels.h, patch_*.hip) ------------------------------------------------------
-struct PatchPlan {
-    bool eligible;
-    int npx, npy, nseg, segl, ntasks;   // patch columns, segments of cube layers along dimension 3, wave tasks
-    int lds_bytes;                      // dynamic LDS per workgroup
-    int pby;                            // rows of cube columns per patch
-    int occ;                            // waves per SIMD the kernel is compiled for
-    int f32acc;                         // ComplexF32 on the FP32 matrix pipe with Float32 accumulators (patch32_kernels.h)
-    int planar;                         // real plans with ntransforms = 2 / 3: that many components spread together (0: one at a time)
-};
 // allow_f32acc: ComplexF32 plans may take the FP32-matrix-pipe kernel where the grid allows it (octets along dimension 3)
 // planar_nc: ntransforms of a real plan whose components may be spread together (2 or 3; 0 = one component per launch)
-PatchPlan patch_plan(int dtype, int is_complex, int D, int M, const Geom& g, bool other, bool allow_f32acc = true, int planar_nc = 0);
+PatchPlan patch_plan(const Options& opts, int dtype, int is_complex, int D, int M, const Geom& g, bool other, bool allow_f32acc = true, int planar_nc = 0);
 // set_points: cuts the patch columns into tasks of about equal point count and decides on the device which engine serves
 // this point set (balance.hip); choice = uint32[8], zeroed once; colsum[columns], first[columns + 1], tasktab[pp.ntasks]
 hipError_t launch_march_tasks(const Geom& g, const ColumnTasks& ct, const uint32_t* offsets, int64_t np, int cus, double advantage, double rho_eff_max,
@@ -165,14 +156,14 @@ hipError_t launch_gather_values(int dtype, int is_complex, int D, const void* so
 // ---- spreading on the z-marching LDS ring (smarch_kernels.h, smarch_*.hip) -------------------------------------------
 // 3-D plans with 4-cell bins and the default window evaluation whose axes are long enough; cus: compute units, C: components
 // halo: 0 = output-driven in x and y; 2 = the halo variant (real data, grids the column divides; falls back to 0 where it cannot run)
-SMarchPlan smarch_plan(int dtype, int is_complex, int D, int M, const Geom& g, bool other, int cus, int C, int halo, int parts = 1);
+SMarchPlan smarch_plan(const Options& opts, int dtype, int is_complex, int D, int M, const Geom& g, bool other, int cus, int C, int halo, int parts = 1);
 hipError_t prepare_spread_march(int dtype, int is_complex, int M, int halo);
 // flag: device flag of set_points (1: the ring serves this point set); tasktab: its task table
 hipError_t launch_spread_march(const TileKernelArgs& a, const SMarchPlan& sp, const uint32_t* flag, const uint2* tasktab, uint32_t* halo_state, bool dense, hipStream_t stream);
 bool spread_dense_available(int dtype, int is_complex, int M, bool poly, const SMarchPlan& sp);
 hipError_t prepare_spread_dense(int dtype, int M, bool poly);
 // halo variant: grid += side buffer (a.halo); the dimension-1 FFT pass of real plans does the same while it loads its lines (launch_real_lines)
-hipError_t launch_smarch_halo_add(const TileKernelArgs& a, const SMarchPlan& sp, const uint32_t* flag, hipStream_t stream);
+hipError_t launch_smarch_halo_add(const Options& opts, const TileKernelArgs& a, const SMarchPlan& sp, const uint32_t* flag, hipStream_t stream);
 // set_points: tasks of the ring for this point set and whether it serves it (advantage <= 0: always)
 hipError_t launch_smarch_tasks(const Geom& g, const SMarchPlan& sp, const uint32_t* offsets, int64_t np, int cus, double advantage,
                                uint32_t* choice, uint32_t* slots_in_use, uint32_t* colsum, uint32_t* first, uint2* tasktab, hipStream_t stream);

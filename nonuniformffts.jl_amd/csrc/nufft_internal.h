@@ -68,7 +68,7 @@ struct TileGeom {
 
 // Chooses bins and both tile shapes under the LDS budget; `forced_*` (cells, 0 = automatic) override
 // the search.  Returns false if not even the smallest tile fits (-> NUFFT_ERR_LDS_TOO_SMALL).
-bool choose_tiles(int D, int M, int ncomp, int real_bytes, const int64_t* Nover, int lds_budget_bytes,
+bool choose_tiles(const Options& opts, int D, int M, int ncomp, int real_bytes, const int64_t* Nover, int lds_budget_bytes,
                   int spread_waves, int interp_waves, const int* forced_sp, const int* forced_ip, int bin_log2,
                   TileGeom& g);
 
@@ -130,10 +130,7 @@ struct nufft_plan {
     bool spread_cubes = false;         // LDS-tile spreading accumulates cube by cube (v_mfma_f64_4x4x4 + one ds_add_f64 per cube)
     int spread_method = NUFFT_SPREAD_LDS_TILES;   // what nufft_spread launches (NUFFT_SPREAD_*)
     int spread_method_req = NUFFT_SPREAD_AUTO;    // what the caller asked for
-    struct Patch {                                // decomposition of the MFMA-patch spreading (patch_kernels.h)
-        bool eligible = false;
-        int npx = 0, npy = 0, nseg = 0, segl = 0, ntasks = 0, lds_bytes = 0, pby = 0, occ = 2, f32acc = 0, planar = 0;
-    } patch;
+    nufft::PatchPlan patch{};                     // decomposition of the MFMA-patch spreading (patch_kernels.h); eligible = false: none
     uint32_t* d_patch_choice = nullptr;   // [16]: scratch of patch_split_kernel; [2] = 1: this point set is spread by the patches
     uint32_t* d_patch_cols = nullptr;     // [columns] points per patch column, then [columns + 1] first task of each column
     void* d_patch_tasks = nullptr;        // uint2[ntasks]: {column, end layer << 16 | first layer}, rebuilt by every set_points
@@ -189,7 +186,7 @@ struct nufft_plan {
     bool dense_available = false;      // the spreading window's dense-set engine exists for this plan (dmarch_kernels.h)
     bool dense_now = false;            // ... and serves the current point set (set_points: mean bin load >= dense_min)
     int dense_min = 1 << 30;
-    int sort_column_pred[2] = {0, 0};  // host-only plans: the column-layer sort a device plan of these parameters would take (predict_sort_column)
+    int sort_column_pred[2] = {0, 0};  // host-only plans: the column-layer sort a device plan of these parameters would take (decide_engines for 256 CUs)
     int slab_max_keys = 0;             // keys the level-1 table was allocated for: min(kCoarseMaxKeys, nb[1] * nb[2])
     nufft::CoarseSort coarse{};        // column-layer sort (binsort.hip): enabled on plans whose two rings own the same columns; table allocated
     void* d_binrank = nullptr;         // uint2[Np]: (tile, rank)
@@ -237,3 +234,45 @@ struct nufft_plan {
     void* ev_end[NUFFT_NUM_STAGES] = {};
     bool ev_valid[NUFFT_NUM_STAGES] = {};
 };
+
+// -------------------------------------------------------------------------------------------
+// Engine decisions and per-point-set policy (plan_engines.cpp): functions of the plan's parameters, host arithmetic only
+// -------------------------------------------------------------------------------------------
+namespace nufft {
+
+struct Geom;
+Geom make_geom(const nufft_plan* p);
+
+struct FftPath { bool pruned, compact_dim1; };
+struct InterpRing { bool available; int mode, parts; };      // NUFFT_INTERP_MARCH; 2 parts: ComplexF64 through the real kernels
+// What build_device allocates for
+struct EngineDecision {
+    int spread_method;             // NUFFT_SPREAD_*
+    bool ring_lost;                // the caller asked for the marching ring, and this device has no decomposition for it
+    SMarchPlan smarch;             // the spreading ring's plan for this device (halo = 2: it wants the side buffer)
+    InterpRing interp;
+    ColumnTasks march_ct;          // the interpolation ring's column: its own, or
+    bool shared_column;            // ... the spreading window's (column-layer sort)
+    bool dense_available;
+    int dense_min;
+    bool slab;                     // two-level slab sort, and its parameters
+    int slab_min_points, slab_fill, slab_max_keys;
+    bool adaptive;                 // the rings' decisions feed back into the choice of the sort
+};
+
+SMarchPlan ring_ladder(const nufft_plan& p, int num_cus, int want_halo, int parts);
+SMarchPlan creation_stage_ring(const nufft_plan& p, int* parts_out);
+int auto_spread_method(const nufft_plan& p, const SMarchPlan& sm);
+FftPath fft_path(const nufft_plan& p);
+InterpRing choose_interp_ring(const nufft_plan& p);
+bool shared_ring_column(const nufft_plan& p, const SMarchPlan& sm, int interp_parts, ColumnTasks* shared);
+EngineDecision decide_engines(const nufft_plan& p, int num_cus, bool halo_allowed);
+
+int64_t sort_scratch_bytes(const nufft_plan& p, int64_t np, bool slab_sort);
+int slab_height(const nufft_plan& p, int64_t np);
+double patch_advantage(const nufft_plan& p);
+double smarch_advantage(const nufft_plan& p);
+double march_advantage(const nufft_plan& p, int64_t np);
+double march_rho_bound(const nufft_plan& p);
+
+}  // namespace nufft

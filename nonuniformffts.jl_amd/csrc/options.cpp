@@ -4,8 +4,6 @@
 
 namespace nufft {
 
-static thread_local const Options* g_current = nullptr;
-
 void Options::parse(const char* text) {
     if (!text) return;
     std::string s(text);
@@ -29,14 +27,9 @@ std::string Options::str() const {
     return out;
 }
 
-void set_current_options(const Options* o) { g_current = o; }
-const Options* current_options() { return g_current; }
-
-const char* option_str(const char* name) {
-    if (g_current) {
-        auto it = g_current->kv.find(name);
-        if (it != g_current->kv.end()) return it->second.c_str();
-    }
+const char* Options::option_str(const char* name) const {
+    auto it = kv.find(name);
+    if (it != kv.end()) return it->second.c_str();
 #if defined(NUFFT_ENV_SWITCHES) && NUFFT_ENV_SWITCHES
     const char* v = std::getenv(name);
     if (v && *v) return v;
@@ -44,14 +37,14 @@ const char* option_str(const char* name) {
     return nullptr;
 }
 
-bool option_present(const char* name) { return option_str(name) != nullptr; }
+bool Options::option_present(const char* name) const { return option_str(name) != nullptr; }
 
-int option_int(const char* name, int fallback) {
+int Options::option_int(const char* name, int fallback) const {
     const char* v = option_str(name);
     return (v && *v) ? std::atoi(v) : fallback;
 }
 
-double option_double(const char* name, double fallback) {
+double Options::option_double(const char* name, double fallback) const {
     const char* v = option_str(name);
     return (v && *v) ? std::atof(v) : fallback;
 }

@@ -6,6 +6,8 @@
 // falls back to getenv for names the options string does not hold.
 // (The Python development harness, nonuniformffts.jl_amd/plan.py, forwards NUFFT_* environment variables of ITS process as this
 // string, so the helper scripts and tests keep their command lines; the Julia binding forwards nothing.)
+//
+// There is no "current" set of options: whatever reads a switch is handed the plan's Options (or the value latched at plan creation).
 #pragma once
 
 #include <map>
@@ -15,18 +17,13 @@ namespace nufft {
 
 struct Options {
     std::map<std::string, std::string> kv;
-    void parse(const char* text);            // "A=1;B=2" (also ',' or whitespace between entries); later entries win
+    void parse(const char* text);            // "A=1;B=2" (also whitespace between entries); later entries win
     std::string str() const;                 // canonical form, sorted by name
+
+    int option_int(const char* name, int fallback) const;
+    double option_double(const char* name, double fallback) const;
+    bool option_present(const char* name) const;
+    const char* option_str(const char* name) const;    // nullptr when absent
 };
-
-// Options the calling thread currently works under: those of the plan being created, or of the plan the current API call was made on
-// (set at the top of every entry point that can reach a switch; cleared when that plan is destroyed).
-void set_current_options(const Options* o);
-const Options* current_options();
-
-int option_int(const char* name, int fallback);
-double option_double(const char* name, double fallback);
-bool option_present(const char* name);
-const char* option_str(const char* name);    // nullptr when absent
 
 }  // namespace nufft

@@ -25,33 +25,6 @@ static std::once_flag g_rocfft_once;
 
 static size_t value_bytes(const nufft_plan* p) { return real_bytes(p->dtype) * (p->is_complex ? 2 : 1); }
 
-static TileShape make_shape(const nufft::TileShapeHost& h) {
-    TileShape t{};
-    for (int d = 0; d < 3; ++d) {
-        t.n[d] = h.n[d];
-        t.nt[d] = h.nt[d];
-    }
-    t.row_stride = h.row_stride;
-    t.plane_stride = h.plane_stride;
-    t.elems = (int)h.elems;
-    t.ntiles = (int)h.ntiles;
-    t.max_items = h.max_items;
-    return t;
-}
-
-static Geom make_geom(const nufft_plan* p) {
-    Geom g{};
-    for (int d = 0; d < 3; ++d) {
-        g.Nover[d] = (int)p->Nover[d];
-        g.blog[d] = p->tile.blog[d];
-        g.nb[d] = p->tile.nb[d];
-    }
-    g.nbins = (int)p->tile.nbins;
-    g.sp = make_shape(p->tile.sp);
-    g.ip = make_shape(p->tile.ip);
-    return g;
-}
-
 // Every device allocation of a plan goes through here: workspace_bytes and the per-buffer breakdown (nufft_workspace_breakdown) are
 // what the registry holds, so they cannot drift apart.  `name`: the row of DESIGN.md section 3 the buffer belongs to.
 static int dev_alloc(nufft_plan* p, void** ptr, size_t bytes, const char* name = "tables") {
@@ -85,6 +58,10 @@ static int upload(nufft_plan* p, void** dst, const std::vector<double>& src) {
     return NUFFT_OK;
 }
 
+static int upload_real(nufft_plan* p, void** dst, const std::vector<double>& src) {      // ... in the plan's precision
+    return p->dtype == NUFFT_F32 ? upload<float>(p, dst, src) : upload<double>(p, dst, src);
+}
+
 static int upload_i32(nufft_plan* p, int32_t** dst, const std::vector<int32_t>& src) {
     int rc = dev_alloc(p, reinterpret_cast<void**>(dst), src.size() * sizeof(int32_t));
     if (rc) return rc;
@@ -113,38 +90,9 @@ struct StageTimer {
 // ------------------------------------------------------------------------------------------
 // plan construction
 // ------------------------------------------------------------------------------------------
-// development switches: nufft_params.options of the plan at hand (options.h) — never the environment in a release build
-static int env_int(const char* name, int fallback) { return option_int(name, fallback); }
-
-// Default of the spreading ring's halo variant for this plan (0: clipped columns, 2: halo variant); see DESIGN.md section 4.9.
-// Measured (256^3 -> 512^3, Np = 1e7; spread + FFT stages, ms; scripts/r4_halo_matrix.sh): Float64 m = 2 ... 7: 2.08 / 2.57 / 3.03 / 5.72 /
-// 11.4 / 20.7 with clipped columns, 1.88 / 2.22 / 2.62 / 4.68 / 8.35 / 14.8 with the halo variant; Float32 alike (m = 8: 17.3 -> 13.1).
-// Only where the plan's own dimension-1 pass adds the side buffer (real plans on the pruned FFT path); smarch_plan falls back to the
-// clipped columns where the variant cannot run (axes the column does not divide, LDS).
-// Complex data (interleaved components double the window): it pays where a 32 x 16 column or larger still fits — ComplexF64 m = 2 (3.29 -> 2.84 ms),
-// ComplexF32 m = 2, 3 (2.55 -> 1.97, 4.03 -> 3.51); with 16 x 16 columns the reach is 1.2 x the grid (ComplexF64 m = 3: 4.70 -> 5.08 ms).
-static int smarch_halo_default(const nufft_plan* p) {      // (build_device: ... and only on the plan's own pruned FFT path)
-    if (p->D != 3) return 0;
-    if (!p->is_complex || p->smarch_parts == 2) return 2;      // (complex data part by part through the real kernel: as real data)
-    return p->M <= (p->dtype == NUFFT_F32 ? 3 : 2) ? 2 : 0;
-}
-
-// Largest half-support for which the automatic choice takes the marching window (measured spread + FFT stages):
-// real data 6 (Float32 with the halo variant: 7); complex data part by part through the real kernel: 6 — measured round 5, 256^3 -> 512^3,
-// Np = 1e7, spread + FFT stages in ms, window against patches: ComplexF64 m = 4 5.46 / 6.31 (interleaved window), m = 5 9.87 / 14.30, m = 6 14.47 / 24.88,
-// m = 7 24.10 / 24.29; ComplexF32 m = 4 4.65 / 5.61, m = 5 8.78 / 9.94, m = 6 13.08 / 15.08, m = 7 20.67 / 14.94; the interleaved complex
-// instantiations (NUFFT_SMARCH_SPLIT=0): ComplexF64 4, ComplexF32 3
-static int ring_max_half_support(const nufft_plan* p) {
-    if (!p->is_complex) return (p->dtype == NUFFT_F32 && p->smarch.halo == 2) ? 7 : 6;
-    if (p->smarch.parts == 2 && p->smarch.halo == 2) return 6;
-    return p->dtype == NUFFT_F64 ? 4 : 3;
-}
-
-static void predict_sort_column(nufft_plan* p);
-
 static int build_host(nufft_plan* p, const nufft_params* in) {
     p->opts.parse(in->options);
-    set_current_options(&p->opts);
+    const Options& o = p->opts;      // development switches: nufft_params.options of this plan (options.h) — never the environment in a release build
     p->dtype = in->dtype;
     p->is_complex = in->is_complex != 0;
     p->D = in->ndim;
@@ -265,19 +213,19 @@ static int build_host(nufft_plan* p, const nufft_params* in) {
     }
 
     // bins and tile geometry
-    p->spread_threads = in->spread_threads > 0 ? in->spread_threads : env_int("NUFFT_SPREAD_THREADS", 1024);
-    p->interp_threads = in->interp_threads > 0 ? in->interp_threads : env_int("NUFFT_INTERP_THREADS", 1024);
+    p->spread_threads = in->spread_threads > 0 ? in->spread_threads : o.option_int("NUFFT_SPREAD_THREADS", 1024);
+    p->interp_threads = in->interp_threads > 0 ? in->interp_threads : o.option_int("NUFFT_INTERP_THREADS", 1024);
     if (p->spread_threads % 64 || p->interp_threads % 64 || p->spread_threads > 1024 || p->interp_threads > 1024 ||
         p->spread_threads < 64 || p->interp_threads < 64)
         return fail(NUFFT_ERR_INVALID_ARG, "workgroup sizes must be multiples of 64 in 64..1024");
-    int budget = in->lds_budget_bytes > 0 ? in->lds_budget_bytes : env_int("NUFFT_LDS_BUDGET", kLdsLimit);
+    int budget = in->lds_budget_bytes > 0 ? in->lds_budget_bytes : o.option_int("NUFFT_LDS_BUDGET", kLdsLimit);
     if (budget > kLdsLimit - 256) budget = kLdsLimit - 256;   // small margin for compiler-generated LDS
     const int ncomp = p->is_complex ? 2 : 1;
     const int rb = (int)real_bytes(p->dtype);
     int forced_sp[3] = {in->tile_dims[0], in->tile_dims[1], in->tile_dims[2]};
     int forced_ip[3] = {in->interp_tile_dims[0], in->interp_tile_dims[1], in->interp_tile_dims[2]};
-    auto env_tile = [](const char* name, int* out) {
-        const char* e = option_str(name);
+    auto env_tile = [&o](const char* name, int* out) {
+        const char* e = o.option_str(name);
         if (e && *e && out[0] <= 0) {
             int a = 0, b = 0, c = 0;
             const int n = std::sscanf(e, "%d,%d,%d", &a, &b, &c);
@@ -286,13 +234,13 @@ static int build_host(nufft_plan* p, const nufft_params* in) {
     };
     env_tile("NUFFT_SPREAD_TILE", forced_sp);
     env_tile("NUFFT_INTERP_TILE", forced_ip);
-    int bin_log2 = in->bin_log2 > 0 ? in->bin_log2 : env_int("NUFFT_BIN_LOG2", 2);
+    int bin_log2 = in->bin_log2 > 0 ? in->bin_log2 : o.option_int("NUFFT_BIN_LOG2", 2);
     if (bin_log2 < 1 || bin_log2 > 4) return fail(NUFFT_ERR_INVALID_ARG, "bin_log2 must be in 1..4");
     // Default configuration on a large grid: take the compile-time interpolation tile, whose kernel
     // variant has constant LDS strides (fixed_interp_tile, device_common.h).
     int fixed_ip[4] = {0, 0, 0, 0};
     if (forced_ip[0] <= 0 && bin_log2 == 2 && p->interp_threads == 1024 && budget == kLdsLimit - 256 &&
-        env_int("NUFFT_INTERP_FIXED", 1)) {
+        o.option_int("NUFFT_INTERP_FIXED", 1)) {
         interp_fixed_dims(p->dtype, p->is_complex, p->D, p->M, fixed_ip);
         bool ok = fixed_ip[0] > 0;
         for (int d = 0; d < p->D && ok; ++d) ok = fixed_ip[d] < p->Nover[d];
@@ -302,7 +250,7 @@ static int build_host(nufft_plan* p, const nufft_params* in) {
     // the same for the spreading tile (fixed_spread_tile): every edge must leave room for the clipped halo
     int fixed_sp[5] = {0, 0, 0, 0, 0};
     if (forced_sp[0] <= 0 && bin_log2 == 2 && p->spread_threads == 1024 && budget == kLdsLimit - 256 &&
-        env_int("NUFFT_SPREAD_FIXED", 1)) {
+        o.option_int("NUFFT_SPREAD_FIXED", 1)) {
         spread_fixed_dims(p->dtype, p->is_complex, p->D, p->M, fixed_sp);
         bool ok = fixed_sp[0] > 0;
         for (int d = 0; d < p->D && ok; ++d) ok = fixed_sp[d] + 2 * p->M - 1 <= p->Nover[d] && fixed_sp[d] < p->Nover[d];
@@ -313,14 +261,14 @@ static int build_host(nufft_plan* p, const nufft_params* in) {
     // complex Float64) retry with smaller bins down to single cells.
     bool found = false;
     for (; bin_log2 >= 0 && !found; --bin_log2) {
-        found = choose_tiles(p->D, p->M, ncomp, rb, p->Nover, budget, p->spread_threads / 64, p->interp_threads / 64,
+        found = choose_tiles(o, p->D, p->M, ncomp, rb, p->Nover, budget, p->spread_threads / 64, p->interp_threads / 64,
                              forced_sp, forced_ip, bin_log2, p->tile);
         if (!found && (fixed_sp[0] > 0 || fixed_ip[0] > 0)) {
             // the compile-time tiles are not the caller's choice: fall back to the run-time search
             if (fixed_sp[0] > 0) forced_sp[0] = forced_sp[1] = forced_sp[2] = 0;
             if (fixed_ip[0] > 0) forced_ip[0] = forced_ip[1] = forced_ip[2] = 0;
             fixed_sp[0] = fixed_ip[0] = 0;
-            found = choose_tiles(p->D, p->M, ncomp, rb, p->Nover, budget, p->spread_threads / 64, p->interp_threads / 64,
+            found = choose_tiles(o, p->D, p->M, ncomp, rb, p->Nover, budget, p->spread_threads / 64, p->interp_threads / 64,
                                  forced_sp, forced_ip, bin_log2, p->tile);
         }
     }
@@ -337,7 +285,7 @@ static int build_host(nufft_plan* p, const nufft_params* in) {
     // cube accumulation: the tile's cubes must be the grid's cubes (oversampled sizes that are multiples of 4)
     // (opt-in: measured slower than the face mapping at C2, 3.94 against 3.09 ms — the LDS pipe is saturated either way,
     // DESIGN.md section 4.4)
-    p->spread_cubes = p->spread_fixed && env_int("NUFFT_SPREAD_CUBES", 0) != 0 &&
+    p->spread_cubes = p->spread_fixed && o.option_int("NUFFT_SPREAD_CUBES", 0) != 0 &&
                       spread_cubes_available(p->dtype, p->is_complex, p->D, p->M);
     for (int d = 0; d < p->D; ++d) p->spread_cubes = p->spread_cubes && p->Nover[d] % 4 == 0;
     p->lds_spread = lds_layout((int)p->tile.sp.elems, 8, rb, p->D, p->M, ncomp, p->spread_threads / 64, p->tile.sp.max_items,
@@ -346,149 +294,47 @@ static int build_host(nufft_plan* p, const nufft_params* in) {
     if (p->lds_spread > kLdsLimit || p->lds_interp > kLdsLimit)
         return fail(NUFFT_ERR_LDS_TOO_SMALL, "LDS is too small for the chosen problem: work-item table does not fit");
     if (p->tile.nbins >= ((int64_t)1 << 31) - 2) return fail(NUFFT_ERR_UNSUPPORTED, "too many bins");
+    const FftPath fft = fft_path(*p);
+    p->pruned_fft = fft.pruned;
+    p->compact_dim1 = fft.compact_dim1;
     // spreading engine: MFMA patches where they apply (3-D, 4-cell bins, default window evaluation), LDS tiles otherwise
     {
-        int req = in->spread_method != NUFFT_SPREAD_AUTO ? in->spread_method : env_int("NUFFT_SPREAD_METHOD", NUFFT_SPREAD_AUTO);
+        int req = in->spread_method != NUFFT_SPREAD_AUTO ? in->spread_method : o.option_int("NUFFT_SPREAD_METHOD", NUFFT_SPREAD_AUTO);
         if (req < NUFFT_SPREAD_AUTO || req > NUFFT_SPREAD_MARCHING_RING) return fail(NUFFT_ERR_INVALID_ARG, "unknown spread_method");
         p->spread_method_req = req;
         // NUFFT_PATCH_F32ACC=0: ComplexF32 plans keep the Float64-accumulating patch kernel (A/B runs)
         // NUFFT_PATCH_PLANAR=0: the components of a real plan with ntransforms = 2 / 3 are spread one after the other (A/B runs)
-        const int planar_nc = (!p->is_complex && (p->C == 2 || p->C == 3) && env_int("NUFFT_PATCH_PLANAR", 1) != 0) ? p->C : 0;
-        const PatchPlan pp = patch_plan(p->dtype, p->is_complex, p->D, p->M, make_geom(p), needs_other_eval(p->kernel, p->evalmode),
-                                        env_int("NUFFT_PATCH_F32ACC", 1) != 0, planar_nc);
-        p->patch.eligible = pp.eligible;
-        p->patch.npx = pp.npx; p->patch.npy = pp.npy; p->patch.nseg = pp.nseg; p->patch.segl = pp.segl;
-        p->patch.ntasks = pp.ntasks; p->patch.lds_bytes = pp.lds_bytes; p->patch.pby = pp.pby; p->patch.occ = pp.occ; p->patch.f32acc = pp.f32acc; p->patch.planar = pp.planar;
-        if (req == NUFFT_SPREAD_MFMA_PATCHES && !pp.eligible)
+        const int planar_nc = (!p->is_complex && (p->C == 2 || p->C == 3) && o.option_int("NUFFT_PATCH_PLANAR", 1) != 0) ? p->C : 0;
+        p->patch = patch_plan(o, p->dtype, p->is_complex, p->D, p->M, make_geom(p), needs_other_eval(p->kernel, p->evalmode),
+                             o.option_int("NUFFT_PATCH_F32ACC", 1) != 0, planar_nc);
+        if (req == NUFFT_SPREAD_MFMA_PATCHES && !p->patch.eligible)
             return fail(NUFFT_ERR_UNSUPPORTED, "spread_method = MFMA patches needs a 3-D grid of 4-cell bins with every oversampled "
                                                "axis a multiple of 4 and at least 2 (patch + stencil) bins long, and the default window evaluation");
-        // automatic choice, from the measurements in DESIGN.md section 4.4: the patches win where the stencil carries
-        // more matrix work per point visit (complex data, M >= 5: 1.15x ... 2x), the LDS tiles for real data at M <= 4
-        // — and for real plans with ntransforms = 2 / 3, whose components the patches spread together (shared windows and operands:
-        // C4 9.1 -> 7.5 ms, two components 6.1 -> 5.2 ms)
-        const bool prefer_patches = p->is_complex || p->M >= 5 || pp.planar != 0 || env_int("NUFFT_PREFER_PATCHES", 0) != 0;     // (the switch: test runs)
-        p->spread_method = (pp.eligible && (req == NUFFT_SPREAD_MFMA_PATCHES || (req == NUFFT_SPREAD_AUTO && prefer_patches)))
-                               ? NUFFT_SPREAD_MFMA_PATCHES : NUFFT_SPREAD_LDS_TILES;
-        // third engine, the z-marching LDS window (smarch_kernels.h): the per-point arithmetic of the LDS tiles with 1.5 instead of
-        // 2.1 visits per point and no per-plane control.  Automatic choice from the measured spread stage of the three engines
-        // (256^3 -> 512^3, Np = 1e7): real data up to M = 6 (M = 4: 2.44 ms against 3.07 tiles / 4.05 patches;
-        // M = 6: 10.8 / 15.5 / 13.2; M = 7: 20.1 against 13.4 patches), ntransforms components one after the other (C = 3: 7.3 ms
-        // against 7.5 with the planar patches); ComplexF64 up to M = 4 (5.06 against 5.36 patches), ComplexF32 up to M = 3 (M = 4:
-        // 4.71 against 4.10 patches).  256 CUs assumed here, build_device() redoes the decomposition for the device.
-        // halo variant of the ring (every point spread once, the stencil reach through a side buffer that the first FFT pass adds):
-        // real data on grids whose axes the column divides; NUFFT_SMARCH_HALO=0 / 2 forces the choice (A/B runs, tests)
-        // complex data part by part through the REAL window kernel (smarch_kernels.h: 8 x 8 faces, 32 x 32 columns, halo variant — ComplexF64
-        // m = 4: 5.06 -> 3.9 ms); NUFFT_SMARCH_SPLIT=0: the interleaved complex instantiations (A/B runs, tests)
-        p->smarch_parts = (p->is_complex && env_int("NUFFT_SMARCH_SPLIT", 1) != 0) ? 2 : 1;
-        const int want_halo = env_int("NUFFT_SMARCH_HALO", smarch_halo_default(p)) == 2 ? 2 : 0;
-        p->smarch = smarch_plan(p->dtype, p->is_complex, p->D, p->M, make_geom(p), needs_other_eval(p->kernel, p->evalmode), 256, p->C, want_halo, p->smarch_parts);
-        if (!p->smarch.eligible && want_halo)
-            p->smarch = smarch_plan(p->dtype, p->is_complex, p->D, p->M, make_geom(p), needs_other_eval(p->kernel, p->evalmode), 256, p->C, 0, p->smarch_parts);
-        if (!p->smarch.eligible && p->smarch_parts == 2) {      // no real-kernel decomposition: the complex instantiations as before
-            p->smarch_parts = 1;
-            const int wh = env_int("NUFFT_SMARCH_HALO", smarch_halo_default(p)) == 2 ? 2 : 0;
-            p->smarch = smarch_plan(p->dtype, p->is_complex, p->D, p->M, make_geom(p), needs_other_eval(p->kernel, p->evalmode), 256, p->C, wh, 1);
-            if (!p->smarch.eligible && wh)
-                p->smarch = smarch_plan(p->dtype, p->is_complex, p->D, p->M, make_geom(p), needs_other_eval(p->kernel, p->evalmode), 256, p->C, 0, 1);
-        }
+        // the ring's decomposition for 256 CUs, then the engine (plan_engines.cpp: the rules and their measurements)
+        p->smarch = creation_stage_ring(*p, &p->smarch_parts);
         if (req == NUFFT_SPREAD_MARCHING_RING && !p->smarch.eligible)
             return fail(NUFFT_ERR_UNSUPPORTED, "spread_method = marching ring needs a 3-D grid of 4-cell bins with every oversampled axis a multiple "
                                                "of 4 and longer than a column plus a stencil, and the default window evaluation");
-        // (with the halo variant the window also beats the patches for Float32 at M = 7: 10.8 against 12.8 ms spread + FFT)
-        const int ring_max_m = ring_max_half_support(p);
-        const bool prefer_ring = env_int("NUFFT_PREFER_RING", 1) != 0 && p->M <= ring_max_m && env_int("NUFFT_PREFER_PATCHES", 0) == 0;
-        if (p->smarch.eligible && (req == NUFFT_SPREAD_MARCHING_RING || (req == NUFFT_SPREAD_AUTO && prefer_ring)))
-            p->spread_method = NUFFT_SPREAD_MARCHING_RING;
+        p->spread_method = auto_spread_method(*p, p->smarch);
     }
-    if (p->device < 0) predict_sort_column(p);
+    if (p->device < 0) {      // host-only plans report the sort column of a device plan on 256 CUs whose side buffer can be allocated
+        const EngineDecision e = decide_engines(*p, 256, true);
+        p->sort_column_pred[0] = e.shared_column ? e.march_ct.bxw : 0;
+        p->sort_column_pred[1] = e.shared_column ? e.march_ct.byw : 0;
+    }
     return NUFFT_OK;
 }
 
-// Column-layer sort: ONE column for both rings — the spreading window's (chosen for this grid by its launch model, smarch_plan); the
-// interpolation ring takes it wherever its kernels can hold it (a column <= their compile-time one: march_setup.inc).  Round 6; before,
-// only plans whose two rings happened to pick the same column qualified (Float64 / ComplexF64 m = 4).  `sm`: the window's final plan
-// (halo variant), p->interp_parts decided.  Pure host arithmetic: also what the prediction for host-only plans runs (predict_sort_column).
-static bool shared_ring_column(const nufft_plan* p, const SMarchPlan& sm, ColumnTasks* shared) {
-    if (!sm.eligible || sm.halo != 2 || p->D != 3) return false;
-    const int nkeys = sm.ct.ncolx * sm.ct.ncoly * p->tile.nb[2];
-    const int mcplx = p->interp_parts == 2 ? 0 : (int)p->is_complex;
-    const bool poly = p->evalmode != NUFFT_EVAL_DIRECT;
-    if (p->Nover[0] % sm.n1 != 0 || p->Nover[1] % sm.n2 != 0 || nkeys > kCoarseMaxKeys) return false;
-    // Measured (256^3 -> 512^3, Np = 1e7, set_points + spread / set_points + interpolation against the plan without it, ms; scripts/r6_e.sh,
-    // profiles/round6_*): Float64 m = 2 / 3 / 4 -0.18 / -0.18 / -0.12 and -0.14 / -0.20 / -0.21, ComplexF64 m = 4 -0.12 / -0.29, Float32 m = 3 / 4
-    // -0.06 / -0.03 and -0.07 / -0.04, ComplexF32 m = 3 / 4 -0.15 / -0.04 and -0.02 / -0.02 (polynomial window: +0.02) — and Float32 m = 2
-    // -0.11 but +0.12 (Direct) / +0.22 (polynomial) on the type-2 side: its ring gathers through the LDS strips (no register window at 4-lane
-    // rows) from a 64 x 64 column of its own, which the 32 x 32 window column cannot replace.  That one keeps its own column
-    // (NUFFT_COARSE_SORT=2: shared all the same — the test of its staged instantiation).
-    if (p->dtype == NUFFT_F32 && !p->is_complex && p->M == 2 && env_int("NUFFT_COARSE_SORT", 1) != 2) return false;
-    if (!interp_march_staged_available(p->dtype, mcplx, p->M, poly, sm.n1, sm.n2)) return false;
-    const ColumnTasks ct = march_column_tasks(p->dtype, mcplx, p->M, poly, make_geom(p), sm.n1, sm.n2);
-    if (ct.ntasks <= 0 || ct.ncolx != sm.ct.ncolx || ct.ncoly != sm.ct.ncoly || (size_t)ct.ncolx * ct.ncoly >= 65536 || p->tile.nb[2] > 2048) return false;
-    *shared = ct;
-    return true;
-}
-
-// interpolation ring: which form (complex data part by part through the real kernels?) and whether it exists for this plan — host arithmetic
-static bool choose_interp_ring(nufft_plan* p) {
-    p->interp_march_mode = env_int("NUFFT_INTERP_MARCH", 1);
-    // ComplexF64 part by part through the REAL ring kernels (march_setup.inc, MarchGeom::parts = 2): the complex instantiation reads 128-bit pairs
-    // from LDS at a quarter of the rate (scripts/microbench7.hip) and owns a narrower column — two passes of the real kernel are faster from
-    // m = 4 on (interpolation stage 256^3 -> 512^3, Np = 1e7: 2.76 against 2 x 1.2 ms; m = 8: 20.4 against 2 x 5.8), and the plan can then share
-    // its columns with the spreading window (column-layer sort).  ComplexF32 keeps its paired-lane kernel (1.25 ms against 2 x 1.08).
-    // NUFFT_INTERP_SPLIT=0: the complex instantiations (A/B runs, tests)
-    p->interp_parts = (p->is_complex && p->dtype == NUFFT_F64 && env_int("NUFFT_INTERP_SPLIT", 1) != 0) ? 2 : 1;
-    const bool other = needs_other_eval(p->kernel, p->evalmode), poly = p->evalmode != NUFFT_EVAL_DIRECT;
-    bool ok = p->interp_march_mode != 0 && interp_march_available(p->dtype, p->interp_parts == 2 ? 0 : (int)p->is_complex, p->D, p->M, poly, make_geom(p), other);
-    if (!ok && p->interp_parts == 2) {
-        p->interp_parts = 1;
-        ok = p->interp_march_mode != 0 && interp_march_available(p->dtype, p->is_complex, p->D, p->M, poly, make_geom(p), other);
-    }
-    return ok;
-}
-
-// What a device plan of these parameters would report as nufft_info.sort_column on a 256-CU device whose side buffer can be allocated:
-// the decisions of build_device that need no device, in its order.  Host-only plans report it (tests compute a GPU test's eligibility here).
-static void predict_sort_column(nufft_plan* p) {
-    p->sort_column_pred[0] = p->sort_column_pred[1] = 0;
-    if (p->D != 3 || p->spread_method != NUFFT_SPREAD_MARCHING_RING || env_int("NUFFT_COARSE_SORT", 1) == 0) return;
-    bool pruned = env_int("NUFFT_PRUNED_FFT", 1) != 0;
-    for (int d = p->is_complex ? 0 : 1; d < p->D && pruned; ++d) pruned = fft_lines_supported(p->dtype, p->Nover[d]);
-    const bool compact = pruned && (p->is_complex || (real_lines_supported(p->dtype, p->Nover[0]) && env_int("NUFFT_COMPACT_DIM1", 1) != 0));
-    int want_halo = p->smarch.halo;
-    if (want_halo == 2 && !(pruned && compact) && env_int("NUFFT_SMARCH_HALO", 0) != 2) want_halo = 0;
-    if (want_halo != 2) return;
-    SMarchPlan sm = smarch_plan(p->dtype, p->is_complex, p->D, p->M, make_geom(p), needs_other_eval(p->kernel, p->evalmode), 256, p->C, want_halo, p->smarch_parts);
-    if (!sm.eligible || sm.halo != 2) return;
-    const int save_parts = p->interp_parts, save_mode = p->interp_march_mode;
-    ColumnTasks shared{};
-    if (choose_interp_ring(p) && shared_ring_column(p, sm, &shared)) { p->sort_column_pred[0] = shared.bxw; p->sort_column_pred[1] = shared.byw; }
-    p->interp_parts = save_parts; p->interp_march_mode = save_mode;
-}
-
-static int build_device(nufft_plan* p) {
-    int ndev = 0;
-    NUFFT_HIP(hipGetDeviceCount(&ndev));
-    if (p->device >= ndev) return fail(NUFFT_ERR_INVALID_ARG, "device ordinal out of range");
-    DeviceGuard guard(p->device);
-    std::call_once(g_rocfft_once, [] { (void)rocfft_setup(); });
-    {
-        // every engine set-up below (ring launch models, sort slices) sizes itself for this device — not for the default of 256 CUs
-        hipDeviceProp_t prop;
-        NUFFT_HIP(hipGetDeviceProperties(&prop, p->device));
-        p->num_cus = prop.multiProcessorCount;
-    }
-
+static int upload_tables(nufft_plan* p) {
     int rc;
-    const int D = p->D, L = 2 * p->M;
+    const int D = p->D;
     // polynomial coefficients [D][npoly][2M]
     {
         std::vector<double> all;
         for (int d = 0; d < D; ++d)
             for (double c : p->coefs[d]) all.push_back(std::ldexp(c, p->scale_exp[d]));
         if (all.empty()) all.push_back(0.0);      // kernels without a polynomial form (Gaussian, B-spline)
-        (void)L;
-        rc = p->dtype == NUFFT_F32 ? upload<float>(p, &p->d_coefs, all) : upload<double>(p, &p->d_coefs, all);
-        if (rc) return rc;
+        if ((rc = upload_real(p, &p->d_coefs, all))) return rc;
     }
     for (int d = 0; d < D; ++d) {
         {
@@ -498,8 +344,7 @@ static int build_device(nufft_plan* p) {
                 const double v = p->dtype == NUFFT_F32 ? (double)(float)p->phihat[d][i] : p->phihat[d][i];
                 ph[i] = std::ldexp(v, p->scale_exp[d]);
             }
-            rc = p->dtype == NUFFT_F32 ? upload<float>(p, &p->d_phihat[d], ph) : upload<double>(p, &p->d_phihat[d], ph);
-            if (rc) return rc;
+            if ((rc = upload_real(p, &p->d_phihat[d], ph))) return rc;
         }
         std::vector<int32_t> im(p->index_map[d].size());
         std::vector<int32_t> inv((size_t)p->Nspec[d], -1);
@@ -510,7 +355,13 @@ static int build_device(nufft_plan* p) {
         if ((rc = upload_i32(p, &p->d_index_map[d], im))) return rc;
         if ((rc = upload_i32(p, &p->d_inv_map[d], inv))) return rc;
     }
+    return NUFFT_OK;
+}
 
+static int alloc_grids_and_fft(nufft_plan* p) {
+    int rc;
+    const int D = p->D;
+    const Options& o = p->opts;
     // oversampled arrays (init_plan_data, src/plan.jl:37-60), components contiguous
     p->grid_elems = 1;
     p->spec_elems = 1;
@@ -519,19 +370,16 @@ static int build_device(nufft_plan* p) {
         p->spec_elems *= p->Nspec[d];
     }
     if ((rc = dev_alloc(p, &p->d_us, (size_t)p->grid_elems * value_bytes(p) * p->C, "us"))) return rc;
-    // pruned FFT path: D >= 2, every higher dimension (and dimension 1 of complex plans) of an instantiated length — decided before the
+    // pruned FFT path (fft_path, latched at creation) — decided before the
     // spectra and the rocFFT plans are set up: a plan on this path never runs the D-dimensional rocFFT transform, so it neither creates
     // those plans nor allocates their work buffer (round 6: 1.07 GB of C2's 4.5 GB, 8.6 GB of C3's 27.8 GB were that buffer), and a real
     // plan whose dimension-1 pass is the library's own keeps the COMPACT spectrum only (N1/2 + 1 modes per line, rows padded to 128 bytes:
     // 0.57 instead of 1.08 GB per component at C2)
-    p->pruned_fft = D >= 2 && env_int("NUFFT_PRUNED_FFT", 1) != 0;
-    for (int d = p->is_complex ? 0 : 1; d < D && p->pruned_fft; ++d) p->pruned_fft = fft_lines_supported(p->dtype, p->Nover[d]);
-    p->compact_dim1 = p->pruned_fft && (p->is_complex || (real_lines_supported(p->dtype, p->Nover[0]) && env_int("NUFFT_COMPACT_DIM1", 1) != 0));
     // row stride of the compact dimension-1 spectrum and of tmp2: the strided passes read groups of adjacent columns,
     // 128 bytes per row — with rows of N1/2 + 1 = 129 elements every group straddled two cache lines (PMC: 1.6x the bytes
     // read); real plans pad their intermediate rows to 128 bytes
     p->spec_row = p->compact_dim1 ? p->Nout[0] : p->Nspec[0];
-    if (p->compact_dim1 && !p->is_complex && env_int("NUFFT_FFT_PAD_ROWS", 1) != 0) {
+    if (p->compact_dim1 && !p->is_complex && o.option_int("NUFFT_FFT_PAD_ROWS", 1) != 0) {
         const int64_t q = 128 / (int64_t)(2 * real_bytes(p->dtype));
         p->spec_row = (p->Nout[0] + q - 1) / q * q;
         if (p->spec_row > p->Nspec[0]) p->spec_row = p->Nout[0];      // (cannot happen for sigma >= 1.25)
@@ -552,13 +400,13 @@ static int build_device(nufft_plan* p) {
     p->scan_tmp_bytes = binsort_scan_tmp_bytes((int)p->tile.nbins);
     if ((rc = dev_alloc(p, &p->d_scan_tmp, p->scan_tmp_bytes))) return rc;
     // load balance: slot tables for tiles + a budget of extra slices (a quarter of the tiles, at least 1024)
-    p->balance_enabled = env_int("NUFFT_BALANCE", 1) != 0;
+    p->balance_enabled = o.option_int("NUFFT_BALANCE", 1) != 0;
     {
         nufft_plan::Balance& b = p->bal;
         const int64_t nsp = p->tile.sp.ntiles, nip = p->tile.ip.ntiles;
         // budget of extra slices per tiling (NUFFT_BALANCE_EXTRA: tests force 0 so that small grids, where the budget
         // always reaches some tile, still run the engines that serve unsliced point sets)
-        const int64_t extra_env = env_int("NUFFT_BALANCE_EXTRA", -1);
+        const int64_t extra_env = o.option_int("NUFFT_BALANCE_EXTRA", -1);
         b.extra[0] = p->balance_enabled ? (uint32_t)(extra_env >= 0 ? extra_env : std::max<int64_t>(1024, nsp / 4)) : 0u;
         b.extra[1] = p->balance_enabled ? (uint32_t)(extra_env >= 0 ? extra_env : std::max<int64_t>(1024, nip / 4)) : 0u;
         if ((rc = dev_alloc(p, reinterpret_cast<void**>(&b.d_work), balance_work_words((int)(nsp + nip)) * sizeof(uint32_t)))) return rc;
@@ -620,13 +468,11 @@ static int build_device(nufft_plan* p) {
                 const double v = p->dtype == NUFFT_F32 ? (double)(float)p->phihat[d][i] : p->phihat[d][i];
                 inv[i] = 1.0 / std::ldexp(v, p->scale_exp[d]);
             }
-            rc = p->dtype == NUFFT_F32 ? upload<float>(p, &p->d_invphi[d], inv) : upload<double>(p, &p->d_invphi[d], inv);
-            if (rc) return rc;
+            if ((rc = upload_real(p, &p->d_invphi[d], inv))) return rc;
         }
         {
             std::vector<double> one(1, 1.0);
-            rc = p->dtype == NUFFT_F32 ? upload<float>(p, &p->d_one, one) : upload<double>(p, &p->d_one, one);
-            if (rc) return rc;
+            if ((rc = upload_real(p, &p->d_one, one))) return rc;
         }
         for (int d = p->compact_dim1 ? 0 : 1; d < D; ++d) {
             const int64_t n = p->Nover[d];
@@ -636,17 +482,32 @@ static int build_device(nufft_plan* p) {
                 twf[2 * m] = std::cos(ang); twf[2 * m + 1] = -std::sin(ang);
                 twb[2 * m] = std::cos(ang); twb[2 * m + 1] = std::sin(ang);
             }
-            rc = p->dtype == NUFFT_F32 ? upload<float>(p, &p->d_tw_fw[d], twf) : upload<double>(p, &p->d_tw_fw[d], twf);
-            if (rc) return rc;
-            rc = p->dtype == NUFFT_F32 ? upload<float>(p, &p->d_tw_bw[d], twb) : upload<double>(p, &p->d_tw_bw[d], twb);
-            if (rc) return rc;
+            if ((rc = upload_real(p, &p->d_tw_fw[d], twf))) return rc;
+            if ((rc = upload_real(p, &p->d_tw_bw[d], twb))) return rc;
         }
         if (D == 3) {
             const size_t elems = (size_t)(p->compact_dim1 ? p->spec_row : p->Nout[0]) * p->Nout[1] * p->Nover[2];
             if ((rc = dev_alloc(p, &p->d_tmp2, elems * 2 * real_bytes(p->dtype), "tmp2"))) return rc;
         }
     }
+    return NUFFT_OK;
+}
 
+// 16-word record of an engine's task kernels (balance.hip; [2] = 1: the engine serves this point set), [columns] points per column then
+// [columns + 1] first task of each column, and the task table
+static int alloc_task_tables(nufft_plan* p, size_t ncols, size_t entries, uint32_t** choice, uint32_t** cols, void** tasks) {
+    int rc;
+    if ((rc = dev_alloc(p, reinterpret_cast<void**>(choice), 16 * sizeof(uint32_t)))) return rc;
+    NUFFT_HIP(hipMemset(*choice, 0, 16 * sizeof(uint32_t)));
+    if ((rc = dev_alloc(p, reinterpret_cast<void**>(cols), (2 * ncols + 2) * sizeof(uint32_t)))) return rc;
+    return dev_alloc(p, tasks, entries * 8);
+}
+
+// what the decision record says, allocated and latched into the plan: both rings, the patches, the sorts
+static int alloc_engines(nufft_plan* p, const EngineDecision& e) {
+    int rc;
+    const int D = p->D;
+    const bool poly = p->evalmode != NUFFT_EVAL_DIRECT;
     // kernels: allow the large dynamic LDS allocations
     // both variants: the general one also serves per-point weights on the default kernels
     for (int other = 0; other < 2; ++other) {
@@ -654,137 +515,59 @@ static int build_device(nufft_plan* p) {
         NUFFT_HIP(prepare_spread(p->dtype, p->is_complex, D, p->M, (int)p->lds_spread, other != 0));
         NUFFT_HIP(prepare_interp(p->dtype, p->is_complex, D, p->M, (int)p->lds_interp, other != 0));
     }
+    p->debug_tasks = p->opts.option_int("NUFFT_DEBUG_TASKS", 0) != 0;
+    p->halo_fuse = p->opts.option_int("NUFFT_SMARCH_HALO_FUSE", 1) != 0;
 
-    // second interpolation engine (z-marching ring, march_kernels.h): 3-D plans with the default window evaluation.  Which of
-    // the two kernels gathers a point set is decided on the device at set_points (heaviest ring task and total work against the
-    // ring's fitted advantage over the tile kernel: balance.hip, d_march_choice[2]); the mode is latched here —
-    // NUFFT_INTERP_MARCH = 0: never the ring (A/B runs), 2: always (tests of its instantiations on small grids)
-    p->debug_tasks = env_int("NUFFT_DEBUG_TASKS", 0) != 0;
-    p->halo_fuse = env_int("NUFFT_SMARCH_HALO_FUSE", 1) != 0;
-    p->interp_march = choose_interp_ring(p);
-    auto march_cplx = [&]() { return p->interp_parts == 2 ? 0 : (int)p->is_complex; };
+    // interpolation ring (march_kernels.h); its task tables are those of the column it ends up with — its own, or the spreading window's
+    p->interp_march = e.interp.available; p->interp_march_mode = e.interp.mode; p->interp_parts = e.interp.parts;
+    const int mcplx = p->interp_parts == 2 ? 0 : (int)p->is_complex;
     if (p->interp_march) {
-        NUFFT_HIP(prepare_interp_march(p->dtype, march_cplx(), p->M, p->evalmode != NUFFT_EVAL_DIRECT));
-        p->march_ct = march_column_tasks(p->dtype, march_cplx(), p->M, p->evalmode != NUFFT_EVAL_DIRECT, make_geom(p));
-        const size_t ncols = (size_t)p->march_ct.ncolx * p->march_ct.ncoly;
-        if (ncols >= 65536 || p->tile.nb[2] > 2048) p->interp_march = false;      // (beyond the task kernels' table formats)
-        else {
-            if ((rc = dev_alloc(p, reinterpret_cast<void**>(&p->d_march_choice), 16 * sizeof(uint32_t)))) return rc;
-            NUFFT_HIP(hipMemset(p->d_march_choice, 0, 16 * sizeof(uint32_t)));
-            if ((rc = dev_alloc(p, reinterpret_cast<void**>(&p->d_march_cols), (2 * ncols + 2) * sizeof(uint32_t)))) return rc;
-            if ((rc = dev_alloc(p, &p->d_march_tasks, (size_t)column_task_table_entries(p->march_ct, p->tile.nb[2]) * 8))) return rc;
-        }
+        NUFFT_HIP(prepare_interp_march(p->dtype, mcplx, p->M, poly));
+        p->march_ct = e.march_ct;
+        if ((rc = alloc_task_tables(p, (size_t)p->march_ct.ncolx * p->march_ct.ncoly, (size_t)column_task_table_entries(p->march_ct, p->tile.nb[2]),
+                                    &p->d_march_choice, &p->d_march_cols, &p->d_march_tasks))) return rc;
     }
 
-    if (p->spread_method == NUFFT_SPREAD_MARCHING_RING) {
-        const bool other = needs_other_eval(p->kernel, p->evalmode);
-        int want_halo = p->smarch.halo;
-        if (want_halo == 2 && !(p->pruned_fft && p->compact_dim1) && env_int("NUFFT_SMARCH_HALO", 0) != 2) want_halo = 0;   // no fused consumer: not worth it
-        // the side buffer (0.52 x the grid per component at 32 x 32 columns, m = 4) is workspace the clipped columns do not need: when it
-        // does not fit, the plan keeps the ring without it instead of failing
-        for (;;) {
-            p->smarch = smarch_plan(p->dtype, p->is_complex, D, p->M, make_geom(p), other, p->num_cus, p->C, want_halo, p->smarch_parts);
-            if (!p->smarch.eligible && want_halo)
-                p->smarch = smarch_plan(p->dtype, p->is_complex, D, p->M, make_geom(p), other, p->num_cus, p->C, 0, p->smarch_parts);
-            if (!p->smarch.eligible || p->smarch.halo != 2) break;
-            const size_t bytes = (size_t)p->smarch.halo_reals * real_bytes(p->dtype) * p->C * p->smarch.parts;
-            // (NUFFT_TEST_HALO_ALLOC_FAIL=1: the test of this fallback)
-            if (!env_int("NUFFT_TEST_HALO_ALLOC_FAIL", 0) && dev_alloc(p, &p->d_smarch_halo, bytes, "ring_side_buffer") == NUFFT_OK) break;
-            p->d_smarch_halo = nullptr;
-            want_halo = 0;
-        }
-        // build_host chose the engine for 256 CUs and the halo variant it hoped for: redo the automatic choice for what this device got
-        // (Float32 m = 7 belongs to the ring only with the halo variant: 20.1 ms clipped against 13.4 ms with the patches)
-        const int ring_max_m = ring_max_half_support(p);
-        const bool keep = p->smarch.eligible && (p->spread_method_req == NUFFT_SPREAD_MARCHING_RING || p->M <= ring_max_m);
-        if (!keep) {
-            if (p->spread_method_req == NUFFT_SPREAD_MARCHING_RING)
-                return fail(NUFFT_ERR_UNSUPPORTED, "marching-ring spreading: no decomposition for this device");
-            dev_free(p, p->d_smarch_halo);
-            p->smarch.eligible = false;
-            const bool prefer_patches = p->is_complex || p->M >= 5 || p->patch.planar != 0;
-            p->spread_method = (p->patch.eligible && prefer_patches) ? NUFFT_SPREAD_MFMA_PATCHES : NUFFT_SPREAD_LDS_TILES;
-        }
-    }
+    p->spread_method = e.spread_method;
+    p->smarch = e.smarch;
     if (p->spread_method == NUFFT_SPREAD_MARCHING_RING) {
         NUFFT_HIP(prepare_spread_march(p->dtype, p->smarch.parts == 2 ? 0 : p->is_complex, p->M, p->smarch.halo));
-        const size_t ncols = (size_t)p->smarch.ct.ncolx * p->smarch.ct.ncoly;
-        if ((rc = dev_alloc(p, reinterpret_cast<void**>(&p->d_smarch_choice), 16 * sizeof(uint32_t)))) return rc;
-        NUFFT_HIP(hipMemset(p->d_smarch_choice, 0, 16 * sizeof(uint32_t)));
-        if ((rc = dev_alloc(p, reinterpret_cast<void**>(&p->d_smarch_cols), (2 * ncols + 2) * sizeof(uint32_t)))) return rc;
-        if ((rc = dev_alloc(p, &p->d_smarch_tasks, (size_t)column_task_table_entries(p->smarch.ct, p->tile.nb[2]) * 8))) return rc;
+        if ((rc = alloc_task_tables(p, (size_t)p->smarch.ct.ncolx * p->smarch.ct.ncoly, (size_t)column_task_table_entries(p->smarch.ct, p->tile.nb[2]),
+                                    &p->d_smarch_choice, &p->d_smarch_cols, &p->d_smarch_tasks))) return rc;
     }
 
     if (p->spread_method == NUFFT_SPREAD_MFMA_PATCHES) {
         NUFFT_HIP(prepare_spread_patch(p->dtype, p->is_complex, p->M, false, p->patch.planar));
-        if ((rc = dev_alloc(p, reinterpret_cast<void**>(&p->d_patch_choice), 16 * sizeof(uint32_t)))) return rc;
-        NUFFT_HIP(hipMemset(p->d_patch_choice, 0, 16 * sizeof(uint32_t)));
         // task table of the patch engine, rebuilt by every set_points (balance.hip): [columns] points, [columns + 1] first task,
         // [ntasks] {column, layers}
-        const size_t ncols = (size_t)p->patch.npx * p->patch.npy;
-        if ((rc = dev_alloc(p, reinterpret_cast<void**>(&p->d_patch_cols), (2 * ncols + 2) * sizeof(uint32_t)))) return rc;
-        if ((rc = dev_alloc(p, &p->d_patch_tasks, ((size_t)p->patch.ntasks + 2 * ncols) * 8))) return rc;      // patch_task_table_entries
+        if ((rc = alloc_task_tables(p, (size_t)p->patch.npx * p->patch.npy, (size_t)patch_task_table_entries(p->patch),
+                                    &p->d_patch_choice, &p->d_patch_cols, &p->d_patch_tasks))) return rc;
         p->wave_slots = p->num_cus * 4 * p->patch.occ;      // 4 SIMDs per CU
     }
 
-    // Column-layer sort (binsort.hip, CoarseSort): where the spreading window (halo variant: a column visits its own points only) and
-    // the interpolation ring own the same columns, set_points only groups the points by (column, layer of bins) — few enough keys for
-    // LDS histograms, no global atomics — and the interpolation ring's staged variant orders a layer's points by bin on their way
-    // into LDS.  Per point set: only while both rings serve it (device flags); NUFFT_COARSE_SORT=0 keeps the fine sort (A/B runs).
+    // column-layer sort: both rings on the spreading window's column
     p->coarse = CoarseSort{};
-    if (p->spread_method == NUFFT_SPREAD_MARCHING_RING && p->smarch.halo == 2 && p->interp_march && D == 3 && env_int("NUFFT_COARSE_SORT", 1) != 0) {
-        ColumnTasks shared{};
-        const bool same = shared_ring_column(p, p->smarch, &shared);
-        const int nkeys = p->smarch.ct.ncolx * p->smarch.ct.ncoly * p->tile.nb[2];
-        const int mcplx = p->interp_parts == 2 ? 0 : (int)p->is_complex;
-        if (same) {
-            // the ring's task tables for the shared column (they were sized for the ring's own column above)
-            p->march_ct = shared;
-            const ColumnTasks& mc = p->march_ct;
-            const size_t ncols = (size_t)mc.ncolx * mc.ncoly;
-            dev_free(p, p->d_march_cols);
-            dev_free(p, p->d_march_tasks);
-            if ((rc = dev_alloc(p, reinterpret_cast<void**>(&p->d_march_cols), (2 * ncols + 2) * sizeof(uint32_t)))) return rc;
-            if ((rc = dev_alloc(p, &p->d_march_tasks, (size_t)column_task_table_entries(mc, p->tile.nb[2]) * 8))) return rc;
-            p->coarse.enabled = 1;
-            p->coarse.cbx = mc.bxw; p->coarse.cby = mc.byw; p->coarse.ncx = mc.ncolx; p->coarse.ncy = mc.ncoly;
-            p->coarse.nkeys = nkeys;
-            p->coarse.groups = p->num_cus;
-            p->coarse.flag_a = p->d_smarch_choice + 2;
-            p->coarse.flag_b = p->d_march_choice + 2;
-            if ((rc = dev_alloc(p, reinterpret_cast<void**>(&p->coarse.table), (size_t)p->coarse.groups * nkeys * sizeof(uint32_t), "sort_slice_table"))) return rc;
-            NUFFT_HIP(prepare_binsort_coarse(p->dtype, nkeys));
-            NUFFT_HIP(prepare_interp_march_staged(p->dtype, mcplx, p->M, p->evalmode != NUFFT_EVAL_DIRECT));
-        }
+    if (e.shared_column) {
+        const ColumnTasks& mc = p->march_ct;
+        p->coarse.enabled = 1;
+        p->coarse.cbx = mc.bxw; p->coarse.cby = mc.byw; p->coarse.ncx = mc.ncolx; p->coarse.ncy = mc.ncoly;
+        p->coarse.nkeys = p->smarch.ct.ncolx * p->smarch.ct.ncoly * p->tile.nb[2];
+        p->coarse.groups = p->num_cus;
+        p->coarse.flag_a = p->d_smarch_choice + 2;
+        p->coarse.flag_b = p->d_march_choice + 2;
+        if ((rc = dev_alloc(p, reinterpret_cast<void**>(&p->coarse.table), (size_t)p->coarse.groups * p->coarse.nkeys * sizeof(uint32_t), "sort_slice_table"))) return rc;
+        NUFFT_HIP(prepare_binsort_coarse(p->dtype, p->coarse.nkeys));
+        NUFFT_HIP(prepare_interp_march_staged(p->dtype, mcplx, p->M, poly));
     }
 
-    // Dense-set engine of the spreading window (dmarch_kernels.h): the points of a bin accumulated in registers by the FP64 matrix pipe, one flush
-    // per bin.  Taken per point set from the mean bin load (set_points: dense_now); it needs the fine-bin order, so on plans of the
-    // column-layer sort a dense point set takes the slab sort below.  NUFFT_DENSE=0: never; NUFFT_DENSE_MIN: the threshold (points per bin).
-    p->dense_available = p->spread_method == NUFFT_SPREAD_MARCHING_RING && env_int("NUFFT_DENSE", 1) != 0 && !needs_other_eval(p->kernel, p->evalmode) &&
-                         spread_dense_available(p->dtype, p->is_complex, p->M, p->evalmode != NUFFT_EVAL_DIRECT, p->smarch);
-    if (p->dense_available) NUFFT_HIP(prepare_spread_dense(p->dtype, p->M, p->evalmode != NUFFT_EVAL_DIRECT));
-    // Break-even against the stream of atomics, mean points per bin — measured (profiles/round6_dense_engine.md; 256^3 Float64, spread stage, ms, dense /
-    // atomic): m = 4 Direct() 3.69 / 2.97 at 19 per bin, 9.38 / 9.21 at 60; polynomial window 2.76 / 2.72 at 19, 6.66 / 8.40 at 60, and on the
-    // reference's folded N(0, 1) sets 4.52 / 5.57 at a mean of 19; m = 5 Direct() 6.38 / 4.13 at 4.8, 12.99 / 14.18 at 19, polynomial 5.05 / 3.91 and
-    // 8.79 / 13.27; m = 6 Direct() 7.70 / 6.48 and 15.80 / 22.61, polynomial 7.95 / 7.49 and 15.14 / 23.63; m = 2, 3 lose at 19 per bin (1.15 - 1.4 x).
-    // The FP64 matrix instructions run on the SIMD's FP64 vector ALUs (vector 37 % + matrix 25 % + LDS 32 % of the kernel's cycles ADD UP,
-    // counters in the same file): the engine only trades LDS-atomic time for vector time, which pays where a point costs 20 - 36 atomics
-    // (m = 5, 6) or the window evaluation is cheap (polynomial) and the bins are full.
-    static const int dense_min_direct[7] = {0, 0, 1 << 30, 1 << 30, 96, 16, 12};
-    static const int dense_min_poly[7] = {0, 0, 1 << 30, 1 << 30, 24, 10, 6};
-    p->dense_min = env_int("NUFFT_DENSE_MIN", p->M <= 6 ? (p->evalmode == NUFFT_EVAL_DIRECT ? dense_min_direct : dense_min_poly)[p->M] : 1 << 30);
+    p->dense_available = e.dense_available;
+    if (p->dense_available) NUFFT_HIP(prepare_spread_dense(p->dtype, p->M, poly));
+    p->dense_min = e.dense_min;
 
-    // every other 3-D plan: two-level slab sort (column_tasks.h) — the sorted array and offsets of the fine sort, without global atomics
     p->slab = CoarseSort{};
-    if (D == 3 && env_int("NUFFT_SLAB_SORT", 1) != 0 && p->tile.nb[0] <= kSlabMaxBins && p->tile.nb[2] <= kCoarseMaxKeys) {
-        p->slab.enabled = 1;
-        p->slab.mode = 2;
-        p->slab_min_points = env_int("NUFFT_SLAB_MIN_POINTS", 16384);
-        p->slab_fill = std::min(95, std::max(5, env_int("NUFFT_SLAB_FILL", 85)));
-        // [slices][keys] table of level 1: at most one slice per CU; the keys are (rows of bins / slab height) x layers — never more than
-        // nb[1] x nb[2], whatever height set_points picks (a 16^3 plan used to pay the 37.7 MB of the largest grid: ADVICE round 5)
-        p->slab_max_keys = (int)std::min<int64_t>(kCoarseMaxKeys, (int64_t)p->tile.nb[1] * p->tile.nb[2]);
+    if (e.slab) {
+        p->slab.enabled = 1; p->slab.mode = 2;
+        p->slab_min_points = e.slab_min_points; p->slab_fill = e.slab_fill; p->slab_max_keys = e.slab_max_keys;
         if ((rc = dev_alloc(p, reinterpret_cast<void**>(&p->slab.table), (size_t)p->num_cus * p->slab_max_keys * sizeof(uint32_t), "sort_slice_table"))) return rc;
         if ((rc = dev_alloc(p, reinterpret_cast<void**>(&p->slab.flagmem), 32))) return rc;      // [0] fullest slab (running), [4] flag
         NUFFT_HIP(hipMemset(p->slab.flagmem, 0, 32));
@@ -792,27 +575,59 @@ static int build_device(nufft_plan* p) {
         NUFFT_HIP(prepare_binsort_slab(p->dtype, kLdsLimit - 256));
     }
 
-    if (p->coarse.enabled && p->slab.enabled && env_int("NUFFT_SORT_ADAPTIVE", 1) != 0) {
+    if (e.adaptive) {
         // (host-mapped: the scatter pass writes the rings' decisions here, set_points reads them without synchronising — nufft_internal.h)
         NUFFT_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->sort_feedback), 16, hipHostMallocMapped));
         p->sort_feedback[0] = p->sort_feedback[1] = 1u;
         p->sort_feedback[2] = 0u;
     }
     if (p->spread_method == NUFFT_SPREAD_MFMA_PATCHES || p->spread_method == NUFFT_SPREAD_MARCHING_RING || p->interp_march) NUFFT_HIP(prepare_column_tasks());
+    return NUFFT_OK;
+}
 
+static int create_events(nufft_plan* p) {
     for (int s = 0; s < NUFFT_NUM_STAGES; ++s) {
         hipEvent_t a, b;
         NUFFT_HIP(hipEventCreate(&a));
         NUFFT_HIP(hipEventCreate(&b));
-        p->ev_begin[s] = a;
-        p->ev_end[s] = b;
+        p->ev_begin[s] = a; p->ev_end[s] = b;
     }
     return NUFFT_OK;
 }
 
+static int build_device(nufft_plan* p) {
+    int ndev = 0;
+    NUFFT_HIP(hipGetDeviceCount(&ndev));
+    if (p->device >= ndev) return fail(NUFFT_ERR_INVALID_ARG, "device ordinal out of range");
+    DeviceGuard guard(p->device);
+    std::call_once(g_rocfft_once, [] { (void)rocfft_setup(); });
+    {
+        // every engine set-up below (ring launch models, sort slices) sizes itself for this device — not for the default of 256 CUs
+        hipDeviceProp_t prop;
+        NUFFT_HIP(hipGetDeviceProperties(&prop, p->device));
+        p->num_cus = prop.multiProcessorCount;
+    }
+    int rc;
+    if ((rc = upload_tables(p))) return rc;
+    if ((rc = alloc_grids_and_fft(p))) return rc;
+    EngineDecision e = decide_engines(*p, p->num_cus, true);
+    if (e.spread_method == NUFFT_SPREAD_MARCHING_RING && e.smarch.halo == 2) {
+        // the side buffer (0.52 x the grid per component at 32 x 32 columns, m = 4) is workspace the clipped columns do not need: when it
+        // does not fit, the plan keeps the ring without it instead of failing
+        const size_t bytes = (size_t)e.smarch.halo_reals * real_bytes(p->dtype) * p->C * e.smarch.parts;
+        // (NUFFT_TEST_HALO_ALLOC_FAIL=1: the test of this fallback)
+        if (p->opts.option_int("NUFFT_TEST_HALO_ALLOC_FAIL", 0) || dev_alloc(p, &p->d_smarch_halo, bytes, "ring_side_buffer") != NUFFT_OK) {
+            p->d_smarch_halo = nullptr;
+            e = decide_engines(*p, p->num_cus, false);
+        }
+    }
+    if (e.ring_lost) return fail(NUFFT_ERR_UNSUPPORTED, "marching-ring spreading: no decomposition for this device");
+    if ((rc = alloc_engines(p, e))) return rc;
+    return create_events(p);
+}
+
 static void release(nufft_plan* p) {
     if (!p) return;
-    if (current_options() == &p->opts) set_current_options(nullptr);
     if (p->device >= 0) {
         DeviceGuard guard(p->device);
         (void)hipDeviceSynchronize();
@@ -834,7 +649,6 @@ static void release(nufft_plan* p) {
 
 static int require_device(const nufft_plan* p) {
     if (!p) return fail(NUFFT_ERR_INVALID_ARG, "null plan");
-    set_current_options(&p->opts);      // the development switches any code below may consult are this plan's (options.h)
     if (p->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only plan (device = -1) has no device path");
     return NUFFT_OK;
 }
@@ -889,7 +703,7 @@ static TileKernelArgs tile_args(const nufft_plan* p, bool interp) {
     a.ntiles = nt + (int)b.extra[interp ? 1 : 0];     // launch grid: tiles + budget of extra slices
     a.desc = static_cast<const char*>(b.d_desc) + (interp ? ((size_t)p->tile.sp.ntiles + b.extra[0]) * 8 : 0);
     a.desc_total = b.d_slots + (interp ? 1 : 0);
-    a.xcd_chunk = env_int("NUFFT_XCD_CHUNK", 8);
+    a.xcd_chunk = p->opts.option_int("NUFFT_XCD_CHUNK", 8);
     return a;
 }
 
@@ -916,7 +730,7 @@ static int void_halo(nufft_plan* p, hipStream_t stream) {
 static int complete_halo(nufft_plan* p, hipStream_t stream) {
     if (!halo_maybe_pending(p)) return NUFFT_OK;
     TileKernelArgs a = tile_args(p, false);
-    NUFFT_HIP(launch_smarch_halo_add(a, p->smarch, p->d_smarch_choice + kHaloStateWord, stream));      // (returns at once where the word is 0)
+    NUFFT_HIP(launch_smarch_halo_add(p->opts, a, p->smarch, p->d_smarch_choice + kHaloStateWord, stream));      // (returns at once where the word is 0)
     NUFFT_HIP(launch_zero_fill(p->d_smarch_choice + kHaloStateWord, 4, stream));
     p->halo_hint = false;
     return NUFFT_OK;
@@ -1257,7 +1071,7 @@ int nufft_plan_info(const nufft_plan* p, nufft_info* o) {
     o->ring_column[1] = ring ? p->smarch.n2 : 0;
     o->ring_segments = ring ? p->smarch.ct.nseg : 0;
     o->ring_halo = (ring && p->smarch.halo == 2) ? 1 : 0;
-    // (host-only plans: what a device plan of these parameters would report — predict_sort_column)
+    // (host-only plans: what a device plan of these parameters would report — build_host)
     o->sort_column[0] = p->device < 0 ? p->sort_column_pred[0] : (p->coarse.enabled ? p->coarse.cbx : 0);
     o->sort_column[1] = p->device < 0 ? p->sort_column_pred[1] : (p->coarse.enabled ? p->coarse.cby : 0);
     return NUFFT_OK;
@@ -1284,66 +1098,87 @@ int nufft_plan_get_index_map(const nufft_plan* p, int dim, int64_t* out, int64_t
     return NUFFT_OK;
 }
 
-// bytes per point of the {bin, rank} array of the fine sort; plans of the slab sort keep the records of its level 1 in the same allocation
-// (a point set takes one sort or the other)
-// (plans of the column-layer sort use neither unless a point set is clustered — the fine sort, 8 bytes — or dense — the slab sort, a record)
-static int64_t binrank_bytes(const nufft_plan* p, bool slab_sort) {
-    return slab_sort ? std::max<int64_t>(8, (int64_t)point_record_bytes(p->dtype, p->D)) : 8;
+// development check (NUFFT_DEBUG_TASKS): every column's tasks tile [0, nb[2]) without gaps or overlaps
+static void check_task_table(const nufft_plan* p, const char* name, const ColumnTasks& ct, const void* tab, const uint32_t* choice, hipStream_t stream) {
+    const size_t ncols = (size_t)ct.ncolx * ct.ncoly, ntab = (size_t)column_task_table_entries(ct, p->tile.nb[2]);
+    std::vector<uint32_t> h(2 * ntab), ch(8);
+    (void)hipStreamSynchronize(stream);
+    (void)hipMemcpy(h.data(), tab, ntab * 8, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(ch.data(), choice, 32, hipMemcpyDeviceToHost);
+    std::vector<std::vector<std::pair<int, int>>> segs(ncols);
+    size_t used = 0, maxlen = 0;
+    for (size_t t = 0; t < ntab; ++t) {
+        const uint32_t c = h[2 * t], y = h[2 * t + 1];
+        if (!y) continue;
+        ++used;
+        if (c >= ncols) { fprintf(stderr, "[tasks %s] entry %zu: column %u out of range\n", name, t, c); continue; }
+        segs[c].push_back({(int)(y & 0xffffu), (int)(y >> 16)});
+        maxlen = std::max(maxlen, (size_t)((y >> 16) - (y & 0xffffu)));
+    }
+    size_t bad = 0;
+    for (size_t c = 0; c < ncols; ++c) {
+        std::sort(segs[c].begin(), segs[c].end());
+        int z = 0;
+        for (auto& sg : segs[c]) { if (sg.first != z) ++bad; z = sg.second; }
+        if (z != p->tile.nb[2]) ++bad;
+    }
+    fprintf(stderr, "[tasks %s] columns %zu, table %zu, in use %zu, longest %zu layers, flag %u, uniform %u, bad columns %zu\n", name, ncols, ntab,
+            used, maxlen, ch[2], ch[3], bad);
+}
+static void check_task_tables(const nufft_plan* p, hipStream_t stream) {
+    if (p->spread_method == NUFFT_SPREAD_MFMA_PATCHES) {
+        ColumnTasks ct{p->patch.npx, p->patch.npy, 4, p->patch.pby, p->patch.nseg, p->patch.segl, p->patch.ntasks, 1, 0, 0, 0};
+        check_task_table(p, "patches", ct, p->d_patch_tasks, p->d_patch_choice, stream);
+    }
+    if (p->interp_march) check_task_table(p, "ring", p->march_ct, p->d_march_tasks, p->d_march_choice, stream);
+    if (p->spread_method == NUFFT_SPREAD_MARCHING_RING) check_task_table(p, "spreading ring", p->smarch.ct, p->d_smarch_tasks, p->d_smarch_choice, stream);
 }
 
-int nufft_set_points(nufft_plan* p, int64_t np, const void* const* coords, void* stream_) {
-    int rc = require_device(p);
-    if (rc) return rc;
-    if (np < 0) return fail(NUFFT_ERR_INVALID_ARG, "negative number of points");
-    if (np >= ((int64_t)1 << 31) - 1) return fail(NUFFT_ERR_UNSUPPORTED, "number of points exceeds 2^31 - 2");
-    if (!coords) return fail(NUFFT_ERR_INVALID_ARG, "null coordinate table");
-    for (int d = 0; d < p->D; ++d)
-        if (np > 0 && !coords[d]) return fail(NUFFT_ERR_INVALID_ARG, "null coordinate vector");
-    DeviceGuard guard(p->device);
-    hipStream_t stream = static_cast<hipStream_t>(stream_);
-    p->Np = -1;      // no valid point set until everything below has been enqueued (a failed call leaves the plan without points)
-    if (np > p->Np_capacity) {
-        // resize_no_copy!, src/blocking/blocking.jl:55-61 (old contents are discarded).  hipFree / hipMalloc are not
-        // capturable: pre-size the plan with the largest point set before capturing set_points in a hipGraph.
-        dev_free(p, p->d_sorted);
-        dev_free(p, p->d_vsorted);
-        p->Np_capacity = 0;
-        if (p->spread_method == NUFFT_SPREAD_MFMA_PATCHES && (rc = dev_alloc(p, &p->d_vsorted, (size_t)np * value_bytes(p) * p->C, "vsorted"))) return rc;
-        if ((rc = dev_alloc(p, &p->d_sorted, (size_t)np * point_record_bytes(p->dtype, p->D), "sorted"))) return rc;
-        p->Np_capacity = np;
-    }
+// set_points, step 1: the buffers that hold np points (resize_no_copy!, src/blocking/blocking.jl:55-61: old contents are discarded).
+// hipFree / hipMalloc are not capturable: pre-size the plan with the largest point set before capturing set_points in a hipGraph.
+static int grow_point_buffers(nufft_plan* p, int64_t np) {
+    if (np <= p->Np_capacity) return NUFFT_OK;
+    int rc;
+    dev_free(p, p->d_sorted);
+    dev_free(p, p->d_vsorted);
+    p->Np_capacity = 0;
+    if (p->spread_method == NUFFT_SPREAD_MFMA_PATCHES && (rc = dev_alloc(p, &p->d_vsorted, (size_t)np * value_bytes(p) * p->C, "vsorted"))) return rc;
+    if ((rc = dev_alloc(p, &p->d_sorted, (size_t)np * point_record_bytes(p->dtype, p->D), "sorted"))) return rc;
+    p->Np_capacity = np;
+    return NUFFT_OK;
+}
+
+// set_points, step 2: which sort this point set takes (p->dense_now, p->coarse_now; the slab height, 0 = not the slab sort), and its scratch
+static int choose_sort(nufft_plan* p, int64_t np, hipStream_t stream, int* slab_rows) {
     // dense point set (mean load of the 4^3-cell bins): the matrix-pipe engine serves it where the ring does, from the fine-bin order
     p->dense_now = p->dense_available && np >= (int64_t)p->dense_min * p->tile.nbins;
-    {
-        // scratch of the sort this point set takes: {bin, rank} of the fine sort (8 bytes per point; also what a clustered set of a
-        // column-layer plan falls back to, decided on the device), or the level-1 records of the slab sort
-        // adaptive choice (nufft_internal.h: sort_feedback): what the rings decided for the point sets before this one
-        if (p->sort_feedback) {
-            hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-            const bool capturing = hipStreamIsCapturing(stream, &st) == hipSuccess && st != hipStreamCaptureStatusNone;
-            if (!capturing) (void)hipGetLastError();
-            const uint32_t seq = __atomic_load_n(&p->sort_feedback[2], __ATOMIC_ACQUIRE);
-            if (!capturing && seq != p->sort_seq_seen && seq == p->sort_seq) {      // the record of the latest point set has arrived: count it once
-                p->sort_seq_seen = seq;
-                const bool both = p->sort_feedback[0] != 0u && p->sort_feedback[1] != 0u;
-                if (both) { p->sort_miss_streak = 0; p->sort_prefer_slab = false; }
-                else if (++p->sort_miss_streak >= 2) p->sort_prefer_slab = true;
-            }
-        }
-        p->coarse_now = p->coarse.enabled && !p->dense_now && !(p->sort_prefer_slab && p->slab.enabled);
-        const bool slab_scratch = p->slab.enabled && !p->coarse_now;
-        const int64_t need = np * binrank_bytes(p, slab_scratch);
-        if (need > p->binrank_capacity) {
-            dev_free(p, p->d_binrank);
-            p->binrank_capacity = 0;
-            if ((rc = dev_alloc(p, &p->d_binrank, (size_t)need, "sort_scratch"))) return rc;
-            p->binrank_capacity = need;
+    // adaptive choice (nufft_internal.h: sort_feedback): what the rings decided for the point sets before this one
+    if (p->sort_feedback) {
+        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+        const bool capturing = hipStreamIsCapturing(stream, &st) == hipSuccess && st != hipStreamCaptureStatusNone;
+        if (!capturing) (void)hipGetLastError();
+        const uint32_t seq = __atomic_load_n(&p->sort_feedback[2], __ATOMIC_ACQUIRE);
+        if (!capturing && seq != p->sort_seq_seen && seq == p->sort_seq) {      // the record of the latest point set has arrived: count it once
+            p->sort_seq_seen = seq;
+            const bool both = p->sort_feedback[0] != 0u && p->sort_feedback[1] != 0u;
+            if (both) { p->sort_miss_streak = 0; p->sort_prefer_slab = false; }
+            else if (++p->sort_miss_streak >= 2) p->sort_prefer_slab = true;
         }
     }
-    note_capture(p, stream);
-    p->halo_hint = false;              // a deferred spread of the previous point set that was never consumed is void (the ring's task kernel
-                                       // below clears the device word with the rest of its per-point-set record)
-    StageTimer tm(p, NUFFT_STAGE_SET_POINTS, stream);
+    p->coarse_now = p->coarse.enabled && !p->dense_now && !(p->sort_prefer_slab && p->slab.enabled);
+    const int64_t need = sort_scratch_bytes(*p, np, p->slab.enabled && !p->coarse_now);
+    if (need > p->binrank_capacity) {
+        dev_free(p, p->d_binrank);
+        p->binrank_capacity = 0;
+        if (int rc = dev_alloc(p, &p->d_binrank, (size_t)need, "sort_scratch")) return rc;
+        p->binrank_capacity = need;
+    }
+    *slab_rows = p->coarse_now ? 0 : slab_height(*p, np);
+    return NUFFT_OK;
+}
+
+// set_points, step 3: the arguments of the sort kernels
+static SortArgs sort_args(nufft_plan* p, int64_t np, const void* const* coords, int slab_rows) {
     SortArgs s{};
     s.dtype = p->dtype;
     s.D = p->D;
@@ -1360,43 +1195,77 @@ int nufft_set_points(nufft_plan* p, int64_t np, const void* const* coords, void*
     s.scan_tmp = p->d_scan_tmp;
     s.scan_tmp_bytes = p->scan_tmp_bytes;
     s.cs = p->coarse;
-    const bool coarse = p->coarse_now;
-    if (p->coarse.enabled && !coarse) s.cs = CoarseSort{};
-    if (coarse && p->sort_feedback) {      // (the scatter pass of the column-layer sort reports the rings' decisions: it runs behind their task kernels)
+    if (p->coarse.enabled && !p->coarse_now) s.cs = CoarseSort{};
+    if (p->coarse_now && p->sort_feedback) {      // (the scatter pass of the column-layer sort reports the rings' decisions: it runs behind their task kernels)
         s.cs.fb_a = p->coarse.flag_a; s.cs.fb_b = p->coarse.flag_b;
         s.cs.feedback = p->sort_feedback; s.cs.seq = ++p->sort_seq;
     }
-    bool slab = false;
-    if (!coarse && p->slab.enabled && np >= std::max<int64_t>(p->slab_min_points, 1)) {
-        // slab height for this point set: the tallest slab (longest runs in level 1: C3 `set_points` 5.2 ms with 32 768 slabs, 4.4 ms with 16 384)
-        // whose average load is at most 85 % of what a level-2 workgroup can hold (fuller slabs take its two-pass form), while there are
-        // slabs enough to fill the chip
+    if (slab_rows > 0) {
         const int capmax = slab_sort_capacity(p->dtype, kLdsLimit - 256);
-        int best = -1;
-        for (int sby = 1; sby <= p->tile.nb[1] && (int64_t)sby * p->tile.nb[0] <= kSlabMaxBins; sby *= 2) {
-            const int64_t nkeys = (int64_t)p->tile.nb[2] * ((p->tile.nb[1] + sby - 1) / sby);
-            if (nkeys > p->slab_max_keys) continue;
-            if (np / nkeys > (int64_t)capmax * p->slab_fill / 100) break;
-            if (best > 0 && nkeys < 2048) break;
-            best = sby;
-        }
-        if (best > 0) {
-            slab = true;
-            s.cs = p->slab;
-            s.cs.cbx = p->tile.nb[0]; s.cs.ncx = 1;
-            s.cs.cby = best; s.cs.ncy = (p->tile.nb[1] + best - 1) / best;
-            s.cs.nkeys = p->tile.nb[2] * s.cs.ncy;
-            s.cs.groups = (int)std::min<int64_t>(p->num_cus, std::max<int64_t>(1, (np + 16383) / 16384));
-            const int64_t mean = np / s.cs.nkeys;
-            s.cs.cap = (int)std::min<int64_t>(capmax, (std::max<int64_t>(2 * mean, mean + 1536) + 63) / 64 * 64);
-            s.cs.lds2 = slab_sort_lds_bytes(p->dtype, s.cs.cap);
-            s.cs.temp = p->d_binrank;
-        }
+        s.cs = p->slab;
+        s.cs.cbx = p->tile.nb[0]; s.cs.ncx = 1;
+        s.cs.cby = slab_rows; s.cs.ncy = (p->tile.nb[1] + slab_rows - 1) / slab_rows;
+        s.cs.nkeys = p->tile.nb[2] * s.cs.ncy;
+        s.cs.groups = (int)std::min<int64_t>(p->num_cus, std::max<int64_t>(1, (np + 16383) / 16384));
+        const int64_t mean = np / s.cs.nkeys;
+        s.cs.cap = (int)std::min<int64_t>(capmax, (std::max<int64_t>(2 * mean, mean + 1536) + 63) / 64 * 64);
+        s.cs.lds2 = slab_sort_lds_bytes(p->dtype, s.cs.cap);
+        s.cs.temp = p->d_binrank;
     }
+    return s;
+}
+
+// slices per tile from the work each tile now holds (balance.hip)
+static int balance_tiles(nufft_plan* p, const SortArgs& s, hipStream_t stream) {
+    const nufft_plan::Balance& b = p->bal;
+    const bool coarse = p->coarse_now;
+    BalanceArgs q{};
+    q.g = s.g;
+    q.D = p->D;
+    q.M = p->M;
+    q.enabled = p->balance_enabled && s.np > 0;
+    q.extra_sp = b.extra[0];
+    q.extra_ip = b.extra[1];
+    q.smax = 4096;
+    q.offsets = p->d_offsets;
+    q.work = b.d_work;
+    q.nslices = b.d_nslices;
+    q.desc_off = b.d_desc_off;
+    q.desc = static_cast<uint2*>(b.d_desc);
+    q.slots_in_use = b.d_slots;
+    q.scan_tmp = b.d_tmp;
+    q.scan_tmp_bytes = b.tmp_bytes;
+    q.skip_a = coarse ? p->coarse.flag_a : nullptr;
+    q.skip_b = coarse ? p->coarse.flag_b : nullptr;
+    q.sp_served = coarse ? p->coarse.flag_a : nullptr;      // (otherwise the task kernels below clear the spreading slots)
+    NUFFT_HIP(launch_balance(q, stream));
+    return NUFFT_OK;
+}
+
+int nufft_set_points(nufft_plan* p, int64_t np, const void* const* coords, void* stream_) {
+    int rc = require_device(p);
+    if (rc) return rc;
+    if (np < 0) return fail(NUFFT_ERR_INVALID_ARG, "negative number of points");
+    if (np >= ((int64_t)1 << 31) - 1) return fail(NUFFT_ERR_UNSUPPORTED, "number of points exceeds 2^31 - 2");
+    if (!coords) return fail(NUFFT_ERR_INVALID_ARG, "null coordinate table");
+    for (int d = 0; d < p->D; ++d)
+        if (np > 0 && !coords[d]) return fail(NUFFT_ERR_INVALID_ARG, "null coordinate vector");
+    DeviceGuard guard(p->device);
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    p->Np = -1;      // no valid point set until everything below has been enqueued (a failed call leaves the plan without points)
+    int slab_rows = 0;
+    if ((rc = grow_point_buffers(p, np))) return rc;
+    if ((rc = choose_sort(p, np, stream, &slab_rows))) return rc;
+    note_capture(p, stream);
+    p->halo_hint = false;              // a deferred spread of the previous point set that was never consumed is void (the ring's task kernel
+                                       // below clears the device word with the rest of its per-point-set record)
+    StageTimer tm(p, NUFFT_STAGE_SET_POINTS, stream);
+    const SortArgs s = sort_args(p, np, coords, slab_rows);
+    const bool coarse = p->coarse_now;
     // plans of the column-layer sort: histogram by column layers first — its offsets are all the task kernels below need to decide
     // whether both rings serve this point set; the scatter pass (of whichever sort that decision selects) and the tile tables follow
     if (coarse) NUFFT_HIP(launch_binsort_coarse_count(s, stream));
-    else if (slab) {
+    else if (slab_rows > 0) {
         // (nothing else decides here: the fullest slab does, on the device — both halves back to back)
         NUFFT_HIP(launch_binsort_coarse_count(s, stream));
         NUFFT_HIP(launch_binsort_coarse_finish(s, stream));
@@ -1404,133 +1273,37 @@ int nufft_set_points(nufft_plan* p, int64_t np, const void* const* coords, void*
         if (p->slab.enabled) NUFFT_HIP(launch_zero_fill(p->slab.flagmem + 4, 16, stream));      // (what nufft_sort_columns_used reports)
         NUFFT_HIP(launch_binsort(s, stream));
     }
-    // slices per tile from the work each tile now holds (balance.hip)
-    auto balance = [&]() -> int {
-        const nufft_plan::Balance& b = p->bal;
-        BalanceArgs q{};
-        q.g = s.g;
-        q.D = p->D;
-        q.M = p->M;
-        q.enabled = p->balance_enabled && np > 0;
-        q.extra_sp = b.extra[0];
-        q.extra_ip = b.extra[1];
-        q.smax = 4096;
-        q.offsets = p->d_offsets;
-        q.work = b.d_work;
-        q.nslices = b.d_nslices;
-        q.desc_off = b.d_desc_off;
-        q.desc = static_cast<uint2*>(b.d_desc);
-        q.slots_in_use = b.d_slots;
-        q.scan_tmp = b.d_tmp;
-        q.scan_tmp_bytes = b.tmp_bytes;
-        q.skip_a = coarse ? p->coarse.flag_a : nullptr;
-        q.skip_b = coarse ? p->coarse.flag_b : nullptr;
-        q.sp_served = coarse ? p->coarse.flag_a : nullptr;      // (otherwise the task kernels below clear the spreading slots)
-        NUFFT_HIP(launch_balance(q, stream));
-        return NUFFT_OK;
-    };
-    if (!coarse && (rc = balance())) return rc;
+    if (!coarse && (rc = balance_tiles(p, s, stream))) return rc;
     if (p->spread_method == NUFFT_SPREAD_MFMA_PATCHES) {
         // which engine serves this point set: decided on the device from the heaviest patch task (balance.hip)
-        PatchPlan pp{};
-        pp.eligible = true;
-        pp.npx = p->patch.npx; pp.npy = p->patch.npy; pp.nseg = p->patch.nseg; pp.segl = p->patch.segl;
-        pp.ntasks = p->patch.ntasks; pp.lds_bytes = p->patch.lds_bytes; pp.pby = p->patch.pby; pp.f32acc = p->patch.f32acc; pp.planar = p->patch.planar;
-        // the patches' measured advantage over the LDS tiles on uniform points grows with the matrix work per point visit
-        // (ComplexF64 m = 4 1.17, m = 7 3.7; Float64 m = 6 1.5-1.7, m = 9 3.7; ComplexF32 on the FP32
-        // matrix pipe m = 8 3.4-4): 1.15 x g^(m - 4) with g = 1.2 (real) / 1.45 (complex), x 1.3 with Float32 accumulators,
-        // x 0.85 because the estimate counts a task's own column only and no scheduling tail.  An explicit request always
-        // takes the patches.
-        double advantage = 0.85 * 1.15 * std::pow(p->is_complex ? 1.45 : 1.2, (double)std::max(p->M - 4, 0)) * (p->patch.f32acc ? 1.3 : 1.0);
-        if (p->spread_method_req == NUFFT_SPREAD_MFMA_PATCHES) advantage = 0.0;
-        const int slots = p->wave_slots;
+        const PatchPlan& pp = p->patch;
         const int clo = -((p->M + 2) / 4), chi = (3 + p->M) / 4;          // cubes a stencil reaches beside its bin (PatchCfg::CLO, CHI)
         const size_t ncols = (size_t)pp.npx * pp.npy;
-        NUFFT_HIP(launch_patch_tasks(s.g, pp, clo, chi, p->d_offsets, np, slots, advantage, p->d_patch_choice, p->bal.d_slots, p->d_patch_cols,
+        NUFFT_HIP(launch_patch_tasks(s.g, pp, clo, chi, p->d_offsets, np, p->wave_slots, patch_advantage(*p), p->d_patch_choice, p->bal.d_slots, p->d_patch_cols,
                                      p->d_patch_cols + ncols, static_cast<uint2*>(p->d_patch_tasks), stream));
     }
     if (p->spread_method == NUFFT_SPREAD_MARCHING_RING) {
-        // tasks of the spreading ring for this point set, and whether it serves it (balance.hip): while the heaviest task stays
-        // within its measured advantage over the LDS tiles on uniform points (x 0.85 for what the estimate leaves out); an
-        // explicit request always takes the ring
-        // (halo variant: 1.87 instead of 2.44 ms at C2, + 0.15 ms in the FFT pass: 3.67 / 2.62 = 1.4 against the tiles, stage + FFT; the
-        // reference's benchmark distribution — folded N(0, 1), sigma = 1.5, Np = 1.68e7 — sits at the threshold: tiles 6.78 + 0.32 ms
-        // below 1.19, window 6.18 + 0.38 ms from 1.3 on, hence 0.93 instead of 0.85 here)
-        const double adv_env = option_double("NUFFT_SMARCH_ADVANTAGE", 0.0);
-        double advantage = p->smarch.halo == 2 ? 0.93 * 1.4 : 0.85 * 1.3;
-        if (adv_env > 0.0) advantage = adv_env;       // (experiments)
-        if (p->spread_method_req == NUFFT_SPREAD_MARCHING_RING) advantage = 0.0;
+        // tasks of the spreading ring for this point set, and whether it serves it (balance.hip, smarch_advantage)
         const size_t ncols = (size_t)p->smarch.ct.ncolx * p->smarch.ct.ncoly;
         // (the C components are independent workgroups of one launch: each component has num_cus / C compute units' worth of the chip)
-        NUFFT_HIP(launch_smarch_tasks(s.g, p->smarch, p->d_offsets, np, std::max(1, p->num_cus / (p->C * p->smarch.parts)), advantage, p->d_smarch_choice, p->bal.d_slots, p->d_smarch_cols,
+        NUFFT_HIP(launch_smarch_tasks(s.g, p->smarch, p->d_offsets, np, std::max(1, p->num_cus / (p->C * p->smarch.parts)), smarch_advantage(*p), p->d_smarch_choice, p->bal.d_slots, p->d_smarch_cols,
                                       p->d_smarch_cols + ncols, static_cast<uint2*>(p->d_smarch_tasks), stream));
     }
     if (p->interp_march) {
-        // tasks of the interpolation ring for this point set, and whether it serves it (balance.hip).  What the ring saves
-        // over interp_tile_kernel is grid traffic (halo 1.5x instead of 2.6x at m = 4, 3.75x instead of 12.5x at m = 8), which
-        // it also takes off the critical path; its gather itself is ~9 % slower per point (ring index arithmetic, two barriers
-        // per bin layer).  So its advantage falls with the point density rho = points per oversampled cell,
-        //   advantage = (rho + c_t) / (1.09 rho + c_r),  c_t = 0.038 (m/4)^1.85,  c_r = 0.0086 (m/4)^1.2
-        // fitted to: C2 (m = 4, rho = 0.075) 1.26, Float64 m = 6 1.55, C3 (m = 8, rho = 0.093) 1.9, and Float64 m = 4 at
-        // rho = 0.3 (1.68e7 points on 384^3) 1.0 — above that density the tile kernel is the faster one even for uniform points.
-        // (NUFFT_INTERP_MARCH=2: always the ring — tests of its instantiations on small grids)
-        const double rho = (double)np / (double)std::max<int64_t>(p->grid_elems, 1), mr = (double)p->M / 4.0;
-        const double fitted = (rho + 0.038 * std::pow(mr, 1.85)) / (1.09 * rho + 0.0086 * std::pow(mr, 1.2));
-        const double advantage = p->interp_march_mode == 2 ? 0.0 : fitted;      // (<= 0: always the ring)
-        // Point sets far from uniform (tasks of equal point count): the same trade at the density the points themselves see,
-        // rho_eff = sum n^2 / (sum n x cells) over the column layers (balance.hip).  Uniform sets break even at
-        // rho* = (c_t - c_r) / 0.09 (0.33 at m = 4); cut tasks amortise the window loads better — measured at m = 4, Np = 1e7 ... 1.7e7:
-        // rho_eff = 0.42 (folded N(0, 1) on 512^3, Gaussian cluster of 1 rad) ring 1.87 / 1.88 ms against 2.10 / 2.09 tiles;
-        // 1.66 (folded N(0, 1), 1.68e7 points on 384^3) 3.42 against 2.58; 3.3 (cluster of 0.5 rad) 2.01 against 1.43 — so the ring
-        // keeps such sets up to 2.5 rho*.
-        const double rho_star = (0.038 * std::pow(mr, 1.85) - 0.0086 * std::pow(mr, 1.2)) / 0.09;
+        // tasks of the interpolation ring for this point set, and whether it serves it (balance.hip, march_advantage)
         const size_t ncols = (size_t)p->march_ct.ncolx * p->march_ct.ncoly;
-        NUFFT_HIP(launch_march_tasks(s.g, p->march_ct, p->d_offsets, np, p->num_cus, advantage, 2.5 * rho_star, p->d_march_choice, p->d_march_cols,
+        NUFFT_HIP(launch_march_tasks(s.g, p->march_ct, p->d_offsets, np, p->num_cus, march_advantage(*p, np), march_rho_bound(*p), p->d_march_choice, p->d_march_cols,
                                      p->d_march_cols + ncols, static_cast<uint2*>(p->d_march_tasks), stream));
     }
     if (coarse) {
         // both rings have decided: column-layer scatter, or the fine sort for a point set one of them hands to the tile kernels
         NUFFT_HIP(launch_binsort_coarse_finish(s, stream));
-        if ((rc = balance())) return rc;
+        if ((rc = balance_tiles(p, s, stream))) return rc;
     } else if (p->sort_feedback && p->coarse.enabled && !p->dense_now) {
         // a plan of the column-layer sort on the slab sort (the sets before this one went to the tile kernels): what the rings say about THIS set
         NUFFT_HIP(launch_sort_feedback(p->coarse.flag_a, p->coarse.flag_b, p->sort_feedback, ++p->sort_seq, stream));
     }
-    if (p->debug_tasks) {
-        // development check: every column's tasks tile [0, nb[2]) without gaps or overlaps
-        auto check = [&](const char* name, const ColumnTasks& ct, const void* tab, const uint32_t* choice) {
-            const size_t ncols = (size_t)ct.ncolx * ct.ncoly, ntab = (size_t)column_task_table_entries(ct, p->tile.nb[2]);
-            std::vector<uint32_t> h(2 * ntab), ch(8);
-            (void)hipStreamSynchronize(stream);
-            (void)hipMemcpy(h.data(), tab, ntab * 8, hipMemcpyDeviceToHost);
-            (void)hipMemcpy(ch.data(), choice, 32, hipMemcpyDeviceToHost);
-            std::vector<std::vector<std::pair<int, int>>> segs(ncols);
-            size_t used = 0, maxlen = 0;
-            for (size_t t = 0; t < ntab; ++t) {
-                const uint32_t c = h[2 * t], y = h[2 * t + 1];
-                if (!y) continue;
-                ++used;
-                if (c >= ncols) { fprintf(stderr, "[tasks %s] entry %zu: column %u out of range\n", name, t, c); continue; }
-                segs[c].push_back({(int)(y & 0xffffu), (int)(y >> 16)});
-                maxlen = std::max(maxlen, (size_t)((y >> 16) - (y & 0xffffu)));
-            }
-            size_t bad = 0;
-            for (size_t c = 0; c < ncols; ++c) {
-                std::sort(segs[c].begin(), segs[c].end());
-                int z = 0;
-                for (auto& sg : segs[c]) { if (sg.first != z) ++bad; z = sg.second; }
-                if (z != p->tile.nb[2]) ++bad;
-            }
-            fprintf(stderr, "[tasks %s] columns %zu, table %zu, in use %zu, longest %zu layers, flag %u, uniform %u, bad columns %zu\n", name, ncols, ntab,
-                    used, maxlen, ch[2], ch[3], bad);
-        };
-        if (p->spread_method == NUFFT_SPREAD_MFMA_PATCHES) {
-            ColumnTasks ct{p->patch.npx, p->patch.npy, 4, p->patch.pby, p->patch.nseg, p->patch.segl, p->patch.ntasks, 1, 0, 0, 0};
-            check("patches", ct, p->d_patch_tasks, p->d_patch_choice);
-        }
-        if (p->interp_march) check("ring", p->march_ct, p->d_march_tasks, p->d_march_choice);
-        if (p->spread_method == NUFFT_SPREAD_MARCHING_RING) check("spreading ring", p->smarch.ct, p->d_smarch_tasks, p->d_smarch_choice);
-    }
+    if (p->debug_tasks) check_task_tables(p, stream);
     p->Np = np;
     p->counts_clean = np > 0;      // the scatter pass has cleared the histogram (no point, no scatter pass: cleared next time)
     return NUFFT_OK;
@@ -1643,10 +1416,7 @@ static int spread_impl(nufft_plan* p, const void* const* values_in, void* stream
             for (int c = 0; c < p->C; ++c)
                 NUFFT_HIP(launch_gather_values(p->dtype, p->is_complex, p->D, p->d_sorted, p->Np, values_in[c], p->cb_point_weights,
                                                static_cast<char*>(p->d_vsorted) + (size_t)c * vstride * real_bytes(p->dtype), enabled, stream));
-        PatchPlan pp{};
-        pp.eligible = true;
-        pp.npx = p->patch.npx; pp.npy = p->patch.npy; pp.nseg = p->patch.nseg; pp.segl = p->patch.segl;
-        pp.ntasks = p->patch.ntasks; pp.lds_bytes = p->patch.lds_bytes; pp.pby = p->patch.pby; pp.f32acc = p->patch.f32acc; pp.planar = p->patch.planar;
+        const PatchPlan& pp = p->patch;
         NUFFT_HIP(launch_spread_patch(a, pp, p->d_vsorted, vstride, enabled, static_cast<const uint2*>(p->d_patch_tasks), stream));
     }
     return NUFFT_OK;

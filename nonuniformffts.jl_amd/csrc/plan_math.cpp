@@ -225,12 +225,12 @@ static void edge_candidates(int64_t N, int b, int M, int cap, std::vector<int>& 
 // LDS row stride (in Float64 reals) of the spreading tile.  A wave instruction of the accumulation
 // touches consecutive rows with `stencil_inner` contiguous reals each; the rows land on disjoint banks
 // when the stride is congruent to the stencil width modulo the 128-byte bank period.
-int lds_row_stride(int inner_elems, int stencil_inner, int real_bytes) {
-    const bool no_pad = option_present("NUFFT_LDS_NO_PAD");
+// (`no_pad`: NUFFT_LDS_NO_PAD of the plan's options, read once by choose_tiles)
+static int lds_row_stride(int inner_elems, int stencil_inner, int real_bytes, bool no_pad) {
     return no_pad ? inner_elems : padded_row_stride(inner_elems, stencil_inner, real_bytes);
 }
 
-static void fill_shape(TileShapeHost& t, int D, int M, int ncomp, int real_bytes, const int64_t* Nover, const int n[3], bool padded, int bin_log2) {
+static void fill_shape(TileShapeHost& t, int D, int M, int ncomp, int real_bytes, const int64_t* Nover, const int n[3], bool padded, int bin_log2, bool no_pad) {
     const int halo = padded ? 2 * M - 1 : 0;
     int P[3] = {1, 1, 1};
     t.ntiles = 1;
@@ -240,7 +240,7 @@ static void fill_shape(TileShapeHost& t, int D, int M, int ncomp, int real_bytes
         P[d] = d < D ? n[d] + halo : 1;
         t.ntiles *= t.nt[d];
     }
-    t.row_stride = (!padded && D >= 2) ? lds_row_stride(ncomp * P[0], ncomp * 2 * M, 8) : ncomp * P[0];
+    t.row_stride = (!padded && D >= 2) ? lds_row_stride(ncomp * P[0], ncomp * 2 * M, 8, no_pad) : ncomp * P[0];
     t.rows[0] = P[1];
     t.rows[1] = P[2];
     t.plane_stride = padded ? t.row_stride * P[1] : spread_plane_stride(t.row_stride, P[1], D, ncomp);
@@ -297,9 +297,10 @@ static int64_t candidate_lds(bool spreading, int D, int M, int ncomp, int real_b
                       spreading ? spread_strip_pad(D, ncomp) : 0).total;
 }
 
-bool choose_tiles(int D, int M, int ncomp, int real_bytes, const int64_t* Nover, int lds_budget_bytes,
+bool choose_tiles(const Options& opts, int D, int M, int ncomp, int real_bytes, const int64_t* Nover, int lds_budget_bytes,
                   int spread_waves, int interp_waves, const int* forced_sp, const int* forced_ip, int bin_log2,
                   TileGeom& g) {
+    const bool no_pad = opts.option_present("NUFFT_LDS_NO_PAD");
     const int halo = 2 * M - 1;
     g.nbins = 1;
     for (int d = 0; d < 3; ++d) {
@@ -330,10 +331,10 @@ bool choose_tiles(int D, int M, int ncomp, int real_bytes, const int64_t* Nover,
                 }
                 bn[d] = n;
             }
-            if (!fits((int64_t)spread_plane_stride(D >= 2 ? lds_row_stride(ncomp * bn[0], ncomp * 2 * M, 8) : ncomp * bn[0], bn[1], D, ncomp) * bn[2], bn)) return false;
+            if (!fits((int64_t)spread_plane_stride(D >= 2 ? lds_row_stride(ncomp * bn[0], ncomp * 2 * M, 8, no_pad) : ncomp * bn[0], bn[1], D, ncomp) * bn[2], bn)) return false;
         } else {
             for (int n3 : cand[2]) for (int n2 : cand[1]) for (int n1 : cand[0]) {
-                const int64_t elems = (int64_t)spread_plane_stride(D >= 2 ? lds_row_stride(ncomp * n1, ncomp * 2 * M, 8) : ncomp * n1, n2, D, ncomp) * n3;
+                const int64_t elems = (int64_t)spread_plane_stride(D >= 2 ? lds_row_stride(ncomp * n1, ncomp * 2 * M, 8, no_pad) : ncomp * n1, n2, D, ncomp) * n3;
                 const int n[3] = {n1, n2, n3};
                 if (!fits(elems, n)) continue;
                 double cost = 1.0;
@@ -345,7 +346,7 @@ bool choose_tiles(int D, int M, int ncomp, int real_bytes, const int64_t* Nover,
             }
             if (bn[0] == 0) return false;
         }
-        fill_shape(g.sp, D, M, ncomp, real_bytes, Nover, bn, false, bin_log2);
+        fill_shape(g.sp, D, M, ncomp, real_bytes, Nover, bn, false, bin_log2, no_pad);
         if (exact_tile_runs(true, D, M, Nover, bin_log2, g.sp) > g.sp.max_items) return false;
     }
     // --- interpolation tile: padded, grid precision; cost = halo amplification of the tile load ---
@@ -390,7 +391,7 @@ bool choose_tiles(int D, int M, int ncomp, int real_bytes, const int64_t* Nover,
             }
             if (bn[0] == 0) return false;
         }
-        fill_shape(g.ip, D, M, ncomp, real_bytes, Nover, bn, true, bin_log2);
+        fill_shape(g.ip, D, M, ncomp, real_bytes, Nover, bn, true, bin_log2, no_pad);
         if (exact_tile_runs(false, D, M, Nover, bin_log2, g.ip) > g.ip.max_items) return false;
     }
     return true;

@@ -136,7 +136,7 @@ static double smarch_makespan(const std::vector<double>& task_work, int C, int c
 // (multiples of the bin edge) and the number of segments along z that minimise  point visits / chip utilisation,
 // where visits = prod (n + 2M - 1) / n over x, y (partial last columns counted) x (segl + c_z) / segl for the layers a
 // segment visits beyond its own, and the utilisation comes from the launch model above.
-SMarchPlan smarch_plan(int dtype, int is_complex, int D, int M, const Geom& g, bool other, int cus, int C, int halo, int parts) {
+SMarchPlan smarch_plan(const Options& opts, int dtype, int is_complex, int D, int M, const Geom& g, bool other, int cus, int C, int halo, int parts) {
     SMarchPlan sp{};
     int lds = 0, n[5];
     if (halo != 2) halo = 0;
@@ -156,8 +156,8 @@ SMarchPlan smarch_plan(int dtype, int is_complex, int D, int M, const Geom& g, b
     if (8 + L - 1 > g.Nover[0] || 8 + L - 1 > g.Nover[1] || g.nb[2] < 2 * (hlo + hhi) || g.nb[2] > 2048) return sp;
     // input-driven dimensions: the window (column + 2M) must not wrap onto itself
     if ((hx && 8 + 2 * L > g.Nover[0]) || (hy && 8 + 2 * L > g.Nover[1])) return sp;
-    const int xcd_chunk = option_int("NUFFT_XCD_CHUNK", 8);
-    const int force_n1 = option_int("NUFFT_SMARCH_N1", 0), force_n2 = option_int("NUFFT_SMARCH_N2", 0), force_nseg = option_int("NUFFT_SMARCH_NSEG", 0);
+    const int xcd_chunk = opts.option_int("NUFFT_XCD_CHUNK", 8);
+    const int force_n1 = opts.option_int("NUFFT_SMARCH_N1", 0), force_n2 = opts.option_int("NUFFT_SMARCH_N2", 0), force_nseg = opts.option_int("NUFFT_SMARCH_NSEG", 0);
     const double cz = 0.5 * (hlo + hhi);               // a halo layer's points are visited, but add about half their planes
     const double fixed = 0.15;                         // per task, in layers: ring zero fill, first table, launch
     double best = 1e300;
@@ -445,7 +445,7 @@ static const void* patch_kernel(int dtype, int is_complex, int M, bool other, in
 // Patch decomposition of a plan, or eligible = false: 3-D grids of 4-cell bins whose axes are multiples of the bin
 // edge and long enough that the bins a patch visits are distinct and a stencil cannot reach a patch from both
 // sides; default window evaluation without per-point weights (those use the LDS-tile kernel).
-PatchPlan patch_plan(int dtype, int is_complex, int D, int M, const Geom& g, bool other, bool allow_f32acc, int planar_nc) {
+PatchPlan patch_plan(const Options& opts, int dtype, int is_complex, int D, int M, const Geom& g, bool other, bool allow_f32acc, int planar_nc) {
     PatchPlan pp{};
     int lds = 0, pby = 0;
     if (D != 3 || !patch_kernel(dtype, is_complex, M, other, &lds, &pby)) return pp;
@@ -474,7 +474,7 @@ PatchPlan patch_plan(int dtype, int is_complex, int D, int M, const Geom& g, boo
     // segments along dimension 3: enough tasks for ~4 rounds of the 2048 resident waves, at least 8 cube layers each
     // (a segment visits ncb - 1 bin layers beyond its own)
     const int cols = pp.npx * pp.npy;
-    const int task_target = option_int("NUFFT_PATCH_TASKS", 8192);
+    const int task_target = opts.option_int("NUFFT_PATCH_TASKS", 8192);
     int nseg = (task_target + cols - 1) / cols;
     const int max_seg = g.nb[2] / 8 > 0 ? g.nb[2] / 8 : 1;
     if (nseg > max_seg) nseg = max_seg;
@@ -677,7 +677,7 @@ static hipError_t launch_smarch_t(const TileKernelArgs& a, const SMarchPlan& sp,
 hipError_t launch_spread_march(const TileKernelArgs& a, const SMarchPlan& sp, const uint32_t* flag, const uint2* tasktab, uint32_t* halo_state, bool dense, hipStream_t stream) {
     return a.dtype == NUFFT_F32 ? launch_smarch_t<float>(a, sp, flag, tasktab, halo_state, dense, stream) : launch_smarch_t<double>(a, sp, flag, tasktab, halo_state, dense, stream);
 }
-hipError_t launch_smarch_halo_add(const TileKernelArgs& a, const SMarchPlan& sp, const uint32_t* flag, hipStream_t stream) {
+hipError_t launch_smarch_halo_add(const Options& opts, const TileKernelArgs& a, const SMarchPlan& sp, const uint32_t* flag, hipStream_t stream) {
     if (sp.halo != 2) return hipSuccess;
     if (!a.halo) return hipErrorInvalidValue;
     const int ncr = a.is_complex ? 2 : 1;
@@ -687,7 +687,7 @@ hipError_t launch_smarch_halo_add(const TileKernelArgs& a, const SMarchPlan& sp,
         return launch_halo_add_lines(a.dtype, a.grid, a.halo, a.grid_stride * ncr, sp.halo_reals, a.g.Nover[0], a.g.Nover[1], a.g.Nover[2], a.C, h, flag, stream, true);
     }
     // line by line through LDS (fft_lines.hip: 0.6 ms at C2); the element-wise gather kernel (1.5 ms) where a line does not fit
-    const bool gather = option_int("NUFFT_SMARCH_HALO_ADD_GATHER", 0) != 0;
+    const bool gather = opts.option_int("NUFFT_SMARCH_HALO_ADD_GATHER", 0) != 0;
     if (!gather) {
         const HaloLayout h = make_halo_layout(sp.n1, sp.n2, a.M, ncr, sp.ct.ncolx, sp.ct.ncoly);
         hipError_t e = launch_halo_add_lines(a.dtype, a.grid, a.halo, a.grid_stride * ncr, sp.halo_reals, a.g.Nover[0], a.g.Nover[1], a.g.Nover[2], a.C, h, flag, stream);

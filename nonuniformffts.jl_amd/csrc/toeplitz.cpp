@@ -503,9 +503,8 @@ int nufft_toeplitz_create(nufft_toeplitz** out, const nufft_plan* plan) {
     t->point_transform = plan->point_transform;
     t->sigma_req = plan->sigma_req;
     t->options = plan->opts.str();
-    nufft::set_current_options(&plan->opts);
-    bool fused = plan->D >= 2 && nufft::option_int("NUFFT_TOEPLITZ_FUSED", 1) != 0;
-    t->maps_inpass = nufft::option_int("NUFFT_TOEPLITZ_MAPS_INPASS", 1) != 0;
+    bool fused = plan->D >= 2 && plan->opts.option_int("NUFFT_TOEPLITZ_FUSED", 1) != 0;
+    t->maps_inpass = plan->opts.option_int("NUFFT_TOEPLITZ_MAPS_INPASS", 1) != 0;
     for (int d = 0; d < 3; ++d) {
         const bool in = d < plan->D;
         t->N[d] = in ? plan->N[d] : 1;

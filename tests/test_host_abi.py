@@ -361,7 +361,7 @@ def test_development_switches_travel_in_the_params_not_in_the_environment(nufft,
 def test_gpu_parametrisations_are_eligible_by_construction(nufft, monkeypatch):
     """VERDICT round 5 (weak 2, item 7c): 8 of the 13 parametrisations of the round's headline GPU test skipped ("no common column").  The
     eligibility of every parametrisation of the column-layer-sort test is computed here from host-only plans (device = -1: the decisions
-    of build_device that need no device, plan.cpp predict_sort_column) — the test itself asserts instead of skipping, and this one fails
+    of build_device that need no device, plan_engines.cpp decide_engines) — the test itself asserts instead of skipping, and this one fails
     on the CPU when more than 10 % of a list would not be eligible."""
     import importlib.util
     spec = importlib.util.spec_from_file_location("gpu_parity_list", os.path.join(ROOT, "tests", "test_gpu_parity.py"))
