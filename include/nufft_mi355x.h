@@ -1696,6 +1696,112 @@ int nufft_coilcomp_get_matrix(nufft_coilcomp* h, double* host_out, void* stream)
 int nufft_coilcomp_get_spectrum(nufft_coilcomp* h, double* lambda_out, int32_t* sweeps_out, int32_t* status_out, void* stream);
 int64_t nufft_sizeof_coilcomp_info(void);
 
+/* ---- Off-resonance correction by time segmentation: the segmented Toeplitz operator ----
+ * With a field map ω(x) the signal model is y_j = Σ_x exp(−i ω(x) t_j) a_j(x) S_c(x) u(x), a_j(x) the plan's type-2 kernel.  Time
+ * segmentation writes exp(−i ω t) ≈ Σ_l φ_l(t) exp(−i ω τ_l), l = 0 ... L − 1, so with the factors B_l(x) = exp(−i ω(x) τ_l)
+ *
+ *     y ≈ Σ_l φ_l ⊙ A (B_l ⊙ S_c ⊙ u)
+ *     G_ω u = Σ_c conj(S_c) ⊙ Σ_a conj(B_a) ⊙ Σ_b Toeplitz(T_ab) (B_b ⊙ S_c ⊙ u),     T_ab from  w conj(φ_a) φ_b
+ *
+ * The inner L × L block is the block multiplier of a coupled operator; outside, the operator has ONE component.  A SEGMENTED operator
+ * is that: nufft_toeplitz_info.ntransforms is 1 for life, so the solvers (CG, FISTA, TV, nufft_toeplitz_max_eigenvalue), the wavelet
+ * transform, the total variation and everything else created for it see one image; nufft_toeplitz_num_coupled and
+ * nufft_toeplitz_num_frames return 0 and nufft_toeplitz_num_segments returns L.
+ *
+ * Builds: nufft_toeplitz_set_points_coupled (basis = the L rows φ_l) and nufft_toeplitz_set_spectra_coupled (the L (L + 1) / 2 pair
+ * spectra) with K = L, and nufft_toeplitz_multiplier_pair_ptr, work as on a coupled operator.  nufft_toeplitz_set_points,
+ * _set_spectrum, _set_points_frames, _set_spectra_frames and nufft_toeplitz_multiplier_ptr return NUFFT_ERR_UNSUPPORTED.
+ *
+ * Factors: L complex arrays shaped like û, 16-byte aligned, BORROWED like coil maps (they must stay alive and unchanged while set);
+ * any values, not only unit-modulus exponentials.  Builds, factors and coil maps are independent and may come in any order.
+ * has_spectrum is 1 only while a build and the factors are both in force; nufft_toeplitz_apply before that returns
+ * NUFFT_ERR_NO_POINTS.
+ *
+ * nufft_toeplitz_apply, all with the kernels of the coupled apply, on the fused and on the dense path:
+ *   without coil maps   for b = 0 ... L − 1 the backward half of û into intermediate b with B_b where the coil's map would multiply;
+ *                       the block multiply; for a = 0 ... L − 1 the forward half into out with conj(B_a), a = 0 storing, a > 0 adding.
+ *   with coil maps      per coil c in index order: v = S_c ⊙ û; the sequence above from v into w; out (+)= conj(S_c) ⊙ w.  v and w are
+ *                       two N^D scratch arrays, allocated when maps and factors are both set (never on a capturing stream), counted in
+ *                       workspace_bytes and freed when either is cleared.  NUFFT_TOEPLITZ_MAPS_INPASS plays no part.
+ * out == in is refused (NUFFT_ERR_INVALID_ARG).  The order is fixed and there are no atomics: two runs and a replayed graph give the
+ * same bits; the apply allocates nothing and never synchronises.  Storage: that of a coupled operator of L components.
+ * nufft_precond_create, _create_block and _update on a segmented operator return NUFFT_ERR_UNSUPPORTED.
+ *
+ * Added after ABI 104 without changing NUFFT_MI355X_VERSION or nufft_toeplitz_info: detect by symbol (dlsym
+ * nufft_toeplitz_create_segmented). */
+/* As nufft_toeplitz_create, with its refusals first; then: a plan with ntransforms != 1, nsegments < 1 NUFFT_ERR_INVALID_ARG;
+ * nsegments > 16 NUFFT_ERR_UNSUPPORTED; on the fused path, L lines of 2 N_1 cells that do not fit the coupled dimension-1 kernel
+ * NUFFT_ERR_UNSUPPORTED (the message names the plan option NUFFT_TOEPLITZ_FUSED=0). */
+int nufft_toeplitz_create_segmented(nufft_toeplitz** out, const nufft_plan* plan, int32_t nsegments);
+/* L of a segmented operator, 0 of any other. */
+int32_t nufft_toeplitz_num_segments(const nufft_toeplitz* tz);
+/* B[0 .. L): host table of device pointers.  Refusals: a null object or table, an operator that is not segmented
+ * NUFFT_ERR_INVALID_ARG; a host-only object NUFFT_ERR_NO_DEVICE; a null or not 16-byte aligned factor NUFFT_ERR_INVALID_ARG; with coil
+ * maps set and the scratch arrays not yet held, a capturing stream NUFFT_ERR_INVALID_ARG. */
+int nufft_toeplitz_set_factors(nufft_toeplitz* tz, const void* const* B, void* stream);
+/* Forgets the factors (has_spectrum returns to 0) and frees the two scratch arrays. */
+int nufft_toeplitz_clear_factors(nufft_toeplitz* tz);
+
+/* ---- The segment fit of a field map ----
+ * The histogram least-squares fit of Sutton, Noll & Fessler (IEEE TMI 2003): the interpolators φ_l(t) minimise
+ * Σ_b h_b |exp(−i ω_b t) − Σ_l φ_l(t) exp(−i ω_b τ_l)|² over the histogram (h_b, ω_b) of the field map.  Like coil compression the
+ * object needs no plan: it knows the element type, 1 <= L <= 16, 1 <= nbins <= 1024 and the device.
+ *
+ *     range       FP64 minimum and maximum of ω over the mask, and the count of values that are not finite
+ *     histogram   bin = min(nbins − 1, (int)((ω − ωmin) · scale)) in FP64, scale = nbins / (ωmax − ωmin) from the host; uint32 counts by
+ *                 integer atomics: exact and the same in every run.  ωmax == ωmin: one bin, at that value
+ *     centres     ω_b = ωmin + (b + 1/2) (ωmax − ωmin) / nbins
+ *     Gm[l, l']   = Σ_b h_b exp(−i ω_b (τ_l' − τ_l))                               host, FP64
+ *     P           = (Gm + ridge · (tr Gm / L) · I)^-1 by Cholesky                   host, FP64
+ *     φ(t_j)      = P r,  r_l = Σ_b h_b exp(−i ω_b (t_j − τ_l))                     device, FP64, rounded once to the element type
+ *     B_l(x)      = exp(−i ω(x) τ_l)                                               device, FP64, rounded once
+ *
+ * interpolators and factors allocate nothing, never synchronise and are hipGraph-capture safe; two runs give the same bits.  fit and
+ * the read-backs synchronise `stream` and are refused on a capturing one.  One call at a time per object.  Added after ABI 104 without
+ * changing NUFFT_MI355X_VERSION: detect by symbol (dlsym nufft_fieldseg_create) and compare nufft_sizeof_fieldseg_info() with your own. */
+typedef struct nufft_fieldseg nufft_fieldseg; /* opaque */
+
+typedef struct nufft_fieldseg_info {
+    int32_t struct_size;     /* sizeof(nufft_fieldseg_info) of the caller's header, set before the call (0 = this layout)           */
+    int32_t dtype, nsegments, nbins, device;
+    int32_t threads;         /* of a workgroup of every kernel; the interpolator kernel runs one sample per thread                 */
+    int32_t segment_tier;    /* accumulators of the interpolator kernel's instantiation: 1, 2, 4, 8 or 16                          */
+    int32_t reseed_bins;     /* bins between two exact sincos of the recurrence = bins of one staged piece of the table            */
+    int32_t max_workgroups;  /* of the range kernel = rows of partials the object holds                                            */
+    int32_t lds_bytes_interpolators, lds_bytes_histogram;   /* of one workgroup                                                   */
+    int32_t bins_used;       /* 0 before the first fit, 1 for a constant field map, else nbins                                     */
+    int64_t workspace_bytes; /* device bytes owned: partials, counts, centres, the table h_b exp(i ω_b τ_l), Gm and P             */
+} nufft_fieldseg_info;
+
+/* dtype: the real type of ω, of the times and of the complex outputs.  Refusals, in order: a null argument, an unknown dtype,
+ * nsegments < 1, nbins outside 1 ... 1024 NUFFT_ERR_INVALID_ARG; nsegments > 16 NUFFT_ERR_UNSUPPORTED; device < 0 NUFFT_ERR_NO_DEVICE. */
+int nufft_fieldseg_create(nufft_fieldseg** out, int dtype, int32_t nsegments, int32_t nbins, int device);
+int nufft_fieldseg_destroy(nufft_fieldseg* h);
+/* What an object of these arguments would launch, without a device: the same checks in the same order; device = -1. */
+int nufft_fieldseg_layout(int dtype, int32_t nsegments, int32_t nbins, nufft_fieldseg_info* out);
+/* Does not synchronise. */
+int nufft_fieldseg_get_info(const nufft_fieldseg* h, nufft_fieldseg_info* out);
+/* omega: real(T)[n] on the device; mask: NULL or uint8[n] on the device, nonzero = counted; tau: nsegments doubles on the HOST,
+ * strictly increasing; ridge >= 0.  Refusals, in order: a null object, omega or tau, n < 1, misaligned omega, tau not finite or not
+ * strictly increasing, ridge negative or not finite, a capturing stream, an empty mask, a counted value that is not finite, a range
+ * whose scale is not finite, a pivot of the Cholesky factor that is not positive (the message names ridge): all
+ * NUFFT_ERR_INVALID_ARG.  After a refused fit the object is unfitted. */
+int nufft_fieldseg_fit(nufft_fieldseg* h, const void* omega, const uint8_t* mask, int64_t n, const double* tau, double ridge, void* stream);
+/* times: real(T)[num_points] on the device; phi_rows[0 .. nsegments): host table of device pointers to complex(T)[num_points], 16-byte
+ * aligned: row l receives φ_l(t_j).  Refusals: a null argument, no fit yet, num_points < 1, misaligned times, a null or misaligned row
+ * NUFFT_ERR_INVALID_ARG. */
+int nufft_fieldseg_interpolators(nufft_fieldseg* h, const void* times, int64_t num_points, void* const* phi_rows, void* stream);
+/* B[0 .. nsegments): host table of device pointers to complex(T)[n], 16-byte aligned: B[l][x] = exp(−i omega[x] τ_l) with the τ of the
+ * last fit; nufft_toeplitz_set_factors takes the same table.  Refusals as above. */
+int nufft_fieldseg_factors(nufft_fieldseg* h, const void* omega, int64_t n, void* const* B, void* stream);
+/* Copies to the host (each output may be NULL): bins_used counts and centres; Gm and P as nsegments x nsegments complex doubles
+ * (re, im), row-major; tau as nsegments doubles.  Refused before the first fit and on a capturing stream. */
+int nufft_fieldseg_get_histogram(nufft_fieldseg* h, uint32_t* counts_out, double* centres_out, void* stream);
+int nufft_fieldseg_get_gram(nufft_fieldseg* h, double* host_out, void* stream);
+int nufft_fieldseg_get_solver_matrix(nufft_fieldseg* h, double* host_out, void* stream);
+int nufft_fieldseg_get_tau(nufft_fieldseg* h, double* host_out, void* stream);
+int64_t nufft_sizeof_fieldseg_info(void);
+
 /* ---- misc ----------------------------------------------------------------------------- */
 /* sizeof(nufft_params) / sizeof(nufft_info) of the library build: a binding that mirrors the structs by hand
  * (ctypes, Julia) compares them with its own layout before the first call. */

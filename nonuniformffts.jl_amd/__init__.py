@@ -28,6 +28,7 @@ from .lps import GlobalLowRank, TemporalSparsity, ToeplitzLPS  # noqa: F401
 from .dcf import DensityCompensation, density_weights  # noqa: F401
 from .coilmaps import CoilMapEstimator, calibration_weights, estimate_maps  # noqa: F401
 from .coilcomp import CoilCompressor, compress_coils  # noqa: F401
+from .field import FieldSegments, field_corrected_operator  # noqa: F401
 from . import autograd  # noqa: F401
 
 __all__ = [
@@ -43,4 +44,5 @@ __all__ = [
     "DensityCompensation", "density_weights",
     "CoilMapEstimator", "estimate_maps", "calibration_weights",
     "CoilCompressor", "compress_coils",
+    "FieldSegments", "field_corrected_operator",
 ]

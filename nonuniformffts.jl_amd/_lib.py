@@ -315,6 +315,15 @@ DCF_MAX_ITER, DCF_CONVERGED, DCF_BREAKDOWN = 0, 1, 2
 DCF_STATUS_NAMES = {DCF_MAX_ITER: "max_iter", DCF_CONVERGED: "converged", DCF_BREAKDOWN: "breakdown"}
 DCF_NORMALIZE = {"sum": 0, "none": 1}
 
+class NufftFieldsegInfo(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("dtype", C.c_int32), ("nsegments", C.c_int32), ("nbins", C.c_int32), ("device", C.c_int32),
+        ("threads", C.c_int32), ("segment_tier", C.c_int32), ("reseed_bins", C.c_int32), ("max_workgroups", C.c_int32),
+        ("lds_bytes_interpolators", C.c_int32), ("lds_bytes_histogram", C.c_int32), ("bins_used", C.c_int32),
+        ("workspace_bytes", C.c_int64),
+    ]
+
+
 NUM_STAGES3 = 6
 STAGE_NAMES3 = ("prep_sources", "prep_targets", "premultiply", "spread", "type2", "postmultiply")
 
@@ -525,6 +534,22 @@ SYMBOLS = {
     "nufft_coilcomp_get_matrix": (C.c_int, [_P, C.POINTER(C.c_double), _P]),
     "nufft_coilcomp_get_spectrum": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
     "nufft_sizeof_coilcomp_info": (C.c_int64, []),
+    "nufft_toeplitz_create_segmented": (C.c_int, [C.POINTER(_P), _P, C.c_int32]),
+    "nufft_toeplitz_num_segments": (C.c_int32, [_P]),
+    "nufft_toeplitz_set_factors": (C.c_int, [_P, _PP, _P]),
+    "nufft_toeplitz_clear_factors": (C.c_int, [_P]),
+    "nufft_fieldseg_create": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int32, C.c_int32, C.c_int]),
+    "nufft_fieldseg_destroy": (C.c_int, [_P]),
+    "nufft_fieldseg_layout": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.POINTER(NufftFieldsegInfo)]),
+    "nufft_fieldseg_get_info": (C.c_int, [_P, C.POINTER(NufftFieldsegInfo)]),
+    "nufft_fieldseg_fit": (C.c_int, [_P, _P, _P, C.c_int64, C.POINTER(C.c_double), C.c_double, _P]),
+    "nufft_fieldseg_interpolators": (C.c_int, [_P, _P, C.c_int64, _PP, _P]),
+    "nufft_fieldseg_factors": (C.c_int, [_P, _P, C.c_int64, _PP, _P]),
+    "nufft_fieldseg_get_histogram": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_double), _P]),
+    "nufft_fieldseg_get_gram": (C.c_int, [_P, C.POINTER(C.c_double), _P]),
+    "nufft_fieldseg_get_solver_matrix": (C.c_int, [_P, C.POINTER(C.c_double), _P]),
+    "nufft_fieldseg_get_tau": (C.c_int, [_P, C.POINTER(C.c_double), _P]),
+    "nufft_sizeof_fieldseg_info": (C.c_int64, []),
     "nufft_sizeof_params": (C.c_int64, []),
     "nufft_sizeof_info": (C.c_int64, []),
     "nufft_strerror": (C.c_char_p, [C.c_int]),
@@ -564,7 +589,8 @@ def _load():
                          ("nufft_sizeof_tvt_params", NufftTvtParams), ("nufft_sizeof_glr_info", NufftGlrInfo),
                          ("nufft_sizeof_tsparse_info", NufftTsparseInfo), ("nufft_sizeof_lps_params", NufftLpsParams),
                          ("nufft_sizeof_lps_info", NufftLpsInfo), ("nufft_sizeof_coilmaps_params", NufftCoilmapsParams),
-                         ("nufft_sizeof_coilmaps_info", NufftCoilmapsInfo), ("nufft_sizeof_coilcomp_info", NufftCoilcompInfo)):
+                         ("nufft_sizeof_coilmaps_info", NufftCoilmapsInfo), ("nufft_sizeof_coilcomp_info", NufftCoilcompInfo),
+                         ("nufft_sizeof_fieldseg_info", NufftFieldsegInfo)):
         if getattr(lib, name)() != C.sizeof(mirror):
             raise ImportError(f"{LIB_PATH}: {name}() = {getattr(lib, name)()} but the ctypes mirror has {C.sizeof(mirror)} bytes "
                               "(include/nufft_mi355x.h and _lib.py disagree)")

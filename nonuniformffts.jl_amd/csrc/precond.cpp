@@ -187,6 +187,9 @@ int check_coupling(const nufft_precond* p) {
     if (nufft_toeplitz_num_frames(p->tz) > 0)
         return fail(NUFFT_ERR_UNSUPPORTED, "the operator is framed (nufft_toeplitz_set_points_frames / _set_spectra_frames: one multiplier per component): "
                                            "a preconditioner of per-frame circulants is not built");
+    if (nufft_toeplitz_num_segments(p->tz) > 0)
+        return fail(NUFFT_ERR_UNSUPPORTED, "the operator is segmented (nufft_toeplitz_create_segmented: field-map factors around a block of segments): "
+                                           "a preconditioner of the folded operator is not built");
     const int K = nufft_toeplitz_num_coupled(p->tz);
     if (p->K == 0 && K > 0)
         return fail(NUFFT_ERR_UNSUPPORTED, "the operator couples its components: nufft_precond_create builds the preconditioner of independent components; a "
@@ -435,6 +438,9 @@ int create(nufft_precond** out, nufft_toeplitz* tz, const nufft_precond_params* 
     if (nufft_toeplitz_num_frames(tz) > 0)
         return fail(NUFFT_ERR_UNSUPPORTED, "the operator is framed (nufft_toeplitz_set_points_frames / _set_spectra_frames: one multiplier per component): "
                                            "a preconditioner of per-frame circulants is not built");
+    if (nufft_toeplitz_num_segments(tz) > 0)
+        return fail(NUFFT_ERR_UNSUPPORTED, "the operator is segmented (nufft_toeplitz_create_segmented: field-map factors around a block of segments): "
+                                           "a preconditioner of the folded operator is not built");
 
     nufft_precond* p = new (std::nothrow) nufft_precond();
     if (!p) return fail(NUFFT_ERR_ALLOC, "out of host memory");

@@ -13,6 +13,11 @@
 // With a coupled build the C components are one block operator, out[a] = Σ_b Toeplitz(T_ab) in[b]: the halves of
 // the apply before and after the multiply run per component into C intermediates, and one kernel applies the C × C block of
 // multipliers (C real grids K_aa, C (C − 1) / 2 complex grids K_ab, a < b; K_ba = conj(K_ab)) to every cell in between.
+//
+// A segmented operator (off-resonance correction by time segmentation) has one component outside and L coupled
+// segments inside: G_ω û = Σ_a conj(B_a) ⊙ Σ_b Toeplitz(T_ab) (B_b ⊙ û).  It is the coupled apply with in[b] = û for every b, the factor
+// B_b where the coil's map multiplies, and every forward half accumulating into the one output; coil maps go around it through two
+// scratch arrays.
 #include <hip/hip_runtime.h>
 #include <rocfft/rocfft.h>
 
@@ -70,12 +75,19 @@ struct nufft_toeplitz {
     // coupled one
     bool framed = false;
     void* d_kf = nullptr;                              // C arrays like d_K, frame_stride bytes apart
+    // time segments: fixed at creation; C = 1 outside, `seg` coupled segments inside
+    int seg = 0;                                       // L of nufft_toeplitz_create_segmented, 0 on an ordinary operator
+    std::vector<const void*> factors;                  // B_l: borrowed device pointers, the host table is the operator's
+    void* d_sv = nullptr;                              // complex<T>[N_1, N_2, N_3] each: S_c ⊙ û and the folded product of one coil,
+    void* d_sw = nullptr;                              // held while coil maps and factors are both set
 };
 
 namespace {
 
 int64_t grid_cells(const nufft_toeplitz* t) { return t->N2[0] * t->N2[1] * t->N2[2]; }
 int64_t num_modes(const nufft_toeplitz* t) { return t->N[0] * t->N[1] * t->N[2]; }
+// The size of the coupled block: the segments of a segmented operator, the components of any other.
+int inner(const nufft_toeplitz* t) { return t->seg > 0 ? t->seg : t->C; }
 
 // Bytes of every buffer the object holds at rest, in allocation order (a host-only object reports their sum; rocFFT's own work
 // buffer, known only on a device, comes on top for the dense path).
@@ -105,19 +117,19 @@ int alloc(nufft_toeplitz* t, void** ptr, size_t bytes) { return alloc_buffer(t->
 
 // The buffers of a coupled build: C real and C (C − 1) / 2 complex multiplier grids, and C intermediates (each padded on its own:
 // the components of d_grids are grid_stride complex elements apart).
-size_t coupled_kd_bytes(const nufft_toeplitz* t) { return (size_t)t->C * (size_t)grid_cells(t) * real_bytes(t->dtype); }
-size_t coupled_kc_bytes(const nufft_toeplitz* t) { return (size_t)(t->C * (t->C - 1) / 2) * (size_t)grid_cells(t) * 2 * real_bytes(t->dtype); }
+size_t coupled_kd_bytes(const nufft_toeplitz* t) { return (size_t)inner(t) * (size_t)grid_cells(t) * real_bytes(t->dtype); }
+size_t coupled_kc_bytes(const nufft_toeplitz* t) { return (size_t)(inner(t) * (inner(t) - 1) / 2) * (size_t)grid_cells(t) * 2 * real_bytes(t->dtype); }
 size_t coupled_grid_stride(const nufft_toeplitz* t) {
     const size_t cb = 2 * real_bytes(t->dtype);
     const size_t n = t->path == NUFFT_TOEPLITZ_PATH_FUSED ? (size_t)(t->N[0] * t->N2[1] * t->N2[2]) : (size_t)grid_cells(t);
     return padded(n * cb) / cb;
 }
-size_t coupled_grids_bytes(const nufft_toeplitz* t) { return (size_t)t->C * coupled_grid_stride(t) * 2 * real_bytes(t->dtype); }
+size_t coupled_grids_bytes(const nufft_toeplitz* t) { return (size_t)inner(t) * coupled_grid_stride(t) * 2 * real_bytes(t->dtype); }
 
 int acquire_coupled(nufft_toeplitz* t) {
     int rc;
     if (!t->d_kd && (rc = alloc(t, &t->d_kd, coupled_kd_bytes(t)))) return rc;
-    if (!t->d_kc && t->C > 1 && (rc = alloc(t, &t->d_kc, coupled_kc_bytes(t)))) return rc;
+    if (!t->d_kc && inner(t) > 1 && (rc = alloc(t, &t->d_kc, coupled_kc_bytes(t)))) return rc;
     if (!t->d_grids && (rc = alloc(t, &t->d_grids, coupled_grids_bytes(t)))) return rc;
     return NUFFT_OK;
 }
@@ -169,7 +181,7 @@ void release(nufft_toeplitz* t) {
             if (t->d_tw_fw[d]) (void)hipFree(t->d_tw_fw[d]);
             if (t->d_tw_bw[d]) (void)hipFree(t->d_tw_bw[d]);
         }
-        for (void* p : {t->d_ones, t->d_K, t->d_tmpA, t->d_tmpB, t->d_work, t->d_fft_work, t->d_coil, t->d_kd, t->d_kc, t->d_grids, t->d_kf})
+        for (void* p : {t->d_ones, t->d_K, t->d_tmpA, t->d_tmpB, t->d_work, t->d_fft_work, t->d_coil, t->d_kd, t->d_kc, t->d_grids, t->d_kf, t->d_sv, t->d_sw})
             if (p) (void)hipFree(p);
         if (t->fft_bw) (void)rocfft_plan_destroy(t->fft_bw);
         if (t->fft_fw) (void)rocfft_plan_destroy(t->fft_fw);
@@ -264,7 +276,7 @@ int multiplier_pair_from(nufft_toeplitz* t, void* grid, const void* src, int a, 
     if (a == b) {
         NUFFT_HIP(nufft::launch_tz_real_part(g, static_cast<char*>(t->d_kd) + (size_t)a * (size_t)grid_cells(t) * rb, grid, scale, t->num_cus, stream));
     } else {
-        void* kc = static_cast<char*>(t->d_kc) + (size_t)nufft::coupled_offdiag_index(a, b, t->C) * (size_t)grid_cells(t) * 2 * rb;
+        void* kc = static_cast<char*>(t->d_kc) + (size_t)nufft::coupled_offdiag_index(a, b, inner(t)) * (size_t)grid_cells(t) * 2 * rb;
         NUFFT_HIP(nufft::launch_tz_complex_part(g, kc, grid, scale, t->num_cus, stream));
     }
     return NUFFT_OK;
@@ -386,54 +398,97 @@ int apply_coil(nufft_toeplitz* t, const void* K, void* out, const void* in, cons
     return NUFFT_OK;
 }
 
-// One coil (or the plain operator, smap = null) of the coupled apply: out[a] (+)= conj(S) ⊙ Σ_b Toeplitz(T_ab) (S ⊙ in[b]).  All C
-// backward halves first, each into its own intermediate, then the block multiply across them, then the C forward halves.
-int apply_coupled(nufft_toeplitz* t, void* const* out, const void* const* in, const void* smap, bool accumulate, hipStream_t stream) {
+// One coil (or the plain operator, smap = null) of the coupled apply: out[a] (+)= conj(S) ⊙ Σ_b Toeplitz(T_ab) (S ⊙ in[b]).  All K
+// backward halves first, each into its own intermediate, then the block multiply across them, then the K forward halves.
+// `fold` (a segmented operator: its K factors): out[0] = Σ_a conj(B_a) ⊙ Σ_b Toeplitz(T_ab) (B_b ⊙ in[0]), segment 0 storing and the
+// others adding in index order.
+int apply_coupled(nufft_toeplitz* t, void* const* out, const void* const* in, const void* smap, bool accumulate, hipStream_t stream,
+                  const void* const* fold = nullptr) {
     const size_t stride = coupled_grid_stride(t), cb = 2 * real_bytes(t->dtype);
     auto grid_at = [&](int c) { return static_cast<void*>(static_cast<char*>(t->d_grids) + (size_t)c * stride * cb); };
     const bool fused = t->path == NUFFT_TOEPLITZ_PATH_FUSED;
     const nufft::TzGrid g = grid_of(t);
+    const int K = inner(t);
     int rc;
-    for (int b = 0; b < t->C; ++b) {
+    for (int b = 0; b < K; ++b) {
+        const void* src = fold ? in[0] : in[b];
+        const void* m = fold ? fold[b] : smap;
         if (fused) {
-            if ((rc = fused_backward(t, grid_at(b), in[b], stream, smap))) return rc;
+            if ((rc = fused_backward(t, grid_at(b), src, stream, m))) return rc;
             continue;
         }
         void* io[1] = {grid_at(b)};
-        if (smap) NUFFT_HIP(nufft::launch_tz_pad_map(g, io[0], in[b], smap, t->num_cus, stream));
-        else NUFFT_HIP(nufft::launch_tz_pad(g, io[0], in[b], t->num_cus, stream));
+        if (m) NUFFT_HIP(nufft::launch_tz_pad_map(g, io[0], src, m, t->num_cus, stream));
+        else NUFFT_HIP(nufft::launch_tz_pad(g, io[0], src, t->num_cus, stream));
         NUFFT_ROCFFT(rocfft_execute(t->fft_bw, io, nullptr, t->fft_info));
     }
     if (fused)
-        NUFFT_HIP(nufft::launch_toeplitz_lines_coupled(t->dtype, t->N2[0], t->C, t->d_grids, (int64_t)stride, t->d_kd, t->d_kc, t->N2[1] * t->N2[2],
+        NUFFT_HIP(nufft::launch_toeplitz_lines_coupled(t->dtype, t->N2[0], K, t->d_grids, (int64_t)stride, t->d_kd, t->d_kc, t->N2[1] * t->N2[2],
                                                     (int)t->N[0], t->d_map[0], t->d_tw_fw[0], stream));
     else
-        NUFFT_HIP(nufft::launch_tz_multiply_coupled(g, t->d_grids, (int64_t)stride, t->C, t->d_kd, t->d_kc, t->num_cus, stream));
-    for (int a = 0; a < t->C; ++a) {
+        NUFFT_HIP(nufft::launch_tz_multiply_coupled(g, t->d_grids, (int64_t)stride, K, t->d_kd, t->d_kc, t->num_cus, stream));
+    for (int a = 0; a < K; ++a) {
+        void* dst = fold ? out[0] : out[a];
+        const void* m = fold ? fold[a] : smap;
+        const bool acc = fold ? a > 0 : accumulate;
         if (fused) {
-            if ((rc = fused_forward(t, out[a], grid_at(a), stream, smap, accumulate))) return rc;
+            if ((rc = fused_forward(t, dst, grid_at(a), stream, m, acc))) return rc;
             continue;
         }
         void* io[1] = {grid_at(a)};
         NUFFT_ROCFFT(rocfft_execute(t->fft_fw, io, nullptr, t->fft_info));
-        if (smap) NUFFT_HIP(nufft::launch_tz_crop_map(g, out[a], io[0], smap, accumulate, t->num_cus, stream));
-        else NUFFT_HIP(nufft::launch_tz_crop(g, out[a], io[0], t->num_cus, stream));
+        if (m) NUFFT_HIP(nufft::launch_tz_crop_map(g, dst, io[0], m, acc, t->num_cus, stream));
+        else NUFFT_HIP(nufft::launch_tz_crop(g, dst, io[0], t->num_cus, stream));
+    }
+    return NUFFT_OK;
+}
+
+// The segmented operator.  Without coil maps one folded pass from `in` into `out`; with them, per coil in index order, v = S_c ⊙ in,
+// the folded pass from v into w, out (+)= conj(S_c) ⊙ w.
+int apply_segmented(nufft_toeplitz* t, void* out, const void* in, hipStream_t stream) {
+    const void* const* B = t->factors.data();
+    const int ncoils = (int)t->coil_maps.size();
+    if (ncoils == 0) {
+        void* outs[1] = {out};
+        const void* ins[1] = {in};
+        return apply_coupled(t, outs, ins, nullptr, false, stream, B);
+    }
+    for (int c = 0; c < ncoils; ++c) {
+        void* v[1] = {t->d_sv};
+        void* w[1] = {t->d_sw};
+        const void* vin[1] = {t->d_sv};
+        const void* win[1] = {t->d_sw};
+        const void* map[1] = {t->coil_maps[(size_t)c]};
+        NUFFT_HIP(nufft::launch_coil_expand(t->dtype, num_modes(t), 1, v, map, in, t->num_cus, stream));
+        if (int rc = apply_coupled(t, w, vin, nullptr, false, stream, B)) return rc;
+        NUFFT_HIP(nufft::launch_coil_combine(t->dtype, num_modes(t), 1, out, map, win, c > 0, t->num_cus, stream));
     }
     return NUFFT_OK;
 }
 
 // What every coupled build checks before it touches the device, in the order of the header.
 int coupled_refusals(const nufft_toeplitz* t, const char* fn) {
-    if (t->C > nufft::kMaxCoupled)
+    const int K = inner(t);
+    if (K > nufft::kMaxCoupled)
         return fail(NUFFT_ERR_UNSUPPORTED, std::string(fn) + ": at most " + std::to_string(nufft::kMaxCoupled) + " coupled components (ntransforms)");
-    if (t->path == NUFFT_TOEPLITZ_PATH_FUSED && !nufft::toeplitz_lines_coupled_supported(t->dtype, t->N2[0], t->C))
-        return fail(NUFFT_ERR_UNSUPPORTED, std::string(fn) + ": the " + std::to_string(t->C) + " lines of 2 N_1 = " + std::to_string(t->N2[0]) +
+    if (t->path == NUFFT_TOEPLITZ_PATH_FUSED && !nufft::toeplitz_lines_coupled_supported(t->dtype, t->N2[0], K))
+        return fail(NUFFT_ERR_UNSUPPORTED, std::string(fn) + ": the " + std::to_string(K) + " lines of 2 N_1 = " + std::to_string(t->N2[0]) +
                                                " cells of a line id do not fit the LDS of one wave of the fused dimension-1 kernel; create the "
                                                "operator from a plan with the option NUFFT_TOEPLITZ_FUSED=0 (the dense path)");
-    if (t->path == NUFFT_TOEPLITZ_PATH_FUSED && !t->maps_inpass && !t->coil_maps.empty())
+    if (!t->seg && t->path == NUFFT_TOEPLITZ_PATH_FUSED && !t->maps_inpass && !t->coil_maps.empty())
         return fail(NUFFT_ERR_UNSUPPORTED, std::string(fn) + ": coil maps on the route NUFFT_TOEPLITZ_MAPS_INPASS=0 do not combine with coupled components");
     return NUFFT_OK;
 }
+
+// What a segmented operator has no use for: one shared multiplier or one per frame.
+int segmented_refusal(const nufft_toeplitz* t, const char* fn) {
+    if (!t->seg) return NUFFT_OK;
+    return fail(NUFFT_ERR_UNSUPPORTED, std::string(fn) + ": the operator is segmented (nufft_toeplitz_create_segmented): its multiplier is the block of "
+                                           "its segments, built by nufft_toeplitz_set_points_coupled / _set_spectra_coupled");
+}
+
+// A build and, on a segmented operator, the factors: what nufft_toeplitz_apply needs.
+bool ready(const nufft_toeplitz* t) { return t->has_spectrum && (!t->seg || !t->factors.empty()); }
 
 // The internal 2N plan's parameters: the parent plan's window unless `build` overrides it (nufft_toeplitz_set_points).
 int build_plan_params(const nufft_toeplitz* t, const nufft_params* build, nufft_params& prm) {
@@ -471,6 +526,28 @@ size_t coil_scratch_bytes(const nufft_toeplitz* t) { return (size_t)num_modes(t)
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// The two scratch arrays of a segmented operator with coil maps: held exactly while maps and factors are both set.
+int acquire_segment_scratch(nufft_toeplitz* t, const char* fn, void* stream_) {
+    if (!t->seg || t->coil_maps.empty() || t->factors.empty() || t->d_sv) return NUFFT_OK;
+    DeviceGuard guard(t->device);
+    if (capturing(static_cast<hipStream_t>(stream_)))
+        return fail(NUFFT_ERR_INVALID_ARG, std::string(fn) + " allocates the two scratch arrays of a segmented operator with coil maps: not on a capturing stream");
+    int rc;
+    if ((rc = alloc(t, &t->d_sv, coil_scratch_bytes(t))) || (rc = alloc(t, &t->d_sw, coil_scratch_bytes(t)))) {
+        free_buffer(t->own_bytes, t->d_sv, coil_scratch_bytes(t));
+        return rc;
+    }
+    return NUFFT_OK;
+}
+void drop_segment_scratch(nufft_toeplitz* t) {
+    if (!t->d_sv && !t->d_sw) return;
+    DeviceGuard guard(t->device);
+    free_buffer(t->own_bytes, t->d_sv, coil_scratch_bytes(t));      // hipFree waits for the applies in flight
+    free_buffer(t->own_bytes, t->d_sw, coil_scratch_bytes(t));
+}
+
+int create(nufft_toeplitz** out, const nufft_plan* plan, int nsegments);
+
 }  // namespace
 
 const std::vector<const void*>& nufft::toeplitz_coil_maps(const nufft_toeplitz* t) { return t->coil_maps; }
@@ -479,7 +556,22 @@ extern "C" {
 
 int64_t nufft_sizeof_toeplitz_info(void) { return (int64_t)sizeof(nufft_toeplitz_info); }
 
-int nufft_toeplitz_create(nufft_toeplitz** out, const nufft_plan* plan) {
+int nufft_toeplitz_create(nufft_toeplitz** out, const nufft_plan* plan) { return create(out, plan, 0); }
+
+int nufft_toeplitz_create_segmented(nufft_toeplitz** out, const nufft_plan* plan, int32_t nsegments) {
+    if (!out || !plan) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    if (nsegments < 1) return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_create_segmented: nsegments = " + std::to_string(nsegments) + " must be at least 1");
+    if (nsegments > nufft::kMaxCoupled)
+        return fail(NUFFT_ERR_UNSUPPORTED, "nufft_toeplitz_create_segmented: at most " + std::to_string(nufft::kMaxCoupled) + " segments");
+    return create(out, plan, nsegments);
+}
+
+}  // extern "C"
+
+namespace {
+// nsegments = 0: an ordinary operator
+int create(nufft_toeplitz** out, const nufft_plan* plan, int nsegments) {
     if (!out || !plan) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
     *out = nullptr;
     if (!plan->is_complex)
@@ -489,11 +581,15 @@ int nufft_toeplitz_create(nufft_toeplitz** out, const nufft_plan* plan) {
                     "embedding aliases");
     for (int d = 0; d < plan->D; ++d)
         if (plan->N[d] > ((int64_t)1 << 29)) return fail(NUFFT_ERR_UNSUPPORTED, "2 N exceeds 2^30 cells per axis");
+    if (nsegments > 0 && plan->C != 1)
+        return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_create_segmented: a segmented operator has one component outside: the plan must have "
+                                           "ntransforms = 1 (got " + std::to_string(plan->C) + ")");
     nufft_toeplitz* t = new (std::nothrow) nufft_toeplitz();
     if (!t) return fail(NUFFT_ERR_ALLOC, "out of host memory");
     t->dtype = plan->dtype;
     t->D = plan->D;
     t->C = plan->C;
+    t->seg = nsegments;
     t->device = plan->device;
     t->num_cus = plan->num_cus;
     t->fftshift = plan->fftshift;
@@ -525,6 +621,13 @@ int nufft_toeplitz_create(nufft_toeplitz** out, const nufft_plan* plan) {
         for (size_t k = 0; k < t->map[d].size(); ++k) t->inv[d][(size_t)t->map[d][k]] = (int32_t)k;
     }
     t->path = fused ? NUFFT_TOEPLITZ_PATH_FUSED : NUFFT_TOEPLITZ_PATH_DENSE;
+    if (t->seg > 0) {
+        if (int rc = coupled_refusals(t, "nufft_toeplitz_create_segmented")) {
+            const std::string keep = nufft_last_error_message();
+            release(t);
+            return fail(rc, keep);
+        }
+    }
     if (t->device >= 0) {
         const int rc = build_device(t);
         if (rc) {
@@ -536,6 +639,9 @@ int nufft_toeplitz_create(nufft_toeplitz** out, const nufft_plan* plan) {
     *out = t;
     return NUFFT_OK;
 }
+}  // namespace
+
+extern "C" {
 
 int nufft_toeplitz_destroy(nufft_toeplitz* t) {
     release(t);
@@ -552,7 +658,7 @@ int nufft_toeplitz_get_info(const nufft_toeplitz* t, nufft_toeplitz_info* o) {
     i.fftshift = t->fftshift;
     i.device = t->device;
     i.path = t->path;
-    i.has_spectrum = t->has_spectrum;
+    i.has_spectrum = ready(t);
     for (int d = 0; d < 3; ++d) { i.N[d] = t->N[d]; i.N2[d] = t->N2[d]; }
     i.multiplier_bytes = grid_cells(t) * (int64_t)real_bytes(t->dtype);
     i.workspace_bytes = t->device >= 0 ? t->own_bytes + t->build_bytes : (int64_t)sizes_of(t).total();
@@ -562,6 +668,7 @@ int nufft_toeplitz_get_info(const nufft_toeplitz* t, nufft_toeplitz_info* o) {
 
 int nufft_toeplitz_multiplier_ptr(const nufft_toeplitz* t, void** out_ptr, int64_t* out_bytes) {
     if (!t || !out_ptr) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    if (int rc = segmented_refusal(t, "nufft_toeplitz_multiplier_ptr")) return rc;
     if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
     *out_ptr = t->d_K;
     if (out_bytes) *out_bytes = grid_cells(t) * (int64_t)real_bytes(t->dtype);
@@ -570,6 +677,7 @@ int nufft_toeplitz_multiplier_ptr(const nufft_toeplitz* t, void** out_ptr, int64
 
 int nufft_toeplitz_set_spectrum(nufft_toeplitz* t, const void* T_modes, void* stream_) {
     if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    if (int rc = segmented_refusal(t, "nufft_toeplitz_set_spectrum")) return rc;
     if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
     if (!T_modes) return fail(NUFFT_ERR_INVALID_ARG, "null spectrum");
     DeviceGuard guard(t->device);
@@ -591,6 +699,7 @@ int nufft_toeplitz_set_spectrum(nufft_toeplitz* t, const void* T_modes, void* st
 int nufft_toeplitz_set_points(nufft_toeplitz* t, const nufft_params* build, int64_t np, const void* const* coords, const void* weights,
                               void* stream_) {
     if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    if (int rc = segmented_refusal(t, "nufft_toeplitz_set_points")) return rc;
     if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
     if (np < 0) return fail(NUFFT_ERR_INVALID_ARG, "negative number of points");
     if (!coords) return fail(NUFFT_ERR_INVALID_ARG, "null coordinate table");
@@ -646,7 +755,7 @@ int nufft_toeplitz_set_spectra_coupled(nufft_toeplitz* t, const void* const* T_p
     if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
     if (!T_pairs) return fail(NUFFT_ERR_INVALID_ARG, "null table of spectra");
     if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
-    const int npairs = t->C * (t->C + 1) / 2;
+    const int K = inner(t), npairs = K * (K + 1) / 2;
     for (int p = 0; p < npairs; ++p)
         if (!T_pairs[p]) return fail(NUFFT_ERR_INVALID_ARG, "null spectrum");
     int rc;
@@ -661,8 +770,8 @@ int nufft_toeplitz_set_spectra_coupled(nufft_toeplitz* t, const void* const* T_p
     if ((rc = acquire_coupled(t))) return rc;
     Scratch s(t);
     if ((rc = s.acquire_grid()) || (rc = s.acquire_fft_work())) return rc;
-    for (int a = 0, p = 0; a < t->C; ++a)
-        for (int b = a; b < t->C; ++b, ++p)
+    for (int a = 0, p = 0; a < K; ++a)
+        for (int b = a; b < K; ++b, ++p)
             if ((rc = multiplier_pair_from(t, s.grid, T_pairs[p], a, b, stream))) return rc;
     NUFFT_HIP(hipStreamSynchronize(stream));      // the temporaries are freed on return
     t->coupled = true;
@@ -679,7 +788,8 @@ int nufft_toeplitz_set_points_coupled(nufft_toeplitz* t, const nufft_params* bui
     if (!coords) return fail(NUFFT_ERR_INVALID_ARG, "null coordinate table");
     for (int d = 0; d < t->D; ++d)
         if (np > 0 && !coords[d]) return fail(NUFFT_ERR_INVALID_ARG, "null coordinate vector");
-    for (int c = 0; c < t->C; ++c)
+    const int K = inner(t);
+    for (int c = 0; c < K; ++c)
         if (np > 0 && (!basis[c] || !aligned16(basis[c]))) return fail(NUFFT_ERR_INVALID_ARG, "null or not 16-byte aligned basis function");
     int rc;
     if ((rc = coupled_refusals(t, "nufft_toeplitz_set_points_coupled"))) return rc;
@@ -708,8 +818,8 @@ int nufft_toeplitz_set_points_coupled(nufft_toeplitz* t, const nufft_params* bui
         t->build_bytes = bp->workspace_bytes;
     }
     bool in_type1 = true;
-    for (int a = 0; a < t->C && rc == NUFFT_OK; ++a)
-        for (int b = a; b < t->C && rc == NUFFT_OK; ++b) {
+    for (int a = 0; a < K && rc == NUFFT_OK; ++a)
+        for (int b = a; b < K && rc == NUFFT_OK; ++b) {
             in_type1 = true;
             hipError_t e = nufft::launch_tz_pair_weights(t->dtype, values, weights, basis[a], basis[b], np, t->num_cus, stream);
             if (e != hipSuccess) rc = fail(NUFFT_ERR_HIP, std::string("launch_tz_pair_weights: ") + hipGetErrorString(e));
@@ -734,6 +844,7 @@ int nufft_toeplitz_set_points_coupled(nufft_toeplitz* t, const nufft_params* bui
 
 int nufft_toeplitz_set_spectra_frames(nufft_toeplitz* t, const void* const* T, void* stream_) {
     if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    if (int rc = segmented_refusal(t, "nufft_toeplitz_set_spectra_frames")) return rc;
     if (!T) return fail(NUFFT_ERR_INVALID_ARG, "null table of spectra");
     if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
     for (int c = 0; c < t->C; ++c)
@@ -760,6 +871,7 @@ int nufft_toeplitz_set_spectra_frames(nufft_toeplitz* t, const void* const* T, v
 int nufft_toeplitz_set_points_frames(nufft_toeplitz* t, const nufft_params* build, const int64_t* np, const void* const* coords,
                                      const void* const* weights, void* stream_) {
     if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    if (int rc = segmented_refusal(t, "nufft_toeplitz_set_points_frames")) return rc;
     if (!np || !coords) return fail(NUFFT_ERR_INVALID_ARG, "null table of point counts or coordinates");
     if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
     int64_t most = 1;
@@ -830,19 +942,22 @@ int nufft_toeplitz_multiplier_frame_ptr(const nufft_toeplitz* t, int32_t c, void
     return NUFFT_OK;
 }
 
-int32_t nufft_toeplitz_num_coupled(const nufft_toeplitz* t) { return t && t->coupled ? (int32_t)t->C : 0; }
+int32_t nufft_toeplitz_num_coupled(const nufft_toeplitz* t) { return t && t->coupled && !t->seg ? (int32_t)t->C : 0; }
+
+int32_t nufft_toeplitz_num_segments(const nufft_toeplitz* t) { return t ? (int32_t)t->seg : 0; }
 
 int nufft_toeplitz_multiplier_pair_ptr(const nufft_toeplitz* t, int32_t a, int32_t b, void** out_ptr, int64_t* out_bytes) {
     if (!t || !out_ptr) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
     if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
     if (!t->coupled) return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_multiplier_pair_ptr: no coupled build is in force");
-    if (a < 0 || b < a || b >= t->C) return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_multiplier_pair_ptr: the pair must satisfy 0 <= a <= b < ntransforms");
+    if (a < 0 || b < a || b >= inner(t))
+        return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_multiplier_pair_ptr: the pair must satisfy 0 <= a <= b < ntransforms (segmented: nsegments)");
     const int64_t rb = (int64_t)real_bytes(t->dtype);
     if (a == b) {
         *out_ptr = static_cast<char*>(t->d_kd) + a * grid_cells(t) * rb;
         if (out_bytes) *out_bytes = grid_cells(t) * rb;
     } else {
-        *out_ptr = static_cast<char*>(t->d_kc) + nufft::coupled_offdiag_index(a, b, t->C) * grid_cells(t) * 2 * rb;
+        *out_ptr = static_cast<char*>(t->d_kc) + nufft::coupled_offdiag_index(a, b, inner(t)) * grid_cells(t) * 2 * rb;
         if (out_bytes) *out_bytes = grid_cells(t) * 2 * rb;
     }
     return NUFFT_OK;
@@ -851,6 +966,9 @@ int nufft_toeplitz_multiplier_pair_ptr(const nufft_toeplitz* t, int32_t a, int32
 int nufft_toeplitz_apply(nufft_toeplitz* t, void* const* out, const void* const* in, void* stream_) {
     if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
     if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
+    if (t->seg && !ready(t))
+        return fail(NUFFT_ERR_NO_POINTS, "a coupled build (nufft_toeplitz_set_points_coupled / _set_spectra_coupled) and nufft_toeplitz_set_factors must "
+                                         "both be in force before nufft_toeplitz_apply on a segmented operator");
     if (!t->has_spectrum) return fail(NUFFT_ERR_NO_POINTS, "nufft_toeplitz_set_spectrum or nufft_toeplitz_set_points must be called before nufft_toeplitz_apply");
     if (!out || !in) return fail(NUFFT_ERR_INVALID_ARG, "null table");
     for (int c = 0; c < t->C; ++c)
@@ -859,6 +977,10 @@ int nufft_toeplitz_apply(nufft_toeplitz* t, void* const* out, const void* const*
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     if (t->path == NUFFT_TOEPLITZ_PATH_DENSE) NUFFT_ROCFFT(rocfft_execution_info_set_stream(t->fft_info, stream));
     const int ncoils = (int)t->coil_maps.size();
+    if (t->seg) {
+        if (out[0] == in[0]) return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_apply on a segmented operator: the output array is also the input array");
+        return apply_segmented(t, out[0], in[0], stream);
+    }
     if (ncoils > 0 || t->coupled) {       // coil 0 stores into out[c] what coil 1 still has to read from in[c']; coupled: every output needs every input
         for (int c = 0; c < t->C; ++c)
             for (int c2 = 0; c2 < t->C; ++c2)
@@ -890,21 +1012,27 @@ int nufft_toeplitz_set_maps(nufft_toeplitz* t, int32_t ncoils, const void* const
         if (!maps[c]) return fail(NUFFT_ERR_INVALID_ARG, "null coil map");
         if (!aligned16(maps[c])) return fail(NUFFT_ERR_INVALID_ARG, "coil maps must be 16-byte aligned");
     }
-    if (t->coupled && t->path == NUFFT_TOEPLITZ_PATH_FUSED && !t->maps_inpass)
+    if (t->coupled && !t->seg && t->path == NUFFT_TOEPLITZ_PATH_FUSED && !t->maps_inpass)
         return fail(NUFFT_ERR_UNSUPPORTED, "nufft_toeplitz_set_maps: coil maps on the route NUFFT_TOEPLITZ_MAPS_INPASS=0 do not combine with coupled components");
-    if (t->path == NUFFT_TOEPLITZ_PATH_FUSED && !t->maps_inpass && !t->d_coil) {
+    if (!t->seg && t->path == NUFFT_TOEPLITZ_PATH_FUSED && !t->maps_inpass && !t->d_coil) {
         DeviceGuard guard(t->device);
         if (capturing(static_cast<hipStream_t>(stream_)))
             return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_set_maps allocates on the streaming route: not on a capturing stream");
         if (int rc = alloc(t, &t->d_coil, coil_scratch_bytes(t))) return rc;
     }
+    const std::vector<const void*> before = t->coil_maps;
     t->coil_maps.assign(maps, maps + ncoils);
+    if (int rc = acquire_segment_scratch(t, "nufft_toeplitz_set_maps", stream_)) {
+        t->coil_maps = before;
+        return rc;
+    }
     return NUFFT_OK;
 }
 
 int nufft_toeplitz_clear_maps(nufft_toeplitz* t) {
     if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
     t->coil_maps.clear();
+    drop_segment_scratch(t);
     if (t->d_coil) {
         DeviceGuard guard(t->device);
         free_buffer(t->own_bytes, t->d_coil, coil_scratch_bytes(t));      // hipFree waits for the applies in flight
@@ -913,6 +1041,31 @@ int nufft_toeplitz_clear_maps(nufft_toeplitz* t) {
 }
 
 int32_t nufft_toeplitz_num_coils(const nufft_toeplitz* t) { return t ? (int32_t)t->coil_maps.size() : 0; }
+
+int nufft_toeplitz_set_factors(nufft_toeplitz* t, const void* const* B, void* stream_) {
+    if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    if (!t->seg) return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_set_factors: the operator is not segmented (nufft_toeplitz_create_segmented)");
+    if (!B) return fail(NUFFT_ERR_INVALID_ARG, "null table of factors");
+    if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
+    for (int l = 0; l < t->seg; ++l) {
+        if (!B[l]) return fail(NUFFT_ERR_INVALID_ARG, "null factor");
+        if (!aligned16(B[l])) return fail(NUFFT_ERR_INVALID_ARG, "the factors must be 16-byte aligned");
+    }
+    const std::vector<const void*> before = t->factors;
+    t->factors.assign(B, B + t->seg);
+    if (int rc = acquire_segment_scratch(t, "nufft_toeplitz_set_factors", stream_)) {
+        t->factors = before;
+        return rc;
+    }
+    return NUFFT_OK;
+}
+
+int nufft_toeplitz_clear_factors(nufft_toeplitz* t) {
+    if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    t->factors.clear();
+    drop_segment_scratch(t);
+    return NUFFT_OK;
+}
 
 namespace {
 int coil_args(int dtype, int64_t n, int32_t ncoils, const void* const* a, const void* const* b, const void* single) {

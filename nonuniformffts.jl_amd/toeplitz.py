@@ -15,6 +15,10 @@ With coil sensitivity maps (``op.set_maps(maps)``, parallel MRI) the same ``appl
 Coupled components (subspace models, ``y_j = Σ_a φ_a(j) (A û_a)_j``): ``op.set_points(points, weights, basis=phi)`` with ``phi`` of shape
 ``(ntransforms, Np)`` makes ``apply`` the block operator ``(G_Φ u)_a = Σ_b A^H diag(w conj(φ_a) φ_b) A u_b`` and ``solve`` / ``ToeplitzCG``
 one joint system; a plain ``set_points`` / ``set_spectrum`` returns to independent components.
+
+Off-resonance correction: ``ToeplitzOperator(plan, segments=L)`` is ONE component outside and L time segments inside,
+``G_ω u = Σ_a conj(B_a) ⊙ Σ_b A^H diag(w conj(φ_a) φ_b) A (B_b ⊙ u)``: ``set_points(points, weights, basis=phi)`` with ``phi`` of shape
+``(L, Np)`` and ``set_factors(B)``; ``field.py`` computes ``phi`` and ``B`` from a field map.
 """
 from __future__ import annotations
 
@@ -36,11 +40,19 @@ class ToeplitzOperator:
     convention, window parameters, device); the plan itself is not kept and may be closed afterwards.  Real-data plans are refused:
     their type 2 extends the half spectrum Hermitian-ly, which for even N adds the mode +N/2, and the 2N embedding aliases."""
 
-    def __init__(self, plan: PlanNUFFT):
+    def __init__(self, plan: PlanNUFFT, segments: Optional[int] = None):
         if not isinstance(plan, PlanNUFFT):
             raise ValueError("ToeplitzOperator takes a PlanNUFFT")
+        if segments is not None and (isinstance(segments, bool) or not isinstance(segments, int)):
+            raise ValueError(f"segments must be an integer (got {segments!r})")
         self._handle = C.c_void_p()
-        _check(lib.nufft_toeplitz_create(C.byref(self._handle), plan._handle))
+        self._factors = ()
+        if segments is None:
+            _check(lib.nufft_toeplitz_create(C.byref(self._handle), plan._handle))
+        else:
+            _check(lib.nufft_toeplitz_create_segmented(C.byref(self._handle), plan._handle, segments))
+        #: time segments of a segmented operator (``segments=L``: one component outside, L coupled segments inside), else 0
+        self.segments = 0 if segments is None else segments
         self.Z, self.T = plan.eltype, plan.T
         self.device = plan.device
         self.shape = plan.shape
@@ -55,6 +67,7 @@ class ToeplitzOperator:
             lib.nufft_toeplitz_destroy(h)
             self._handle = C.c_void_p()
         self._maps = ()
+        self._factors = ()
 
     def _require_open(self):
         if not self._handle.value:
@@ -113,14 +126,20 @@ class ToeplitzOperator:
         return a * K - a * (a - 1) // 2 + (b - a)
 
     @property
+    def _inner(self) -> int:
+        """Size of the coupled block: the segments of a segmented operator, ``ntransforms`` of any other."""
+        return self.segments or self.ntransforms
+
+    @property
     def coupled(self) -> bool:
         """True while a coupled build (``set_points(..., basis=)`` / ``set_spectra``) is in force."""
         return bool(self._handle.value) and lib.nufft_toeplitz_num_coupled(self._handle) > 0
 
     def set_spectra(self, T) -> "ToeplitzOperator":
         """The coupled counterpart of ``set_spectrum``: ``T`` of shape ``(K (K + 1) / 2, *padded_shape)`` or a sequence of that many
-        ``padded_shape`` tensors, ``T[pair_index(a, b, K)] = T_ab`` on the mode set of a 2N plan, ``K = ntransforms``.  Only read."""
-        K = self.ntransforms
+        ``padded_shape`` tensors, ``T[pair_index(a, b, K)] = T_ab`` on the mode set of a 2N plan, ``K = ntransforms`` (``K = segments`` on
+        a segmented operator).  Only read."""
+        K = self._inner
         npairs = K * (K + 1) // 2
         if isinstance(T, torch.Tensor):
             if T.dim() != self.ndim + 1 or T.shape[0] != npairs:
@@ -140,8 +159,8 @@ class ToeplitzOperator:
         return self
 
     def _basis_rows(self, basis):
-        """``basis`` as a ``(K, Np)`` tensor: a vector counts as one row where ``ntransforms == 1``."""
-        K = self.ntransforms
+        """``basis`` as a ``(K, Np)`` tensor: a vector counts as one row where ``K == 1``."""
+        K = self._inner
         if not isinstance(basis, torch.Tensor):
             raise ValueError("basis must be a torch tensor of shape (ntransforms, Np)")
         if basis.dim() == 1 and K == 1:
@@ -152,7 +171,7 @@ class ToeplitzOperator:
 
     def _check_basis(self, basis, n):
         """``basis`` (from ``_basis_rows``) as a tuple of K aligned ``(Np,)`` tensors (the exception types of ``_check_uniform``)."""
-        K = self.ntransforms
+        K = self._inner
         if basis.device != self.device:
             raise ValueError(f"basis must be a torch tensor on {self.device}")
         if basis.dtype != self.Z:
@@ -228,7 +247,8 @@ class ToeplitzOperator:
         ComplexF64).  ``m`` / ``sigma`` / ``kernel`` / ``kernel_evalmode`` override the parent plan's window for this build.
 
         ``basis``: a contiguous complex tensor ``(ntransforms, Np)`` of the plan's element type (a ``(Np,)`` vector when
-        ``ntransforms == 1``): the components are then coupled, ``(G u)_a = Σ_b A^H diag(w conj(φ_a) φ_b) A u_b``."""
+        ``ntransforms == 1``): the components are then coupled, ``(G u)_a = Σ_b A^H diag(w conj(φ_a) φ_b) A u_b``.  On a segmented
+        operator ``basis`` is required and has ``segments`` rows: the temporal interpolators ``φ_l(t_j)``."""
         if basis is not None:
             basis = self._basis_rows(basis)        # the component count needs no device
         self._require_gpu()
@@ -317,6 +337,38 @@ class ToeplitzOperator:
         self._maps = maps
         return self
 
+    def set_factors(self, B) -> "ToeplitzOperator":
+        """The factors ``B_l`` of a segmented operator (``B_l = exp(−i ω τ_l)`` for a field map ω; any values are taken): a contiguous
+        complex tensor of shape ``(segments, *plan.shape)`` or a sequence of ``plan.shape`` tensors.  Borrowed like coil maps: this
+        object keeps references, and the values must not change while they are set.  Independent of the builds and of ``set_maps``."""
+        self._require_gpu()
+        self._require_open()
+        if not self.segments:
+            raise ValueError("set_factors needs a segmented operator: ToeplitzOperator(plan, segments=L)")
+        if isinstance(B, torch.Tensor):
+            if B.dim() != self.ndim + 1:
+                raise DimensionMismatch(f"wrong dimensions of the factors (expected tensor shape ({self.segments}, {', '.join(map(str, self.shape))}), "
+                                        f"got {tuple(B.shape)})")
+            if not B.is_contiguous():
+                raise ValueError("the factors must be contiguous")
+            B = tuple(B[l] for l in range(B.shape[0]))
+        else:
+            B = tuple(B)
+        if len(B) != self.segments:
+            raise DimensionMismatch(f"wrong amount of factors (expected {self.segments}, got {len(B)})")
+        _check_coil_arrays(B, self.device, self.Z, self.shape, "the factors")
+        B = _aligned(B)
+        _check(lib.nufft_toeplitz_set_factors(self._handle, _ptr_table(B), self._stream()))
+        self._factors = B
+        return self
+
+    def clear_factors(self) -> "ToeplitzOperator":
+        """Forgets the factors (``apply`` is refused until the next ``set_factors``)."""
+        self._require_open()
+        _check(lib.nufft_toeplitz_clear_factors(self._handle))
+        self._factors = ()
+        return self
+
     def clear_maps(self) -> "ToeplitzOperator":
         """Back to the plain operator ``G``."""
         self._require_open()
@@ -360,6 +412,8 @@ class ToeplitzOperator:
                 raise ValueError("with coil maps set the output must not be the input")
             if self.coupled and any(o is v or o.data_ptr() == v.data_ptr() for o in out_t for v in u_t):
                 raise ValueError("on coupled components the output must not be the input: every output depends on every input")
+            if self.segments and any(o is v or o.data_ptr() == v.data_ptr() for o in out_t for v in u_t):
+                raise ValueError("on a segmented operator the output must not be the input: every segment reads the input")
         _check(lib.nufft_toeplitz_apply(self._handle, _ptr_table(out_t), _ptr_table(u_t), self._stream()))
         return out
 
@@ -402,7 +456,8 @@ class ToeplitzOperator:
 
         On a coupled operator ``multiplier(a, b)`` is the block ``K_ab``: a real view for ``a == b``, a complex view for ``a < b``
         (``K_ba = conj(K_ab)``: ``a > b`` raises), freed by the next uncoupled build.  On a framed operator ``multiplier(frame=c)``
-        is the real multiplier of frame c, freed by the next plain or coupled build."""
+        is the real multiplier of frame c, freed by the next plain or coupled build.  A segmented operator has the block of its segments:
+        ``multiplier(a, b)`` with ``a <= b < segments``."""
         self._require_gpu()
         self._require_open()
         ptr, nbytes = C.c_void_p(), C.c_int64()
@@ -416,10 +471,10 @@ class ToeplitzOperator:
         if a is None and self.coupled:
             raise ValueError("a coupled operator has a block of multipliers: ask for multiplier(a, b) with a <= b")
         if a is not None:
-            if not self.coupled:
+            if not self.coupled and not self.segments:
                 raise ValueError("multiplier(a, b) needs a coupled build (set_points(..., basis=) or set_spectra)")
-            if not 0 <= a < self.ntransforms or not 0 <= b < self.ntransforms:
-                raise ValueError(f"components must lie in 0 ... {self.ntransforms - 1}")
+            if not 0 <= a < self._inner or not 0 <= b < self._inner:
+                raise ValueError(f"components must lie in 0 ... {self._inner - 1}")
             if a > b:
                 raise ValueError("only the pairs a <= b are stored: multiplier(b, a) is the conjugate of multiplier(a, b)")
             _check(lib.nufft_toeplitz_multiplier_pair_ptr(self._handle, a, b, C.byref(ptr), C.byref(nbytes)))
@@ -444,7 +499,7 @@ class ToeplitzOperator:
     def __repr__(self):
         i = self.info()
         return (f"ToeplitzOperator of a {self.ndim}-dimensional {self.Z} plan, N = {tuple(int(i.N[d]) for d in range(self.ndim))}, "
-                f"{self.path} path, {'coupled components, ' if self.coupled else ''}{'one multiplier per frame, ' if self.framed else ''}{f'{self.ncoils} coil maps, ' if self.ncoils else ''}{i.workspace_bytes / 1e6:.1f} MB")
+                f"{self.path} path, {f'{self.segments} time segments, ' if self.segments else ''}{'coupled components, ' if self.coupled else ''}{'one multiplier per frame, ' if self.framed else ''}{f'{self.ncoils} coil maps, ' if self.ncoils else ''}{i.workspace_bytes / 1e6:.1f} MB")
 
 
 def _check_coil_arrays(arrays, device, Z, shape, what):
