@@ -34,6 +34,11 @@
 
 using namespace nufft;
 
+namespace {
+// The build in force: none, one shared multiplier (d_K), the C × C block of a coupled build, or one multiplier per frame.
+enum Mode { MODE_NONE, MODE_PLAIN, MODE_COUPLED, MODE_FRAMED };
+}  // namespace
+
 struct nufft_toeplitz {
     int dtype = NUFFT_F64, D = 1, C = 1, device = -1, num_cus = 256;
     bool fftshift = false;
@@ -60,20 +65,18 @@ struct nufft_toeplitz {
     void* d_fft_work = nullptr;                        // dense: kept; fused: lives inside set_spectrum
     size_t fft_work_bytes = 0;
     int64_t own_bytes = 0, build_bytes = 0;
-    bool has_spectrum = false;
+    Mode mode = MODE_NONE;                             // set by a build that succeeded (begin_build resets it)
     // coil sensitivity maps: borrowed device pointers, the host table is the operator's
     std::vector<const void*> coil_maps;
     bool maps_inpass = true;                           // fused: the maps ride in the outermost passes (false: expand / apply / combine)
     void* d_coil = nullptr;                            // fused, streaming route: complex<T>[N_1, N_2, N_3], held while maps are set
     // coupled components: the C × C block multiplier and one intermediate per component, held from the first
     // coupled build to the next uncoupled one
-    bool coupled = false;
     void* d_kd = nullptr;                              // T[C][2N_1, 2N_2, 2N_3]: the diagonal blocks K_aa
     void* d_kc = nullptr;                              // complex<T>[C (C − 1) / 2][2N_1, 2N_2, 2N_3]: K_ab, a < b, row-major
     void* d_grids = nullptr;                           // fused: C arrays like d_tmpB; dense: C arrays like d_work
     // frames: one real multiplier per component, held from the first framed build to the next plain or
     // coupled one
-    bool framed = false;
     void* d_kf = nullptr;                              // C arrays like d_K, frame_stride bytes apart
     // time segments: fixed at creation; C = 1 outside, `seg` coupled segments inside
     int seg = 0;                                       // L of nufft_toeplitz_create_segmented, 0 on an ordinary operator
@@ -126,32 +129,54 @@ size_t coupled_grid_stride(const nufft_toeplitz* t) {
 }
 size_t coupled_grids_bytes(const nufft_toeplitz* t) { return (size_t)inner(t) * coupled_grid_stride(t) * 2 * real_bytes(t->dtype); }
 
-int acquire_coupled(nufft_toeplitz* t) {
-    int rc;
-    if (!t->d_kd && (rc = alloc(t, &t->d_kd, coupled_kd_bytes(t)))) return rc;
-    if (!t->d_kc && inner(t) > 1 && (rc = alloc(t, &t->d_kc, coupled_kc_bytes(t)))) return rc;
-    if (!t->d_grids && (rc = alloc(t, &t->d_grids, coupled_grids_bytes(t)))) return rc;
-    return NUFFT_OK;
-}
-
 // The multipliers of a framed build: C real grids, each padded on its own (the alignment of d_K for every frame).
 size_t frame_stride(const nufft_toeplitz* t) { return padded((size_t)grid_cells(t) * real_bytes(t->dtype)); }
 size_t frames_bytes(const nufft_toeplitz* t) { return (size_t)t->C * frame_stride(t); }
-void* frame_multiplier(const nufft_toeplitz* t, int c) { return static_cast<char*>(t->d_kf) + (size_t)c * frame_stride(t); }
 
-// Back to one shared multiplier (hipFree waits for the applies in flight).
-void drop_frames(nufft_toeplitz* t) {
-    t->framed = false;
-    free_buffer(t->own_bytes, t->d_kf, frames_bytes(t));
+// What every build starts with: no build is in force, the storage of the other modes goes (hipFree waits for the applies in flight)
+// and this mode's is taken unless an earlier build of the mode left it.  `acquire` = false: the build is refused after this and takes
+// nothing new.
+int begin_build(nufft_toeplitz* t, Mode mode, bool acquire = true) {
+    t->mode = MODE_NONE;
+    if (mode != MODE_COUPLED) {
+        free_buffer(t->own_bytes, t->d_kd, coupled_kd_bytes(t));
+        free_buffer(t->own_bytes, t->d_kc, coupled_kc_bytes(t));
+        free_buffer(t->own_bytes, t->d_grids, coupled_grids_bytes(t));
+    }
+    if (mode != MODE_FRAMED) free_buffer(t->own_bytes, t->d_kf, frames_bytes(t));
+    if (!acquire) return NUFFT_OK;
+    int rc;
+    if (mode == MODE_COUPLED) {
+        if (!t->d_kd && (rc = alloc(t, &t->d_kd, coupled_kd_bytes(t)))) return rc;
+        if (!t->d_kc && inner(t) > 1 && (rc = alloc(t, &t->d_kc, coupled_kc_bytes(t)))) return rc;
+        if (!t->d_grids && (rc = alloc(t, &t->d_grids, coupled_grids_bytes(t)))) return rc;
+    }
+    if (mode == MODE_FRAMED && !t->d_kf && (rc = alloc(t, &t->d_kf, frames_bytes(t)))) return rc;
+    return NUFFT_OK;
 }
 
-// Back to independent components (hipFree waits for the applies in flight).
-void drop_coupled(nufft_toeplitz* t) {
-    t->coupled = false;
-    free_buffer(t->own_bytes, t->d_kd, coupled_kd_bytes(t));
-    free_buffer(t->own_bytes, t->d_kc, coupled_kc_bytes(t));
-    free_buffer(t->own_bytes, t->d_grids, coupled_grids_bytes(t));
+// Where the multipliers of a mode live, in build order: the one of a plain build, one per frame, the pairs a <= b of a coupled build
+// row-major.  Real grids but for the pairs a < b, which are complex.
+struct Multiplier {
+    void* ptr;
+    bool complex;
+};
+int num_multipliers(const nufft_toeplitz* t, Mode mode) {
+    return mode == MODE_COUPLED ? inner(t) * (inner(t) + 1) / 2 : mode == MODE_FRAMED ? t->C : 1;
 }
+Multiplier pair_multiplier(const nufft_toeplitz* t, int a, int b) {        // a <= b
+    const size_t real_grid = (size_t)grid_cells(t) * real_bytes(t->dtype);
+    if (a == b) return {static_cast<char*>(t->d_kd) + (size_t)a * real_grid, false};
+    return {static_cast<char*>(t->d_kc) + (size_t)nufft::coupled_offdiag_index(a, b, inner(t)) * 2 * real_grid, true};
+}
+Multiplier multiplier_at(const nufft_toeplitz* t, Mode mode, int i) {
+    if (mode == MODE_PLAIN) return {t->d_K, false};
+    if (mode == MODE_FRAMED) return {static_cast<char*>(t->d_kf) + (size_t)i * frame_stride(t), false};
+    int a = 0;
+    for (const int K = inner(t); i >= K - a; ++a) i -= K - a;        // row a holds the K − a pairs (a, a + i)
+    return pair_multiplier(t, a, a + i);
+}
+int64_t multiplier_bytes(const nufft_toeplitz* t, const Multiplier& m) { return grid_cells(t) * (int64_t)real_bytes(t->dtype) * (m.complex ? 2 : 1); }
 
 template <typename T>
 int upload_real(nufft_toeplitz* t, void** dst, const std::vector<double>& src) {
@@ -252,33 +277,16 @@ int build_device(nufft_toeplitz* t) {
 }
 
 // K from the spectrum held in `grid` (complex<T>[2N...], overwritten): Nyquist planes zeroed, backward transform, scaled real part.
-// `src` may be `grid` itself.  `K`: where the multiplier goes (d_K, or a frame's slot).
-int multiplier_from(nufft_toeplitz* t, void* K, void* grid, const void* src, hipStream_t stream) {
+// `src` may be `grid` itself.  `K`: where the multiplier goes; a complex one (K_ab, a < b) keeps the scaled complex value.
+int multiplier_from(nufft_toeplitz* t, Multiplier K, void* grid, const void* src, hipStream_t stream) {
     const nufft::TzGrid g = grid_of(t);
-    NUFFT_HIP(nufft::launch_tz_spectrum_load(g, grid, src, t->num_cus, stream));
-    NUFFT_ROCFFT(rocfft_execution_info_set_stream(t->fft_info, stream));
-    void* io[1] = {grid};
-    NUFFT_ROCFFT(rocfft_execute(t->fft_bw, io, nullptr, t->fft_info));
-    NUFFT_HIP(nufft::launch_tz_real_part(g, K, grid, 1.0 / (double)grid_cells(t), t->num_cus, stream));
-    return NUFFT_OK;
-}
-
-// The multiplier of the pair a <= b of a coupled operator from the spectrum T_ab, as multiplier_from: the scaled real part for a = b
-// (K_aa is real), the scaled complex value for a < b.
-int multiplier_pair_from(nufft_toeplitz* t, void* grid, const void* src, int a, int b, hipStream_t stream) {
-    const nufft::TzGrid g = grid_of(t);
-    const size_t rb = real_bytes(t->dtype);
     NUFFT_HIP(nufft::launch_tz_spectrum_load(g, grid, src, t->num_cus, stream));
     NUFFT_ROCFFT(rocfft_execution_info_set_stream(t->fft_info, stream));
     void* io[1] = {grid};
     NUFFT_ROCFFT(rocfft_execute(t->fft_bw, io, nullptr, t->fft_info));
     const double scale = 1.0 / (double)grid_cells(t);
-    if (a == b) {
-        NUFFT_HIP(nufft::launch_tz_real_part(g, static_cast<char*>(t->d_kd) + (size_t)a * (size_t)grid_cells(t) * rb, grid, scale, t->num_cus, stream));
-    } else {
-        void* kc = static_cast<char*>(t->d_kc) + (size_t)nufft::coupled_offdiag_index(a, b, inner(t)) * (size_t)grid_cells(t) * 2 * rb;
-        NUFFT_HIP(nufft::launch_tz_complex_part(g, kc, grid, scale, t->num_cus, stream));
-    }
+    if (K.complex) NUFFT_HIP(nufft::launch_tz_complex_part(g, K.ptr, grid, scale, t->num_cus, stream));
+    else NUFFT_HIP(nufft::launch_tz_real_part(g, K.ptr, grid, scale, t->num_cus, stream));
     return NUFFT_OK;
 }
 
@@ -371,24 +379,39 @@ int apply_fused(nufft_toeplitz* t, const void* K, void* out, const void* in, hip
     return fused_forward(t, out, t->d_tmpB, stream, smap, accumulate);
 }
 
-int apply_dense(nufft_toeplitz* t, const void* K, void* out, const void* in, hipStream_t stream, const void* smap = nullptr, bool accumulate = false) {
+// The halves of an apply before and after the multiply, on either path.  `grid`: like d_tmpB (fused) or d_work (dense).
+// backward: grid = backward transform of pad(map ⊙ src); forward: dst (+)= conj(map) ⊙ crop(forward transform of grid).  map = null:
+// no product, and the forward half stores.
+int backward_half(nufft_toeplitz* t, void* grid, const void* src, const void* map, hipStream_t stream) {
+    if (t->path == NUFFT_TOEPLITZ_PATH_FUSED) return fused_backward(t, grid, src, stream, map);
     const nufft::TzGrid g = grid_of(t);
-    void* io[1] = {t->d_work};
-    if (smap) NUFFT_HIP(nufft::launch_tz_pad_map(g, t->d_work, in, smap, t->num_cus, stream));
-    else NUFFT_HIP(nufft::launch_tz_pad(g, t->d_work, in, t->num_cus, stream));
+    void* io[1] = {grid};
+    if (map) NUFFT_HIP(nufft::launch_tz_pad_map(g, grid, src, map, t->num_cus, stream));
+    else NUFFT_HIP(nufft::launch_tz_pad(g, grid, src, t->num_cus, stream));
     NUFFT_ROCFFT(rocfft_execute(t->fft_bw, io, nullptr, t->fft_info));
-    NUFFT_HIP(nufft::launch_tz_multiply(g, t->d_work, K, t->num_cus, stream));
+    return NUFFT_OK;
+}
+int forward_half(nufft_toeplitz* t, void* dst, void* grid, const void* map, bool accumulate, hipStream_t stream) {
+    if (t->path == NUFFT_TOEPLITZ_PATH_FUSED) return fused_forward(t, dst, grid, stream, map, accumulate);
+    const nufft::TzGrid g = grid_of(t);
+    void* io[1] = {grid};
     NUFFT_ROCFFT(rocfft_execute(t->fft_fw, io, nullptr, t->fft_info));
-    if (smap) NUFFT_HIP(nufft::launch_tz_crop_map(g, out, t->d_work, smap, accumulate, t->num_cus, stream));
-    else NUFFT_HIP(nufft::launch_tz_crop(g, out, t->d_work, t->num_cus, stream));
+    if (map) NUFFT_HIP(nufft::launch_tz_crop_map(g, dst, grid, map, accumulate, t->num_cus, stream));
+    else NUFFT_HIP(nufft::launch_tz_crop(g, dst, grid, t->num_cus, stream));
     return NUFFT_OK;
 }
 
-// One coil of G_S: out (+)= conj(S) ⊙ G (S ⊙ in).  The streaming route of the fused path expands into d_coil, runs the plain apply
-// in place on it and combines into out.
+int apply_dense(nufft_toeplitz* t, const void* K, void* out, const void* in, hipStream_t stream, const void* smap = nullptr, bool accumulate = false) {
+    if (int rc = backward_half(t, t->d_work, in, smap, stream)) return rc;
+    NUFFT_HIP(nufft::launch_tz_multiply(grid_of(t), t->d_work, K, t->num_cus, stream));
+    return forward_half(t, out, t->d_work, smap, accumulate, stream);
+}
+
+// One coil of G_S: out (+)= conj(S) ⊙ G (S ⊙ in), or the plain apply (smap = null).  The streaming route of the fused path expands
+// into d_coil, runs the plain apply in place on it and combines into out.
 int apply_coil(nufft_toeplitz* t, const void* K, void* out, const void* in, const void* smap, bool accumulate, hipStream_t stream) {
     if (t->path == NUFFT_TOEPLITZ_PATH_DENSE) return apply_dense(t, K, out, in, stream, smap, accumulate);
-    if (t->maps_inpass) return apply_fused(t, K, out, in, stream, smap, accumulate);
+    if (t->maps_inpass || !smap) return apply_fused(t, K, out, in, stream, smap, accumulate);
     void* outs[1] = {t->d_coil};
     const void* maps[1] = {smap};
     const void* ins[1] = {t->d_coil};
@@ -406,40 +429,17 @@ int apply_coupled(nufft_toeplitz* t, void* const* out, const void* const* in, co
                   const void* const* fold = nullptr) {
     const size_t stride = coupled_grid_stride(t), cb = 2 * real_bytes(t->dtype);
     auto grid_at = [&](int c) { return static_cast<void*>(static_cast<char*>(t->d_grids) + (size_t)c * stride * cb); };
-    const bool fused = t->path == NUFFT_TOEPLITZ_PATH_FUSED;
-    const nufft::TzGrid g = grid_of(t);
     const int K = inner(t);
     int rc;
-    for (int b = 0; b < K; ++b) {
-        const void* src = fold ? in[0] : in[b];
-        const void* m = fold ? fold[b] : smap;
-        if (fused) {
-            if ((rc = fused_backward(t, grid_at(b), src, stream, m))) return rc;
-            continue;
-        }
-        void* io[1] = {grid_at(b)};
-        if (m) NUFFT_HIP(nufft::launch_tz_pad_map(g, io[0], src, m, t->num_cus, stream));
-        else NUFFT_HIP(nufft::launch_tz_pad(g, io[0], src, t->num_cus, stream));
-        NUFFT_ROCFFT(rocfft_execute(t->fft_bw, io, nullptr, t->fft_info));
-    }
-    if (fused)
+    for (int b = 0; b < K; ++b)
+        if ((rc = backward_half(t, grid_at(b), fold ? in[0] : in[b], fold ? fold[b] : smap, stream))) return rc;
+    if (t->path == NUFFT_TOEPLITZ_PATH_FUSED)
         NUFFT_HIP(nufft::launch_toeplitz_lines_coupled(t->dtype, t->N2[0], K, t->d_grids, (int64_t)stride, t->d_kd, t->d_kc, t->N2[1] * t->N2[2],
                                                     (int)t->N[0], t->d_map[0], t->d_tw_fw[0], stream));
     else
-        NUFFT_HIP(nufft::launch_tz_multiply_coupled(g, t->d_grids, (int64_t)stride, K, t->d_kd, t->d_kc, t->num_cus, stream));
-    for (int a = 0; a < K; ++a) {
-        void* dst = fold ? out[0] : out[a];
-        const void* m = fold ? fold[a] : smap;
-        const bool acc = fold ? a > 0 : accumulate;
-        if (fused) {
-            if ((rc = fused_forward(t, dst, grid_at(a), stream, m, acc))) return rc;
-            continue;
-        }
-        void* io[1] = {grid_at(a)};
-        NUFFT_ROCFFT(rocfft_execute(t->fft_fw, io, nullptr, t->fft_info));
-        if (m) NUFFT_HIP(nufft::launch_tz_crop_map(g, dst, io[0], m, acc, t->num_cus, stream));
-        else NUFFT_HIP(nufft::launch_tz_crop(g, dst, io[0], t->num_cus, stream));
-    }
+        NUFFT_HIP(nufft::launch_tz_multiply_coupled(grid_of(t), t->d_grids, (int64_t)stride, K, t->d_kd, t->d_kc, t->num_cus, stream));
+    for (int a = 0; a < K; ++a)
+        if ((rc = forward_half(t, fold ? out[0] : out[a], grid_at(a), fold ? fold[a] : smap, fold ? a > 0 : accumulate, stream))) return rc;
     return NUFFT_OK;
 }
 
@@ -487,8 +487,26 @@ int segmented_refusal(const nufft_toeplitz* t, const char* fn) {
                                            "its segments, built by nufft_toeplitz_set_points_coupled / _set_spectra_coupled");
 }
 
+int host_only_refusal(const nufft_toeplitz* t) {
+    return t->device < 0 ? fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)") : NUFFT_OK;
+}
+
+// `why`: what `fn` does that a capture cannot record.
+int capture_refusal(hipStream_t stream, const char* fn, const char* why) {
+    return capturing(stream) ? fail(NUFFT_ERR_INVALID_ARG, std::string(fn) + " " + why + ": not on a capturing stream") : NUFFT_OK;
+}
+
+// One point set as the point builds take it: `coords` has a vector per dimension unless there are no points.
+int points_refusal(const nufft_toeplitz* t, int64_t np, const void* const* coords) {
+    if (np < 0) return fail(NUFFT_ERR_INVALID_ARG, "negative number of points");
+    if (!coords) return fail(NUFFT_ERR_INVALID_ARG, "null coordinate table");
+    for (int d = 0; d < t->D; ++d)
+        if (np > 0 && !coords[d]) return fail(NUFFT_ERR_INVALID_ARG, "null coordinate vector");
+    return NUFFT_OK;
+}
+
 // A build and, on a segmented operator, the factors: what nufft_toeplitz_apply needs.
-bool ready(const nufft_toeplitz* t) { return t->has_spectrum && (!t->seg || !t->factors.empty()); }
+bool ready(const nufft_toeplitz* t) { return t->mode != MODE_NONE && (!t->seg || !t->factors.empty()); }
 
 // The internal 2N plan's parameters: the parent plan's window unless `build` overrides it (nufft_toeplitz_set_points).
 int build_plan_params(const nufft_toeplitz* t, const nufft_params* build, nufft_params& prm) {
@@ -530,9 +548,8 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 int acquire_segment_scratch(nufft_toeplitz* t, const char* fn, void* stream_) {
     if (!t->seg || t->coil_maps.empty() || t->factors.empty() || t->d_sv) return NUFFT_OK;
     DeviceGuard guard(t->device);
-    if (capturing(static_cast<hipStream_t>(stream_)))
-        return fail(NUFFT_ERR_INVALID_ARG, std::string(fn) + " allocates the two scratch arrays of a segmented operator with coil maps: not on a capturing stream");
     int rc;
+    if ((rc = capture_refusal(static_cast<hipStream_t>(stream_), fn, "allocates the two scratch arrays of a segmented operator with coil maps"))) return rc;
     if ((rc = alloc(t, &t->d_sv, coil_scratch_bytes(t))) || (rc = alloc(t, &t->d_sw, coil_scratch_bytes(t)))) {
         free_buffer(t->own_bytes, t->d_sv, coil_scratch_bytes(t));
         return rc;
@@ -544,6 +561,94 @@ void drop_segment_scratch(nufft_toeplitz* t) {
     DeviceGuard guard(t->device);
     free_buffer(t->own_bytes, t->d_sv, coil_scratch_bytes(t));      // hipFree waits for the applies in flight
     free_buffer(t->own_bytes, t->d_sw, coil_scratch_bytes(t));
+}
+
+// A build from spectra: T[i] is the spectrum of the mode's i-th multiplier (multiplier_at).
+int build_from_spectra(nufft_toeplitz* t, Mode mode, const void* const* T, hipStream_t stream) {
+    int rc;
+    if ((rc = begin_build(t, mode))) return rc;
+    Scratch s(t);
+    if ((rc = s.acquire_grid()) || (rc = s.acquire_fft_work())) return rc;
+    for (int i = 0; i < num_multipliers(t, mode); ++i)
+        if ((rc = multiplier_from(t, multiplier_at(t, mode, i), s.grid, T[i], stream))) return rc;
+    NUFFT_HIP(hipStreamSynchronize(stream));      // the temporaries are freed on return
+    t->mode = mode;
+    return NUFFT_OK;
+}
+
+// What a build from points spreads for the mode's i-th multiplier.
+struct PointItem {
+    const void* const* coords;      // the point set to bind first, or null: the one the item before left bound
+    int64_t np;
+    const void* weights;            // null: ones
+    bool pair;                      // values = w conj(φ_a) φ_b (launch_tz_pair_weights); false: values = w (launch_tz_weights)
+    const void *phi_a, *phi_b;
+};
+
+// The prefix of a failed build from points, [mode][the failure lies in the plan, its points or the type 1].
+const char* const kBuildPrefix[][2] = {
+    {"", ""},
+    {"Toeplitz build (type 1 of the weights on the 2N grid): ", "Toeplitz build (type 1 of the weights on the 2N grid): "},
+    {"coupled Toeplitz build: ", "coupled Toeplitz build (type 1 of a pair's weights on the 2N grid): "},
+    {"framed Toeplitz build: ", "framed Toeplitz build (type 1 of a frame's weights on the 2N grid): "}};
+
+// A build from points with an internal 2N plan that lives inside this call: per multiplier the type 1 of `values` (of at most `most`
+// points) onto the scratch grid, then multiplier_from in place.
+int build_from_points(nufft_toeplitz* t, Mode mode, const nufft_params* build, const PointItem* items, int64_t most, hipStream_t stream) {
+    nufft_params prm;
+    const int refused = build_plan_params(t, build, prm);      // reads `t` only; refused parameters end the build in force all the same
+    int rc;
+    if ((rc = begin_build(t, mode, !refused))) return rc;
+    if (refused) return refused;
+    // The one place the modes differ.  A plain build has a single multiplier, so it transforms it after the 2N plan is destroyed and
+    // takes rocFFT's work buffer only then: the two never coexist.  The others transform every multiplier while the plan exists, so
+    // the work buffer lives next to it from the start.
+    const bool late = mode == MODE_PLAIN;
+    Scratch s(t);
+    if ((rc = s.acquire_grid()) || (!late && (rc = s.acquire_fft_work()))) return rc;
+    void* values = nullptr;
+    const size_t vbytes = (size_t)most * 2 * real_bytes(t->dtype);
+    if ((rc = alloc(t, &values, vbytes))) return rc;
+    nufft_plan* bp = nullptr;
+    rc = nufft_plan_create_ex(&bp, &prm);
+    bool in_type1 = true;
+    for (int i = 0; i < num_multipliers(t, mode) && rc == NUFFT_OK; ++i) {
+        const PointItem& it = items[i];
+        in_type1 = true;
+        if (it.coords) {
+            t->build_bytes = bp->workspace_bytes;
+            rc = nufft_set_points(bp, it.np, it.coords, stream);
+            t->build_bytes = bp->workspace_bytes;
+            // a coupled build binds its one point set ahead of its pairs: a failure there keeps the type-1 prefix, where a framed
+            // build, which binds a set per frame, has always reported the short one
+            if (rc && mode == MODE_COUPLED) break;
+        }
+        if (rc == NUFFT_OK) {
+            hipError_t e = it.pair ? nufft::launch_tz_pair_weights(t->dtype, values, it.weights, it.phi_a, it.phi_b, it.np, t->num_cus, stream)
+                                   : nufft::launch_tz_weights(t->dtype, values, it.weights, it.np, t->num_cus, stream);
+            if (e != hipSuccess) rc = fail(NUFFT_ERR_HIP, std::string(it.pair ? "launch_tz_pair_weights: " : "launch_tz_weights: ") + hipGetErrorString(e));
+        }
+        if (rc == NUFFT_OK) {
+            void* outs[1] = {s.grid};
+            const void* ins[1] = {values};
+            rc = nufft_exec_type1(bp, outs, ins, stream);
+        }
+        in_type1 = false;
+        if (rc == NUFFT_OK && !late) rc = multiplier_from(t, multiplier_at(t, mode, i), s.grid, s.grid, stream);
+    }
+    if (rc == NUFFT_OK && hipStreamSynchronize(stream) != hipSuccess) rc = fail(NUFFT_ERR_HIP, "hipStreamSynchronize failed");
+    const std::string keep = rc ? nufft_last_error_message() : "";
+    if (bp) nufft_plan_destroy(bp);
+    t->build_bytes = 0;
+    free_buffer(t->own_bytes, values, vbytes);
+    if (rc) return fail(rc, kBuildPrefix[mode][in_type1] + keep);
+    if (late) {
+        if ((rc = s.acquire_fft_work())) return rc;
+        if ((rc = multiplier_from(t, multiplier_at(t, mode, 0), s.grid, s.grid, stream))) return rc;
+        NUFFT_HIP(hipStreamSynchronize(stream));
+    }
+    t->mode = mode;
+    return NUFFT_OK;
 }
 
 int create(nufft_toeplitz** out, const nufft_plan* plan, int nsegments);
@@ -669,307 +774,140 @@ int nufft_toeplitz_get_info(const nufft_toeplitz* t, nufft_toeplitz_info* o) {
 int nufft_toeplitz_multiplier_ptr(const nufft_toeplitz* t, void** out_ptr, int64_t* out_bytes) {
     if (!t || !out_ptr) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
     if (int rc = segmented_refusal(t, "nufft_toeplitz_multiplier_ptr")) return rc;
-    if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
+    if (int rc = host_only_refusal(t)) return rc;
     *out_ptr = t->d_K;
     if (out_bytes) *out_bytes = grid_cells(t) * (int64_t)real_bytes(t->dtype);
     return NUFFT_OK;
 }
 
+// The six builds: the checks of each in the order of the header, then build_from_spectra or build_from_points.
+
 int nufft_toeplitz_set_spectrum(nufft_toeplitz* t, const void* T_modes, void* stream_) {
     if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
-    if (int rc = segmented_refusal(t, "nufft_toeplitz_set_spectrum")) return rc;
-    if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
+    int rc;
+    if ((rc = segmented_refusal(t, "nufft_toeplitz_set_spectrum")) || (rc = host_only_refusal(t))) return rc;
     if (!T_modes) return fail(NUFFT_ERR_INVALID_ARG, "null spectrum");
     DeviceGuard guard(t->device);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (capturing(stream))
-        return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_set_spectrum allocates and synchronises: not on a capturing stream");
-    t->has_spectrum = false;
-    drop_coupled(t);
-    drop_frames(t);
-    Scratch s(t);
-    int rc;
-    if ((rc = s.acquire_grid()) || (rc = s.acquire_fft_work())) return rc;
-    if ((rc = multiplier_from(t, t->d_K, s.grid, T_modes, stream))) return rc;
-    NUFFT_HIP(hipStreamSynchronize(stream));      // the temporaries are freed on return
-    t->has_spectrum = true;
-    return NUFFT_OK;
+    if ((rc = capture_refusal(stream, "nufft_toeplitz_set_spectrum", "allocates and synchronises"))) return rc;
+    return build_from_spectra(t, MODE_PLAIN, &T_modes, stream);
 }
 
 int nufft_toeplitz_set_points(nufft_toeplitz* t, const nufft_params* build, int64_t np, const void* const* coords, const void* weights,
                               void* stream_) {
     if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
-    if (int rc = segmented_refusal(t, "nufft_toeplitz_set_points")) return rc;
-    if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
-    if (np < 0) return fail(NUFFT_ERR_INVALID_ARG, "negative number of points");
-    if (!coords) return fail(NUFFT_ERR_INVALID_ARG, "null coordinate table");
-    for (int d = 0; d < t->D; ++d)
-        if (np > 0 && !coords[d]) return fail(NUFFT_ERR_INVALID_ARG, "null coordinate vector");
+    int rc;
+    if ((rc = segmented_refusal(t, "nufft_toeplitz_set_points")) || (rc = host_only_refusal(t)) || (rc = points_refusal(t, np, coords))) return rc;
     DeviceGuard guard(t->device);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (capturing(stream))
-        return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_set_points builds and destroys a plan: not on a capturing stream");
-    t->has_spectrum = false;
-    drop_coupled(t);
-    drop_frames(t);
-
-    nufft_params prm;
-    if (int prc = build_plan_params(t, build, prm)) return prc;
-
-    Scratch s(t);
-    int rc;
-    if ((rc = s.acquire_grid())) return rc;
-    void* values = nullptr;
-    const size_t vbytes = (size_t)std::max<int64_t>(np, 1) * 2 * real_bytes(t->dtype);
-    if ((rc = alloc(t, &values, vbytes))) return rc;
-    nufft_plan* bp = nullptr;
-    rc = nufft_plan_create_ex(&bp, &prm);
-    if (rc == NUFFT_OK) {
-        t->build_bytes = bp->workspace_bytes;
-        rc = nufft_set_points(bp, np, coords, stream);
-        t->build_bytes = bp->workspace_bytes;
-    }
-    if (rc == NUFFT_OK) {
-        hipError_t e = nufft::launch_tz_weights(t->dtype, values, weights, np, t->num_cus, stream);
-        if (e != hipSuccess) rc = fail(NUFFT_ERR_HIP, std::string("launch_tz_weights: ") + hipGetErrorString(e));
-    }
-    if (rc == NUFFT_OK) {
-        void* outs[1] = {s.grid};
-        const void* ins[1] = {values};
-        rc = nufft_exec_type1(bp, outs, ins, stream);
-    }
-    if (rc == NUFFT_OK && hipStreamSynchronize(stream) != hipSuccess) rc = fail(NUFFT_ERR_HIP, "hipStreamSynchronize failed");
-    const std::string keep = rc ? nufft_last_error_message() : "";
-    if (bp) nufft_plan_destroy(bp);            // before the transform's own work buffer is allocated
-    t->build_bytes = 0;
-    free_buffer(t->own_bytes, values, vbytes);
-    if (rc) return fail(rc, "Toeplitz build (type 1 of the weights on the 2N grid): " + keep);
-    if ((rc = s.acquire_fft_work())) return rc;
-    if ((rc = multiplier_from(t, t->d_K, s.grid, s.grid, stream))) return rc;
-    NUFFT_HIP(hipStreamSynchronize(stream));
-    t->has_spectrum = true;
-    return NUFFT_OK;
+    if ((rc = capture_refusal(stream, "nufft_toeplitz_set_points", "builds and destroys a plan"))) return rc;
+    const PointItem item{coords, np, weights, false, nullptr, nullptr};
+    return build_from_points(t, MODE_PLAIN, build, &item, std::max<int64_t>(np, 1), stream);
 }
 
 int nufft_toeplitz_set_spectra_coupled(nufft_toeplitz* t, const void* const* T_pairs, void* stream_) {
     if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
     if (!T_pairs) return fail(NUFFT_ERR_INVALID_ARG, "null table of spectra");
-    if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
-    const int K = inner(t), npairs = K * (K + 1) / 2;
-    for (int p = 0; p < npairs; ++p)
-        if (!T_pairs[p]) return fail(NUFFT_ERR_INVALID_ARG, "null spectrum");
     int rc;
+    if ((rc = host_only_refusal(t))) return rc;
+    for (int p = 0; p < num_multipliers(t, MODE_COUPLED); ++p)
+        if (!T_pairs[p]) return fail(NUFFT_ERR_INVALID_ARG, "null spectrum");
     if ((rc = coupled_refusals(t, "nufft_toeplitz_set_spectra_coupled"))) return rc;
     DeviceGuard guard(t->device);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (capturing(stream))
-        return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_set_spectra_coupled allocates and synchronises: not on a capturing stream");
-    t->has_spectrum = false;
-    t->coupled = false;
-    drop_frames(t);
-    if ((rc = acquire_coupled(t))) return rc;
-    Scratch s(t);
-    if ((rc = s.acquire_grid()) || (rc = s.acquire_fft_work())) return rc;
-    for (int a = 0, p = 0; a < K; ++a)
-        for (int b = a; b < K; ++b, ++p)
-            if ((rc = multiplier_pair_from(t, s.grid, T_pairs[p], a, b, stream))) return rc;
-    NUFFT_HIP(hipStreamSynchronize(stream));      // the temporaries are freed on return
-    t->coupled = true;
-    t->has_spectrum = true;
-    return NUFFT_OK;
+    if ((rc = capture_refusal(stream, "nufft_toeplitz_set_spectra_coupled", "allocates and synchronises"))) return rc;
+    return build_from_spectra(t, MODE_COUPLED, T_pairs, stream);
 }
 
 int nufft_toeplitz_set_points_coupled(nufft_toeplitz* t, const nufft_params* build, int64_t np, const void* const* coords, const void* weights,
                                       const void* const* basis, void* stream_) {
     if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
     if (!basis) return fail(NUFFT_ERR_INVALID_ARG, "null table of basis functions");
-    if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
-    if (np < 0) return fail(NUFFT_ERR_INVALID_ARG, "negative number of points");
-    if (!coords) return fail(NUFFT_ERR_INVALID_ARG, "null coordinate table");
-    for (int d = 0; d < t->D; ++d)
-        if (np > 0 && !coords[d]) return fail(NUFFT_ERR_INVALID_ARG, "null coordinate vector");
+    int rc;
+    if ((rc = host_only_refusal(t)) || (rc = points_refusal(t, np, coords))) return rc;
     const int K = inner(t);
     for (int c = 0; c < K; ++c)
         if (np > 0 && (!basis[c] || !aligned16(basis[c]))) return fail(NUFFT_ERR_INVALID_ARG, "null or not 16-byte aligned basis function");
-    int rc;
     if ((rc = coupled_refusals(t, "nufft_toeplitz_set_points_coupled"))) return rc;
     DeviceGuard guard(t->device);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (capturing(stream))
-        return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_set_points_coupled builds and destroys a plan: not on a capturing stream");
-    t->has_spectrum = false;
-    t->coupled = false;
-    drop_frames(t);
-    nufft_params prm;
-    if ((rc = build_plan_params(t, build, prm))) return rc;
-    if ((rc = acquire_coupled(t))) return rc;
-
-    Scratch s(t);
-    // (the transform's own work buffer lives next to the plan here: every pair is transformed while the plan exists)
-    if ((rc = s.acquire_grid()) || (rc = s.acquire_fft_work())) return rc;
-    void* values = nullptr;
-    const size_t vbytes = (size_t)std::max<int64_t>(np, 1) * 2 * real_bytes(t->dtype);
-    if ((rc = alloc(t, &values, vbytes))) return rc;
-    nufft_plan* bp = nullptr;
-    rc = nufft_plan_create_ex(&bp, &prm);
-    if (rc == NUFFT_OK) {
-        t->build_bytes = bp->workspace_bytes;
-        rc = nufft_set_points(bp, np, coords, stream);      // once for all pairs
-        t->build_bytes = bp->workspace_bytes;
-    }
-    bool in_type1 = true;
-    for (int a = 0; a < K && rc == NUFFT_OK; ++a)
-        for (int b = a; b < K && rc == NUFFT_OK; ++b) {
-            in_type1 = true;
-            hipError_t e = nufft::launch_tz_pair_weights(t->dtype, values, weights, basis[a], basis[b], np, t->num_cus, stream);
-            if (e != hipSuccess) rc = fail(NUFFT_ERR_HIP, std::string("launch_tz_pair_weights: ") + hipGetErrorString(e));
-            if (rc == NUFFT_OK) {
-                void* outs[1] = {s.grid};
-                const void* ins[1] = {values};
-                rc = nufft_exec_type1(bp, outs, ins, stream);
-            }
-            in_type1 = false;
-            if (rc == NUFFT_OK) rc = multiplier_pair_from(t, s.grid, s.grid, a, b, stream);
-        }
-    if (rc == NUFFT_OK && hipStreamSynchronize(stream) != hipSuccess) rc = fail(NUFFT_ERR_HIP, "hipStreamSynchronize failed");
-    const std::string keep = rc ? nufft_last_error_message() : "";
-    if (bp) nufft_plan_destroy(bp);
-    t->build_bytes = 0;
-    free_buffer(t->own_bytes, values, vbytes);
-    if (rc) return fail(rc, (in_type1 ? "coupled Toeplitz build (type 1 of a pair's weights on the 2N grid): " : "coupled Toeplitz build: ") + keep);
-    t->coupled = true;
-    t->has_spectrum = true;
-    return NUFFT_OK;
+    if ((rc = capture_refusal(stream, "nufft_toeplitz_set_points_coupled", "builds and destroys a plan"))) return rc;
+    std::vector<PointItem> items;
+    for (int a = 0; a < K; ++a)
+        for (int b = a; b < K; ++b) items.push_back({items.empty() ? coords : nullptr, np, weights, true, basis[a], basis[b]});      // one point set for all pairs
+    return build_from_points(t, MODE_COUPLED, build, items.data(), std::max<int64_t>(np, 1), stream);
 }
 
 int nufft_toeplitz_set_spectra_frames(nufft_toeplitz* t, const void* const* T, void* stream_) {
     if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
-    if (int rc = segmented_refusal(t, "nufft_toeplitz_set_spectra_frames")) return rc;
+    int rc;
+    if ((rc = segmented_refusal(t, "nufft_toeplitz_set_spectra_frames"))) return rc;
     if (!T) return fail(NUFFT_ERR_INVALID_ARG, "null table of spectra");
-    if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
+    if ((rc = host_only_refusal(t))) return rc;
     for (int c = 0; c < t->C; ++c)
         if (!T[c]) return fail(NUFFT_ERR_INVALID_ARG, "null spectrum");
     DeviceGuard guard(t->device);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (capturing(stream))
-        return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_set_spectra_frames allocates and synchronises: not on a capturing stream");
-    t->has_spectrum = false;
-    t->framed = false;
-    drop_coupled(t);
-    int rc;
-    if (!t->d_kf && (rc = alloc(t, &t->d_kf, frames_bytes(t)))) return rc;
-    Scratch s(t);
-    if ((rc = s.acquire_grid()) || (rc = s.acquire_fft_work())) return rc;
-    for (int c = 0; c < t->C; ++c)
-        if ((rc = multiplier_from(t, frame_multiplier(t, c), s.grid, T[c], stream))) return rc;
-    NUFFT_HIP(hipStreamSynchronize(stream));      // the temporaries are freed on return
-    t->framed = true;
-    t->has_spectrum = true;
-    return NUFFT_OK;
+    if ((rc = capture_refusal(stream, "nufft_toeplitz_set_spectra_frames", "allocates and synchronises"))) return rc;
+    return build_from_spectra(t, MODE_FRAMED, T, stream);
 }
 
 int nufft_toeplitz_set_points_frames(nufft_toeplitz* t, const nufft_params* build, const int64_t* np, const void* const* coords,
                                      const void* const* weights, void* stream_) {
     if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
-    if (int rc = segmented_refusal(t, "nufft_toeplitz_set_points_frames")) return rc;
+    int rc;
+    if ((rc = segmented_refusal(t, "nufft_toeplitz_set_points_frames"))) return rc;
     if (!np || !coords) return fail(NUFFT_ERR_INVALID_ARG, "null table of point counts or coordinates");
-    if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
+    if ((rc = host_only_refusal(t))) return rc;
     int64_t most = 1;
+    std::vector<PointItem> items;
     for (int c = 0; c < t->C; ++c) {
-        if (np[c] < 0) return fail(NUFFT_ERR_INVALID_ARG, "negative number of points");
-        for (int d = 0; d < t->D; ++d)
-            if (np[c] > 0 && !coords[(size_t)c * t->D + d]) return fail(NUFFT_ERR_INVALID_ARG, "null coordinate vector");
+        if ((rc = points_refusal(t, np[c], coords + (size_t)c * t->D))) return rc;
         most = std::max(most, np[c]);
+        items.push_back({coords + (size_t)c * t->D, np[c], weights ? weights[c] : nullptr, false, nullptr, nullptr});
     }
     DeviceGuard guard(t->device);
     hipStream_t stream = static_cast<hipStream_t>(stream_);
-    if (capturing(stream))
-        return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_set_points_frames builds and destroys a plan: not on a capturing stream");
-    t->has_spectrum = false;
-    t->framed = false;
-    drop_coupled(t);
-    nufft_params prm;
-    int rc;
-    if ((rc = build_plan_params(t, build, prm))) return rc;
-    if (!t->d_kf && (rc = alloc(t, &t->d_kf, frames_bytes(t)))) return rc;
-
-    Scratch s(t);
-    // (the transform's own work buffer lives next to the plan here: every frame is transformed while the plan exists)
-    if ((rc = s.acquire_grid()) || (rc = s.acquire_fft_work())) return rc;
-    void* values = nullptr;
-    const size_t vbytes = (size_t)most * 2 * real_bytes(t->dtype);
-    if ((rc = alloc(t, &values, vbytes))) return rc;
-    nufft_plan* bp = nullptr;
-    rc = nufft_plan_create_ex(&bp, &prm);
-    bool in_type1 = true;
-    for (int c = 0; c < t->C && rc == NUFFT_OK; ++c) {
-        in_type1 = true;
-        t->build_bytes = bp->workspace_bytes;
-        rc = nufft_set_points(bp, np[c], coords + (size_t)c * t->D, stream);
-        t->build_bytes = bp->workspace_bytes;
-        if (rc == NUFFT_OK) {
-            hipError_t e = nufft::launch_tz_weights(t->dtype, values, weights ? weights[c] : nullptr, np[c], t->num_cus, stream);
-            if (e != hipSuccess) rc = fail(NUFFT_ERR_HIP, std::string("launch_tz_weights: ") + hipGetErrorString(e));
-        }
-        if (rc == NUFFT_OK) {
-            void* outs[1] = {s.grid};
-            const void* ins[1] = {values};
-            rc = nufft_exec_type1(bp, outs, ins, stream);
-        }
-        in_type1 = false;
-        if (rc == NUFFT_OK) rc = multiplier_from(t, frame_multiplier(t, c), s.grid, s.grid, stream);
-    }
-    if (rc == NUFFT_OK && hipStreamSynchronize(stream) != hipSuccess) rc = fail(NUFFT_ERR_HIP, "hipStreamSynchronize failed");
-    const std::string keep = rc ? nufft_last_error_message() : "";
-    if (bp) nufft_plan_destroy(bp);
-    t->build_bytes = 0;
-    free_buffer(t->own_bytes, values, vbytes);
-    if (rc) return fail(rc, (in_type1 ? "framed Toeplitz build (type 1 of a frame's weights on the 2N grid): " : "framed Toeplitz build: ") + keep);
-    t->framed = true;
-    t->has_spectrum = true;
-    return NUFFT_OK;
+    if ((rc = capture_refusal(stream, "nufft_toeplitz_set_points_frames", "builds and destroys a plan"))) return rc;
+    return build_from_points(t, MODE_FRAMED, build, items.data(), most, stream);
 }
 
-int32_t nufft_toeplitz_num_frames(const nufft_toeplitz* t) { return t && t->framed ? (int32_t)t->C : 0; }
+int32_t nufft_toeplitz_num_frames(const nufft_toeplitz* t) { return t && t->mode == MODE_FRAMED ? (int32_t)t->C : 0; }
 
 int nufft_toeplitz_multiplier_frame_ptr(const nufft_toeplitz* t, int32_t c, void** out_ptr, int64_t* out_bytes) {
     if (!t || !out_ptr) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
-    if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
-    if (!t->framed) return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_multiplier_frame_ptr: no framed build is in force");
+    if (int rc = host_only_refusal(t)) return rc;
+    if (t->mode != MODE_FRAMED) return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_multiplier_frame_ptr: no framed build is in force");
     if (c < 0 || c >= t->C) return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_multiplier_frame_ptr: the frame must satisfy 0 <= c < ntransforms");
-    *out_ptr = frame_multiplier(t, c);
-    if (out_bytes) *out_bytes = grid_cells(t) * (int64_t)real_bytes(t->dtype);
+    const Multiplier m = multiplier_at(t, MODE_FRAMED, c);
+    *out_ptr = m.ptr;
+    if (out_bytes) *out_bytes = multiplier_bytes(t, m);
     return NUFFT_OK;
 }
 
-int32_t nufft_toeplitz_num_coupled(const nufft_toeplitz* t) { return t && t->coupled && !t->seg ? (int32_t)t->C : 0; }
+int32_t nufft_toeplitz_num_coupled(const nufft_toeplitz* t) { return t && t->mode == MODE_COUPLED && !t->seg ? (int32_t)t->C : 0; }
 
 int32_t nufft_toeplitz_num_segments(const nufft_toeplitz* t) { return t ? (int32_t)t->seg : 0; }
 
 int nufft_toeplitz_multiplier_pair_ptr(const nufft_toeplitz* t, int32_t a, int32_t b, void** out_ptr, int64_t* out_bytes) {
     if (!t || !out_ptr) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
-    if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
-    if (!t->coupled) return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_multiplier_pair_ptr: no coupled build is in force");
+    if (int rc = host_only_refusal(t)) return rc;
+    if (t->mode != MODE_COUPLED) return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_multiplier_pair_ptr: no coupled build is in force");
     if (a < 0 || b < a || b >= inner(t))
         return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_multiplier_pair_ptr: the pair must satisfy 0 <= a <= b < ntransforms (segmented: nsegments)");
-    const int64_t rb = (int64_t)real_bytes(t->dtype);
-    if (a == b) {
-        *out_ptr = static_cast<char*>(t->d_kd) + a * grid_cells(t) * rb;
-        if (out_bytes) *out_bytes = grid_cells(t) * rb;
-    } else {
-        *out_ptr = static_cast<char*>(t->d_kc) + nufft::coupled_offdiag_index(a, b, inner(t)) * grid_cells(t) * 2 * rb;
-        if (out_bytes) *out_bytes = grid_cells(t) * 2 * rb;
-    }
+    const Multiplier m = pair_multiplier(t, a, b);
+    *out_ptr = m.ptr;
+    if (out_bytes) *out_bytes = multiplier_bytes(t, m);
     return NUFFT_OK;
 }
 
 int nufft_toeplitz_apply(nufft_toeplitz* t, void* const* out, const void* const* in, void* stream_) {
     if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
-    if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
+    if (int rc = host_only_refusal(t)) return rc;
     if (t->seg && !ready(t))
         return fail(NUFFT_ERR_NO_POINTS, "a coupled build (nufft_toeplitz_set_points_coupled / _set_spectra_coupled) and nufft_toeplitz_set_factors must "
                                          "both be in force before nufft_toeplitz_apply on a segmented operator");
-    if (!t->has_spectrum) return fail(NUFFT_ERR_NO_POINTS, "nufft_toeplitz_set_spectrum or nufft_toeplitz_set_points must be called before nufft_toeplitz_apply");
+    if (t->mode == MODE_NONE) return fail(NUFFT_ERR_NO_POINTS, "nufft_toeplitz_set_spectrum or nufft_toeplitz_set_points must be called before nufft_toeplitz_apply");
     if (!out || !in) return fail(NUFFT_ERR_INVALID_ARG, "null table");
     for (int c = 0; c < t->C; ++c)
         if (!out[c] || !in[c]) return fail(NUFFT_ERR_INVALID_ARG, "null data vector");
@@ -981,48 +919,50 @@ int nufft_toeplitz_apply(nufft_toeplitz* t, void* const* out, const void* const*
         if (out[0] == in[0]) return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_apply on a segmented operator: the output array is also the input array");
         return apply_segmented(t, out[0], in[0], stream);
     }
-    if (ncoils > 0 || t->coupled) {       // coil 0 stores into out[c] what coil 1 still has to read from in[c']; coupled: every output needs every input
+    const bool coupled = t->mode == MODE_COUPLED;
+    if (ncoils > 0 || coupled) {       // coil 0 stores into out[c] what coil 1 still has to read from in[c']; coupled: every output needs every input
         for (int c = 0; c < t->C; ++c)
             for (int c2 = 0; c2 < t->C; ++c2)
                 if (out[c] == in[c2])
                     return fail(NUFFT_ERR_INVALID_ARG, ncoils > 0 ? "nufft_toeplitz_apply with coil maps set: an output array is also an input array"
                                                                   : "nufft_toeplitz_apply on coupled components: an output array is also an input array");
     }
-    if (t->coupled) {
-        int rc = ncoils == 0 ? apply_coupled(t, out, in, nullptr, false, stream) : NUFFT_OK;
-        for (int s = 0; s < ncoils && !rc; ++s) rc = apply_coupled(t, out, in, t->coil_maps[(size_t)s], s > 0, stream);
+    // The passes over the coil maps: without maps one pass with a null map that stores, with maps one per coil, accumulating from the
+    // second coil on.
+    const int passes = std::max(ncoils, 1);
+    auto map_of = [&](int s) -> const void* { return ncoils ? t->coil_maps[(size_t)s] : nullptr; };
+    int rc = NUFFT_OK;
+    if (coupled) {
+        for (int s = 0; s < passes && !rc; ++s) rc = apply_coupled(t, out, in, map_of(s), s > 0, stream);
         return rc;
     }
-    for (int c = 0; c < t->C; ++c) {
-        int rc = NUFFT_OK;
-        const void* K = t->framed ? frame_multiplier(t, c) : t->d_K;
-        if (ncoils == 0) rc = t->path == NUFFT_TOEPLITZ_PATH_FUSED ? apply_fused(t, K, out[c], in[c], stream) : apply_dense(t, K, out[c], in[c], stream);
-        for (int s = 0; s < ncoils && !rc; ++s) rc = apply_coil(t, K, out[c], in[c], t->coil_maps[(size_t)s], s > 0, stream);
-        if (rc) return rc;
+    for (int c = 0; c < t->C && !rc; ++c) {
+        const void* K = multiplier_at(t, t->mode, c).ptr;      // the frame's, or d_K for every component
+        for (int s = 0; s < passes && !rc; ++s) rc = apply_coil(t, K, out[c], in[c], map_of(s), s > 0, stream);
     }
-    return NUFFT_OK;
+    return rc;
 }
 
 int nufft_toeplitz_set_maps(nufft_toeplitz* t, int32_t ncoils, const void* const* maps, void* stream_) {
     if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
     if (!maps) return fail(NUFFT_ERR_INVALID_ARG, "null table of coil maps");
     if (ncoils < 1 || ncoils > 1024) return fail(NUFFT_ERR_INVALID_ARG, "the number of coils must lie in 1 ... 1024");
-    if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
+    int rc;
+    if ((rc = host_only_refusal(t))) return rc;
     for (int32_t c = 0; c < ncoils; ++c) {
         if (!maps[c]) return fail(NUFFT_ERR_INVALID_ARG, "null coil map");
         if (!aligned16(maps[c])) return fail(NUFFT_ERR_INVALID_ARG, "coil maps must be 16-byte aligned");
     }
-    if (t->coupled && !t->seg && t->path == NUFFT_TOEPLITZ_PATH_FUSED && !t->maps_inpass)
+    if (t->mode == MODE_COUPLED && !t->seg && t->path == NUFFT_TOEPLITZ_PATH_FUSED && !t->maps_inpass)
         return fail(NUFFT_ERR_UNSUPPORTED, "nufft_toeplitz_set_maps: coil maps on the route NUFFT_TOEPLITZ_MAPS_INPASS=0 do not combine with coupled components");
     if (!t->seg && t->path == NUFFT_TOEPLITZ_PATH_FUSED && !t->maps_inpass && !t->d_coil) {
         DeviceGuard guard(t->device);
-        if (capturing(static_cast<hipStream_t>(stream_)))
-            return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_set_maps allocates on the streaming route: not on a capturing stream");
-        if (int rc = alloc(t, &t->d_coil, coil_scratch_bytes(t))) return rc;
+        if ((rc = capture_refusal(static_cast<hipStream_t>(stream_), "nufft_toeplitz_set_maps", "allocates on the streaming route"))) return rc;
+        if ((rc = alloc(t, &t->d_coil, coil_scratch_bytes(t)))) return rc;
     }
     const std::vector<const void*> before = t->coil_maps;
     t->coil_maps.assign(maps, maps + ncoils);
-    if (int rc = acquire_segment_scratch(t, "nufft_toeplitz_set_maps", stream_)) {
+    if ((rc = acquire_segment_scratch(t, "nufft_toeplitz_set_maps", stream_))) {
         t->coil_maps = before;
         return rc;
     }
@@ -1046,7 +986,7 @@ int nufft_toeplitz_set_factors(nufft_toeplitz* t, const void* const* B, void* st
     if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
     if (!t->seg) return fail(NUFFT_ERR_INVALID_ARG, "nufft_toeplitz_set_factors: the operator is not segmented (nufft_toeplitz_create_segmented)");
     if (!B) return fail(NUFFT_ERR_INVALID_ARG, "null table of factors");
-    if (t->device < 0) return fail(NUFFT_ERR_NO_DEVICE, "host-only Toeplitz object (device = -1)");
+    if (int rc = host_only_refusal(t)) return rc;
     for (int l = 0; l < t->seg; ++l) {
         if (!B[l]) return fail(NUFFT_ERR_INVALID_ARG, "null factor");
         if (!aligned16(B[l])) return fail(NUFFT_ERR_INVALID_ARG, "the factors must be 16-byte aligned");

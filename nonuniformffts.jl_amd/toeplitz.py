@@ -135,26 +135,37 @@ class ToeplitzOperator:
         """True while a coupled build (``set_points(..., basis=)`` / ``set_spectra``) is in force."""
         return bool(self._handle.value) and lib.nufft_toeplitz_num_coupled(self._handle) > 0
 
+    def _checked_tuple(self, x, shape, what, expected, count=None, counted=None, *, stacked_count=False, empty=None):
+        """A contiguous stacked tensor ``(count, *shape)`` or a sequence of ``shape`` tensors -> the tuple of its arrays, checked like
+        ``_check_uniform`` checks.  ``what`` names the arrays in the messages and ``expected`` is the stacked shape they quote.
+        ``count``: how many there must be, ``counted`` in words (default: the number); None: at least one, else ``ValueError(empty)``.
+        ``stacked_count``: a stacked tensor of another count has the wrong dimensions, not the wrong amount."""
+        if isinstance(x, torch.Tensor):
+            if x.dim() != self.ndim + 1 or (stacked_count and x.shape[0] != count):
+                raise DimensionMismatch(f"wrong dimensions of the {what.removeprefix('the ')} (expected tensor shape {expected}, "
+                                        f"got {tuple(x.shape)})")
+            if not x.is_contiguous():
+                raise ValueError(f"{what} must be contiguous")
+            x = tuple(x[i] for i in range(x.shape[0]))
+        else:
+            x = tuple(x)
+        if count is None and not x:
+            raise ValueError(empty)
+        if count is not None and len(x) != count:
+            raise DimensionMismatch(f"wrong amount of {what.removeprefix('the ')} (expected {counted or count}, got {len(x)})")
+        self._require_gpu()
+        self._require_open()
+        _check_coil_arrays(x, self.device, self.Z, shape, what)
+        return x
+
     def set_spectra(self, T) -> "ToeplitzOperator":
         """The coupled counterpart of ``set_spectrum``: ``T`` of shape ``(K (K + 1) / 2, *padded_shape)`` or a sequence of that many
         ``padded_shape`` tensors, ``T[pair_index(a, b, K)] = T_ab`` on the mode set of a 2N plan, ``K = ntransforms`` (``K = segments`` on
         a segmented operator).  Only read."""
         K = self._inner
         npairs = K * (K + 1) // 2
-        if isinstance(T, torch.Tensor):
-            if T.dim() != self.ndim + 1 or T.shape[0] != npairs:
-                raise DimensionMismatch(f"wrong dimensions of the spectra (expected tensor shape ({npairs}, ...) for {K} components, "
-                                        f"got {tuple(T.shape)})")
-            if not T.is_contiguous():
-                raise ValueError("the spectra must be contiguous")
-            T = tuple(T[p] for p in range(npairs))
-        else:
-            T = tuple(T)
-            if len(T) != npairs:
-                raise DimensionMismatch(f"wrong amount of spectra (expected {npairs} for {K} components, got {len(T)})")
-        self._require_gpu()
-        self._require_open()
-        _check_coil_arrays(T, self.device, self.Z, self.padded_shape, "the spectra")
+        T = self._checked_tuple(T, self.padded_shape, "the spectra", f"({npairs}, ...) for {K} components", npairs, f"{npairs} for {K} components",
+                                stacked_count=True)
         _check(lib.nufft_toeplitz_set_spectra_coupled(self._handle, _ptr_table(T), self._stream()))
         return self
 
@@ -297,19 +308,7 @@ class ToeplitzOperator:
         """The framed counterpart of ``set_spectrum``: ``T`` of shape ``(ntransforms, *padded_shape)`` or a sequence of that many
         ``padded_shape`` tensors, ``T[c]`` the spectrum of frame c.  Only read."""
         K = self.ntransforms
-        if isinstance(T, torch.Tensor):
-            if T.dim() != self.ndim + 1 or T.shape[0] != K:
-                raise DimensionMismatch(f"wrong dimensions of the spectra (expected tensor shape ({K}, ...), got {tuple(T.shape)})")
-            if not T.is_contiguous():
-                raise ValueError("the spectra must be contiguous")
-            T = tuple(T[c] for c in range(K))
-        else:
-            T = tuple(T)
-            if len(T) != K:
-                raise DimensionMismatch(f"wrong amount of spectra (expected {K} frames, got {len(T)})")
-        self._require_gpu()
-        self._require_open()
-        _check_coil_arrays(T, self.device, self.Z, self.padded_shape, "the spectra")
+        T = self._checked_tuple(T, self.padded_shape, "the spectra", f"({K}, ...)", K, f"{K} frames", stacked_count=True)
         _check(lib.nufft_toeplitz_set_spectra_frames(self._handle, _ptr_table(T), self._stream()))
         return self
 
@@ -320,19 +319,8 @@ class ToeplitzOperator:
         that are not 16-byte aligned (an odd element count in ComplexF32) are copied to their own allocations."""
         self._require_gpu()
         self._require_open()
-        if isinstance(maps, torch.Tensor):
-            if maps.dim() != self.ndim + 1:
-                raise DimensionMismatch(f"wrong dimensions of the coil maps (expected tensor shape (ncoils, {', '.join(map(str, self.shape))}), "
-                                        f"got {tuple(maps.shape)})")
-            if not maps.is_contiguous():
-                raise ValueError("coil maps must be contiguous")
-            maps = tuple(maps[c] for c in range(maps.shape[0]))
-        else:
-            maps = tuple(maps)
-        if len(maps) < 1:
-            raise ValueError("at least one coil map is needed")
-        _check_coil_arrays(maps, self.device, self.Z, self.shape, "coil maps")
-        maps = _aligned(maps)
+        maps = _aligned(self._checked_tuple(maps, self.shape, "coil maps", f"(ncoils, {', '.join(map(str, self.shape))})",
+                                            empty="at least one coil map is needed"))
         _check(lib.nufft_toeplitz_set_maps(self._handle, len(maps), _ptr_table(maps), self._stream()))
         self._maps = maps
         return self
@@ -345,19 +333,7 @@ class ToeplitzOperator:
         self._require_open()
         if not self.segments:
             raise ValueError("set_factors needs a segmented operator: ToeplitzOperator(plan, segments=L)")
-        if isinstance(B, torch.Tensor):
-            if B.dim() != self.ndim + 1:
-                raise DimensionMismatch(f"wrong dimensions of the factors (expected tensor shape ({self.segments}, {', '.join(map(str, self.shape))}), "
-                                        f"got {tuple(B.shape)})")
-            if not B.is_contiguous():
-                raise ValueError("the factors must be contiguous")
-            B = tuple(B[l] for l in range(B.shape[0]))
-        else:
-            B = tuple(B)
-        if len(B) != self.segments:
-            raise DimensionMismatch(f"wrong amount of factors (expected {self.segments}, got {len(B)})")
-        _check_coil_arrays(B, self.device, self.Z, self.shape, "the factors")
-        B = _aligned(B)
+        B = _aligned(self._checked_tuple(B, self.shape, "the factors", f"({self.segments}, {', '.join(map(str, self.shape))})", self.segments))
         _check(lib.nufft_toeplitz_set_factors(self._handle, _ptr_table(B), self._stream()))
         self._factors = B
         return self
@@ -408,12 +384,11 @@ class ToeplitzOperator:
         else:
             out_t = (out,) if isinstance(out, torch.Tensor) else tuple(out)
             self._check_uniform(out_t, "output")
-            if self._maps and any(o is v or o.data_ptr() == v.data_ptr() for o in out_t for v in u_t):
-                raise ValueError("with coil maps set the output must not be the input")
-            if self.coupled and any(o is v or o.data_ptr() == v.data_ptr() for o in out_t for v in u_t):
-                raise ValueError("on coupled components the output must not be the input: every output depends on every input")
-            if self.segments and any(o is v or o.data_ptr() == v.data_ptr() for o in out_t for v in u_t):
-                raise ValueError("on a segmented operator the output must not be the input: every segment reads the input")
+            refusal = ("with coil maps set the output must not be the input" if self._maps else
+                       "on coupled components the output must not be the input: every output depends on every input" if self.coupled else
+                       "on a segmented operator the output must not be the input: every segment reads the input" if self.segments else None)
+            if refusal and any(o is v or o.data_ptr() == v.data_ptr() for o in out_t for v in u_t):
+                raise ValueError(refusal)
         _check(lib.nufft_toeplitz_apply(self._handle, _ptr_table(out_t), _ptr_table(u_t), self._stream()))
         return out
 

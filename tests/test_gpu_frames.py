@@ -5,7 +5,9 @@ Systems: tvt_cases.frames (one analytic spectrum per frame, exact).  Bars:
     bit-equal, also in place and with coil maps;
   * multipliers built from points: spreading uses atomics, so a frame's multiplier agrees with that of ``set_points`` on the same points
     within the operator's parity bar (1e-12 / 1e-5 relative), not to the bit; a frame without points is exactly zero;
-  * CG: x within the solver bar (1e-11 / 1e-4) of K single-frame solves, statuses equal.
+  * CG: x within the solver bar (1e-11 / 1e-4) of K single-frame solves, statuses equal;
+  * changes of build mode (plain, coupled, framed; points and spectra): after every build the operator holds the bytes and returns the
+    bits of a fresh operator given that build alone, and a refused build changes nothing.
 """
 import numpy as np
 import pytest
@@ -204,4 +206,77 @@ def test_cg_and_the_refused_preconditioner(Ns, K, path, Z):
     with pytest.raises(ValueError, match="framed"):
         pc.update()
     pc.close()
+    op.close()
+
+
+# ---- every change of build mode ----------------------------------------------------------------------------------------------------
+
+# plain, coupled, framed: every ordered pair once, a mode after itself included; the steps alternate between points and spectra, which
+# gives every mode both entry points
+CHAIN = "PPCCFFPFCP"
+
+
+class _Builds:
+    """Seeded inputs of every build of a 3-component operator.  The point sets have at most two points: a sum of two terms does not
+    depend on the order of the atomic adds of the spreading, so a build from them is the same to the bit every time."""
+
+    def __init__(self, Ns, T, Zc, padded_shape):
+        rng = np.random.default_rng(7 * sum(Ns))
+        D = len(Ns)
+        cplx = lambda *shape: _dev((rng.standard_normal(shape) + 1j * rng.standard_normal(shape)).astype(Zc))      # noqa: E731
+        pts = lambda n: tuple(_dev((rng.random(n) * 2 * np.pi).astype(T)) for _ in range(D))                       # noqa: E731
+        self.spectrum, self.pairs, self.per_frame = cplx(*padded_shape), cplx(6, *padded_shape), cplx(3, *padded_shape)
+        self.points, self.weights, self.basis = pts(2), _dev((rng.random(2) + 0.1).astype(T)), cplx(3, 2)
+        self.frame_points, self.frame_weights = [pts(2), pts(1), pts(2)], [_dev((rng.random(2) + 0.1).astype(T)), None, None]
+        self.u = tuple(cplx(*Ns[::-1]) for _ in range(3))
+
+    def build(self, op, mode, by_points):
+        if mode == "P":
+            return op.set_points(self.points, self.weights) if by_points else op.set_spectrum(self.spectrum)
+        if mode == "C":
+            return op.set_points(self.points, self.weights, basis=self.basis) if by_points else op.set_spectra(self.pairs)
+        return op.set_points_frames(self.frame_points, self.frame_weights) if by_points else op.set_spectra_frames(self.per_frame)
+
+
+def _operator(nufft, Zc, Ns, path, ntransforms=1, segments=None):
+    plan = nufft.PlanNUFFT(Zc, Ns, backend=nufft.ROCBackend(0), options={"NUFFT_TOEPLITZ_FUSED": 0} if path == "dense" else {},
+                           ntransforms=ntransforms)
+    op = nufft.ToeplitzOperator(plan, segments=segments)
+    plan.close()
+    assert op.path == path
+    return op
+
+
+@pytest.mark.parametrize("Z", TYPES)
+@pytest.mark.parametrize("Ns,path", [((12, 10), "dense"), ((32, 40), "fused")])
+def test_every_change_of_build_mode(Ns, path, Z):
+    """After each build of the chain the operator is what a fresh operator is after that build alone: the same bytes held, the same
+    bits out of ``apply``, the mode reported."""
+    from nufft_pkg import nufft
+    T, Zc = TC.dt(Z)[:2]
+    op = _operator(nufft, Zc, Ns, path, ntransforms=3)
+    b = _Builds(Ns, T, Zc, op.padded_shape)
+    for step, mode in enumerate(CHAIN):
+        fresh = _operator(nufft, Zc, Ns, path, ntransforms=3)
+        for o in (op, fresh):
+            b.build(o, mode, by_points=step % 2 == 0)
+            assert (o.coupled, o.framed) == (mode == "C", mode == "F"), (step, mode)
+        assert op.info().workspace_bytes == fresh.info().workspace_bytes, (step, mode)
+        assert all(torch.equal(x, y) for x, y in zip(op(b.u), fresh(b.u))), (step, mode)
+        fresh.close()
+    op.close()
+
+
+@pytest.mark.parametrize("Z", TYPES)
+@pytest.mark.parametrize("Ns,path", [((12, 10), "dense"), ((32, 40), "fused")])
+def test_a_refused_build_leaves_the_build_in_force(Ns, path, Z):
+    from nufft_pkg import nufft
+    T, Zc = TC.dt(Z)[:2]
+    op = _operator(nufft, Zc, Ns, path, segments=3)                               # set_spectrum is refused before it touches anything
+    b = _Builds(Ns, T, Zc, op.padded_shape)
+    op.set_spectra(b.pairs).set_factors(b.u)
+    held, want = op.info().workspace_bytes, op(b.u[0]).clone()
+    with pytest.raises(ValueError, match="segmented"):
+        op.set_spectrum(b.spectrum)
+    assert op.info().has_spectrum == 1 and op.info().workspace_bytes == held and torch.equal(op(b.u[0]), want)
     op.close()
