@@ -319,6 +319,23 @@ int nufft_get_sort_result(nufft_plan* plan, int32_t* perm_host, int64_t perm_cap
  * a workgroup's LDS).  Reads device flags back (synchronises `stream`).  Inspection only. */
 int nufft_sort_columns_used(nufft_plan* plan, int* used_out, void* stream);
 
+/* Whether the last nufft_set_points took the steady path (1) or the full one (0).  Plans with nufft_info.sort_column decide on the device, per
+ * point set, whether the two rings or the tile kernels serve it, so the full path enqueues both alternatives and one of them returns on a
+ * device flag.  The decisions come back to the host through mapped memory, without a synchronisation; once the newest record the host has
+ * seen reports three point sets in a row that both rings served from their equal-length task tables, set_points enqueues the rings' path
+ * alone — no stand-by of the fine sort, no tile tables, no task-table kernels — and spreading / interpolation launch no tile kernel for that
+ * set.  The rings are then FORCED for it (either engine computes the same transform for any point set; nufft_spread_engine_used,
+ * nufft_interp_engine_used and nufft_sort_columns_used report the rings and the column-layer sort, which is what ran); what they would have
+ * decided still comes back, and the first set they would not have served from those tables sends the next call seen to report it back to
+ * the full path.  Never taken while `stream` is capturing, nor on a plan that has had any call captured into a hipGraph; option
+ * NUFFT_STEADY_PATH=0 (nufft_params.options) turns it off.  A host flag: no device read, no synchronisation.  Inspection only. */
+int nufft_steady_path_used(const nufft_plan* plan, int* used_out);
+
+/* The host bookkeeping behind it, as a function (no plan, no device): state[0] = sequence number of the newest feedback record seen,
+ * state[1] = 1 while that record reports the streak; (seq, streak) = a record as the host reads it.  A record whose sequence number is
+ * not new is ignored.  Updates `state`: state[1] = 1 means that a set_points seeing it is eligible for the steady path. */
+int nufft_steady_path_observe(uint32_t* state, uint32_t seq, uint32_t streak);
+
 /* ---- timing (TimerOutputs analogue, src/plan.jl:397-417) -------------------------------- */
 
 /* enable != 0: bracket every stage with hipEvents on the caller's stream. */

@@ -361,6 +361,8 @@ SYMBOLS = {
     "nufft_copy_grid": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int64, _P]),
     "nufft_get_sort_result": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_uint32), C.c_int64, _P]),
     "nufft_sort_columns_used": (C.c_int, [_P, C.POINTER(C.c_int), _P]),
+    "nufft_steady_path_used": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "nufft_steady_path_observe": (C.c_int, [C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32]),
     "nufft_set_timing": (C.c_int, [_P, C.c_int]),
     "nufft_get_stage_times": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "nufft_spread_engine_used": (C.c_int, [_P, C.POINTER(C.c_int), _P]),

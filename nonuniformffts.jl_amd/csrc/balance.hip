@@ -458,6 +458,27 @@ __global__ __launch_bounds__(1024) void patch_task_sort_kernel(int ntasks, int n
     }
 }
 
+// Steady path of set_points (plan.cpp: steady_now; rings only): the host launches this behind patch_column_sums_kernel INSTEAD of the three table
+// kernels above.  The equal-length table (choice[3] = 1) is a function of the plan alone — first[c] = c nseg, entry k ncols + c = {c, layers
+// [k segl, (k + 1) segl)}, nothing behind — so the one the previous point set left in place is reused as it is.  The decision is computed as
+// patch_task_counts_kernel computes it, but only ADVISES: choice[2] reads "ring" whatever it says (either engine computes the same transform, and
+// the host has launched nothing for the other one); what the ring would have decided goes to choice[kAdvisoryWord], and choice[kSteadyModeWord]
+// says whether this set keeps the equal-length table in place.  A set that would have left equal-length mode gets no verdict here (that one
+// needs patch_split_kernel's sums: the advisory word reads "served") — the mode word ends the streak, and the next set takes the full path.
+__global__ void ring_steady_decision_kernel(int ntasks, unsigned long long np, unsigned long long limit, unsigned long long slots_eff, int uniform_always,
+                                            uint32_t* __restrict__ choice, uint32_t* __restrict__ slots_in_use) {
+    const double mean = (double)np / (double)ntasks;
+    const uint32_t heaviest = choice[6];
+    choice[6] = 0u;                                        // (as patch_task_counts_kernel: the next maximum starts from zero, a side buffer is void)
+    choice[kHaloStateWord] = 0u;
+    const bool uniform_mode = (double)heaviest <= 1.1 * mean + 5.0 * sqrt(mean) + 8.0;
+    const bool keep = uniform_always || np == 0ull || ((unsigned long long)heaviest <= limit && np <= limit * slots_eff);
+    choice[kAdvisoryWord] = (uniform_mode && !keep) ? 0u : 1u;
+    choice[kSteadyModeWord] = (uniform_mode && choice[3] != 0u) ? 1u : 0u;
+    choice[2] = 1u;
+    if (slots_in_use) slots_in_use[0] = 0u;
+}
+
 bool patch_tasks_supported(const Geom& g) { return g.nb[2] <= kPatchMaxLayers; }
 
 // plan creation: the sort kernel's 128 KiB of dynamic LDS (the attribute is per device)
@@ -470,11 +491,17 @@ int patch_task_table_entries(const PatchPlan& pp) { return pp.ntasks + 2 * pp.np
 // tasks of equal point count)
 static hipError_t launch_column_tasks(const Geom& g, const ColumnTasks& ct, const uint32_t* offsets, int64_t np, unsigned long long limit,
                                       unsigned long long limit_cut, unsigned long long slots_eff, bool uniform_always, uint32_t* choice, uint32_t* slots_in_use,
-                                      uint32_t* colsum, uint32_t* first, uint2* tasktab, hipStream_t stream, double rho_eff_max = 0.0) {
+                                      uint32_t* colsum, uint32_t* first, uint2* tasktab, hipStream_t stream, double rho_eff_max = 0.0, bool force = false) {
     const int ncols = ct.ncolx * ct.ncoly, wpb = 256 / kWave;
     const int ntab = column_task_table_entries(ct, g.nb[2]);
     hipLaunchKernelGGL(patch_column_sums_kernel, dim3((unsigned)((ncols + wpb - 1) / wpb)), dim3(256), 0, stream, g, ct.ncolx, ct.ncoly, ct.bxw, ct.byw,
                        ct.segl, offsets, colsum, choice);
+    if (force) {
+        // steady path: the engine is this one and its equal-length table stays in place; the decision only advises
+        hipLaunchKernelGGL(ring_steady_decision_kernel, dim3(1), dim3(1), 0, stream, ct.ntasks, (unsigned long long)np, limit, slots_eff, uniform_always ? 1 : 0,
+                           choice, slots_in_use);
+        return hipGetLastError();
+    }
     const int min_seg = ct.maxlen > 0 ? (g.nb[2] + ct.maxlen - 1) / ct.maxlen : 1;
     hipLaunchKernelGGL(patch_task_counts_kernel, dim3(1), dim3(1024), 0, stream, ncols, ct.ntasks, ntab, ct.nseg, min_seg, g.nb[2] / ct.zq,
                        (unsigned long long)np, limit, slots_eff, uniform_always ? 1 : 0, colsum, first, tasktab, choice, slots_in_use);
@@ -512,7 +539,7 @@ hipError_t launch_patch_tasks(const Geom& g, const PatchPlan& pp, int clo, int c
 // max(heaviest task, all points / workgroups at work) stays within `advantage` x an even share of the whole chip
 // (np / cus): small grids, whose few tasks cannot fill the chip, go to the LDS-tile kernel with its slices.
 hipError_t launch_march_tasks(const Geom& g, const ColumnTasks& ct, const uint32_t* offsets, int64_t np, int cus, double advantage, double rho_eff_max,
-                              uint32_t* choice, uint32_t* colsum, uint32_t* first, uint2* tasktab, hipStream_t stream) {
+                              uint32_t* choice, uint32_t* colsum, uint32_t* first, uint2* tasktab, hipStream_t stream, bool force) {
     const unsigned long long slots_eff = (unsigned long long)std::max(1, std::min(cus, ct.ntasks));
     // advantage <= 0: always the ring (a limit that no product with slots_eff can overflow)
     const bool always = advantage <= 0.0;
@@ -521,7 +548,7 @@ hipError_t launch_march_tasks(const Geom& g, const ColumnTasks& ct, const uint32
     // folded N(0, 1) points at 0.3 points per cell: the ring takes 1.27x its time for uniform points)
     const unsigned long long limit_cut = always ? limit : (unsigned long long)(0.85 * advantage * (double)np / (double)cus) + 64ull;
     return launch_column_tasks(g, ct, offsets, np, limit, limit_cut, slots_eff, always, choice, nullptr, colsum, first, tasktab, stream,
-                               always ? 0.0 : rho_eff_max);
+                               always ? 0.0 : rho_eff_max, force);
 }
 
 // The same for the z-marching spreading ring (smarch_kernels.h): a task is a workgroup that owns a column for a segment of bin
@@ -529,22 +556,24 @@ hipError_t launch_march_tasks(const Geom& g, const ColumnTasks& ct, const uint32
 // regions multiply the visits as they do for the patches.  The ring keeps a point set while max(heaviest task, all tasks /
 // workgroups at work) stays within `advantage` x an even share of the chip; when it does, the LDS-tile kernel gets no slots.
 hipError_t launch_smarch_tasks(const Geom& g, const SMarchPlan& sp, const uint32_t* offsets, int64_t np, int cus, double advantage,
-                               uint32_t* choice, uint32_t* slots_in_use, uint32_t* colsum, uint32_t* first, uint2* tasktab, hipStream_t stream) {
+                               uint32_t* choice, uint32_t* slots_in_use, uint32_t* colsum, uint32_t* first, uint2* tasktab, hipStream_t stream, bool force) {
     const ColumnTasks& ct = sp.ct;
     const unsigned long long slots_eff = (unsigned long long)std::max(1, std::min(cus, ct.ntasks));
     const double infl0 = (double)(ct.segl + sp.hlo + sp.hhi) / (double)ct.segl;
     const unsigned long long limit = advantage > 0.0 ? (unsigned long long)(advantage * infl0 * (double)np / (double)cus) + 64ull
                                                      : ~0ull / (slots_eff + 1ull);
-    return launch_column_tasks(g, ct, offsets, np, limit, limit, slots_eff, advantage <= 0.0, choice, slots_in_use, colsum, first, tasktab, stream);
+    return launch_column_tasks(g, ct, offsets, np, limit, limit, slots_eff, advantage <= 0.0, choice, slots_in_use, colsum, first, tasktab, stream, 0.0, force);
 }
 
 // Zero the interior of the spreading tiles that are processed by several slices (they accumulate with
 // atomics; tiles with one slice store every cell exactly once and need no zero fill).
+// (served, or null: device flag "a ring spreads this point set" — nothing to zero then, and on the steady path of set_points nslices is stale)
 template <typename T>
 __global__ __launch_bounds__(256) void zero_split_tiles_kernel(Geom g, int D, int ncr, const uint32_t* __restrict__ nslices,
-                                                              T* grid, int64_t grid_stride) {
+                                                              T* grid, int64_t grid_stride, const uint32_t* served) {
     const TileShape& ts = g.sp;
     const int tile = blockIdx.x;
+    if (served && *served != 0u) return;
     if (nslices[tile] <= 1) return;
     T* gr = grid + (int64_t)blockIdx.y * grid_stride;
     int rem = tile, t[3], org[3], neff[3];
@@ -568,15 +597,15 @@ __global__ __launch_bounds__(256) void zero_split_tiles_kernel(Geom g, int D, in
 }
 
 hipError_t launch_zero_split_tiles(int dtype, const Geom& g, int D, int is_complex, int C, const uint32_t* nslices,
-                                   void* grid, int64_t grid_stride_reals, hipStream_t stream) {
+                                   void* grid, int64_t grid_stride_reals, hipStream_t stream, const uint32_t* served) {
     const dim3 grid_dim((unsigned)g.sp.ntiles, (unsigned)C, 1);
     const int ncr = is_complex ? 2 : 1;
     if (dtype == NUFFT_F32)
         hipLaunchKernelGGL(zero_split_tiles_kernel<float>, grid_dim, dim3(256), 0, stream, g, D, ncr, nslices,
-                           static_cast<float*>(grid), grid_stride_reals);
+                           static_cast<float*>(grid), grid_stride_reals, served);
     else
         hipLaunchKernelGGL(zero_split_tiles_kernel<double>, grid_dim, dim3(256), 0, stream, g, D, ncr, nslices,
-                           static_cast<double*>(grid), grid_stride_reals);
+                           static_cast<double*>(grid), grid_stride_reals, served);
     return hipGetLastError();
 }
 

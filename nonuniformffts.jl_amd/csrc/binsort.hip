@@ -296,19 +296,32 @@ __global__ __launch_bounds__(256) void coarse_clear_kernel(Geom g, CoarseGeom c,
     if (k < c.nkeys) counts[coarse_rep_bin(g, c, k)] = 0u;
 }
 
+// The feedback record of a point set (one thread; host-mapped memory, no synchronisation): {what ring a / ring b decided — or, on the steady path
+// of set_points, would have decided —, sequence number, streak}.  The streak is device state (so a replayed hipGraph keeps it truthful): the
+// number of consecutive point sets that both rings served, or would have, from their equal-length task tables (ma, mb: the mode words).
+__device__ inline void write_sort_feedback(const uint32_t* ra, const uint32_t* rb, const uint32_t* ma, const uint32_t* mb, uint32_t* streak,
+                                           uint32_t* feedback, uint32_t seq) {
+    const uint32_t a = *ra, b = *rb;
+    const uint32_t n = (a != 0u && b != 0u && *ma != 0u && *mb != 0u) ? *streak + 1u : 0u;
+    *streak = n;
+    __atomic_store_n(&feedback[0], a, __ATOMIC_RELAXED);
+    __atomic_store_n(&feedback[1], b, __ATOMIC_RELAXED);
+    __atomic_store_n(&feedback[3], n, __ATOMIC_RELAXED);
+    __threadfence_system();
+    __atomic_store_n(&feedback[2], seq, __ATOMIC_RELAXED);
+}
+
 // pass 2: cursors of the slice in LDS (start of the column layer + what the earlier slices put there), one record store per point
 template <typename T>
 __global__ __launch_bounds__(kCoarseThreads) void coarse_scatter_kernel(BinArgs<T, 3> a, CoarseGeom c, const uint32_t* __restrict__ table,
                                                                        const uint32_t* __restrict__ offsets, PointRec<T, 3>* __restrict__ sorted,
                                                                        uint32_t* __restrict__ counts, const uint32_t* fa, const uint32_t* fb,
-                                                                       const uint32_t* ra, const uint32_t* rb, uint32_t* feedback, uint32_t seq) {
+                                                                       const uint32_t* ra, const uint32_t* rb, const uint32_t* ma, const uint32_t* mb,
+                                                                       uint32_t* streak, uint32_t* feedback, uint32_t seq) {
     extern __shared__ uint32_t cursor[];
     if (feedback && blockIdx.x == 0 && threadIdx.x == 0) {
         // what the rings decided for this point set, for the host's choice of sort at the NEXT set_points (host-mapped memory, no synchronisation)
-        __atomic_store_n(&feedback[0], *ra, __ATOMIC_RELAXED);
-        __atomic_store_n(&feedback[1], *rb, __ATOMIC_RELAXED);
-        __threadfence_system();
-        __atomic_store_n(&feedback[2], seq, __ATOMIC_RELAXED);
+        write_sort_feedback(ra, rb, ma, mb, streak, feedback, seq);
     }
     if (*fa == 0u || *fb == 0u) return;                 // fine sort
     const int tid = threadIdx.x, w = blockIdx.x;
@@ -513,23 +526,27 @@ static hipError_t coarse_finish_t(const SortArgs& s, hipStream_t stream) {
     const uint32_t *fa = s.cs.flag_a, *fb = s.cs.flag_b;
     // fine sort, only where the flags ask for it: clear the fake histogram, count by fine bins; the scan runs either way (on the
     // unchanged fake histogram it reproduces the offsets it already holds)
-    hipLaunchKernelGGL(coarse_clear_kernel, dim3((unsigned)((c.nkeys + 255) / 256)), dim3(256), 0, stream, s.g, c, s.counts, fa, fb);
-    if (s.np > 0) {
-        int64_t blocks = (s.np + kCountThreads * kCountPPT - 1) / (kCountThreads * kCountPPT);
-        if (blocks > 256 * 16) blocks = 256 * 16;
-        hipLaunchKernelGGL((bin_count_kernel<T, 3>), dim3((unsigned)blocks), dim3(kCountThreads), 0, stream, a, s.counts, static_cast<uint2*>(s.binrank), fa, fb);
+    // (steady path of set_points, CoarseSort::steady: the flags read "served" by construction — nothing of the fine sort is launched)
+    const bool steady = s.cs.steady != 0 && s.cs.mode != 2;
+    if (!steady) {
+        hipLaunchKernelGGL(coarse_clear_kernel, dim3((unsigned)((c.nkeys + 255) / 256)), dim3(256), 0, stream, s.g, c, s.counts, fa, fb);
+        if (s.np > 0) {
+            int64_t blocks = (s.np + kCountThreads * kCountPPT - 1) / (kCountThreads * kCountPPT);
+            if (blocks > 256 * 16) blocks = 256 * 16;
+            hipLaunchKernelGGL((bin_count_kernel<T, 3>), dim3((unsigned)blocks), dim3(kCountThreads), 0, stream, a, s.counts, static_cast<uint2*>(s.binrank), fa, fb);
+        }
+        size_t tmp = s.scan_tmp_bytes;
+        hipError_t e = hipcub::DeviceScan::ExclusiveSum(s.scan_tmp, tmp, s.counts, s.offsets, s.g.nbins + 1, stream);
+        if (e != hipSuccess) return e;
     }
-    size_t tmp = s.scan_tmp_bytes;
-    hipError_t e = hipcub::DeviceScan::ExclusiveSum(s.scan_tmp, tmp, s.counts, s.offsets, s.g.nbins + 1, stream);
-    if (e != hipSuccess) return e;
     // (slab sort: level 1 leaves its records in the temporary array, level 2 sorts every slab by fine bin into `sorted`)
     hipLaunchKernelGGL((coarse_scatter_kernel<T>), dim3((unsigned)s.cs.groups), dim3(kCoarseThreads), (size_t)c.nkeys * 4, stream, a, c, s.cs.table, s.offsets,
-                       static_cast<PointRec<T, 3>*>(s.cs.mode == 2 ? s.cs.temp : s.sorted), s.counts, fa, fb, s.cs.fb_a, s.cs.fb_b,
-                       (s.cs.fb_a && s.cs.fb_b) ? s.cs.feedback : (uint32_t*)nullptr, s.cs.seq);
+                       static_cast<PointRec<T, 3>*>(s.cs.mode == 2 ? s.cs.temp : s.sorted), s.counts, fa, fb, s.cs.fb_a, s.cs.fb_b, s.cs.fb_mode_a, s.cs.fb_mode_b,
+                       s.cs.streak, (s.cs.fb_a && s.cs.fb_b && s.cs.fb_mode_a && s.cs.fb_mode_b && s.cs.streak) ? s.cs.feedback : (uint32_t*)nullptr, s.cs.seq);
     if (s.cs.mode == 2)
         hipLaunchKernelGGL((slab_sort_kernel<T>), dim3((unsigned)c.nkeys), dim3(kSlabThreads), (size_t)s.cs.lds2, stream, s.g, c, s.cs.cap,
                            static_cast<const PointRec<T, 3>*>(s.cs.temp), static_cast<PointRec<T, 3>*>(s.sorted), s.offsets, fa);
-    if (s.np > 0) {
+    if (s.np > 0 && !steady) {
         int64_t blocks = (s.np + 255) / 256;
         if (blocks > 256 * 32) blocks = 256 * 32;
         hipLaunchKernelGGL((bin_scatter_kernel<T, 3>), dim3((unsigned)blocks), dim3(256), 0, stream, a, s.offsets, static_cast<const uint2*>(s.binrank),
@@ -539,14 +556,13 @@ static hipError_t coarse_finish_t(const SortArgs& s, hipStream_t stream) {
 }
 
 // the rings' decisions for the host's next choice of sort, where no scatter pass of the column-layer sort carries them (CoarseSort::feedback)
-__global__ void sort_feedback_kernel(const uint32_t* ra, const uint32_t* rb, uint32_t* feedback, uint32_t seq) {
-    __atomic_store_n(&feedback[0], *ra, __ATOMIC_RELAXED);
-    __atomic_store_n(&feedback[1], *rb, __ATOMIC_RELAXED);
-    __threadfence_system();
-    __atomic_store_n(&feedback[2], seq, __ATOMIC_RELAXED);
+__global__ void sort_feedback_kernel(const uint32_t* ra, const uint32_t* rb, const uint32_t* ma, const uint32_t* mb, uint32_t* streak, uint32_t* feedback,
+                                     uint32_t seq) {
+    write_sort_feedback(ra, rb, ma, mb, streak, feedback, seq);
 }
-hipError_t launch_sort_feedback(const uint32_t* ra, const uint32_t* rb, uint32_t* feedback, uint32_t seq, hipStream_t stream) {
-    hipLaunchKernelGGL(sort_feedback_kernel, dim3(1), dim3(1), 0, stream, ra, rb, feedback, seq);
+hipError_t launch_sort_feedback(const uint32_t* ra, const uint32_t* rb, const uint32_t* ma, const uint32_t* mb, uint32_t* streak, uint32_t* feedback,
+                                uint32_t seq, hipStream_t stream) {
+    hipLaunchKernelGGL(sort_feedback_kernel, dim3(1), dim3(1), 0, stream, ra, rb, ma, mb, streak, feedback, seq);
     return hipGetLastError();
 }
 

@@ -100,11 +100,18 @@ struct CoarseSort {
     int cap, lds2;
     uint32_t* flagmem;
     // feedback of the device-side decisions to the host, without a synchronisation: workgroup 0 of the scatter pass writes {ring flag a, ring flag b,
-    // sequence number} into host-mapped memory; the NEXT set_points reads whatever has arrived (plan.cpp: adaptive sort choice)
+    // sequence number, streak} into host-mapped memory; the NEXT set_points reads whatever has arrived (plan.cpp: adaptive sort choice)
     const uint32_t* fb_a;
     const uint32_t* fb_b;
     uint32_t* feedback;
     uint32_t seq;
+    // steady path (plan.cpp: steady_now): fb_a / fb_b are then the rings' ADVISORY words (flag_a / flag_b read "served" whatever they say),
+    // fb_mode_a / fb_mode_b say whether each ring's equal-length task table is in place, and `streak` is the device-resident count of consecutive
+    // point sets that both rings would have served from that table — the record's fourth word
+    const uint32_t* fb_mode_a;
+    const uint32_t* fb_mode_b;
+    uint32_t* streak;
+    int steady;                // 1: only the column-layer scatter is launched (no stand-by of the fine sort)
 };
 // Two-level fine sort (mode 2; plans without a column-layer sort, D = 3): the same two passes with a SLAB of bins as the key — cbx = nb[0]
 // (one column along x), cby rows of bins, one layer: a contiguous range of fine bins — into a temporary array; then one workgroup per slab
@@ -115,7 +122,11 @@ struct CoarseSort {
 // capacities (clusters) take the fine sort with global atomics instead (device flag, flagmem[4]).
 constexpr int kSlabMaxBins = 4096;         // fine bins of a slab (16 KiB of LDS counters in level 2)
 constexpr int kHaloStateWord = 12;         // word of the spreading ring's 16-word device record: 1 = side buffer written, not yet added to the grid
-constexpr int kSlabOverfill = 8;           // a slab may hold this many LDS capacities (level 2 then sorts it through global memory)
+constexpr int kAdvisoryWord = 13;          // word of a ring's record, steady path: what the ring WOULD have decided for this point set ([2] then reads 1 regardless)
+constexpr int kSteadyModeWord = 14;        // ... and 1 while the point set keeps the equal-length task table that is in place
+constexpr int kStreakWord = 15;            // word of the SPREADING ring's record: consecutive point sets both rings would have served from equal-length tables
+constexpr int kSteadyStreak = 3;           // the host takes the steady path once the newest feedback record reports this streak
+constexpr int kSlabOverfill = 8;          // a slab may hold this many LDS capacities (level 2 then sorts it through global memory)
 constexpr int kCoarseMaxKeys = 36864;      // 144 KiB of LDS counters
 
 }  // namespace nufft

@@ -39,7 +39,9 @@ int slab_sort_lds_bytes(int dtype, int cap);
 hipError_t prepare_binsort_slab(int dtype, int lds_bytes);
 hipError_t launch_binsort_coarse_count(const SortArgs& s, hipStream_t stream);
 hipError_t launch_binsort_coarse_finish(const SortArgs& s, hipStream_t stream);
-hipError_t launch_sort_feedback(const uint32_t* ra, const uint32_t* rb, uint32_t* feedback, uint32_t seq, hipStream_t stream);
+// the feedback record of a point set whose scatter pass does not carry it: {ra, rb, seq, streak} (binsort.hip: write_sort_feedback)
+hipError_t launch_sort_feedback(const uint32_t* ra, const uint32_t* rb, const uint32_t* ma, const uint32_t* mb, uint32_t* streak, uint32_t* feedback,
+                                uint32_t seq, hipStream_t stream);
 // zero fill by a kernel (hipGraph-safe, see binsort.hip); dst 16-byte aligned, bytes a multiple of 4
 hipError_t launch_zero_fill(void* dst, size_t bytes, hipStream_t stream);
 hipError_t launch_extract_perm(int dtype, int D, const void* sorted, int64_t np, int32_t* perm_dev, hipStream_t stream);
@@ -68,7 +70,7 @@ size_t balance_scan_tmp_bytes(int ntiles_both);
 size_t balance_work_words(int ntiles_both);       // 32-bit words of BalanceArgs::work (tile counters + partial sums)
 hipError_t launch_balance(const BalanceArgs& b, hipStream_t stream);
 hipError_t launch_zero_split_tiles(int dtype, const Geom& g, int D, int is_complex, int C, const uint32_t* nslices,
-                                   void* grid, int64_t grid_stride_reals, hipStream_t stream);
+                                   void* grid, int64_t grid_stride_reals, hipStream_t stream, const uint32_t* served = nullptr);
 
 // ---- spreading / interpolation (spread_*.hip, interp_*.hip) -------------------------------------
 
@@ -101,6 +103,7 @@ struct TileKernelArgs {
     int cubes;                 // spreading with the compile-time tile: accumulate cube by cube with the FP64 matrix instruction
     void* halo;                // marching ring, halo variant: side buffer of the stencil reach (C components, SMarchPlan::halo_reals each)
     int interp_parts;          // 2: complex data interpolated part by part by the real ring kernels (march_kernels.h, MarchGeom::parts); else 1
+    int ring_only;             // interpolation, steady path of set_points: the staged ring alone (no tile tables exist for this point set)
     int coarse;                // plan of the column-layer sort (CoarseSort): point sets with both flags nonzero are sorted that way
     const uint32_t* coarse_a;
     const uint32_t* coarse_b;
@@ -133,7 +136,7 @@ PatchPlan patch_plan(const Options& opts, int dtype, int is_complex, int D, int 
 // set_points: cuts the patch columns into tasks of about equal point count and decides on the device which engine serves
 // this point set (balance.hip); choice = uint32[8], zeroed once; colsum[columns], first[columns + 1], tasktab[pp.ntasks]
 hipError_t launch_march_tasks(const Geom& g, const ColumnTasks& ct, const uint32_t* offsets, int64_t np, int cus, double advantage, double rho_eff_max,
-                              uint32_t* choice, uint32_t* colsum, uint32_t* first, uint2* tasktab, hipStream_t stream);
+                              uint32_t* choice, uint32_t* colsum, uint32_t* first, uint2* tasktab, hipStream_t stream, bool force = false);
 // advantage: how much faster than the LDS tiles the patches are on uniform points (<= 0: always the patches)
 hipError_t launch_patch_tasks(const Geom& g, const PatchPlan& pp, int clo, int chi, const uint32_t* offsets, int64_t np,
                               int wave_slots, double advantage, uint32_t* choice, uint32_t* slots_in_use, uint32_t* colsum, uint32_t* first,
@@ -165,8 +168,10 @@ hipError_t prepare_spread_dense(int dtype, int M, bool poly);
 // halo variant: grid += side buffer (a.halo); the dimension-1 FFT pass of real plans does the same while it loads its lines (launch_real_lines)
 hipError_t launch_smarch_halo_add(const Options& opts, const TileKernelArgs& a, const SMarchPlan& sp, const uint32_t* flag, hipStream_t stream);
 // set_points: tasks of the ring for this point set and whether it serves it (advantage <= 0: always)
+// force (here and in launch_march_tasks; the steady path of set_points): the ring serves the set from the equal-length table in place, and the
+// decision goes to choice[kAdvisoryWord] / choice[kSteadyModeWord] instead (balance.hip: ring_steady_decision_kernel)
 hipError_t launch_smarch_tasks(const Geom& g, const SMarchPlan& sp, const uint32_t* offsets, int64_t np, int cus, double advantage,
-                               uint32_t* choice, uint32_t* slots_in_use, uint32_t* colsum, uint32_t* first, uint2* tasktab, hipStream_t stream);
+                               uint32_t* choice, uint32_t* slots_in_use, uint32_t* colsum, uint32_t* first, uint2* tasktab, hipStream_t stream, bool force = false);
 
 // ---- type-2 gradient gather (interp_grad_kernels.h, interp_grad_*.hip) ---------------------------------------------
 // Walks the sorted records directly (every sort); values (optional) and D derivatives per component in caller order.

@@ -75,6 +75,17 @@ bool choose_tiles(const Options& opts, int D, int M, int ncomp, int real_bytes, 
 
 }  // namespace nufft
 
+namespace nufft {
+// Host bookkeeping of set_points' steady path (plan_engines.cpp): the newest feedback record seen, and whether it reports the streak
+struct SteadyState {
+    uint32_t seq_seen = 0;
+    bool ok = false;
+};
+void steady_observe(SteadyState& s, uint32_t seq, uint32_t streak);
+// (coarse: a column-layer plan taking the column-layer sort for this set; barred: capturing now, or a call of the plan was captured before)
+bool steady_eligible(const SteadyState& s, bool enabled, bool coarse, bool dense, int64_t np, bool barred);
+}  // namespace nufft
+
 // -------------------------------------------------------------------------------------------
 // The plan
 // -------------------------------------------------------------------------------------------
@@ -178,11 +189,20 @@ struct nufft_plan {
     // (CoarseSort::feedback); after two point sets in a row that a ring handed to the tile kernels (the column-layer attempt then ends in the
     // fine sort with global atomics: 1.8 ms at 1.7e7 folded-normal points against 1.1 ms for the slab sort) set_points takes the slab sort
     // directly, and returns to the column-layer sort as soon as both rings would serve a set again
-    uint32_t* sort_feedback = nullptr;       // host-mapped {flag a, flag b, sequence}
+    uint32_t* sort_feedback = nullptr;       // host-mapped {flag a, flag b, sequence, streak (the steady path, below)}
     uint32_t sort_seq = 0, sort_seq_seen = 0;
     int sort_miss_streak = 0;
     bool sort_prefer_slab = false;
     bool coarse_now = false;                 // the current point set went through the column-layer path (set_points)
+    // steady path of set_points on such plans: the fourth word of the record is the device's count of consecutive point sets that both rings
+    // served from their equal-length task tables.  Once the newest record the host has seen reports kSteadyStreak of them, set_points enqueues
+    // the column-layer path alone — no fine-sort stand-by, no tile tables, no task-table kernels — with the rings forced (balance.hip:
+    // ring_steady_decision_kernel), and the consumers launch no tile kernel for that point set (steady_now).  The record may be many calls
+    // old: the forced ring is correct for any point set, only one call's speed is at stake.  Never while capturing, nor on a plan that has
+    // had a call captured (halo_sticky: a replay changes the device state behind the host's back).
+    bool steady_enabled = true;              // NUFFT_STEADY_PATH (latched at creation): 0 = always the full path
+    nufft::SteadyState steady{};
+    bool steady_now = false;                 // the current point set took the steady path: it has NO tile tables (bal.*), and both rings serve it
     bool dense_available = false;      // the spreading window's dense-set engine exists for this plan (dmarch_kernels.h)
     bool dense_now = false;            // ... and serves the current point set (set_points: mean bin load >= dense_min)
     int dense_min = 1 << 30;

@@ -579,8 +579,9 @@ static int alloc_engines(nufft_plan* p, const EngineDecision& e) {
         // (host-mapped: the scatter pass writes the rings' decisions here, set_points reads them without synchronising — nufft_internal.h)
         NUFFT_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->sort_feedback), 16, hipHostMallocMapped));
         p->sort_feedback[0] = p->sort_feedback[1] = 1u;
-        p->sort_feedback[2] = 0u;
+        p->sort_feedback[2] = p->sort_feedback[3] = 0u;
     }
+    p->steady_enabled = p->opts.option_int("NUFFT_STEADY_PATH", 1) != 0;
     if (p->spread_method == NUFFT_SPREAD_MFMA_PATCHES || p->spread_method == NUFFT_SPREAD_MARCHING_RING || p->interp_march) NUFFT_HIP(prepare_column_tasks());
     return NUFFT_OK;
 }
@@ -689,6 +690,7 @@ static TileKernelArgs tile_args(const nufft_plan* p, bool interp) {
     a.fixed_tile = interp ? p->interp_fixed : p->spread_fixed;
     a.march = interp && p->interp_march;      // (the ring applies per-point weights itself)
     a.interp_parts = p->interp_parts;
+    a.ring_only = interp && p->steady_now;
     a.coarse = p->coarse_now;      // (a dense point set of a column-layer plan, or one behind two clustered ones, was sorted by fine bins: the plain ring gathers it)
     a.coarse_a = p->coarse.flag_a;
     a.coarse_b = p->coarse.flag_b;
@@ -716,6 +718,15 @@ static void note_capture(nufft_plan* p, hipStream_t stream) {
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(stream, &st) != hipSuccess) { (void)hipGetLastError(); return; }
     if (st != hipStreamCaptureStatusNone) p->halo_sticky = true;
+}
+// steady path of set_points: the consumers skip the tile kernels of a point set without tile tables — except into a hipGraph, whose replays may
+// follow a LATER set_points (from then on always the full path: halo_sticky) that hands its set to the tiles.  A captured consumer therefore
+// carries every launch, each gated on the device flags as ever (the forced flags of the current set send the tile kernels home at once).
+static bool skip_tile_launches(const nufft_plan* p, hipStream_t stream) {
+    if (!p->steady_now || p->halo_sticky) return false;
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return st == hipStreamCaptureStatusNone;
 }
 static bool halo_maybe_pending(const nufft_plan* p) { return halo_plan(p) && (p->halo_hint || p->halo_sticky); }
 // the grids are about to be overwritten: an unconsumed side buffer is void
@@ -1125,6 +1136,7 @@ static void check_task_table(const nufft_plan* p, const char* name, const Column
     fprintf(stderr, "[tasks %s] columns %zu, table %zu, in use %zu, longest %zu layers, flag %u, uniform %u, bad columns %zu\n", name, ncols, ntab,
             used, maxlen, ch[2], ch[3], bad);
 }
+// (it reads the rings' task tables and records only, never the tile tables: on the steady path of set_points it finds the equal-length tables in place)
 static void check_task_tables(const nufft_plan* p, hipStream_t stream) {
     if (p->spread_method == NUFFT_SPREAD_MFMA_PATCHES) {
         ColumnTasks ct{p->patch.npx, p->patch.npy, 4, p->patch.pby, p->patch.nseg, p->patch.segl, p->patch.ntasks, 1, 0, 0, 0};
@@ -1148,10 +1160,11 @@ static int grow_point_buffers(nufft_plan* p, int64_t np) {
     return NUFFT_OK;
 }
 
-// set_points, step 2: which sort this point set takes (p->dense_now, p->coarse_now; the slab height, 0 = not the slab sort), and its scratch
+// set_points, step 2: which sort this point set takes (p->dense_now, p->coarse_now, p->steady_now; the slab height, 0 = not the slab sort), and its scratch
 static int choose_sort(nufft_plan* p, int64_t np, hipStream_t stream, int* slab_rows) {
     // dense point set (mean load of the 4^3-cell bins): the matrix-pipe engine serves it where the ring does, from the fine-bin order
     p->dense_now = p->dense_available && np >= (int64_t)p->dense_min * p->tile.nbins;
+    bool barred = true;      // (the steady path: never while capturing, nor after a capture)
     // adaptive choice (nufft_internal.h: sort_feedback): what the rings decided for the point sets before this one
     if (p->sort_feedback) {
         hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
@@ -1164,8 +1177,11 @@ static int choose_sort(nufft_plan* p, int64_t np, hipStream_t stream, int* slab_
             if (both) { p->sort_miss_streak = 0; p->sort_prefer_slab = false; }
             else if (++p->sort_miss_streak >= 2) p->sort_prefer_slab = true;
         }
+        if (!capturing) steady_observe(p->steady, seq, __atomic_load_n(&p->sort_feedback[3], __ATOMIC_RELAXED));
+        barred = capturing || p->halo_sticky;
     }
     p->coarse_now = p->coarse.enabled && !p->dense_now && !(p->sort_prefer_slab && p->slab.enabled);
+    p->steady_now = p->sort_feedback && steady_eligible(p->steady, p->steady_enabled, p->coarse_now, p->dense_now, np, barred);
     const int64_t need = sort_scratch_bytes(*p, np, p->slab.enabled && !p->coarse_now);
     if (need > p->binrank_capacity) {
         dev_free(p, p->d_binrank);
@@ -1197,8 +1213,13 @@ static SortArgs sort_args(nufft_plan* p, int64_t np, const void* const* coords, 
     s.cs = p->coarse;
     if (p->coarse.enabled && !p->coarse_now) s.cs = CoarseSort{};
     if (p->coarse_now && p->sort_feedback) {      // (the scatter pass of the column-layer sort reports the rings' decisions: it runs behind their task kernels)
-        s.cs.fb_a = p->coarse.flag_a; s.cs.fb_b = p->coarse.flag_b;
+        // (steady path: the flags are forced, the record carries the advisory words)
+        const int dw = p->steady_now ? kAdvisoryWord : 2, mw = p->steady_now ? kSteadyModeWord : 3;
+        s.cs.fb_a = p->d_smarch_choice + dw; s.cs.fb_b = p->d_march_choice + dw;
+        s.cs.fb_mode_a = p->d_smarch_choice + mw; s.cs.fb_mode_b = p->d_march_choice + mw;
+        s.cs.streak = p->d_smarch_choice + kStreakWord;
         s.cs.feedback = p->sort_feedback; s.cs.seq = ++p->sort_seq;
+        s.cs.steady = p->steady_now ? 1 : 0;
     }
     if (slab_rows > 0) {
         const int capmax = slab_sort_capacity(p->dtype, kLdsLimit - 256);
@@ -1261,7 +1282,7 @@ int nufft_set_points(nufft_plan* p, int64_t np, const void* const* coords, void*
                                        // below clears the device word with the rest of its per-point-set record)
     StageTimer tm(p, NUFFT_STAGE_SET_POINTS, stream);
     const SortArgs s = sort_args(p, np, coords, slab_rows);
-    const bool coarse = p->coarse_now;
+    const bool coarse = p->coarse_now, steady = p->steady_now;
     // plans of the column-layer sort: histogram by column layers first — its offsets are all the task kernels below need to decide
     // whether both rings serve this point set; the scatter pass (of whichever sort that decision selects) and the tile tables follow
     if (coarse) NUFFT_HIP(launch_binsort_coarse_count(s, stream));
@@ -1287,21 +1308,23 @@ int nufft_set_points(nufft_plan* p, int64_t np, const void* const* coords, void*
         const size_t ncols = (size_t)p->smarch.ct.ncolx * p->smarch.ct.ncoly;
         // (the C components are independent workgroups of one launch: each component has num_cus / C compute units' worth of the chip)
         NUFFT_HIP(launch_smarch_tasks(s.g, p->smarch, p->d_offsets, np, std::max(1, p->num_cus / (p->C * p->smarch.parts)), smarch_advantage(*p), p->d_smarch_choice, p->bal.d_slots, p->d_smarch_cols,
-                                      p->d_smarch_cols + ncols, static_cast<uint2*>(p->d_smarch_tasks), stream));
+                                      p->d_smarch_cols + ncols, static_cast<uint2*>(p->d_smarch_tasks), stream, steady));
     }
     if (p->interp_march) {
         // tasks of the interpolation ring for this point set, and whether it serves it (balance.hip, march_advantage)
         const size_t ncols = (size_t)p->march_ct.ncolx * p->march_ct.ncoly;
         NUFFT_HIP(launch_march_tasks(s.g, p->march_ct, p->d_offsets, np, p->num_cus, march_advantage(*p, np), march_rho_bound(*p), p->d_march_choice, p->d_march_cols,
-                                     p->d_march_cols + ncols, static_cast<uint2*>(p->d_march_tasks), stream));
+                                     p->d_march_cols + ncols, static_cast<uint2*>(p->d_march_tasks), stream, steady));
     }
     if (coarse) {
         // both rings have decided: column-layer scatter, or the fine sort for a point set one of them hands to the tile kernels
+        // (steady path: the column-layer scatter alone, and no tile tables — steady_now tells the consumers)
         NUFFT_HIP(launch_binsort_coarse_finish(s, stream));
-        if ((rc = balance_tiles(p, s, stream))) return rc;
+        if (!steady && (rc = balance_tiles(p, s, stream))) return rc;
     } else if (p->sort_feedback && p->coarse.enabled && !p->dense_now) {
         // a plan of the column-layer sort on the slab sort (the sets before this one went to the tile kernels): what the rings say about THIS set
-        NUFFT_HIP(launch_sort_feedback(p->coarse.flag_a, p->coarse.flag_b, p->sort_feedback, ++p->sort_seq, stream));
+        NUFFT_HIP(launch_sort_feedback(p->coarse.flag_a, p->coarse.flag_b, p->d_smarch_choice + 3, p->d_march_choice + 3, p->d_smarch_choice + kStreakWord,
+                                       p->sort_feedback, ++p->sort_seq, stream));
     }
     if (p->debug_tasks) check_task_tables(p, stream);
     p->Np = np;
@@ -1345,6 +1368,23 @@ int nufft_sort_columns_used(nufft_plan* p, int* used_out, void* stream_) {
     NUFFT_HIP(hipMemcpyAsync(&fb, p->coarse.flag_b, sizeof(fb), hipMemcpyDeviceToHost, stream));
     NUFFT_HIP(hipStreamSynchronize(stream));
     *used_out = (fa != 0 && fb != 0) ? 1 : 0;
+    return NUFFT_OK;
+}
+
+int nufft_steady_path_used(const nufft_plan* p, int* used_out) {
+    int rc = require_points(p);
+    if (rc) return rc;
+    if (!used_out) return fail(NUFFT_ERR_INVALID_ARG, "null output");
+    *used_out = p->steady_now ? 1 : 0;
+    return NUFFT_OK;
+}
+
+int nufft_steady_path_observe(uint32_t* state, uint32_t seq, uint32_t streak) {
+    if (!state) return fail(NUFFT_ERR_INVALID_ARG, "null state");
+    SteadyState s;
+    s.seq_seen = state[0]; s.ok = state[1] != 0u;
+    steady_observe(s, seq, streak);
+    state[0] = s.seq_seen; state[1] = steady_eligible(s, true, true, false, 1, false) ? 1u : 0u;
     return NUFFT_OK;
 }
 
@@ -1393,10 +1433,12 @@ static int spread_impl(nufft_plan* p, const void* const* values_in, void* stream
     a.values_in = values_in;
     // LDS-tile engine.  On plans of the MFMA-patch engine set_points has decided on the device which of the two serves
     // this point set (balance.hip): the other one finds no work (no slots / flag = 0) and returns at once.
-    if (p->balance_enabled)    // tiles shared by several workgroups accumulate with atomics: zero them first
+    // (steady path of set_points: no tile tables for this point set, the ring serves it — neither launch; into a hipGraph both, see skip_tile_launches)
+    const bool tiles = !skip_tile_launches(p, stream);
+    if (p->balance_enabled && tiles)    // tiles shared by several workgroups accumulate with atomics: zero them first
         NUFFT_HIP(launch_zero_split_tiles(p->dtype, a.g, p->D, p->is_complex, p->C, p->bal.d_nslices, p->d_us,
-                                          p->grid_elems * (p->is_complex ? 2 : 1), stream));
-    NUFFT_HIP(launch_spread(a, stream));
+                                          p->grid_elems * (p->is_complex ? 2 : 1), stream, p->steady_now ? p->d_smarch_choice + 2 : nullptr));
+    if (tiles) NUFFT_HIP(launch_spread(a, stream));
     if (p->spread_method == NUFFT_SPREAD_MARCHING_RING) {
         // (halo variant: the kernel sets the device word "side buffer pending")
         NUFFT_HIP(launch_spread_march(a, p->smarch, p->d_smarch_choice + 2, static_cast<const uint2*>(p->d_smarch_tasks), p->d_smarch_choice + kHaloStateWord, p->dense_now, stream));
@@ -1547,6 +1589,7 @@ int nufft_interpolate(nufft_plan* p, void* const* values_out, void* stream_) {
     if (p->Np == 0) return NUFFT_OK;
     TileKernelArgs a = tile_args(p, true);
     a.values_out = values_out;
+    if (a.ring_only && !skip_tile_launches(p, stream)) a.ring_only = 0;      // (into a hipGraph: every launch, gated on the device flags)
     NUFFT_HIP(launch_interp(a, stream));
     return NUFFT_OK;
 }

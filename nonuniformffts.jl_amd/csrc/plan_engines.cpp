@@ -223,6 +223,18 @@ EngineDecision decide_engines(const nufft_plan& p, int num_cus, bool halo_allowe
 // ------------------------------------------------------------------------------------------
 // per-point-set policy (nufft_set_points)
 // ------------------------------------------------------------------------------------------
+// steady path (nufft_internal.h: steady_now).  A record is counted when its sequence number is new to the host — not only the record of the latest
+// call, as the exact two-misses logic of the slab sort wants it: the host may run many calls ahead of the device, and the streak it reads is the
+// device's own count, so ANY record tells how the sets up to it went.  A record that reports a miss carries a streak of 0.
+void steady_observe(SteadyState& s, uint32_t seq, uint32_t streak) {
+    if (seq == s.seq_seen) return;
+    s.seq_seen = seq;
+    s.ok = streak >= (uint32_t)kSteadyStreak;
+}
+bool steady_eligible(const SteadyState& s, bool enabled, bool coarse, bool dense, int64_t np, bool barred) {
+    return enabled && coarse && !dense && np > 0 && s.ok && !barred;
+}
+
 // bytes of the scratch of the sort a point set takes: {bin, rank} of the fine sort (8 bytes per point; also what a clustered set of a
 // column-layer plan falls back to, decided on the device), or the level-1 records of the slab sort in the same allocation
 // (plans of the column-layer sort use neither unless a point set is clustered — the fine sort, 8 bytes — or dense — the slab sort, a record)

@@ -380,13 +380,17 @@ static hipError_t launch_t(bool interp, const TileKernelArgs& a, hipStream_t str
     // and total work against the ring's advantage limit, balance.hip) decides which of the two finds work
     // (the ring applies the per-point weights of the callback menu itself; the tile kernel next to it is then the general variant)
     const bool march = interp && a.march != 0 && !needs_other_eval(a.kernel, a.evalmode);
+    // steady path of set_points (plan.cpp): this point set has no tile tables and its flags read "ring, column-layer sorted" by construction —
+    // the staged ring alone is launched, neither the tile kernel nor the un-staged ring standing by
+    const bool ring_only = interp && a.ring_only != 0;
+    if (ring_only && !(march && a.coarse)) return hipErrorInvalidValue;
     for (int c0 = 0; c0 < a.C; c0 += kMaxCompPerLaunch) {
         const int nc = (a.C - c0) < kMaxCompPerLaunch ? (a.C - c0) : kMaxCompPerLaunch;
         TileArgs<T> k = fill_tile_args<T>(a, c0, nc);
         k.march_flag = march ? a.march_flag : nullptr;
         void* params[] = {&k};
-        hipError_t e = hipLaunchKernel(fn, dim3((unsigned)a.ntiles, (unsigned)nc, 1), dim3((unsigned)a.threads, 1, 1),
-                                       params, (size_t)a.lds_bytes, stream);
+        hipError_t e = hipSuccess;
+        if (!ring_only) e = hipLaunchKernel(fn, dim3((unsigned)a.ntiles, (unsigned)nc, 1), dim3((unsigned)a.threads, 1, 1), params, (size_t)a.lds_bytes, stream);
         if (e != hipSuccess) return e;
         if (march) {
             int lds = 0, n[4];
@@ -409,7 +413,7 @@ static hipError_t launch_t(bool interp, const TileKernelArgs& a, hipStream_t str
             void* mparams[] = {&k, &mg};
             // (parts = 2: both parts of a task side by side on one XCD — march_setup.inc)
             const unsigned gx = parts == 2 ? 2u * (((unsigned)mg.ntasks + 7u) & ~7u) : (unsigned)mg.ntasks;
-            e = hipLaunchKernel(mfn, dim3(gx, (unsigned)nc, 1), dim3((unsigned)n[3], 1, 1), mparams, (size_t)lds, stream);
+            if (!ring_only) e = hipLaunchKernel(mfn, dim3(gx, (unsigned)nc, 1), dim3((unsigned)n[3], 1, 1), mparams, (size_t)lds, stream);
             if (e != hipSuccess) return e;
             if (a.coarse) {
                 // plans of the column-layer sort: the staged kernel serves the point sets sorted that way (device flags), the plain one the others

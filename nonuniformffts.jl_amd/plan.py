@@ -358,6 +358,14 @@ class PlanNUFFT:
         _check(lib.nufft_sort_columns_used(self._handle, C.byref(out), self._stream()))
         return out.value == 1
 
+    def steady_path_used(self) -> bool:
+        """True if the last set_points took the steady path: after three point sets in a row that both rings served, only the rings'
+        path is enqueued (no stand-by launches of the fine sort and the tile kernels; ``NUFFT_STEADY_PATH=0`` turns it off).  A host
+        flag: no synchronisation."""
+        out = C.c_int(0)
+        _check(lib.nufft_steady_path_used(self._handle, C.byref(out)))
+        return out.value == 1
+
     def sort_method_used(self) -> str:
         """Sort of the last set_points: "column_layers", "fine_bins" (histogram with global atomics) or "slabs" (fine bins in two
         levels through LDS: same array and offsets as "fine_bins"); reads device flags back and synchronises."""
