@@ -49,18 +49,21 @@ typedef struct {
 static int g_coord_f32 = 0;
 void oracle_set_coord_f32(int on) { g_coord_f32 = on; }
 
-/* to_unit_cell_cpu, src/blocking/blocking.jl:12-21 */
+/* to_unit_cell, the GPU form src/blocking/blocking.jl:26-33 (rem == fmod, exact), as nufft_oracle.py and the HIP path fold: the
+ * while-loop form (:12-21) rounds once per period and sends x = -tiny to 0, where this form gives L + r = L (cell N - 1, X = 1 by
+ * the clamp of cell_of below) — the two differ by the window's value at its edge, far above the bounds of the parity tests. */
 static inline double fold(double x) {
     if (g_coord_f32) {
-        volatile float xf = (float)x;
         const float L = (float)TWO_PI;
-        while (xf < 0) xf += L;
-        while (xf >= L) xf -= L;
-        return (double)xf;
+        volatile float r = fmodf((float)x, L);
+        if (r == 0) r = 0.0f;
+        if (r < 0) r = L + r;
+        return (double)r;
     }
-    while (x < 0) x += TWO_PI;
-    while (x >= TWO_PI) x -= TWO_PI;
-    return x;
+    volatile double r = fmod(x, TWO_PI);
+    if (r == 0) r = 0.0;
+    if (r < 0) r = TWO_PI + r;
+    return r;
 }
 
 /* point_to_cell (0-based), src/Kernels/Kernels.jl:121-126 */

@@ -563,8 +563,8 @@ def spread(plan: OraclePlan, vp: Sequence[np.ndarray]):
         w = w[:, None, ...] * vals[d].reshape((-1, L) + (1,) * d)
         stride *= plan.Nover[d]
     Np = lin.shape[0]
-    lin = lin.reshape(Np, -1)
-    w = w.reshape(Np, -1)
+    lin = lin.reshape(Np, L ** D)                  # (explicit: -1 cannot be inferred for an empty point set)
+    w = w.reshape(Np, L ** D)
     us = []
     for c in range(len(vp)):
         v = np.asarray(vp[c]).astype(gdtype)
@@ -597,8 +597,8 @@ def interpolate(plan: OraclePlan, us: Sequence[np.ndarray]):
         w = w[:, None, ...] * (vals[d] * T(TWO_PI / plan.Nover[d])).reshape((-1, L) + (1,) * d)
         stride *= plan.Nover[d]
     Np = lin.shape[0]
-    lin = lin.reshape(Np, -1)
-    w = w.reshape(Np, -1)
+    lin = lin.reshape(Np, L ** D)                  # (explicit: -1 cannot be inferred for an empty point set)
+    w = w.reshape(Np, L ** D)
     out = []
     for u in us:
         uf = np.asarray(u).reshape(-1)
