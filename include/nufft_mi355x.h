@@ -1819,7 +1819,107 @@ int nufft_fieldseg_get_solver_matrix(nufft_fieldseg* h, double* host_out, void* 
 int nufft_fieldseg_get_tau(nufft_fieldseg* h, double* host_out, void* stream);
 int64_t nufft_sizeof_fieldseg_info(void);
 
-/* ---- misc ----------------------------------------------------------------------------- */
+/* ---- Second-order total generalized variation, TGV² -------------- */
+/* Total variation turns smooth ramps into stairs; TGV² (Bredies, Kunisch & Pock 2010; Knoll, Bredies, Pock & Stollberger 2011 for
+ * undersampled radial MRI) lets a vector field v take up the slope.  Per component (coupled components: jointly), with x an image and
+ * v = (v_1 ... v_D) a complex vector field of the same shape,
+ *
+ *     minimise over x, v:   ½ <x, (G + μ I) x> − Re<b, x> + α1 Σ_i |(∇x − v)_i|₂ + α0 Σ_i |(E v)_i|_F
+ *
+ * ∇ is the periodic forward difference of the total-variation section.  E is the symmetrised gradient built from periodic BACKWARD
+ * differences (∂⁻_e u)[i] = u[i] − u[i − e_e] on the array as stored:
+ *
+ *     (E v)_de[i]  = ½ ((∂⁻_e v_d)[i] + (∂⁻_d v_e)[i])         two subtractions, one addition, one multiply by ½, in this order:
+ *                                                              the diagonal entry is ∂⁻_d v_d exactly
+ *     |W|_F        = sqrt(Σ_d |W_dd|² + 2 Σ_{d<e} |W_de|²)     the inner product on such tensors carries the same weights 1 / 2
+ *     (Eᴴ r)_d[i]  = Σ_e (r_de[i] − r_de[i + e_e])             r_ed = r_de, summed in the order e = 1 ... D
+ *
+ * A symmetric tensor is S = D (D + 1) / 2 arrays in row-major upper-triangle order, (1,1), (1,2), (1,3), (2,2), (2,3), (3,3) for D = 3
+ * (the order of the coupled operator's pair index); a table of them holds ntransforms · S pointers, component c's entry s at
+ * [c · S + s]; a table of fields holds ntransforms · D pointers as in nufft_tv_gradient.  Both operators commute with every cyclic
+ * shift.
+ *
+ * The operator alone, on a nufft_tv object; rules and refusals as nufft_tv_gradient / _adjoint / _norm (null or misaligned pointers, an
+ * output overlapping an input or another output NUFFT_ERR_INVALID_ARG); no atomics, no synchronisation, hipGraph-capture safe.
+ * nufft_tv_sym_norm: sums_out_device[c] = Σ_i |(E v[c])_i|_F, the entries formed in T, squares, root and sum in FP64 in one fixed
+ * order. */
+int nufft_tv_sym_gradient(nufft_tv* tv, void* const* r_out, const void* const* v, void* stream);
+int nufft_tv_sym_adjoint(nufft_tv* tv, void* const* v_out, const void* const* r, void* stream);
+int nufft_tv_sym_norm(nufft_tv* tv, const void* const* v, double* sums_out_device, void* stream);
+
+/* The solver: Condat–Vũ on K(x, v) = (∇x − v, E v), Kᴴ(p, r) = (∇ᴴp, −p + Eᴴr), fixed steps τ and σ, duals p (D arrays) and r (S arrays):
+ *
+ *     start:  x = x0 (or 0),  v = 0,  p = 0,  r = 0
+ *     for it = 1 ... max_iter:
+ *         q  = G x                                        nufft_toeplitz_apply
+ *         x⁺ = x − τ (q + μ x − b + ∇ᴴ p)                 x̄ = x⁺ + (x⁺ − x)          the primal kernel of the TV solver, p for y
+ *         v⁺ = v − τ (−p + Eᴴ r)                          v̄ = v⁺ + (v⁺ − v)
+ *         p  <- P_α1(p + σ (∇x̄ − v̄))                      P_t(u)_i = u_i · min(1, t / |u_i|₂) over the D entries of a cell
+ *         r  <- P_α0(r + σ E v̄)                           the same with |·|_F over the S entries of a cell
+ *         change = ‖x⁺ − x‖ / ‖x⁺‖ (0 when both are 0);  history row (change, Σ_i |(∇x⁺ − v⁺)_i|₂, Σ_i |(E v⁺)_i|_F)
+ *         done <- change <= tol, or change not finite (NUFFT_TGV_BREAKDOWN)
+ *
+ * ‖K‖² <= 8 D (‖∇x − v‖² + ‖Ev‖² <= 2 ‖∇x‖² + (2 + 4 D) ‖v‖², ‖∇‖², ‖E‖² <= 4 D), so with τ <= 1 / L and the default σ = 1 / (16 D τ)
+ * 1 / τ − σ ‖K‖² >= 1 / (2 τ) >= L / 2, the convergence condition.  Any finite σ > 0 is accepted.  α1 = 0 leaves p exactly zero (x then
+ * runs plain gradient descent), α0 = 0 leaves r exactly zero.  The stopping rule is on x alone.  v, p and r restart at 0 in every solve.
+ *
+ * No launch reads at a neighbour an array it writes.  The solver owns 1 + 3 D + S arrays per component (q, v, v̄, p, r).  Frozen
+ * components, coupled operators (one system: one change, one flag), FP64 sums without atomics in one fixed order, check_every and
+ * hipGraph capture are as in the TV solver above: two runs, both modes and a replayed graph give the same bits.
+ *
+ * Added after ABI 104 without changing NUFFT_MI355X_VERSION: detect by symbol (dlsym nufft_tgv_create) and compare
+ * nufft_sizeof_tgv_params() / nufft_sizeof_tgv_info() with your own. */
+typedef struct nufft_tgv nufft_tgv; /* opaque */
+
+enum { NUFFT_TGV_MAX_ITER = 0,   /* max_iter iterations ran without reaching tol */
+       NUFFT_TGV_CONVERGED = 1,  /* change <= tol                                */
+       NUFFT_TGV_BREAKDOWN = 2   /* change not finite: the component was frozen  */ };
+
+typedef struct nufft_tgv_params {
+    int32_t struct_size;     /* sizeof(nufft_tgv_params) of the caller's header (0 = this layout)                                  */
+    int32_t max_iter;        /* 1 ... 2^24                                                                                         */
+    int32_t check_every;     /* 0, or the number of iterations between two looks at the done flags                                 */
+    int32_t reserved;        /* 0                                                                                                  */
+    double tol;              /* >= 0, finite                                                                                       */
+    double step;             /* τ > 0, finite                                                                                      */
+    double sigma;            /* σ > 0, finite; 0 = 1 / (16 ndim τ)                                                                 */
+    double lambda;           /* the Tikhonov μ: >= 0, finite                                                                       */
+    double alpha1, alpha0;   /* >= 0, finite: the weights of every component until nufft_tgv_set_weights                           */
+} nufft_tgv_params;
+
+typedef struct nufft_tgv_info {
+    int32_t struct_size;     /* sizeof(nufft_tgv_info) of the caller's header, set before the call (0 = this layout)               */
+    int32_t ntransforms, dtype, ndim, max_iter, check_every;
+    int32_t iterations_enqueued; /* by the last nufft_tgv_solve (check_every > 0 stops early); -1 before the first                 */
+    int32_t reserved;
+    double tol, step, sigma, lambda;   /* sigma: the value in use                                                                  */
+    int64_t array_bytes;     /* q, v, v̄, p, r: 1 + 3 ndim + ndim (ndim + 1) / 2 arrays per component                               */
+    int64_t workspace_bytes; /* device bytes owned: array_bytes + partial sums + scalars + history                                 */
+} nufft_tgv_info;
+
+/* The solver keeps the POINTER `tz`, as nufft_tvpd_create.  Refusals, in the order and with the codes of nufft_tvpd_create: null
+ * arguments, max_iter < 1 or > 2^24, check_every < 0, tol, alpha1, alpha0, lambda or sigma negative or not finite, step <= 0 or not
+ * finite NUFFT_ERR_INVALID_ARG; whatever nufft_tv_create refuses for the shape; a host-only operator NUFFT_ERR_NO_DEVICE (after the
+ * argument checks). */
+int nufft_tgv_create(nufft_tgv** out, nufft_toeplitz* tz, const nufft_tgv_params* params);
+int nufft_tgv_destroy(nufft_tgv* s);
+/* One pair of weights per component (host arrays, count = ntransforms, each finite and >= 0) for the following solves. */
+int nufft_tgv_set_weights(nufft_tgv* s, const double* alpha1, const double* alpha0, int64_t count);
+/* As nufft_tvpd_solve, with the same refusals. */
+int nufft_tgv_solve(nufft_tgv* s, void* const* x_inout, const void* const* b, int use_x0, void* stream);
+int nufft_tgv_get_info(const nufft_tgv* s, nufft_tgv_info* out);
+/* As nufft_tvpd_get_result (status: NUFFT_TGV_*). */
+int nufft_tgv_get_result(nufft_tgv* s, int32_t* iterations, int32_t* status, double* change, int64_t capacity, void* stream);
+/* host_out[max_iter][ntransforms][3]: change, Σ_i |(∇x − v)_i|₂ and Σ_i |(E v)_i|_F after every iteration; NaN where the iteration did
+ * not change the component.  Synchronises `stream`. */
+int nufft_tgv_history(nufft_tgv* s, double* host_out, int64_t capacity, void* stream);
+/* v of the last solve into ntransforms · D caller arrays (16-byte aligned, v_d of component c at [c · D + d − 1]): device-to-device
+ * copies on `stream`; does not synchronise; hipGraph-capture safe. */
+int nufft_tgv_copy_field(nufft_tgv* s, void* const* v_out, void* stream);
+int64_t nufft_sizeof_tgv_params(void);
+int64_t nufft_sizeof_tgv_info(void);
+
+/* ---- misc----------------------------------------------------------------------------- */
 /* sizeof(nufft_params) / sizeof(nufft_info) of the library build: a binding that mirrors the structs by hand
  * (ctypes, Julia) compares them with its own layout before the first call. */
 /* Plan-owned device memory right now, buffer by buffer: "name=bytes;name=bytes;..." (NUL-terminated) into `out`; the values sum to

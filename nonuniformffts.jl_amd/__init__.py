@@ -24,6 +24,7 @@ from .wavelet import WaveletTransform  # noqa: F401
 from .llr import LocallyLowRank  # noqa: F401
 from .fista import ToeplitzFISTA  # noqa: F401
 from .tv import ToeplitzTV, TotalVariation  # noqa: F401
+from .tgv import ToeplitzTGV  # noqa: F401
 from .lps import GlobalLowRank, TemporalSparsity, ToeplitzLPS  # noqa: F401
 from .dcf import DensityCompensation, density_weights  # noqa: F401
 from .coilmaps import CoilMapEstimator, calibration_weights, estimate_maps  # noqa: F401
@@ -39,7 +40,7 @@ __all__ = [
     "PlanNUFFT3", "set_points3", "exec_type3", "exec_type3_grad",
     "exec_type2_grad", "interpolate_grad", "autograd",
     "ToeplitzOperator", "ToeplitzCG", "ToeplitzPreconditioner", "coil_expand", "coil_combine",
-    "WaveletTransform", "LocallyLowRank", "ToeplitzFISTA", "TotalVariation", "ToeplitzTV",
+    "WaveletTransform", "LocallyLowRank", "ToeplitzFISTA", "TotalVariation", "ToeplitzTV", "ToeplitzTGV",
     "GlobalLowRank", "TemporalSparsity", "ToeplitzLPS",
     "DensityCompensation", "density_weights",
     "CoilMapEstimator", "estimate_maps", "calibration_weights",

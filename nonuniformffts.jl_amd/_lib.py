@@ -226,6 +226,27 @@ TVPD_MAX_ITER, TVPD_CONVERGED, TVPD_BREAKDOWN = 0, 1, 2
 TVPD_STATUS_NAMES = {TVPD_MAX_ITER: "max_iter", TVPD_CONVERGED: "converged", TVPD_BREAKDOWN: "breakdown"}
 
 
+class NufftTgvParams(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("max_iter", C.c_int32), ("check_every", C.c_int32), ("reserved", C.c_int32),
+        ("tol", C.c_double), ("step", C.c_double), ("sigma", C.c_double), ("lambda_", C.c_double), ("alpha1", C.c_double),
+        ("alpha0", C.c_double),
+    ]
+
+
+class NufftTgvInfo(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32), ("ntransforms", C.c_int32), ("dtype", C.c_int32), ("ndim", C.c_int32), ("max_iter", C.c_int32),
+        ("check_every", C.c_int32), ("iterations_enqueued", C.c_int32), ("reserved", C.c_int32),
+        ("tol", C.c_double), ("step", C.c_double), ("sigma", C.c_double), ("lambda_", C.c_double),
+        ("array_bytes", C.c_int64), ("workspace_bytes", C.c_int64),
+    ]
+
+
+TGV_MAX_ITER, TGV_CONVERGED, TGV_BREAKDOWN = 0, 1, 2
+TGV_STATUS_NAMES = {TGV_MAX_ITER: "max_iter", TGV_CONVERGED: "converged", TGV_BREAKDOWN: "breakdown"}
+
+
 class NufftGlrInfo(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int32), ("ndim", C.c_int32), ("dtype", C.c_int32), ("ntransforms", C.c_int32), ("device", C.c_int32),
@@ -552,6 +573,19 @@ SYMBOLS = {
     "nufft_fieldseg_get_solver_matrix": (C.c_int, [_P, C.POINTER(C.c_double), _P]),
     "nufft_fieldseg_get_tau": (C.c_int, [_P, C.POINTER(C.c_double), _P]),
     "nufft_sizeof_fieldseg_info": (C.c_int64, []),
+    "nufft_tv_sym_gradient": (C.c_int, [_P, _PP, _PP, _P]),
+    "nufft_tv_sym_adjoint": (C.c_int, [_P, _PP, _PP, _P]),
+    "nufft_tv_sym_norm": (C.c_int, [_P, _PP, _P, _P]),
+    "nufft_tgv_create": (C.c_int, [C.POINTER(_P), _P, C.POINTER(NufftTgvParams)]),
+    "nufft_tgv_destroy": (C.c_int, [_P]),
+    "nufft_tgv_set_weights": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int64]),
+    "nufft_tgv_solve": (C.c_int, [_P, _PP, _PP, C.c_int, _P]),
+    "nufft_tgv_get_info": (C.c_int, [_P, C.POINTER(NufftTgvInfo)]),
+    "nufft_tgv_get_result": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int64, _P]),
+    "nufft_tgv_history": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int64, _P]),
+    "nufft_tgv_copy_field": (C.c_int, [_P, _PP, _P]),
+    "nufft_sizeof_tgv_params": (C.c_int64, []),
+    "nufft_sizeof_tgv_info": (C.c_int64, []),
     "nufft_sizeof_params": (C.c_int64, []),
     "nufft_sizeof_info": (C.c_int64, []),
     "nufft_strerror": (C.c_char_p, [C.c_int]),
@@ -592,7 +626,8 @@ def _load():
                          ("nufft_sizeof_tsparse_info", NufftTsparseInfo), ("nufft_sizeof_lps_params", NufftLpsParams),
                          ("nufft_sizeof_lps_info", NufftLpsInfo), ("nufft_sizeof_coilmaps_params", NufftCoilmapsParams),
                          ("nufft_sizeof_coilmaps_info", NufftCoilmapsInfo), ("nufft_sizeof_coilcomp_info", NufftCoilcompInfo),
-                         ("nufft_sizeof_fieldseg_info", NufftFieldsegInfo)):
+                         ("nufft_sizeof_fieldseg_info", NufftFieldsegInfo), ("nufft_sizeof_tgv_params", NufftTgvParams),
+                         ("nufft_sizeof_tgv_info", NufftTgvInfo)):
         if getattr(lib, name)() != C.sizeof(mirror):
             raise ImportError(f"{LIB_PATH}: {name}() = {getattr(lib, name)()} but the ctypes mirror has {C.sizeof(mirror)} bytes "
                               "(include/nufft_mi355x.h and _lib.py disagree)")

@@ -41,6 +41,7 @@
 
 #include "solver_common.h"
 #include "stream_kernels.h"
+#include "tgv.h"
 #include "tv.h"
 
 using namespace nufft;
@@ -194,6 +195,34 @@ int run_operator(nufft_tv* t, TvMode mode, void* const* x, void* const* y, hipSt
     return NUFFT_OK;
 }
 
+// One launch of a symmetrised-gradient kernel (tgv_kernels.hip) per batch of components: the D arrays v[c · D + d] and the
+// S = D (D + 1) / 2 arrays r[c · S + s]
+int run_sym_operator(nufft_tv* t, TgvMode mode, void* const* v, void* const* r, hipStream_t stream) {
+    TgvLaunch a{};
+    a.dtype = t->dtype;
+    a.D = t->D;
+    a.wide = t->wide;
+    a.C = t->C;
+    for (int d = 0; d < 3; ++d) {
+        a.N[d] = (int)t->N[d];
+        a.tiles[d] = t->tiles[d];
+    }
+    a.G = t->G;
+    a.part = static_cast<double*>(t->d_part);
+    const int B = batch_of(t), S = tgv_sym(t->D);
+    for (int c0 = 0; c0 < t->C; c0 += B) {
+        a.c0 = c0;
+        a.nc = std::min(B, t->C - c0);
+        for (int k = 0; k < a.nc; ++k) {
+            for (int d = 0; d < t->D; ++d) a.v[k][d] = v[(size_t)(c0 + k) * t->D + d];
+            for (int e = 0; e < S; ++e) a.r[k][e] = r ? r[(size_t)(c0 + k) * S + e] : nullptr;
+        }
+        hipError_t e = launch_tgv(a, mode, stream);
+        if (e != hipSuccess) return fail(NUFFT_ERR_HIP, std::string("launch of a symmetrised-gradient kernel: ") + hipGetErrorString(e));
+    }
+    return NUFFT_OK;
+}
+
 TvtLaunch launch_template_t(const nufft_tv* t) {
     TvtLaunch a{};
     a.dtype = t->dtype;
@@ -314,6 +343,35 @@ int nufft_tv_norm(nufft_tv* t, const void* const* x, double* sums_out_device, vo
     DeviceGuard guard(t->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (int rc = run_operator(t, TV_NORM, const_cast<void* const*>(x), nullptr, s)) return rc;
+    hipError_t e = launch_tv_sum(static_cast<const double*>(t->d_part), t->G, t->C, sums_out_device, s);
+    if (e != hipSuccess) return fail(NUFFT_ERR_HIP, std::string("launch of a total-variation kernel: ") + hipGetErrorString(e));
+    return NUFFT_OK;
+}
+
+int nufft_tv_sym_gradient(nufft_tv* t, void* const* r_out, const void* const* v, void* stream) {
+    if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    const int S = tgv_sym(t->D);
+    int rc;
+    if ((rc = check_table(r_out, t->C * S)) || (rc = check_table(v, t->C * t->D)) || (rc = check_overlap(t, r_out, t->C * S, v, t->C * t->D))) return rc;
+    DeviceGuard guard(t->device);
+    return run_sym_operator(t, TGV_SYM_GRADIENT, const_cast<void* const*>(v), r_out, static_cast<hipStream_t>(stream));
+}
+
+int nufft_tv_sym_adjoint(nufft_tv* t, void* const* v_out, const void* const* r, void* stream) {
+    if (!t) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    const int S = tgv_sym(t->D);
+    int rc;
+    if ((rc = check_table(v_out, t->C * t->D)) || (rc = check_table(r, t->C * S)) || (rc = check_overlap(t, v_out, t->C * t->D, r, t->C * S))) return rc;
+    DeviceGuard guard(t->device);
+    return run_sym_operator(t, TGV_SYM_ADJOINT, v_out, const_cast<void* const*>(r), static_cast<hipStream_t>(stream));
+}
+
+int nufft_tv_sym_norm(nufft_tv* t, const void* const* v, double* sums_out_device, void* stream) {
+    if (!t || !sums_out_device) return fail(NUFFT_ERR_INVALID_ARG, "null argument");
+    if (int rc = check_table(v, t->C * t->D)) return rc;
+    DeviceGuard guard(t->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = run_sym_operator(t, TGV_SYM_NORM, const_cast<void* const*>(v), nullptr, s)) return rc;
     hipError_t e = launch_tv_sum(static_cast<const double*>(t->d_part), t->G, t->C, sums_out_device, s);
     if (e != hipSuccess) return fail(NUFFT_ERR_HIP, std::string("launch of a total-variation kernel: ") + hipGetErrorString(e));
     return NUFFT_OK;

@@ -108,6 +108,40 @@ class TotalVariation(_HandleObject):
         _check(lib.nufft_tv_norm(self._handle, _ptr_table(x_t), C.c_void_p(sums.data_ptr()), self._stream()))
         return sums
 
+    def _fields(self, y, count):
+        """A tuple of ``count`` tensors (one component) or a tuple of ntransforms such tuples -> (single, tuple of tuples)."""
+        single = len(y) > 0 and isinstance(y[0], torch.Tensor)
+        y_t = (tuple(y),) if single else tuple(tuple(comp) for comp in y)
+        if len(y_t) != self.ntransforms or (single and self.ntransforms != 1):
+            raise DimensionMismatch(f"wrong amount of components (expected {self.ntransforms})")
+        for comp in y_t:
+            self._check_arrays(comp, "input", count)
+        return single, y_t
+
+    def _sym(self, entry, src, count_in, count_out):
+        self._require_open()
+        single, src_t = self._fields(src, count_in)
+        out = tuple(tuple(torch.empty_like(comp[0]) for _ in range(count_out)) for comp in src_t)
+        _check(entry(self._handle, _ptr_table([u for comp in out for u in comp]), _ptr_table([u for comp in src_t for u in comp]), self._stream()))
+        return out[0] if single else out
+
+    def sym_gradient(self, v):
+        """``E v`` for a vector field ``v`` as ``gradient`` returns it: ``(E v)_de = ½(∂⁻_e v_d + ∂⁻_d v_e)`` from periodic
+        backward differences, a tuple of ``D (D + 1) / 2`` tensors in row-major upper-triangle order, (1,1), (1,2), (1,3), (2,2), ..."""
+        return self._sym(lib.nufft_tv_sym_gradient, v, self.ndim, self.ndim * (self.ndim + 1) // 2)
+
+    def sym_adjoint(self, r):
+        """``Eᴴ r`` for ``r`` as ``sym_gradient`` returns it (off-diagonal entries count twice in the inner product): D tensors."""
+        return self._sym(lib.nufft_tv_sym_adjoint, r, self.ndim * (self.ndim + 1) // 2, self.ndim)
+
+    def sym_norm(self, v) -> torch.Tensor:
+        """``Σ_i |(E v)_i|_F`` per component, ``|W|_F² = Σ_d |W_dd|² + 2 Σ_{d<e} |W_de|²``: a float64 device tensor of ntransforms values."""
+        self._require_open()
+        _, v_t = self._fields(v, self.ndim)
+        sums = torch.empty(self.ntransforms, dtype=torch.float64, device=self.device)
+        _check(lib.nufft_tv_sym_norm(self._handle, _ptr_table([u for comp in v_t for u in comp]), C.c_void_p(sums.data_ptr()), self._stream()))
+        return sums
+
     def _frames(self, x, periodic):
         if self.ntransforms < 2:
             raise ValueError("the difference along the components needs ntransforms >= 2")
