@@ -9,6 +9,12 @@ the oversampled size n (n/2 - 1 is odd for every length: the odd kept count); on
 Partial workgroups: the strided passes meet them in their column groups (21 kept columns against groups of 16, 8 or 4).  The
 contiguous-line kernels (real, complex, Toeplitz) cannot meet one through a plan: they run only where every other oversampled size
 is in the table, all multiples of 16, so their line count is a multiple of every lines-per-workgroup value (16, 8, 4).
+
+The coupled dimension-1 kernel (csrc/toeplitz_coupled.hip) and the coil-map variants of the strided pass have tables of their own
+(`coupled_cases`, `coupled_refused`, `maps_cases`).  What an operator cannot reach in the coupled kernel: the kept count of its
+dimension 1 is always n / 2, which is even, so the scalar (odd `k1`) load/store branch of its ComplexF32 instantiations is dead
+there; and the line count is the product of the other padded sizes, all from the table and so multiples of 16 (in these tables 64
+and 4096 line ids, multiples of 64), a multiple of every waves-per-workgroup value (16 … 1), so `line_id >= nlines` never fires.
 """
 from collections import namedtuple
 
@@ -83,6 +89,81 @@ def toeplitz_cases():
     return out
 
 
+# Section 6: toeplitz_lines_coupled_kernel<T, N, KT, TL> (csrc/toeplitz_coupled.hip), dimension 1 of the fused apply for K coupled
+# components.  Three rules of that file decide which instantiation runs and how; they are restated here so that the tables can be
+# checked for what they reach (tests/test_fft_lines_host.py pins the restatement against a literal table).
+LDS_LIMIT = 160 * 1024            # kFftLdsLimit (csrc/fft_line.h): LDS per workgroup
+CSIZE = {"c128": 16, "c64": 8}    # bytes of one complex element
+TIERS = (2, 4, 8, 16)
+TIER_KS = {2: (2,), 4: (3, 4), 8: (5, 6, 7, 8), 16: (9, 12, 16)}
+
+
+def coupled_waves(csize, n, kt):
+    """Waves per workgroup (the template parameter TL) — `coupled_waves` of csrc/toeplitz_coupled.hip (lines 37-46): the most of
+    16, 8, 4 that leave room for two workgroups per CU, else the most of 16 … 1 that fit at all; 0: not even one wave fits."""
+    line = n + (n >> 4) + 1
+    for tl in (16, 8, 4):
+        if csize * (n + tl * kt * line) <= 80 * 1024:
+            return tl
+    for tl in (16, 8, 4, 2, 1):
+        if csize * (n + tl * kt * line) <= LDS_LIMIT:
+            return tl
+    return 0
+
+
+def coupled_tier(K):
+    """The compile-time bound KT of the run-time K — `coupled_tier` of csrc/toeplitz_coupled.hip (line 47)."""
+    return 2 if K <= 2 else (4 if K <= 4 else (8 if K <= 8 else 16))
+
+
+def coupled_prefetch(csize, n, kt):
+    """Whether the instantiation holds the diagonal lines of a lane's first pack in registers across the backward FFTs — `PREFETCH` of
+    csrc/toeplitz_coupled.hip (lines 54-58): KT <= 4 && N / PW >= 64 with PW = 16 / sizeof(T) cells per 16-byte load."""
+    pw = 16 // (csize // 2)
+    return kt <= 4 and n // pw >= 64
+
+
+CoupledCase = namedtuple("CoupledCase", "kind Z n dims K fftshift")
+
+
+def coupled_cases():
+    """One case per launchable (element type, length, tier): dims (n / 2, 32) give the dimension-1 line length n, the other padded size 64
+    and 64 line ids.  K walks through the tier over the lengths, fftshift alternates, oppositely for the two types.  Then four 3-D
+    shapes with 4096 line ids (many workgroups).  The two types of a (length, tier) follow each other: they share the reference."""
+    out = []
+    for i, n in enumerate(SIZES):
+        for tier in TIERS:
+            ks = TIER_KS[tier]
+            for Z in ("c128", "c64"):
+                if coupled_waves(CSIZE[Z], n, tier) > 0:
+                    out.append(CoupledCase("coupled_lines", Z, n, (n // 2, 32), ks[i % len(ks)], (i % 2 == 0) == (Z == "c128")))
+    out.append(CoupledCase("coupled_lines", "c128", 128, (64, 32, 32), 3, False))      # prefetch on
+    out.append(CoupledCase("coupled_lines", "c64", 256, (128, 32, 32), 2, True))       # prefetch on
+    out.append(CoupledCase("coupled_lines", "c64", 64, (32, 32, 32), 7, False))
+    out.append(CoupledCase("coupled_lines", "c128", 80, (40, 32, 32), 9, True))
+    return out
+
+
+def coupled_refused():
+    """(Z, n, K) the fused path must refuse (coupled_waves = 0): ComplexF64, tier 16, from 640 cells on — the smallest K of the tier at
+    each length and the largest at the first."""
+    return [("c128", 640, 9), ("c128", 640, 16), ("c128", 768, 9), ("c128", 1024, 9)]
+
+
+def maps_cases():
+    """Section 7: fft_lines_kernel<..., CMAP = true>, the coil maps inside the outermost strided passes of the fused apply (backward:
+    times S on load; forward: times conj(S) on store, coil 0 storing, coils 1 and 2 accumulating), three coils each.
+    maps_2d, dims (40, n / 2): the strided pass at n carries the map over 40 kept columns (a partial column group against groups of 16, full
+    ones against 8 and 4), dimension 1 runs at 80.  maps_3d, dims (32, 32, n / 2): the pass along dimension 3 at n carries the map, the
+    pass along dimension 2 runs without it.  Each shape for both element types, one after the other (they share the reference)."""
+    out = []
+    for i, n in enumerate(SIZES):
+        for kind, dims, shift in (("maps_2d", (40, n // 2), i % 2 == 0), ("maps_3d", (32, 32, n // 2), i % 2 == 1)):
+            for Z in ("c128", "c64"):
+                out.append(ToeplitzCase(kind, Z, n, dims, shift))
+    return out
+
+
 HaloCase = namedtuple("HaloCase", "Z n dims over")
 
 # Section 5: the halo-adding forward dimension-1 pass behind the spreading window's halo variant (spread_method = "marching_ring",
@@ -107,7 +188,7 @@ def halo_cases():
 
 def case_id(c):
     Z = c.Z if isinstance(c.Z, str) else np.dtype(c.Z).name
-    extra = ""
+    extra = f"-K{c.K}" if hasattr(c, "K") else ""
     if getattr(c, "fftshift", False):
         extra += "-shift"
     if getattr(c, "C", 1) > 1:

@@ -7,7 +7,10 @@ against references.  The case tables live in tests/fft_lines_cases.py (checked o
     in the same test (what tests/test_gpu_toeplitz.py grants the same kind of comparison);
   * the MULT variants (mode factors) with a point-weight callback on top, against the oracle's NUFFTCallbacks;
   * the Toeplitz operator's fused apply against the exact Gram product, the dense path and each other;
-  * the halo-adding forward dimension-1 pass behind the spreading window's halo variant.
+  * the halo-adding forward dimension-1 pass behind the spreading window's halo variant;
+  * the coupled dimension-1 kernel (csrc/toeplitz_coupled.hip) in every launchable (element type, length, tier) against the exact block
+    product, the dense path and each other, and the edge of what it refuses;
+  * the coil-map (CMAP) variants of the strided passes at every length, against the exact SENSE product and the two routes without them.
 
 Lengths without a halo case: none.  At the shapes of fft_lines_cases.halo_shape (half-support 4) plan.info() reports the halo variant for
 all thirteen lengths and all four element types (asserted on the CPU by tests/test_fft_lines_host.py).
@@ -22,6 +25,8 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 import fft_lines_cases as FC  # noqa: E402
+import sense_reference as SR  # noqa: E402
+import subspace_reference as S  # noqa: E402
 import toeplitz_reference as R  # noqa: E402
 from oracle import nufft_oracle as O  # noqa: E402
 
@@ -242,6 +247,172 @@ def test_toeplitz_fused_apply_every_length(case):
     print(f"FFTLINES toeplitz {FC.case_id(case)}: fused l2 {ef:.3e} max {_relmax(got['fused'], ref):.3e}; dense l2 {ed:.3e}; fused vs dense {efd:.3e}; "
           f"ratio {ef / ed:.2f}")
     assert ef <= bar and ed <= bar and efd <= bar, (ef, ed, efd)
+
+
+COUPLED_CASES = FC.coupled_cases()
+
+
+class _CoupledProblem:
+    """Points, weights, basis and the K inputs of one (dims, K), drawn in single precision and widened, so that both element types hold
+    exactly these numbers; the exact spectra of all pairs (direct sums), the three multipliers the tests read back and, per fftshift, the
+    exact block product."""
+
+    def __init__(self, dims, K, seed):
+        rng = np.random.default_rng(seed)
+        Np = FC.NP_TOEPLITZ
+        cplx = lambda *shape: (rng.standard_normal(shape) + 1j * rng.standard_normal(shape)).astype(np.complex64).astype(np.complex128)
+        self.dims, self.K = dims, K
+        self.xs = [(rng.random(Np) * 2 * np.pi).astype(np.float32).astype(np.float64) for _ in dims]
+        self.w = (rng.random(Np) + 0.1).astype(np.float32).astype(np.float64)
+        self.phi = cplx(K, Np) / np.sqrt(2)
+        self.us = [cplx(*dims[::-1]) for _ in range(K)]
+        self.spectra = np.ascontiguousarray(np.stack(S.exact_spectra(dims, self.xs, self.w, self.phi)))     # (einsum may return transposed views)
+        self.mults = {(a, b): R.multiplier(dims, self.spectra[S.pair_index(a, b, K)]) for a, b in ((0, 0), (0, K - 1), (K - 1, K - 1))}
+        for a in [self.phi, self.spectra, *self.us, *self.mults.values()]:
+            a.setflags(write=False)
+        self._gram = {}
+
+    def gram(self, fftshift):
+        if fftshift not in self._gram:
+            self._gram[fftshift] = [np.ascontiguousarray(g) for g in S.exact_block_gram(self.dims, self.xs, self.w, self.phi, self.us, fftshift)]
+            for g in self._gram[fftshift]:
+                g.setflags(write=False)
+        return self._gram[fftshift]
+
+
+@functools.lru_cache(maxsize=2)
+def _coupled_problem(dims, K):
+    return _CoupledProblem(dims, K, seed=5000 + 17 * sum(dims) + K)
+
+
+def _coupled_run(nufft, Zc, dims, K, fftshift, path, p, bar):
+    """One coupled operator from the exact spectra on `path`: the K outputs of the apply; the three multipliers are checked here."""
+    plan = nufft.PlanNUFFT(Zc, dims, backend=nufft.ROCBackend(0), fftshift=fftshift, ntransforms=K,
+                           options={"NUFFT_TOEPLITZ_FUSED": 0} if path == "dense" else {})
+    op = nufft.ToeplitzOperator(plan)
+    assert op.path == path, (dims, K, path, op.path)
+    op.set_spectra(torch.from_numpy(p.spectra.astype(Zc)).cuda())
+    plan.close()
+    assert op.coupled and nufft.lib.nufft_toeplitz_num_coupled(op._handle) == K and op.path == path
+    out = op.apply(tuple(torch.from_numpy(u.astype(Zc)).cuda() for u in p.us))
+    torch.cuda.synchronize()
+    got = [o.cpu().numpy() for o in out]
+    for (a, b), kref in p.mults.items():
+        k = op.multiplier(a, b)
+        assert tuple(k.shape) == tuple(2 * n for n in reversed(dims)) and k.is_complex() == (a != b)
+        ek = R.rel(k.cpu().numpy(), kref.real if a == b else kref)
+        assert ek <= bar, (path, a, b, ek)
+    op.close()
+    return got
+
+
+@pytest.mark.parametrize("case", COUPLED_CASES, ids=FC.case_id)
+def test_toeplitz_coupled_lines_every_length_and_tier(case):
+    """toeplitz_lines_coupled_kernel<T, N, KT, TL> (csrc/toeplitz_coupled.hip) in every launchable (element type, length, tier), with K
+    walking through the tiers: the fused apply of K coupled components from exact spectra against the exact block product from direct
+    sums, the dense path against the same, and the two against each other, per component.  Bars: those of
+    tests/test_gpu_subspace.py `test_exact_spectra` (1e-12 / 1e-5) for every case: ComplexF32 at 2 N_1 >= 512 with K >= 9 measured
+    2.8e-7 … 3.0e-7 fused and 2.9e-7 … 3.2e-7 dense, so no case needs a bar derived from the dense path."""
+    nufft = _nufft()
+    Zc, bar = (np.complex128, 1e-12) if case.Z == "c128" else (np.complex64, 1e-5)
+    dims, K = tuple(case.dims), case.K
+    p = _coupled_problem(dims, K)
+    refs = p.gram(case.fftshift)
+    got = {path: _coupled_run(nufft, Zc, dims, K, case.fftshift, path, p, bar) for path in ("fused", "dense")}
+    ef = [R.rel(got["fused"][a], refs[a]) for a in range(K)]
+    ed = [R.rel(got["dense"][a], refs[a]) for a in range(K)]
+    efd = [R.rel(got["fused"][a], got["dense"][a]) for a in range(K)]
+    mf = max(_relmax(got["fused"][a], refs[a]) for a in range(K))
+    md = max(_relmax(got["dense"][a], refs[a]) for a in range(K))
+    tier = FC.coupled_tier(K)
+    print(f"FFTLINES coupled {FC.case_id(case)} KT={tier} TL={FC.coupled_waves(FC.CSIZE[case.Z], case.n, tier)}: fused l2 {max(ef):.3e} max {mf:.3e}; "
+          f"dense l2 {max(ed):.3e} max {md:.3e}; fused vs dense {max(efd):.3e}; ratio {max(ef) / max(ed):.2f}")
+    assert max(ef) <= bar and max(ed) <= bar and max(efd) <= bar, (ef, ed, efd)
+
+
+def test_toeplitz_coupled_fit_boundary():
+    """The edge of toeplitz_lines_coupled_supported: ComplexF64, tier 16 (K = 9 like K = 16), from 2 N_1 = 640 on.  The fused operator
+    refuses the coupled build (NUFFT_ERR_UNSUPPORTED, the message names the way out) and is left without one; the dense operator of the
+    same shape builds and meets the bar.  (The neighbours that fit, tier 16 at 512 and K = 8 at 640, 768 and 1024, run in the matrix.)"""
+    nufft = _nufft()
+    tab = nufft.plan._ptr_table
+    for Z, n, K in FC.coupled_refused():
+        assert Z == "c128"
+        dims, npairs = (n // 2, 32), K * (K + 1) // 2
+        plan = nufft.PlanNUFFT(np.complex128, dims, backend=nufft.ROCBackend(0), ntransforms=K)
+        op = nufft.ToeplitzOperator(plan)
+        plan.close()
+        assert op.path == "fused"
+        zeros = torch.zeros((npairs, 64, n), dtype=torch.complex128, device="cuda")
+        code = nufft.lib.nufft_toeplitz_set_spectra_coupled(op._handle, tab(tuple(zeros[i] for i in range(npairs))), None)
+        assert code == nufft._lib.ERR_UNSUPPORTED, (n, K, code)
+        with pytest.raises(ValueError, match="NUFFT_TOEPLITZ_FUSED=0"):
+            op.set_spectra(zeros)
+        assert not op.coupled and nufft.lib.nufft_toeplitz_num_coupled(op._handle) == 0 and op.path == "fused" and op.info().has_spectrum == 0
+        op.close()
+        del zeros
+        p = _coupled_problem(dims, K)
+        refs = p.gram(False)
+        got = _coupled_run(nufft, np.complex128, dims, K, False, "dense", p, 1e-12)
+        ed = max(R.rel(got[a], refs[a]) for a in range(K))
+        print(f"FFTLINES coupled boundary c128 n={n} K={K}: refused on the fused path; dense l2 {ed:.3e}")
+        assert ed <= 1e-12, (n, K, ed)
+
+
+MAPS_CASES = FC.maps_cases()
+NCOILS = 3
+
+
+@functools.lru_cache(maxsize=2)
+def _maps_reference(dims, fftshift, seed):
+    """Exact spectrum, three coil maps and the exact SENSE Gram product of one shape, shared by its ComplexF64 and ComplexF32 case: the
+    draws and the maps are rounded to single precision before the reference is formed, so both element types hold exactly these numbers."""
+    rng = np.random.default_rng(seed)
+    Np = FC.NP_TOEPLITZ
+    xs = [(rng.random(Np) * 2 * np.pi).astype(np.float32).astype(np.float64) for _ in dims]
+    w = (rng.random(Np) + 0.1).astype(np.float32).astype(np.float64)
+    u = (rng.standard_normal(dims[::-1]) + 1j * rng.standard_normal(dims[::-1])).astype(np.complex64).astype(np.complex128)
+    maps = SR.smooth_maps(NCOILS, dims[::-1], seed=seed + 100).astype(np.complex64).astype(np.complex128)
+    spec = np.ascontiguousarray(R.exact_spectrum(dims, xs, w))
+    ref = np.ascontiguousarray(SR.exact_sense_gram(dims, xs, w, maps, u, fftshift))
+    for a in (spec, ref, u, maps):
+        a.setflags(write=False)
+    return spec, ref, u, maps
+
+
+@pytest.mark.parametrize("case", MAPS_CASES, ids=FC.case_id)
+def test_toeplitz_coil_maps_in_pass_every_length(case):
+    """fft_lines_kernel<..., CMAP = true> at every length: the outermost strided passes of the fused apply with three coil maps inside
+    (backward times S; forward times conj(S), coil 0 storing, coils 1 and 2 accumulating) against the exact SENSE product from direct
+    sums; the route without them (expand, plain apply, combine) and the dense path against the same, and the three against each other."""
+    nufft = _nufft()
+    Zc, bar = (np.complex128, 1e-12) if case.Z == "c128" else (np.complex64, 1e-5)
+    dims = tuple(case.dims)
+    spec, ref, u, maps = _maps_reference(dims, case.fftshift, 6000 + FC.SIZES.index(case.n))
+    assert not maps[-1].ravel()[0] and np.all(maps[0])               # the exactly zero region of the last coil
+    uz = np.ascontiguousarray(u.astype(Zc))
+    got = {}
+    for route, opts in (("inpass", {"NUFFT_TOEPLITZ_MAPS_INPASS": 1}), ("expand", {"NUFFT_TOEPLITZ_MAPS_INPASS": 0}),
+                        ("dense", {"NUFFT_TOEPLITZ_MAPS_INPASS": 1, "NUFFT_TOEPLITZ_FUSED": 0})):
+        plan = nufft.PlanNUFFT(Zc, dims, backend=nufft.ROCBackend(0), fftshift=case.fftshift, options=opts)
+        op = nufft.ToeplitzOperator(plan)
+        assert op.path == ("dense" if route == "dense" else "fused"), (case, route, op.path)
+        op.set_maps(torch.from_numpy(np.ascontiguousarray(maps.astype(Zc))).cuda())
+        op.set_spectrum(torch.from_numpy(np.ascontiguousarray(spec.astype(Zc))).cuda())
+        plan.close()
+        assert op.ncoils == NCOILS
+        ud = torch.from_numpy(uz).cuda()
+        out = op.apply(ud)
+        torch.cuda.synchronize()
+        got[route] = out.cpu().numpy()
+        assert np.array_equal(ud.cpu().numpy(), uz), route           # the input is only read
+        op.close()
+    err = {route: R.rel(g, ref) for route, g in got.items()}
+    cross = {"inpass vs expand": R.rel(got["inpass"], got["expand"]), "inpass vs dense": R.rel(got["inpass"], got["dense"]),
+             "expand vs dense": R.rel(got["expand"], got["dense"])}
+    print(f"FFTLINES maps {FC.case_id(case)}: inpass l2 {err['inpass']:.3e} max {_relmax(got['inpass'], ref):.3e}; expand l2 {err['expand']:.3e}; "
+          f"dense l2 {err['dense']:.3e}; " + "; ".join(f"{k} {v:.3e}" for k, v in cross.items()) + f"; ratio {err['inpass'] / err['dense']:.2f}")
+    assert all(e <= bar for e in err.values()) and all(e <= bar for e in cross.values()), (err, cross)
 
 
 HALO_CASES = FC.halo_cases()
